@@ -15,9 +15,13 @@ Inputs and outputs are device-resident when the timed region starts; the timed r
 N > 1 (one process per GPU, launched by torch.distributed.run): the graph is sharded by node-id hash, every rank originates
 1M mixed-owner deltas per step; a step = partition by owner + all-to-all (RCCL) + local merge of what arrived. Weak scaling.
 
-After the timed region (never inside it) the run CHECKS ITSELF: every timed batch's winner list, the row count and an
+A plain run sets up, warms up, times the K steps and prints the line (its contract fields, the event and host-enqueue times per
+step, winners per step, table placement). --dump-outputs DIR writes what the last timed step computed (its winner list and the
+stored rows of a seeded sample of its keys) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+
+With --full, after the timed region (never inside it) the run CHECKS ITSELF: every timed batch's winner list, the row count and an
 order-independent digest of the whole device table are compared with the CPU oracle replaying the same batches; a mismatch
-fails the run. Besides the contract fields the line carries
+fails the run. Besides the contract fields the line of a --full run carries
   roofline     — dominant kernel (k_probe_apply): algorithmic bytes per launch / its average duration, measured live with
                  HIP events on the engine's stream in a second pass over fresh batches of the same shape;
   scan_config3 — configs[2]: equals/range scans over an indexed int32 field and a wide int64 field at 10M and 100M rows, with the roofline of the
@@ -73,6 +77,85 @@ def to_dev(cols, dev):
     id, field, ts, val = cols
     return (torch.from_numpy(id.view(np.int64)).to(dev), torch.from_numpy(field.view(np.int32)).to(dev),
             torch.from_numpy(ts).to(dev), torch.from_numpy(val).to(dev))
+
+
+def _i64(c):
+    """a uint64 constant as the int64 with the same bits"""
+    return c - (1 << 64) if c >= (1 << 63) else c
+
+
+def _srl(z, s):
+    """logical right shift of int64 tensors holding uint64 bits"""
+    return (z >> s) & ((1 << (64 - s)) - 1)
+
+
+def _splitmix64_t(z):
+    z = z + _i64(0x9e3779b97f4a7c15)
+    z = (z ^ _srl(z, 30)) * _i64(0xbf58476d1ce4e5b9)
+    z = (z ^ _srl(z, 27)) * _i64(0x94d049bb133111eb)
+    return z ^ _srl(z, 31)
+
+
+def _umod_t(z, m):
+    """(z as uint64) mod m for 0 < m < 2^31"""
+    return ((_srl(z, 32) % m) * ((1 << 32) % m) + (z & 0xffffffff)) % m
+
+
+def _u_t(seed, n, salt, dev):
+    i = torch.arange(n, dtype=torch.int64, device=dev)
+    return _splitmix64_t(i * _i64(0x9E3779B97F4A7C15) + _i64((seed * 0x632BE59BD9B4E019 + salt * 0xD1342543DE82EF95) & ((1 << 64) - 1)))
+
+
+def gen_batch_dev(b, R, dev, D=None, seed=2):
+    """to_dev(gen_batch(b, R, D, seed)) computed on `dev` itself: the same bits as bmx.synth.big_deltas (one field, part (0, 1)), without the
+    ~0.1 s of host time per 1M-delta batch and its upload"""
+    from bmx import synth
+    D = D_PER_STEP if D is None else D
+    if CONFIG == 5:
+        seed, insert_pct, hot_pct, hot_keys, unique, drift = seed + 50, 0, 30, max(1, R // 1000), False, DT // 2
+    else:
+        insert_pct, hot_pct, hot_keys, unique, drift = int(os.environ.get("BMX_BENCH_INSERT_PCT", 10)), 0, 0, True, DT // 16
+    s = seed + 7919 * b
+    u = _umod_t(_u_t(s, D, 3, dev), 100)
+    if unique:
+        j = torch.arange(D, dtype=torch.int64, device=dev)
+        hit_rows = ((j + b * D) * synth.PERM_PRIME + 7) % R
+        ins_rows = R + b * D + j
+    else:
+        hit_rows = _umod_t(_u_t(s, D, 4, dev), R)
+        ins_rows = R + _umod_t(_u_t(s, D, 5, dev), max(1, R // 10))
+    rows = torch.where(u < insert_pct, ins_rows, hit_rows)
+    if hot_pct:
+        rows = torch.where((u >= insert_pct) & (u < insert_pct + hot_pct), _umod_t(_u_t(s, D, 6, dev), max(1, hot_keys)), rows)
+    ids = _splitmix64_t(rows + 1)
+    fh = int(np.array([synth.field_hash(0)], np.uint32).view(np.int32)[0])
+    ts = T0 + b * drift + _umod_t(_u_t(s, D, 8, dev), 2 * DT)
+    val = (_u_t(s, D, 9, dev) & 0xffffffff) - (1 << 31)
+    return ids, torch.full((D,), fh, dtype=torch.int32, device=dev), ts, val
+
+
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs arrays together
+DUMP_ROW_SAMPLE = 1 << 18  # keys of the last timed batch whose stored (ts, val) are dumped
+
+
+def row_sample(ids, fields, seed=20251):
+    """a fixed, seeded sample (ascending positions) of at most DUMP_ROW_SAMPLE of the given keys"""
+    pos = np.arange(len(ids))
+    if len(ids) > DUMP_ROW_SAMPLE:
+        pos = np.sort(np.random.default_rng(seed).choice(len(ids), DUMP_ROW_SAMPLE, replace=False))
+    return ids[pos], fields[pos]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (all values here are integers below 2^53: exact)"""
+    out = {k: np.ascontiguousarray(np.asarray(a), dtype=np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the limit of %d" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    say("outputs of the last timed step written to %s: %s" % (path, ", ".join("%s %s" % (k, a.shape) for k, a in out.items())))
 
 
 def exchange_selftest(dev, dist, rank, world):
@@ -517,13 +600,15 @@ def compact_line(out, detail_path=None):
     cfg = dict(g("config") or {})
     cfg["workload"] = str(cfg.get("workload", ""))[:260]
     line["config"] = cfg
-    rf = g("roofline") or {}
-    line["roofline"] = {k: rf.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "kernel_ms",
-                                                "launches_averaged", "requests_per_launch", "whole_merge_achieved_GBs", "traffic_source") if k in rf}
-    if isinstance(line["roofline"].get("requests_per_launch"), dict):
-        line["roofline"]["requests_per_launch"] = line["roofline"]["requests_per_launch"].get("total")
-    if "traffic_source" in line["roofline"]:
-        line["roofline"]["traffic_source"] = "N=1 PMC passes (profiles/traffic_probe_apply.json)"
+    rf = g("roofline")
+    line["roofline"] = None          # (--full only)
+    if isinstance(rf, dict):
+        line["roofline"] = {k: rf.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "kernel_ms",
+                                                    "launches_averaged", "requests_per_launch", "whole_merge_achieved_GBs", "traffic_source") if k in rf}
+        if isinstance(line["roofline"].get("requests_per_launch"), dict):
+            line["roofline"]["requests_per_launch"] = line["roofline"]["requests_per_launch"].get("total")
+        if "traffic_source" in line["roofline"]:
+            line["roofline"]["traffic_source"] = "N=1 PMC passes (profiles/traffic_probe_apply.json)"
     cb = g("cpu_baseline")
     if isinstance(cb, dict):
         c = {k: _r(cb.get(k), 1) for k in ("value", "unit", "cores", "kind")}
@@ -762,10 +847,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20 for config 2, 90 for config 5)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default: 3 for config 2, 10 for config 5)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 5], help="BASELINE.json configs[1]/[3] (2) or configs[4], streaming hot-key replay (5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run comparison with the CPU oracle")
-    ap.add_argument("--no-scan", action="store_true", help="skip the config-3 index scans (10M and 100M rows)")
-    ap.add_argument("--scan", action="store_true", help="(kept for compatibility: the scans are on by default)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the post-run comparison with the CPU oracle, the per-kernel roofline and unique-keys "
+                                                         "passes, the config-3 index scans, the JS host rate and the CPU baselines (a plain run only sets up, warms up and times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the JS host rate")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the post-run comparison with the CPU oracle")
+    ap.add_argument("--no-scan", action="store_true", help="with --full: skip the config-3 index scans (10M and 100M rows)")
+    ap.add_argument("--scan", action="store_true", help="(kept for compatibility: with --full the scans are on by default)")
     ap.add_argument("--scan-rows", type=str, default="10000000,100000000", help="comma-separated index sizes of the config-3 scans")
     ap.add_argument("--force-sharded", action="store_true", help="run the N>1 code path (partition + all-to-all + merge) even with one rank: rehearsal only")
     ap.add_argument("--rank-timeout", type=float, default=RANK_TIMEOUT_S, help="launcher role (--gpus N > 1 without WORLD_SIZE): seconds after which the ranks' process group is terminated and the run fails")
@@ -792,6 +880,8 @@ def main(argv=None):
     # rows it hits, so later batches win less often: 838k winners per step over steps 3..22, 784k over steps 10..69), which a longer default would book as speed.
     K = args.steps if args.steps is not None else (90 if CONFIG == 5 else 20)
     W = args.warmup if args.warmup is not None else (10 if CONFIG == 5 else 3)
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("--gpus %d needs WORLD_SIZE=%d (launch with torch.distributed.run)" % (args.gpus, args.gpus))
     if not torch.cuda.is_available():
@@ -836,11 +926,13 @@ def main(argv=None):
     verified = None
     refused_why = None
 
+    roofline = None
+    extra = {}
+
     if not sharded:
         rid = gen_resident(R_PER_GPU)
         eng.load_rows(*rid)
-        host_batches = [gen_batch(b, R_PER_GPU) for b in range(nb)]
-        batches = [to_dev(hb, dev) for hb in host_batches]
+        batches = [gen_batch_dev(b, R_PER_GPU, dev) for b in range(nb)]
         applied = torch.zeros((nb, D_PER_STEP), dtype=torch.int32, device=dev)     # every batch keeps its own winner list: compared after the run
         n_applied = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
@@ -868,51 +960,59 @@ def main(argv=None):
         eng.sync()
         elapsed = wall
         winners = n_applied[W:nb].cpu().numpy()
+        wavg = float(winners.mean()) if len(winners) else 0.0
 
-        if not args.no_verify:
-            verified = verify_against_oracle(eng, host_batches, applied, n_applied[:nb], rid)
-        del rid, host_batches
+        if args.dump_outputs:
+            # what a caller of the timed path receives from the last step: the batch indices of its winning deltas (bmx_merge_batch's `applied`),
+            # and the rows the engine then holds for a seeded sample of that batch's keys (bmx_get_rows)
+            ids, flds, _, _ = gen_batch(nb - 1, R_PER_GPU)
+            ts_s, val_s, found_s = eng.get_rows(*row_sample(ids, flds))
+            dump_outputs(args.dump_outputs, {"winners": applied[nb - 1][: int(winners[-1])].cpu().numpy(),
+                                             "row_sample_ts": ts_s, "row_sample_val": val_s, "row_sample_found": found_s})
 
-        # second pass over fresh batches of the same shape: per-kernel HIP-event timing (live roofline figure)
-        pbatches = [to_dev(gen_batch(nb + b, R_PER_GPU), dev) for b in range(min(K, 12))]
-        torch.cuda.synchronize()
-        eng.profile_enable(True)
-        for (i, f, t, v) in pbatches:
-            eng.merge_batch_dev(D_PER_STEP, i, f, t, v, bmx.INSERT_REFERENCE, applied=applied[0], n_applied=n_applied[nb:nb + 1])
-        stage_ms, ncalls = eng.profile_read()
-        extra = {}
-        if CONFIG == 2:
-            # same pass once more in the opt-in mode where the CALLER guarantees unique keys (no claim atomic, no resolve pass)
-            ubatches = [to_dev(gen_batch(nb + 40 + b, R_PER_GPU), dev) for b in range(min(K, 8))]
+        if args.full and not args.no_verify:
+            verified = verify_against_oracle(eng, [gen_batch(b, R_PER_GPU) for b in range(nb)], applied, n_applied[:nb], rid)   # the host stream: also checks gen_batch_dev
+        del rid
+
+        if args.full:
+            # second pass over fresh batches of the same shape: per-kernel HIP-event timing (live roofline figure)
+            pbatches = [to_dev(gen_batch(nb + b, R_PER_GPU), dev) for b in range(min(K, 12))]
             torch.cuda.synchronize()
             eng.profile_enable(True)
-            eng.sync(); eng.timer_start()
-            for (i, f, t, v) in ubatches:
-                eng.merge_batch_dev(D_PER_STEP, i, f, t, v, bmx.INSERT_REFERENCE | bmx.MERGE_UNIQUE_KEYS, applied=applied[0], n_applied=n_applied[nb:nb + 1])
-            ums = eng.timer_stop() / len(ubatches)
-            ustage_ms, _ = eng.profile_read()
-            extra["unique_keys_mode"] = {"note": "opt-in BMX_MERGE_UNIQUE_KEYS (caller guarantees no duplicate keys in the batch); not the headline",
-                                         "ms_per_step_with_event_brackets": round(ums, 5), "kernel_ms": {k: round(v, 5) for k, v in ustage_ms.items()}}
-        eng.profile_enable(False)
-        wavg = float(winners.mean()) if len(winners) else 0.0
-        # algorithmic bytes of one launch of the dominant kernel: delta read 28*D + resident row read 28*D
-        # + (ts,val) store of the winners 16*W. (The 4*W index write belongs to the compaction launches.)
-        alg_bytes = 56.0 * D_PER_STEP + 16.0 * wavg
-        probe_s = stage_ms["probe_apply"] * 1e-3
-        achieved = alg_bytes / probe_s / 1e9 if probe_s > 0 else 0.0
-        traffic = requests = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_probe_apply.json")
-        if os.path.exists(tpath) and CONFIG == 2 and main_kernel == "k_probe_apply":  # HBM bytes per launch from a committed rocprofv3 --pmc run of this same command
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get("bytes_per_launch")
-                requests = {"total": tj.get("requests_per_launch"), "reads": tj.get("read_requests"), "writes_incl_atomics": tj.get("write_requests"), "atomics": tj.get("atomic_requests")}
-            except Exception:
-                traffic = requests = None
-        roofline = {"bound": "hbm", "kernel": main_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "requests_per_launch": requests, "algorithmic_bytes_per_launch": alg_bytes,
-                    "kernel_ms": {k: round(v, 5) for k, v in stage_ms.items()}, "launches_averaged": ncalls,
-                    "whole_merge_achieved_GBs": round((56.0 * D_PER_STEP + 20.0 * wavg) / (elapsed / K) / 1e9, 1)}
+            for (i, f, t, v) in pbatches:
+                eng.merge_batch_dev(D_PER_STEP, i, f, t, v, bmx.INSERT_REFERENCE, applied=applied[0], n_applied=n_applied[nb:nb + 1])
+            stage_ms, ncalls = eng.profile_read()
+            if CONFIG == 2:
+                # same pass once more in the opt-in mode where the CALLER guarantees unique keys (no claim atomic, no resolve pass)
+                ubatches = [to_dev(gen_batch(nb + 40 + b, R_PER_GPU), dev) for b in range(min(K, 8))]
+                torch.cuda.synchronize()
+                eng.profile_enable(True)
+                eng.sync(); eng.timer_start()
+                for (i, f, t, v) in ubatches:
+                    eng.merge_batch_dev(D_PER_STEP, i, f, t, v, bmx.INSERT_REFERENCE | bmx.MERGE_UNIQUE_KEYS, applied=applied[0], n_applied=n_applied[nb:nb + 1])
+                ums = eng.timer_stop() / len(ubatches)
+                ustage_ms, _ = eng.profile_read()
+                extra["unique_keys_mode"] = {"note": "opt-in BMX_MERGE_UNIQUE_KEYS (caller guarantees no duplicate keys in the batch); not the headline",
+                                             "ms_per_step_with_event_brackets": round(ums, 5), "kernel_ms": {k: round(v, 5) for k, v in ustage_ms.items()}}
+            eng.profile_enable(False)
+            # algorithmic bytes of one launch of the dominant kernel: delta read 28*D + resident row read 28*D
+            # + (ts,val) store of the winners 16*W. (The 4*W index write belongs to the compaction launches.)
+            alg_bytes = 56.0 * D_PER_STEP + 16.0 * wavg
+            probe_s = stage_ms["probe_apply"] * 1e-3
+            achieved = alg_bytes / probe_s / 1e9 if probe_s > 0 else 0.0
+            traffic = requests = None
+            tpath = os.path.join(ROOT, "profiles", "traffic_probe_apply.json")
+            if os.path.exists(tpath) and CONFIG == 2 and main_kernel == "k_probe_apply":  # HBM bytes per launch from a committed rocprofv3 --pmc run of this same command
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get("bytes_per_launch")
+                    requests = {"total": tj.get("requests_per_launch"), "reads": tj.get("read_requests"), "writes_incl_atomics": tj.get("write_requests"), "atomics": tj.get("atomic_requests")}
+                except Exception:
+                    traffic = requests = None
+            roofline = {"bound": "hbm", "kernel": main_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "requests_per_launch": requests, "algorithmic_bytes_per_launch": alg_bytes,
+                        "kernel_ms": {k: round(v, 5) for k, v in stage_ms.items()}, "launches_averaged": ncalls,
+                        "whole_merge_achieved_GBs": round((56.0 * D_PER_STEP + 20.0 * wavg) / (elapsed / K) / 1e9, 1)}
         total_units = K * D_PER_STEP
         extra.update({"event_ms_per_step": round(ev_ms / K, 5), "host_enqueue_ms_per_step": round(t_enq / K * 1e3, 5), "winners_per_step": round(wavg, 1),
                       "table_placement": dict(eng.placement(), note="bmx_create allocates a large table several times and keeps the candidate on which the merge kernel's request mix (2^20 random slot reads + exchanges + stores) runs fastest: include/bmx.h bmx_get_placement"),
@@ -1002,9 +1102,16 @@ def main(argv=None):
         tmax = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-        say("timed region done: %.1f us per step here, %.1f max over ranks; verifying" % (wall / K * 1e6, elapsed / K * 1e6))
+        say("timed region done: %.1f us per step here, %.1f max over ranks" % (wall / K * 1e6, elapsed / K * 1e6))
         total_units = K * D_PER_STEP * world
-        if not args.no_verify and world * nb <= 256:
+        if args.dump_outputs and rank == 0:
+            # rank 0's shard after the last step: the rows it holds for a seeded sample of the keys that it owns in its own last batch
+            from bmx import synth
+            ids, flds, _, _ = gen_batch(nb - 1, R_global, seed=2 + 1000 * rank, part=(rank, world))
+            mine = synth.owner_of_np(ids, world) == rank
+            ts_s, val_s, found_s = eng.get_rows(*row_sample(ids[mine], flds[mine]))
+            dump_outputs(args.dump_outputs, {"row_sample_ts": ts_s, "row_sample_val": val_s, "row_sample_found": found_s})
+        if args.full and not args.no_verify and world * nb <= 256:
             # every rank replays, through the CPU oracle, the deltas of ALL originators that it owns (same generator, same order:
             # step by step, originators in rank order) and compares its shard's row count and digest
             from oracle.oracle import Oracle, rows_digest
@@ -1025,33 +1132,34 @@ def main(argv=None):
             verified = {"against": "oracle/bmx_oracle.c: every rank replays the deltas it owns (all originators, step order) and compares its shard's row count and digest",
                         "batches": nb * world, "rows_this_rank": len(o), "ok": True, "per_rank": per_rank, "seconds": round(time.perf_counter() - tv, 2)}
             o.close()
-        # second pass (every rank, same number of collectives): a few more steps with the per-kernel HIP-event brackets on, for this
-        # rank's live k_probe_apply figure. The brackets are event records, i.e. stream bubbles: never part of the timed region.
-        npro = min(K, 8)
-        pb = [to_dev(gen_batch(nb + b, R_global, seed=2 + 1000 * rank, part=(rank, world)), dev) for b in range(npro)]
-        torch.cuda.synchronize()
-        eng.profile_enable(True)
-        won = []
-        for b in range(npro):
-            p = sg.merge(sg.route(D_PER_STEP, *pb[b]))
-            sg.ops.sync()
-            won.append(int(p["n_applied"].cpu()[0]))
-        stage_ms, ncalls = eng.profile_read()
-        eng.profile_enable(False)
-        wavg = float(np.mean(won)) if won else 0.0
-        alg_bytes = 56.0 * D_PER_STEP + 16.0 * wavg         # same accounting as the N=1 line; padding records move no row bytes
-        probe_s = stage_ms["probe_apply"] * 1e-3
-        achieved = alg_bytes / probe_s / 1e9 if probe_s > 0 else 0.0
-        traffic = None
-        try:      # the same kernel on the same 1M-record batch shape: HBM bytes per launch of the committed rocprofv3 --pmc passes over the N=1 run
-            traffic = json.load(open(os.path.join(ROOT, "profiles", "traffic_probe_apply.json"))).get("bytes_per_launch")
-        except Exception:
+        if args.full:
+            # second pass (every rank, same number of collectives): a few more steps with the per-kernel HIP-event brackets on, for this
+            # rank's live k_probe_apply figure. The brackets are event records, i.e. stream bubbles: never part of the timed region.
+            npro = min(K, 8)
+            pb = [to_dev(gen_batch(nb + b, R_global, seed=2 + 1000 * rank, part=(rank, world)), dev) for b in range(npro)]
+            torch.cuda.synchronize()
+            eng.profile_enable(True)
+            won = []
+            for b in range(npro):
+                p = sg.merge(sg.route(D_PER_STEP, *pb[b]))
+                sg.ops.sync()
+                won.append(int(p["n_applied"].cpu()[0]))
+            stage_ms, ncalls = eng.profile_read()
+            eng.profile_enable(False)
+            wavg = float(np.mean(won)) if won else 0.0
+            alg_bytes = 56.0 * D_PER_STEP + 16.0 * wavg         # same accounting as the N=1 line; padding records move no row bytes
+            probe_s = stage_ms["probe_apply"] * 1e-3
+            achieved = alg_bytes / probe_s / 1e9 if probe_s > 0 else 0.0
             traffic = None
-        roofline = {"bound": "hbm", "kernel": main_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "algorithmic_bytes_per_launch": alg_bytes,
-                    "kernel_ms": {k: round(v, 5) for k, v in stage_ms.items()}, "launches_averaged": ncalls,
-                    "traffic_source": "profiles/traffic_probe_apply.json: PMC passes over the N=1 run of this kernel (config 2, SoA columns), not re-collected per rank",
-                    "note": "rank 0, launches without a concurrent exchange (second pass, per-kernel HIP events on the merge stream)"}
+            try:      # the same kernel on the same 1M-record batch shape: HBM bytes per launch of the committed rocprofv3 --pmc passes over the N=1 run
+                traffic = json.load(open(os.path.join(ROOT, "profiles", "traffic_probe_apply.json"))).get("bytes_per_launch")
+            except Exception:
+                traffic = None
+            roofline = {"bound": "hbm", "kernel": main_kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "algorithmic_bytes_per_launch": alg_bytes,
+                        "kernel_ms": {k: round(v, 5) for k, v in stage_ms.items()}, "launches_averaged": ncalls,
+                        "traffic_source": "profiles/traffic_probe_apply.json: PMC passes over the N=1 run of this kernel (config 2, SoA columns), not re-collected per rank",
+                        "note": "rank 0, launches without a concurrent exchange (second pass, per-kernel HIP events on the merge stream)"}
         how = ("direct: the owner partition of batch b+1 stores every slab straight into its owner's IPC-mapped receive memory (peer stores over xGMI) and sets arrival words; no collective, one stream"
                if sg.exchange == "direct" else "rccl: partition + ONE all-to-all of batch b+1 on a second stream under the merge of batch b")
         if sg.exchange != "direct" and refused_why is None:
@@ -1070,12 +1178,12 @@ def main(argv=None):
                "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
                "data": "synthetic", "config": cfg, "roofline": roofline, "verified": verified}
         out.update(extra)
-        if not sharded and not args.no_scan:
+        if args.full and not sharded and not args.no_scan:
             out["scan_config3"] = {}
             for rs in [int(x) for x in args.scan_rows.split(",") if x]:
                 out["scan_config3"]["%dM" % (rs // 1_000_000)] = scan_bench(bmx, dev, R=rs)
                 out["scan_config3"]["%dM_int64" % (rs // 1_000_000)] = scan_bench(bmx, dev, R=rs, wide=True)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if not sharded:
                 out["js_host"] = js_host_rate()
                 out["cpu_baseline"] = cpu_baseline()

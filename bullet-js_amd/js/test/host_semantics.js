@@ -2,7 +2,7 @@
 /*
  * host_semantics.js — CPU-only test of GpuCRT's single-operation path and GpuQuery's host-side behaviour against
  * golden vectors produced by the real reference (tests/golden/g1, g3, g4, g5_query_example).
- * If a reference checkout is available ($BULLET_REF or /root/reference) the same scripts are also replayed
+ * If $BULLET_REF names a reference checkout, the same scripts are also replayed
  * through the REAL Bullet facade with GpuCRT plugged in at the disableCRT seam.
  * Usage: node host_semantics.js <golden dir>
  */
@@ -174,8 +174,8 @@ batchApplyCase(() => new MiniBullet("w"), "mini 2500", 2500);     // more winner
 }
 
 /* With the real reference present: plug into the real Bullet at its two seams */
-const REF = process.env.BULLET_REF || "/root/reference";
-if (fs.existsSync(path.join(REF, "src", "bullet.js"))) {
+const REF = process.env.BULLET_REF;
+if (REF && fs.existsSync(path.join(REF, "src", "bullet.js"))) {
   const Bullet = require(path.join(REF, "src", "bullet.js"));
   const quiet = (fn) => { const l = console.log; console.log = () => {}; try { return fn(); } finally { console.log = l; } };
   const mk = (withQuery) => quiet(() => {

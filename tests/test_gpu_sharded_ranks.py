@@ -58,7 +58,7 @@ def test_a_rank_that_fails_in_the_direct_exchange_sends_every_rank_to_the_fallba
     env[hook] = "1"
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--rank-timeout", "500"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--rank-timeout", "500", "--full"],
                        capture_output=True, text=True, timeout=560, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     assert len(r.stdout.strip().splitlines()) == 1 and len(r.stdout) < 4096
@@ -79,7 +79,7 @@ def test_one_rank_per_physical_gpu_bench_verifies_itself(world):
         pytest.skip("needs %d GPUs" % world)
     root = os.path.dirname(HERE)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
