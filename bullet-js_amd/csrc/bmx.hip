@@ -11,6 +11,7 @@
 #include <cstring>
 #include <thread>
 #include <deque>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -48,17 +49,9 @@ struct DevScalars {  // one small device allocation; zeroed at create
   unsigned long long seqw[2];      // deferred compaction: [0] = number of the latest probe kernel that has started, [1] = of the latest compaction finished on the side stream
 };
 
-struct Index {
-  uint32_t field = 0;
-  uint64_t n = 0, cap = 0;
-  uint64_t* ids = nullptr;
-  int64_t* v64 = nullptr;
-  int32_t* v32 = nullptr;
-  bool fits32 = false;
-  uint64_t version = ~0ull;  // table version it was built from
-  bool has_pos = false;      // its rows' positions are in ctx->slot_pos (it can be maintained from the change log)
-  uint64_t content = 0;      // counts the refreshes that really changed something in the columns (a value, a new row, a rebuild)
-  // value-ordered view (bmx.h bmx_index_set_ordered): the columns once more, sorted by (value, position)
+// The value-ordered view of one index (bmx.h bmx_index_set_ordered): the columns once more, sorted by (value, position), and kept current under writes.
+// Its code is bmx_view.inc and ensure_ordered_view. Copied with its Index (ctx->indexes is a vector): no destructor, release() gives the buffers back.
+struct OrderedView {
   uint32_t ordered_after = 0;     // 0 = off; N: a stale view is sorted again by the N-th query since the columns last changed
   uint32_t stale_queries = 0;     // queries answered by the column scan since the columns last CHANGED (not: since the last sort)
   uint64_t stale_content = ~0ull; // the `content` value that count belongs to: a new change starts it again
@@ -84,34 +77,33 @@ struct Index {
   // the rewrite of main (main - pd + pi -> the second set of columns) runs BEHIND the answer of the query that found it due: in flight until its event has completed
   // and its error word has been looked at; until then (main, pd, pi) go on answering
   bool rewrite_due = false, rewrite_inflight = false; uint64_t rewrite_nz = 0;
+  void release_pending();   // the pending patch's buffers; the patch is empty and no rewrite is due or in flight
+  void release();           // every buffer (the pending patch's too): the view is stale until sorted again
 };
-void free_pending(Index& ix) {
-  for (int i = 0; i < 2; i++) {
-    if (ix.pd_v[i]) (void)hipFree(ix.pd_v[i]); if (ix.pd_p[i]) (void)hipFree(ix.pd_p[i]);
-    if (ix.pi_v[i]) (void)hipFree(ix.pi_v[i]); if (ix.pi_p[i]) (void)hipFree(ix.pi_p[i]); if (ix.pi_ids[i]) (void)hipFree(ix.pi_ids[i]);
-    ix.pd_v[i] = nullptr; ix.pd_p[i] = nullptr; ix.pi_v[i] = nullptr; ix.pi_p[i] = nullptr; ix.pi_ids[i] = nullptr;
-  }
-  if (ix.pi_dead) (void)hipFree(ix.pi_dead);
-  ix.pi_dead = nullptr;
-  ix.npd = ix.npi = 0; ix.pend_cap = 0; ix.pcur = 0; ix.icur = 0; ix.rewrite_due = false; ix.rewrite_inflight = false;
-}
-void free_ordered_view(Index& ix) {
-  free_pending(ix);
-  if (ix.s_val) (void)hipFree(ix.s_val);
-  if (ix.s_pos) (void)hipFree(ix.s_pos);
-  if (ix.s_ids) (void)hipFree(ix.s_ids);
-  if (ix.s_val2) (void)hipFree(ix.s_val2);
-  if (ix.s_pos2) (void)hipFree(ix.s_pos2);
-  if (ix.s_ids2) (void)hipFree(ix.s_ids2);
-  if (ix.cl_pos) (void)hipFree(ix.cl_pos);
-  if (ix.cl_old) (void)hipFree(ix.cl_old);
-  if (ix.cl2_pos) (void)hipFree(ix.cl2_pos);
-  if (ix.cl2_old) (void)hipFree(ix.cl2_old);
-  ix.cl2_pos = nullptr; ix.cl2_old = nullptr;
-  ix.s_val = nullptr; ix.s_pos = nullptr; ix.s_ids = nullptr; ix.ord_cap = 0; ix.ord_n = 0; ix.ord_content = ~0ull;
-  ix.s_val2 = nullptr; ix.s_pos2 = nullptr; ix.s_ids2 = nullptr; ix.ord_cap2 = 0;
-  ix.cl_pos = nullptr; ix.cl_old = nullptr; ix.cl_cap = 0;
-}
+struct Index {
+  uint32_t field = 0;
+  uint64_t n = 0, cap = 0;
+  uint64_t* ids = nullptr; int64_t* v64 = nullptr; int32_t* v32 = nullptr;   // the columns (free_columns)
+  bool fits32 = false;
+  uint64_t version = ~0ull;  // table version it was built from
+  bool has_pos = false;      // its rows' positions are in ctx->slot_pos (it can be maintained from the change log)
+  uint64_t content = 0;      // counts the refreshes that really changed something in the columns (a value, a new row, a rebuild)
+  OrderedView view;
+};
+// What the views of one context share (bmx_view.inc).
+struct ViewShared {
+  // sort scratch of the view patches (view_kernels.h): two key arrays (value 8 B, position 4 B) the merge sort ping-pongs between
+  void* vk_v[2] = {nullptr, nullptr}; uint32_t* vk_p[2] = {nullptr, nullptr}; uint64_t vk_cap = 0;
+  void* vk_sv = nullptr; uint32_t* vk_sp = nullptr; uint32_t* vk_d0 = nullptr; uint32_t* vk_y0 = nullptr; uint64_t vk_tiles_cap = 0;   // per tile of the view: its first key (the sample), deleted indices / inserted keys in front of it
+  uint32_t* err_host = nullptr; hipEvent_t ev = nullptr;      // a background rewrite's error word (page-locked host memory) and completion event
+  bool patching = true;           // BMX_VIEW_PATCH=0: a change makes the view stale as in round 4 (A/B switch)
+  int test_fail = 0;              // BMX_TEST_VIEW_FAIL (test hook): 1 = every patch reports failure (the view goes stale), 2 = every background rewrite reports failure (main + patch go on answering)
+  bool own_sort = false;          // BMX_VIEW_SORT=own: a new view is sorted by the patch path's own kernels (tile sort + merge passes) instead of rocPRIM's radix sort (A/B switch)
+  bool pending = true;            // BMX_VIEW_PENDING=0: every patch rewrites the view's main run at once (no pending patch; A/B switch)
+  bool debug = false;             // BMX_VIEW_DEBUG: diagnostic prints to stderr (patches given up, rewrite and refresh timings)
+  void read_env();                // the switches above, at create
+  void release();
+};
 
 thread_local std::string g_err;
 constexpr uint32_t PROF_MAX_CALLS = 64;
@@ -195,15 +187,8 @@ struct bmx_ctx {
   uint2* chg = nullptr; uint64_t chg_cap = 0, chg_ub = 0;
   bool chg_valid = false; uint32_t chg_par = 0;
   uint64_t ix_full_builds = 0, ix_incremental = 0;
-  // sort scratch of the view patches (view_kernels.h): two key arrays (value 8 B, position 4 B) the merge sort ping-pongs between
-  void* vk_v[2] = {nullptr, nullptr}; uint32_t* vk_p[2] = {nullptr, nullptr}; uint64_t vk_cap = 0;
-  void* vk_sv = nullptr; uint32_t* vk_sp = nullptr; uint32_t* vk_d0 = nullptr; uint32_t* vk_y0 = nullptr; uint64_t vk_tiles_cap = 0;   // per tile of the view: its first key (the sample), deleted indices / inserted keys in front of it
-  bool view_patching = true;          // BMX_VIEW_PATCH=0 in the environment: a change makes the view stale as in round 4 (A/B switch)
+  ViewShared view;                    // what the indexes' value-ordered views share
   volatile unsigned long long* hres = nullptr;                            // mapped page-locked result words (HRES_*): counts the host waits for arrive without a download
-  uint32_t* view_err_host = nullptr; hipEvent_t view_ev = nullptr;      // a background rewrite's error word (page-locked host memory) and completion event
-  int view_test_fail = 0;             // BMX_TEST_VIEW_FAIL (test hook): 1 = every patch reports failure (the view goes stale), 2 = every background rewrite reports failure (main + patch go on answering)
-  bool view_own_sort = false;         // BMX_VIEW_SORT=own: a new view is sorted by the patch path's own kernels (tile sort + merge passes) instead of rocPRIM's radix sort (A/B switch)
-  bool view_pending = true;           // BMX_VIEW_PENDING=0: every patch rewrites the view's main run at once (no pending patch; A/B switch)
   // bmx_merge_notify: words (possibly in other GPUs' memory) that every merge's last workgroup sets to the number of merges finished since
   SeqPtrs notify{}; uint32_t n_notify = 0; uint64_t notify_seq = 0;
   // bmx_merge_tail_wait: armed = the next default-path merge's resolve kernel polls these words before it ends; waited = a resolve kernel that did so has
@@ -272,6 +257,7 @@ void dev_free(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
+void free_columns(Index& ix) { dev_free(ix.ids); dev_free(ix.v64); dev_free(ix.v32); ix.cap = 0; }
 
 // Pull the sticky device status; translate to an error code.
 int check_status(bmx_ctx* ctx) {
@@ -930,8 +916,7 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   HIPCHK(hipMemcpyAsync(&n, &ctx->ds->n_out, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (n + (n >> 4) + (1u << 16) > ix->cap) {   // too little head room left for appended rows: a new set of columns
-    dev_free(ix->ids); dev_free(ix->v64); dev_free(ix->v32);
-    ix->cap = 0;
+    free_columns(*ix);
     uint64_t cap = (n + n / 8 + (1u << 16) + 1023) & ~1023ull;   // head room: rows created later are appended
     int rc;
     if ((rc = dev_alloc(ctx, &ix->ids, cap)) || (rc = dev_alloc(ctx, &ix->v64, cap)) || (rc = dev_alloc(ctx, &ix->v32, cap + 4))) return rc;
@@ -961,284 +946,12 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   return BMX_OK;
 }
 
-// ---- the value-ordered view kept current (view_kernels.h) ----
-constexpr uint64_t VIEW_PATCH_MAX_LOG = 1ull << 24;     // a longer change log is not captured: the view goes stale and is sorted again (a sort of 10^8 rows costs less than a patch that large)
-int ensure_view_scratch(bmx_ctx* ctx, uint64_t keys, uint64_t tiles) {
-  if (keys > ctx->vk_cap) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; i++) { if (ctx->vk_v[i]) (void)hipFree(ctx->vk_v[i]); ctx->vk_v[i] = nullptr; dev_free(ctx->vk_p[i]); }
-    ctx->vk_cap = 0;
-    const uint64_t cap = (keys + keys / 4 + (1u << 16) + 255) & ~255ull;
-    for (int i = 0; i < 2; i++) {
-      if (hipMalloc(&ctx->vk_v[i], cap * 8) != hipSuccess) { (void)hipGetLastError(); ctx->vk_v[i] = nullptr; return fail(ctx, BMX_ERR_NOMEM, "view patch: out of device memory"); }
-      if (int rc = dev_alloc(ctx, &ctx->vk_p[i], cap)) return rc;
-    }
-    ctx->vk_cap = cap;
-  }
-  if (tiles + 1 > ctx->vk_tiles_cap) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (ctx->vk_sv) (void)hipFree(ctx->vk_sv); ctx->vk_sv = nullptr; dev_free(ctx->vk_sp); dev_free(ctx->vk_d0); dev_free(ctx->vk_y0); ctx->vk_tiles_cap = 0;
-    const uint64_t cap = tiles + tiles / 4 + 1024;
-    if (hipMalloc(&ctx->vk_sv, cap * 8) != hipSuccess) { (void)hipGetLastError(); ctx->vk_sv = nullptr; return fail(ctx, BMX_ERR_NOMEM, "view patch: out of device memory"); }
-    int rc;
-    if ((rc = dev_alloc(ctx, &ctx->vk_sp, cap)) || (rc = dev_alloc(ctx, &ctx->vk_d0, cap)) || (rc = dev_alloc(ctx, &ctx->vk_y0, cap))) return rc;
-    ctx->vk_tiles_cap = cap;
-  }
-  return BMX_OK;
-}
-// Z = (X without the sorted keys D, all of which are keys of X) merged with the sorted keys Y — k_view_merge over the tiles of X, with its sample and tile offsets
-// in the context's scratch. X may be empty (then D is, and Z = Y). Enqueue only; a deleted key that is not in X raises ds->view_err.
-template <class T, bool HAS_IDS>
-void launch_run_merge(bmx_ctx* ctx, ViewRun<T> X, uint64_t nx, const T* dv, const uint32_t* dp, uint64_t nd, const T* yv, const uint32_t* yp, uint64_t ny, const uint64_t* ix_ids, ViewRun<T> Z) {
-  hipStream_t st = ctx->stream;
-  if (nx == 0) {
-    if (ny) {
-      (void)hipMemcpyAsync(Z.v, yv, ny * sizeof(T), hipMemcpyDeviceToDevice, st); (void)hipMemcpyAsync(Z.p, yp, ny * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-      if (HAS_IDS) hipLaunchKernelGGL(k_view_gather_ids, dim3((uint32_t)std::min<uint64_t>((ny + 255) / 256, 4096)), dim3(256), 0, st, yp, (uint32_t)ny, ix_ids, Z.ids);
-    }
-    return;
-  }
-  const uint32_t ntiles = (uint32_t)((nx + VIEW_TILE - 1) / VIEW_TILE);
-  T* sv = static_cast<T*>(ctx->vk_sv);
-  hipLaunchKernelGGL((k_view_sample<T>), dim3((ntiles + 255) / 256), dim3(256), 0, st, (const T*)X.v, (const uint32_t*)X.p, ntiles, sv, ctx->vk_sp);
-  hipLaunchKernelGGL((k_view_tile_offsets<T>), dim3((ntiles + 1 + 255) / 256), dim3(256), 0, st, (const T*)sv, (const uint32_t*)ctx->vk_sp, ntiles, dv, dp, (uint32_t)nd, yv, yp, (uint32_t)ny, ctx->vk_d0, ctx->vk_y0);
-  hipLaunchKernelGGL((k_view_merge<T, HAS_IDS>), dim3(ntiles), dim3(256), 0, st, X, (uint32_t)nx, dv, dp, yv, yp, ix_ids, Z, (const uint32_t*)ctx->vk_d0, (const uint32_t*)ctx->vk_y0, &ctx->ds->view_err);
-}
-// the pending patch's buffers for at least `need` keys in each run (what is there is kept)
-template <class T>
-int ensure_pending(bmx_ctx* ctx, Index& ix, uint64_t need) {
-  if (need <= ix.pend_cap) return BMX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint64_t cap = need + need / 8 + (1u << 16);
-  void* nv[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint32_t* np[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint64_t* ni[2] = {nullptr, nullptr};
-  uint8_t* nd = nullptr;
-  bool ok = hipMalloc(reinterpret_cast<void**>(&nd), cap) == hipSuccess;
-  for (int i = 0; i < 2 && ok; i++)
-    ok = hipMalloc(&nv[0][i], cap * sizeof(T)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&np[0][i]), cap * 4) == hipSuccess && hipMalloc(&nv[1][i], cap * sizeof(T)) == hipSuccess &&
-         hipMalloc(reinterpret_cast<void**>(&np[1][i]), cap * 4) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&ni[i]), cap * 8) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (int i = 0; i < 2; i++) { for (int k = 0; k < 2; k++) { if (nv[k][i]) (void)hipFree(nv[k][i]); if (np[k][i]) (void)hipFree(np[k][i]); } if (ni[i]) (void)hipFree(ni[i]); }
-    if (nd) (void)hipFree(nd);
-    return fail(ctx, BMX_ERR_NOMEM, "view patch: out of device memory");
-  }
-  const int c = ix.pcur, ci = ix.icur;
-  if (ix.npd) { HIPCHK(hipMemcpy(nv[0][c], ix.pd_v[c], ix.npd * sizeof(T), hipMemcpyDeviceToDevice)); HIPCHK(hipMemcpy(np[0][c], ix.pd_p[c], ix.npd * 4, hipMemcpyDeviceToDevice)); }
-  if (ix.npi) { HIPCHK(hipMemcpy(nv[1][ci], ix.pi_v[ci], ix.npi * sizeof(T), hipMemcpyDeviceToDevice)); HIPCHK(hipMemcpy(np[1][ci], ix.pi_p[ci], ix.npi * 4, hipMemcpyDeviceToDevice));
-                HIPCHK(hipMemcpy(ni[ci], ix.pi_ids[ci], ix.npi * 8, hipMemcpyDeviceToDevice)); }
-  const uint64_t kd = ix.npd, ki = ix.npi; const bool due = ix.rewrite_due;
-  free_pending(ix);
-  for (int i = 0; i < 2; i++) { ix.pd_v[i] = nv[0][i]; ix.pd_p[i] = np[0][i]; ix.pi_v[i] = nv[1][i]; ix.pi_p[i] = np[1][i]; ix.pi_ids[i] = ni[i]; }
-  ix.pi_dead = nd;
-  ix.npd = kd; ix.npi = ki; ix.pend_cap = cap; ix.pcur = c; ix.icur = ci; ix.rewrite_due = due;
-  return BMX_OK;
-}
-// the second set of the view's columns, for `nz` rows
-template <class T>
-bool ensure_view_spare(bmx_ctx* ctx, Index& ix, uint64_t nz) {
-  if (nz <= ix.ord_cap2 && ix.s_val2) return true;
-  if (ix.s_val2) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ix.s_val2); (void)hipFree(ix.s_pos2); (void)hipFree(ix.s_ids2); }
-  ix.s_val2 = nullptr; ix.s_pos2 = nullptr; ix.s_ids2 = nullptr; ix.ord_cap2 = 0;
-  const uint64_t cap = std::max<uint64_t>(ix.ord_cap, nz + nz / 8 + 1024);
-  if (hipMalloc(&ix.s_val2, cap * sizeof(T)) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&ix.s_pos2), cap * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ix.s_ids2), cap * sizeof(uint64_t)) != hipSuccess) {
-    (void)hipGetLastError();
-    if (ix.s_val2) (void)hipFree(ix.s_val2); if (ix.s_pos2) (void)hipFree(ix.s_pos2); if (ix.s_ids2) (void)hipFree(ix.s_ids2);
-    ix.s_val2 = nullptr; ix.s_pos2 = nullptr; ix.s_ids2 = nullptr;
-    return false;
-  }
-  ix.ord_cap2 = cap;
-  return true;
-}
-// ---- the rewrite of a view's main run, behind the answer ----
-// finish_rewrite: a rewrite in flight whose event has completed (wait = true: wait for it) is looked at: error word 0 -> the second set of columns becomes main and the
-// pending patch is empty; otherwise main and the patch stay what they are (they were never touched).
-template <class T>
-void finish_rewrite(bmx_ctx* ctx, Index& ix, bool wait) {
-  if (!ix.rewrite_inflight) return;
-  if (wait) (void)hipEventSynchronize(ctx->view_ev);
-  else if (hipEventQuery(ctx->view_ev) != hipSuccess) { (void)hipGetLastError(); return; }
-  ix.rewrite_inflight = false;
-  if (*ctx->view_err_host == 0 && ctx->view_test_fail != 2) {
-    std::swap(ix.s_val, ix.s_val2); std::swap(ix.s_pos, ix.s_pos2); std::swap(ix.s_ids, ix.s_ids2); std::swap(ix.ord_cap, ix.ord_cap2);
-    ix.ord_n = ix.rewrite_nz; ix.npd = ix.npi = 0; ix.ord_merges++;
-  }
-}
-// start_rewrite: enqueue main - pd + pi -> the second set of columns, then the copy of the error word and the event. Nothing waits.
-template <class T>
-void start_rewrite(bmx_ctx* ctx, Index& ix) {
-  ix.rewrite_due = false;
-  if (ix.rewrite_inflight || ix.npd + ix.npi == 0 || ix.npd > ix.ord_n) return;
-  if (!ctx->view_err_host && hipHostMalloc(reinterpret_cast<void**>(&ctx->view_err_host), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->view_err_host = nullptr; return; }
-  if (!ctx->view_ev && hipEventCreateWithFlags(&ctx->view_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ctx->view_ev = nullptr; return; }
-  for (auto& o : ctx->indexes) if (o.rewrite_inflight) return;                 // one at a time: they share the error word and the event
-  const uint64_t nz = ix.ord_n - ix.npd + ix.npi;
-  const uint32_t ntiles = (uint32_t)((ix.ord_n + VIEW_TILE - 1) / VIEW_TILE);
-  if (ntiles + 1 > ctx->vk_tiles_cap || !ensure_view_spare<T>(ctx, ix, nz)) return;
-  const int q = ix.pcur, qi = ix.icur;
-  (void)hipMemsetAsync(&ctx->ds->view_err, 0, sizeof(uint32_t), ctx->stream);
-  ViewRun<T> X{static_cast<T*>(ix.s_val), ix.s_pos, ix.s_ids}, Z{static_cast<T*>(ix.s_val2), ix.s_pos2, ix.s_ids2};
-  launch_run_merge<T, true>(ctx, X, ix.ord_n, static_cast<const T*>(ix.pd_v[q]), ix.pd_p[q], ix.npd, static_cast<const T*>(ix.pi_v[qi]), ix.pi_p[qi], ix.npi, (const uint64_t*)ix.ids, Z);
-  *ctx->view_err_host = 1u;                                                       // (overwritten by the copy below: an event that somehow completed without it reads as a failure)
-  if (hipMemcpyAsync(ctx->view_err_host, &ctx->ds->view_err, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipEventRecord(ctx->view_ev, ctx->stream) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->stream); return;    // nothing was swapped: main and the patch go on answering
-  }
-  ix.rewrite_inflight = true; ix.rewrite_nz = nz;
-}
-void view_after_query(bmx_ctx* ctx, Index* ix) {         // behind the answer of an ordered query
-  if (!ix->rewrite_due) return;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (ix->ord_fits32) start_rewrite<int32_t>(ctx, *ix); else start_rewrite<int64_t>(ctx, *ix);
-  if (std::getenv("BMX_VIEW_DEBUG")) std::fprintf(stderr, "bmx: rewrite enqueued in %.1f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-}
-void view_before_use(bmx_ctx* ctx, Index* ix, bool wait) {   // in front of anything that reads or changes the view
-  if (!ix->rewrite_inflight) return;
-  if (ix->ord_fits32) finish_rewrite<int32_t>(ctx, *ix, wait); else finish_rewrite<int64_t>(ctx, *ix, wait);
-}
-
-// Patch the view of `ix` with the change run k_ix_update captured (c changed rows: ix.cl2_pos / ix.cl2_old) and the rows appended at positions [n0, n0 + added).
-// 0 = the (logical) view equals a fresh sort of the columns again; 1 = it could not be patched (no memory, or a deleted key was not where it should be): the caller
-// leaves it stale and the next queries scan / re-sort as ever. Synchronous at its end (one or two words come back).
-//   1. the run's deleted keys (old value, position) and inserted keys (value, position) are sorted;
-//   2. they join the view's PENDING patch (pd, pi): a deleted key that is a pending inserted key cancels it, the others are deleted keys of main; the inserted keys are
-//      merged into pi. All on runs of a few million keys: L2 / Infinity-Cache traffic;
-//   3. once the pending patch holds more than ord_n / 16 keys, main is rewritten BEHIND the answer of the query that brought the refresh about: one streaming pass,
-//      main - pd + pi (start_rewrite / finish_rewrite). Only a run of more than ord_n / 4 keys is merged into main at once, in front of the answer.
-// A 1M-delta merge into a 10^8-row index: steps 1-2 on every refresh, step 3 behind every fourth; into a 10^7-row index: step 3 behind every answer.
-template <class T>
-int patch_view_t(bmx_ctx* ctx, Index& ix, uint64_t c, uint64_t n0, uint64_t added) {
-  const auto t0 = std::chrono::steady_clock::now();
-  if (ctx->view_test_fail == 1) return 1;
-  finish_rewrite<T>(ctx, ix, /*wait=*/true);            // a rewrite still in flight is looked at first: the change run's keys are keys of the view as it is NOW
-  const uint64_t m = c + added, ktot = c + m, nx = ix.ord_n;
-  if (nx + m >= 0xFFFFFFFFull || ktot >= 0xFFFFFFFFull) return 1;
-  auto soft = [&](int line) {
-    if (std::getenv("BMX_VIEW_DEBUG")) std::fprintf(stderr, "bmx: view patch of field %u gave up (bmx.hip:%d): %s\n", ix.field, line, ctx->err.c_str());
-    g_err.clear(); ctx->err.clear(); (void)hipGetLastError(); return 1;
-  };
-  const uint64_t thr = std::max<uint64_t>(nx / 16, 1u << 16);                 // a pending patch beyond this many keys makes a rewrite of main due (behind the answer)
-  const uint64_t thr_direct = std::max<uint64_t>(nx / 4, 1u << 16);          // a run beyond this many keys is merged into main at once, in front of the answer
-  const uint32_t ntiles_main = (uint32_t)((nx + VIEW_TILE - 1) / VIEW_TILE);
-  if (!ensure_hres(ctx) || ensure_view_scratch(ctx, ktot, std::max<uint64_t>(ntiles_main, (ix.npi + ix.npd + VIEW_TILE) / VIEW_TILE + 2))) return soft(__LINE__);
-  hipStream_t st = ctx->stream;
-  T* kv[2] = {static_cast<T*>(ctx->vk_v[0]), static_cast<T*>(ctx->vk_v[1])};
-  uint32_t* kp[2] = {ctx->vk_p[0], ctx->vk_p[1]};
-  const T* col = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix.v32) : reinterpret_cast<const T*>(ix.v64);
-  hipLaunchKernelGGL((k_view_keys<T>), dim3((uint32_t)std::min<uint64_t>((ktot + 255) / 256, 4096)), dim3(256), 0, st, (const uint32_t*)ix.cl2_pos, (const int64_t*)ix.cl2_old, (uint32_t)c, col,
-                     (uint32_t)n0, (uint32_t)added, kv[0], kp[0]);
-  // 1. sort the deleted keys [0, c) and the inserted keys [c, c + m): tiles in LDS, then merge-path passes
-  ViewSegs S{}; S.base[0] = 0; S.len[0] = (uint32_t)c; S.base[1] = (uint32_t)c; S.len[1] = (uint32_t)m;
-  const uint32_t t0b = (uint32_t)((c + VIEW_SORT_TILE - 1) / VIEW_SORT_TILE), t1b = (uint32_t)((m + VIEW_SORT_TILE - 1) / VIEW_SORT_TILE);
-  S.blk0[0] = 0; S.blk0[1] = t0b; S.blk0[2] = t0b + t1b;
-  hipLaunchKernelGGL((k_view_tile_sort<T>), dim3(t0b + t1b), dim3(VIEW_SORT_THREADS), 0, st, (const T*)kv[0], (const uint32_t*)kp[0], kv[1], kp[1], S);
-  int cur = 1;
-  ViewSegs P = S; P.blk0[1] = (uint32_t)((c + VIEW_PASS_KEYS - 1) / VIEW_PASS_KEYS); P.blk0[2] = P.blk0[1] + (uint32_t)((m + VIEW_PASS_KEYS - 1) / VIEW_PASS_KEYS);
-  for (uint64_t L = VIEW_SORT_TILE; L < std::max<uint64_t>(c, m); L *= 2) {
-    hipLaunchKernelGGL((k_view_merge_pass<T>), dim3(P.blk0[2]), dim3(256), 0, st, (const T*)kv[cur], (const uint32_t*)kp[cur], kv[cur ^ 1], kp[cur ^ 1], P, (uint32_t)L);
-    cur ^= 1;
-  }
-  const T* Dv = kv[cur]; const uint32_t* Dp = kp[cur]; const T* Iv = kv[cur] + c; const uint32_t* Ip = kp[cur] + c;
-  (void)hipMemsetAsync(&ctx->ds->view_err, 0, sizeof(uint32_t), st);
-  ViewRun<T> X{static_cast<T*>(ix.s_val), ix.s_pos, ix.s_ids};
-  auto finish = [&]() -> int {       // the error word comes back; 0 = everything enqueued above did what it should
-    hipError_t e = hipGetLastError();
-    ctx->hres[HRES_ERR] = 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<unsigned long long*>(&ctx->hres[HRES_ERR]), &ctx->ds->view_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return (e != hipSuccess || (uint32_t)ctx->hres[HRES_ERR]) ? 1 : 0;
-  };
-  auto rewrite_main = [&](const T* dv, const uint32_t* dp, uint64_t nd, const T* yv, const uint32_t* yp, uint64_t ny) -> bool {   // step 3
-    const uint64_t nz = nx - nd + ny;
-    if (!ensure_view_spare<T>(ctx, ix, nz)) return false;
-    ViewRun<T> Z{static_cast<T*>(ix.s_val2), ix.s_pos2, ix.s_ids2};
-    launch_run_merge<T, true>(ctx, X, nx, dv, dp, nd, yv, yp, ny, (const uint64_t*)ix.ids, Z);
-    if (finish()) return false;
-    std::swap(ix.s_val, ix.s_val2); std::swap(ix.s_pos, ix.s_pos2); std::swap(ix.s_ids, ix.s_ids2); std::swap(ix.ord_cap, ix.ord_cap2);
-    ix.ord_n = nz; ix.ord_merges++;
-    return true;
-  };
-  const bool have = ix.npd + ix.npi > 0;
-  if (!ctx->view_pending || (!have && ktot > thr_direct)) {
-    // the run is a large part of the view (joining it to a patch would cost what the rewrite costs), or the pending patch is switched off (BMX_VIEW_PENDING=0).
-    // A run between thr and thr_direct keys joins the (empty) patch and makes the rewrite due at once: the same work, but BEHIND the answer
-    if (have) return soft(__LINE__);
-    if (c > nx || !rewrite_main(Dv, Dp, c, Iv, Ip, m)) return soft(__LINE__);
-  } else {
-    // room for the patch at its largest (a rewrite falls due beyond thr keys; the run that crosses the line is still taken in), allocated once: a growing
-    // buffer would put its reallocation in front of some query's answer
-    if (ensure_pending<T>(ctx, ix, std::max<uint64_t>(std::max<uint64_t>(ix.npd + c, ix.npi + m), thr + 2 * std::max<uint64_t>(c, m)))) return soft(__LINE__);
-    if (!ctx->view_err_host && hipHostMalloc(reinterpret_cast<void**>(&ctx->view_err_host), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->view_err_host = nullptr; }
-    if (!ctx->view_ev && hipEventCreateWithFlags(&ctx->view_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ctx->view_ev = nullptr; }
-    if (!ix.s_val2 && !ensure_view_spare<T>(ctx, ix, nx + thr + 2 * m)) return soft(__LINE__);     // (the rewrite's target, also allocated now rather than in front of a later answer)
-    T* pdv[2] = {static_cast<T*>(ix.pd_v[0]), static_cast<T*>(ix.pd_v[1])}; T* piv[2] = {static_cast<T*>(ix.pi_v[0]), static_cast<T*>(ix.pi_v[1])};
-    auto merge2 = [&](bool ids, ViewRun<T> A, uint64_t la, const T* bv, const uint32_t* bp, uint64_t lb, ViewRun<T> Z) {
-      if (la + lb == 0) return;
-      const uint32_t g = (uint32_t)((la + lb + VIEW_PASS_KEYS - 1) / VIEW_PASS_KEYS);
-      if (ids) hipLaunchKernelGGL((k_view_merge2<T, true>), dim3(g), dim3(256), 0, st, A, (uint32_t)la, bv, bp, (uint32_t)lb, (const uint64_t*)ix.ids, Z);
-      else hipLaunchKernelGGL((k_view_merge2<T, false>), dim3(g), dim3(256), 0, st, A, (uint32_t)la, bv, bp, (uint32_t)lb, (const uint64_t*)nullptr, Z);
-    };
-    if (!have) {
-      const int dc = ix.pcur, ic = ix.icur;
-      (void)hipMemcpyAsync(pdv[dc], Dv, c * sizeof(T), hipMemcpyDeviceToDevice, st); (void)hipMemcpyAsync(ix.pd_p[dc], Dp, c * 4, hipMemcpyDeviceToDevice, st);
-      ViewRun<T> none{nullptr, nullptr, nullptr}, Zi{piv[ic], ix.pi_p[ic], ix.pi_ids[ic]};
-      merge2(true, none, 0, Iv, Ip, m, Zi);                             // (the inserted keys with their ids)
-      if (hipGetLastError() != hipSuccess) return soft(__LINE__);       // (nothing here raises the error word, and everything that reads the patch is behind it on this stream: no synchronisation)
-      ix.npd = c; ix.npi = m;
-    } else {
-      // 2. which deleted keys are pending inserted keys (they cancel), which are keys of main (they join pd)? one flag per key, two ordered selects by flag
-      T* sel_v = kv[cur ^ 1]; uint32_t* sel_p = kp[cur ^ 1];              // the sort's other buffer: [0, c) keys of main, [c, 2c) pending inserted keys, behind them the flags
-      uint8_t* flag = reinterpret_cast<uint8_t*>(sel_v + 2 * c);
-      const int dc = ix.pcur, ic = ix.icur;
-      unsigned long long hc[2] = {0, 0};
-      if (c) {
-        ctx->hres[HRES_SPLIT] = ctx->hres[HRES_SPLIT + 1] = ~0ull;
-        (void)hipMemsetAsync(ix.pi_dead, 0, ix.npi, st);
-        hipLaunchKernelGGL((k_view_flag_in<T>), dim3((uint32_t)((c + 255) / 256)), dim3(256), 0, st, Dv, Dp, (uint32_t)c, (const T*)piv[ic], (const uint32_t*)ix.pi_p[ic], (uint32_t)ix.npi, flag, ix.pi_dead);
-        SelGeom g = sel_geom<1>(c);
-        for (uint32_t want = 0; want < 2; want++) {
-          PredFlag PF{flag, want};
-          EmitKeys<T> EK{Dv, Dp, sel_v + (want ? c : 0), sel_p + (want ? c : 0)};
-          FinishCount FC{const_cast<unsigned long long*>(&ctx->hres[HRES_SPLIT + want])};
-          hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, c, g.tiles_per_block, ctx->block_counts);
-          hipLaunchKernelGGL((k_sel_write<PredFlag, EmitKeys<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, EK, FC, c, g.tiles_per_block, ctx->block_counts);
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) return soft(__LINE__);
-        hc[0] = ctx->hres[HRES_SPLIT]; hc[1] = ctx->hres[HRES_SPLIT + 1];
-        if (hc[0] + hc[1] != c || hc[1] > ix.npi) return soft(__LINE__);
-      }
-      const uint64_t cX = hc[0], cI = hc[1];
-      // pi' = pi - (deleted keys that were pending inserts) + inserted keys;  pd' = pd + (deleted keys of main): balanced two-run merges (k_view_merge2)
-      int ia = ic; uint64_t na = ix.npi;
-      if (cI) {                                                           // the cancelled inserts leave pi: an ordered select into the other set
-        PredFlag PN{(const uint8_t*)ix.pi_dead, 0u};                           // (k_view_flag_in marked them while it looked the deleted keys up)
-        EmitRun<T> ER{(const T*)piv[ic], (const uint32_t*)ix.pi_p[ic], (const uint64_t*)ix.pi_ids[ic], piv[ic ^ 1], ix.pi_p[ic ^ 1], ix.pi_ids[ic ^ 1]};
-        FinishCount FC{&ctx->ds->view_tmp[0]};
-        SelGeom g = sel_geom<1>(ix.npi);
-        hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, ix.npi, g.tiles_per_block, ctx->block_counts);
-        hipLaunchKernelGGL((k_sel_write<PredFlag, EmitRun<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, ER, FC, ix.npi, g.tiles_per_block, ctx->block_counts);
-        ia = ic ^ 1; na = ix.npi - cI;
-      }
-      ViewRun<T> Ai{piv[ia], ix.pi_p[ia], ix.pi_ids[ia]}, Zi{piv[ia ^ 1], ix.pi_p[ia ^ 1], ix.pi_ids[ia ^ 1]};
-      if (m) merge2(true, Ai, na, Iv, Ip, m, Zi);
-      ViewRun<T> Ad{pdv[dc], ix.pd_p[dc], nullptr}, Zd{pdv[dc ^ 1], ix.pd_p[dc ^ 1], nullptr};
-      if (cX) merge2(false, Ad, ix.npd, (const T*)sel_v, (const uint32_t*)sel_p, cX, Zd);
-      if (hipGetLastError() != hipSuccess) return soft(__LINE__);       // (nothing here raises the error word, and everything that reads the patch is behind it on this stream: no synchronisation)
-      ix.icur = m ? ia ^ 1 : ia; if (cX) ix.pcur = dc ^ 1;
-      ix.npd += cX; ix.npi = na + m;
-    }
-    // 3. the pending patch has grown: main will be rewritten BEHIND the answer of the query that brought this refresh about (view_after_query), not in front of it
-    if (ix.npd + ix.npi > thr) ix.rewrite_due = true;
-  }
-  ix.ord_patches++; ix.ord_patched_keys += ktot;
-  ix.last_patch_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
-}
+#include "bmx_view.inc"
 
 // Bring EVERY maintained index up to date from the change log (they share it), then forget the log. Per index: created rows of its field are
 // appended in log order, then every logged row of the field gets its current value. One host sync at the end (appended counts, wide flags).
 // An index whose value-ordered view is current goes on being current: the refresh captures the change run and the view is patched with it.
 int refresh_from_log(bmx_ctx* ctx) {
-  const bool dbg_t = std::getenv("BMX_VIEW_DEBUG") != nullptr;
   const auto dbg_t0 = std::chrono::steady_clock::now();
   auto dbg_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - dbg_t0).count(); };
   double dbg_sync = 0;
@@ -1254,22 +967,11 @@ int refresh_from_log(bmx_ctx* ctx) {
     for (size_t k = 0; k < ctx->indexes.size(); k++) ctx->hres[HRES_RUN + k] = ~0ull;
     for (size_t k = 0; k < ctx->indexes.size(); k++) {
       Index& ix = ctx->indexes[k];
+      OrderedView& v = ix.view;
       // the view is current and can stay so: capture the change run (needs room for one entry per log entry)
-      if (ctx->view_patching && ix.ordered_after && ix.s_val && ix.ord_content == ix.content && ix.ord_fits32 == ix.fits32 && ix.n && ix.n < 0xFFFFFFFFull && ub <= VIEW_PATCH_MAX_LOG) {
-        if (ix.cl_cap < ub) {
-          HIPCHK(hipStreamSynchronize(ctx->stream));
-          for (void* q : {(void*)ix.cl_pos, (void*)ix.cl_old, (void*)ix.cl2_pos, (void*)ix.cl2_old}) if (q) (void)hipFree(q);
-          ix.cl_pos = nullptr; ix.cl_old = nullptr; ix.cl2_pos = nullptr; ix.cl2_old = nullptr; ix.cl_cap = 0;
-          const uint64_t cap = (ub + ub / 2 + (1u << 16) + 255) & ~255ull;
-          if (hipMalloc(reinterpret_cast<void**>(&ix.cl_pos), cap * sizeof(uint32_t)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&ix.cl_old), cap * sizeof(int64_t)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void**>(&ix.cl2_pos), cap * sizeof(uint32_t)) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&ix.cl2_old), cap * sizeof(int64_t)) == hipSuccess) ix.cl_cap = cap;
-          else {
-            (void)hipGetLastError();
-            for (void* q : {(void*)ix.cl_pos, (void*)ix.cl_old, (void*)ix.cl2_pos, (void*)ix.cl2_old}) if (q) (void)hipFree(q);
-            ix.cl_pos = nullptr; ix.cl_old = nullptr; ix.cl2_pos = nullptr; ix.cl2_old = nullptr;
-          }
-        }
-        capture[k] = ix.cl_cap >= ub;
+      if (ctx->view.patching && v.ordered_after && v.s_val && v.ord_content == ix.content && v.ord_fits32 == ix.fits32 && ix.n && ix.n < 0xFFFFFFFFull && ub <= VIEW_PATCH_MAX_LOG) {
+        if (int crc = ensure_change_run(ctx, v, ub)) return crc;
+        capture[k] = v.cl_cap >= ub;
       }
       unsigned long long* d_added = &ctx->ds->part_totals[2 * k];
       uint32_t* d_wide = reinterpret_cast<uint32_t*>(&ctx->ds->part_totals[2 * k + 1]);
@@ -1285,13 +987,13 @@ int refresh_from_log(bmx_ctx* ctx) {
       LAUNCHCHK("k_sel_write(log)");
       const uint32_t ublocks = (uint32_t)std::min<uint64_t>((ub + 255) / 256, 4096);
       hipLaunchKernelGGL(k_ix_update, dim3(ublocks), dim3(256), 0, ctx->stream, (const uint2*)ctx->chg, n_dev, (const Slot*)ctx->slots, ix.field, (const uint32_t*)ctx->slot_pos,
-                         ix.v64, ix.v32, d_wide, capture[k] ? 2u : (ix.ordered_after ? 1u : 0u), ix.cl_pos, ix.cl_old, (uint64_t)ix.cl_cap);
+                         ix.v64, ix.v32, d_wide, capture[k] ? 2u : (v.ordered_after ? 1u : 0u), v.cl_pos, v.cl_old, (uint64_t)v.cl_cap);
       LAUNCHCHK("k_ix_update");
       if (capture[k]) {      // the change run without its holes, in log order (ordered select: no atomics), and its length
-        PredChanged PC{ix.cl_pos, n_dev};
+        PredChanged PC{v.cl_pos, n_dev};
         SelGeom gc = sel_geom<PredChanged::E>(ub);
         hipLaunchKernelGGL((k_sel_count<PredChanged>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, ub, gc.tiles_per_block, ctx->block_counts);
-        EmitChanged EC{ix.cl_pos, ix.cl_old, ix.cl2_pos, ix.cl2_old};
+        EmitChanged EC{v.cl_pos, v.cl_old, v.cl2_pos, v.cl2_old};
         FinishCount FC{const_cast<unsigned long long*>(&ctx->hres[HRES_RUN + k])};
         hipLaunchKernelGGL((k_sel_write<PredChanged, EmitChanged, FinishCount>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, EC, FC, ub, gc.tiles_per_block, ctx->block_counts);
         LAUNCHCHK("k_sel_write(change run)");
@@ -1321,17 +1023,17 @@ int refresh_from_log(bmx_ctx* ctx) {
     if (ub) {
       const uint64_t n0 = ix.n;
       ix.n += res[k].added; if (res[k].wide) ix.fits32 = false;
-      const bool moved = res[k].added || res[k].changed || !ix.ordered_after;     // (no view: nobody compared, nobody cares)
+      const bool moved = res[k].added || res[k].changed || !ix.view.ordered_after;     // (no view: nobody compared, nobody cares)
       if (moved) ix.content++;
-      if (moved && capture[k] && ix.fits32 == ix.ord_fits32 && res[k].run <= ix.cl_cap && ix.n < 0xFFFFFFFFull) {
-        const int prc = ix.ord_fits32 ? patch_view_t<int32_t>(ctx, ix, res[k].run, n0, res[k].added) : patch_view_t<int64_t>(ctx, ix, res[k].run, n0, res[k].added);
-        if (prc == 0) ix.ord_content = ix.content;       // the view equals a fresh sort of the columns as they are now
+      if (moved && capture[k] && ix.fits32 == ix.view.ord_fits32 && res[k].run <= ix.view.cl_cap && ix.n < 0xFFFFFFFFull) {
+        const int prc = ix.view.ord_fits32 ? patch_view_t<int32_t>(ctx, ix, res[k].run, n0, res[k].added) : patch_view_t<int64_t>(ctx, ix, res[k].run, n0, res[k].added);
+        if (prc == 0) ix.view.ord_content = ix.content;       // the view equals a fresh sort of the columns as they are now
       }
     }
     ix.version = ctx->version;
   }
   ctx->ix_incremental++;
-  if (dbg_t) std::fprintf(stderr, "bmx: refresh from the log: columns up to date after %.1f us, patches done after %.1f us\n", dbg_sync, dbg_us());
+  if (ctx->view.debug) std::fprintf(stderr, "bmx: refresh from the log: columns up to date after %.1f us, patches done after %.1f us\n", dbg_sync, dbg_us());
   return BMX_OK;
 }
 
@@ -1393,69 +1095,61 @@ int ensure_scan_scratch(bmx_ctx* ctx, uint64_t n) {
 constexpr uint64_t SCAN_NT_BYTES = 256ull << 20;
 constexpr uint32_t SCAN_NTX_DEFAULT = 0;      // EmitIds::ntx (profiles/r05_scan_nt_emit_ab.log)
 
-// ---- value-ordered view (bmx.h bmx_index_set_ordered) ----
+// ---- the view's sort (bmx.h bmx_index_set_ordered; the rest of the view is bmx_view.inc) ---- It stays behind refresh_from_log: kernel templates are laid
+// out in the gfx950 code object in the order the source first uses them, and this sort's kernels follow the patch's (in front, they would land elsewhere).
 // Is the view of `ix` usable for the query at hand? A stale one is sorted again by the ordered_after-th query since the columns last changed — the
 // queries in front of that one scan the column as ever (one sort of a 100M-row column costs what ~20 scans cost) —, and never while it cannot be had
 // (no memory: the index goes on without it). Synchronous where it sorts.
 bool ensure_ordered_view(bmx_ctx* ctx, Index* ix) {
-  if (!ix->ordered_after || ix->n == 0 || ix->n > 0xFFFFFFFFull) return false;
-  if (ix->ord_content == ix->content && ix->s_val) { view_before_use(ctx, ix, /*wait=*/false); return true; }   // (a finished rewrite becomes main; an unfinished one changes nothing)
-  view_before_use(ctx, ix, /*wait=*/true);
-  uint32_t after = ix->ordered_after;
+  OrderedView& v = ix->view;
+  if (!v.ordered_after || ix->n == 0 || ix->n > 0xFFFFFFFFull) return false;
+  if (v.ord_content == ix->content && v.s_val) { finish_rewrite(ctx, v, /*wait=*/false); return true; }   // (a finished rewrite becomes main; an unfinished one changes nothing)
+  finish_rewrite(ctx, v, /*wait=*/true);
+  uint32_t after = v.ordered_after;
   if (after == BMX_INDEX_ORDERED_AUTO) {
     // rent or buy: sort once the scans answered since the change have cost what a sort costs — then whatever the caller does next, at most twice
     // the best possible was spent. A scan moves the value column at ~6 TB/s (+ two launches); a sort costs what the last one cost (first time: 60 us per 10^6 rows).
     const double scan_us = 8.0 + (double)ix->n * (ix->fits32 ? 4.0 : 8.0) / 6.0e6;
-    const double sort_us = ix->last_sort_us > 0 ? ix->last_sort_us : 200.0 + (double)ix->n * 0.00006;
+    const double sort_us = v.last_sort_us > 0 ? v.last_sort_us : 200.0 + (double)ix->n * 0.00006;
     after = (uint32_t)std::min<double>(1.0e6, std::max<double>(2.0, std::ceil(sort_us / scan_us)));
   }
-  if (ix->stale_content != ix->content) { ix->stale_content = ix->content; ix->stale_queries = 0; }   // the count starts with every change of the columns
-  if (++ix->stale_queries < after) return false;
+  if (v.stale_content != ix->content) { v.stale_content = ix->content; v.stale_queries = 0; }   // the count starts with every change of the columns
+  if (++v.stale_queries < after) return false;
   const auto t_sort = std::chrono::steady_clock::now();
-  ix->npd = ix->npi = 0;                          // a fresh sort of the columns: whatever patch was pending is in them
+  v.npd = v.npi = 0;                          // a fresh sort of the columns: whatever patch was pending is in them
   const uint64_t n = ix->n;
   const size_t vb = ix->fits32 ? sizeof(int32_t) : sizeof(int64_t);
-  auto give_up = [&]() { (void)hipGetLastError(); free_ordered_view(*ix); ix->stale_queries = 0; return false; };
-  if (n > ix->ord_cap || ix->ord_fits32 != ix->fits32) {
-    free_ordered_view(*ix);
+  auto give_up = [&]() { (void)hipGetLastError(); v.release(); v.stale_queries = 0; return false; };
+  auto sorted = [&]() { v.ord_n = n; v.ord_content = ix->content; v.stale_queries = 0; v.ord_sorts++; v.last_sort_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sort).count(); return true; };
+  if (n > v.ord_cap || v.ord_fits32 != ix->fits32) {
+    v.release();
     const uint64_t cap = n + n / 8 + 1024;
-    if (hipMalloc(&ix->s_val, cap * vb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&ix->s_pos), cap * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ix->s_ids), cap * sizeof(uint64_t)) != hipSuccess) return give_up();
-    ix->ord_cap = cap; ix->ord_fits32 = ix->fits32;
+    if (!alloc_all({{v.s_val, cap * vb}, {v.s_pos, cap * sizeof(uint32_t)}, {v.s_ids, cap * sizeof(uint64_t)}})) return give_up();
+    v.ord_cap = cap; v.ord_fits32 = ix->fits32;
   }
-  if (ctx->view_own_sort && n && n < 0xFFFFFFFFull) {
+  if (ctx->view.own_sort && n && n < 0xFFFFFFFFull) {
     // A/B arm: the whole column through the patch path's sort — (value, position) keys, 4096-key tiles in LDS, then log2(n / 4096) merge-path passes between
     // the view's columns and a scratch pair; a tombstone is the column type's minimum and sorts in front like every other value
     void* tv = nullptr; uint32_t* tp = nullptr;
-    if (hipMalloc(&tv, n * vb) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&tp), n * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); if (tv) (void)hipFree(tv); return give_up(); }
+    if (!alloc_all({{tv, n * vb}, {tp, n * sizeof(uint32_t)}})) return give_up();
     const uint32_t gbo = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
     unsigned passes = 0; for (uint64_t L = VIEW_SORT_TILE; L < n; L *= 2) passes++;
     auto run = [&](auto tag) {
       using T = decltype(tag);
       const T* col = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
-      T* bufv[2] = {static_cast<T*>(ix->s_val), static_cast<T*>(tv)}; uint32_t* bufp[2] = {ix->s_pos, tp};
-      int cur = passes & 1;                                             // the tile sort writes into the buffer from which `passes` swaps end in the view's columns
-      uint32_t* iota = bufp[cur ^ 1];                                   // (the other position buffer is free until the first pass writes it)
+      T* bufv[2] = {static_cast<T*>(v.s_val), static_cast<T*>(tv)}; uint32_t* bufp[2] = {v.s_pos, tp};
+      const int first = passes & 1;                                     // the tile sort writes into the buffer from which `passes` swaps end in the view's columns
+      uint32_t* iota = bufp[first ^ 1];                                 // (the other position buffer is free until the first pass writes it)
       hipLaunchKernelGGL(k_iota_u32, dim3(gbo), dim3(256), 0, ctx->stream, iota, n);
-      ViewSegs S{}; S.base[0] = 0; S.len[0] = (uint32_t)n; S.base[1] = (uint32_t)n; S.len[1] = 0;
-      const uint32_t tiles = (uint32_t)((n + VIEW_SORT_TILE - 1) / VIEW_SORT_TILE);
-      S.blk0[0] = 0; S.blk0[1] = tiles; S.blk0[2] = tiles;
-      hipLaunchKernelGGL((k_view_tile_sort<T>), dim3(tiles), dim3(VIEW_SORT_THREADS), 0, ctx->stream, col, (const uint32_t*)iota, bufv[cur], bufp[cur], S);
-      ViewSegs P = S; P.blk0[1] = (uint32_t)((n + VIEW_PASS_KEYS - 1) / VIEW_PASS_KEYS); P.blk0[2] = P.blk0[1];
-      for (uint64_t L = VIEW_SORT_TILE; L < n; L *= 2) {
-        hipLaunchKernelGGL((k_view_merge_pass<T>), dim3(P.blk0[2]), dim3(256), 0, ctx->stream, (const T*)bufv[cur], (const uint32_t*)bufp[cur], bufv[cur ^ 1], bufp[cur ^ 1], P, (uint32_t)L);
-        cur ^= 1;
-      }
+      sort_view_keys<T>(ctx->stream, col, iota, bufv, bufp, n, 0, first);
     };
     if (ix->fits32) run(int32_t{}); else run(int64_t{});
-    hipLaunchKernelGGL(k_view_gather_ids, dim3(gbo), dim3(256), 0, ctx->stream, (const uint32_t*)ix->s_pos, (uint32_t)n, (const uint64_t*)ix->ids, ix->s_ids);
+    hipLaunchKernelGGL(k_view_gather_ids, dim3(gbo), dim3(256), 0, ctx->stream, (const uint32_t*)v.s_pos, (uint32_t)n, (const uint64_t*)ix->ids, v.s_ids);
     hipError_t eo = hipGetLastError();
     if (eo == hipSuccess) eo = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tv); (void)hipFree(tp);
+    dev_free(tv); dev_free(tp);
     if (eo != hipSuccess) return give_up();
-    ix->ord_n = n; ix->ord_content = ix->content; ix->stale_queries = 0; ix->ord_sorts++;
-    ix->last_sort_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sort).count();
-    return true;
+    return sorted();
   }
   // the column's value range decides how many bits the sort has to look at (csrc/ordered_sort.hip: keys rebased to min = 1, tombstones = 0)
   const uint32_t gb = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192);
@@ -1476,65 +1170,19 @@ bool ensure_ordered_view(bmx_ctx* ctx, Index* ix) {
   uint32_t* iota = nullptr; void* tmp = nullptr; size_t tmp_bytes = 0;
   e = ix->fits32 ? sort_pairs_i32(nullptr, &tmp_bytes, nullptr, 0, bits, nullptr, nullptr, nullptr, n, ctx->stream)
                  : sort_pairs_i64(nullptr, &tmp_bytes, nullptr, 0, bits, nullptr, nullptr, nullptr, n, ctx->stream);
-  if (e != hipSuccess || hipMalloc(reinterpret_cast<void**>(&iota), n * sizeof(uint32_t)) != hipSuccess || hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16)) != hipSuccess) {
-    if (iota) (void)hipFree(iota);
-    return give_up();
-  }
+  if (e != hipSuccess || !alloc_all({{iota, n * sizeof(uint32_t)}, {tmp, std::max<size_t>(tmp_bytes, 16)}})) return give_up();
   hipLaunchKernelGGL(k_iota_u32, dim3(gb), dim3(256), 0, ctx->stream, iota, n);
-  e = ix->fits32 ? sort_pairs_i32(tmp, &tmp_bytes, ix->v32, (int32_t)mm[0], bits, static_cast<uint32_t*>(ix->s_val), iota, ix->s_pos, n, ctx->stream)
-                 : sort_pairs_i64(tmp, &tmp_bytes, ix->v64, (int64_t)mm[0], bits, static_cast<uint64_t*>(ix->s_val), iota, ix->s_pos, n, ctx->stream);
+  e = ix->fits32 ? sort_pairs_i32(tmp, &tmp_bytes, ix->v32, (int32_t)mm[0], bits, static_cast<uint32_t*>(v.s_val), iota, v.s_pos, n, ctx->stream)
+                 : sort_pairs_i64(tmp, &tmp_bytes, ix->v64, (int64_t)mm[0], bits, static_cast<uint64_t*>(v.s_val), iota, v.s_pos, n, ctx->stream);
   if (e == hipSuccess) {
-    if (ix->fits32) hipLaunchKernelGGL((k_gather_ids<int32_t, uint32_t>), dim3(gb), dim3(256), 0, ctx->stream, (const uint64_t*)ix->ids, (const uint32_t*)ix->s_pos, ix->s_ids, n, static_cast<uint32_t*>(ix->s_val), (int32_t)mm[0]);
-    else hipLaunchKernelGGL((k_gather_ids<int64_t, uint64_t>), dim3(gb), dim3(256), 0, ctx->stream, (const uint64_t*)ix->ids, (const uint32_t*)ix->s_pos, ix->s_ids, n, static_cast<uint64_t*>(ix->s_val), (int64_t)mm[0]);
+    if (ix->fits32) hipLaunchKernelGGL((k_gather_ids<int32_t, uint32_t>), dim3(gb), dim3(256), 0, ctx->stream, (const uint64_t*)ix->ids, (const uint32_t*)v.s_pos, v.s_ids, n, static_cast<uint32_t*>(v.s_val), (int32_t)mm[0]);
+    else hipLaunchKernelGGL((k_gather_ids<int64_t, uint64_t>), dim3(gb), dim3(256), 0, ctx->stream, (const uint64_t*)ix->ids, (const uint32_t*)v.s_pos, v.s_ids, n, static_cast<uint64_t*>(v.s_val), (int64_t)mm[0]);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // the scratch goes back below
-  (void)hipFree(iota); (void)hipFree(tmp);
+  dev_free(iota); dev_free(tmp);
   if (e != hipSuccess) return give_up();
-  ix->ord_n = n; ix->ord_content = ix->content; ix->stale_queries = 0; ix->ord_sorts++;
-  ix->last_sort_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sort).count();
-  return true;
-}
-// the query itself: two searches + one contiguous copy; lo/hi are already clamped like the scans' (tombstones sort in front of every legal value)
-template <bool POS, class OutT, class T>
-void launch_ordered_t(bmx_ctx* ctx, const Index* ix, T l, T h, OutT* d_out, uint64_t d_cap, unsigned long long* d_n, const PredFilter* filter) {
-  unsigned long long* ab = ctx->ds->ord_ab;
-  const T* sv = static_cast<const T*>(ix->s_val);
-  const bool pending = ix->npd + ix->npi > 0;           // the logical view = main - pd + pi (patch_view_t)
-  const int q = ix->pcur, qi = ix->icur;
-  const T* dv = static_cast<const T*>(ix->pd_v[q]); const T* iv = static_cast<const T*>(ix->pi_v[qi]);
-  if (pending) hipLaunchKernelGGL((k_ordered_bounds_p<T>), dim3(1), dim3(384), 0, ctx->stream, sv, ix->ord_n, dv, ix->npd, iv, ix->npi, l, h, ab, d_n, filter ? 1u : 0u);
-  else hipLaunchKernelGGL((k_ordered_bounds<T>), dim3(1), dim3(128), 0, ctx->stream, sv, ix->ord_n, l, h, ab, d_n, filter ? 1u : 0u);
-  if (filter) {             // every candidate of the run is looked at whatever the caller can take: the count is the number of survivors
-    if constexpr (!POS) {
-      const uint32_t fb = (uint32_t)std::min<uint64_t>((ix->ord_n + ix->npi + 2047) / 2048, 4096);
-      if (pending) hipLaunchKernelGGL((k_ordered_filter_p<T, PredFilter>), dim3(fb), dim3(256), 0, ctx->stream, sv, (const uint32_t*)ix->s_pos, (const uint64_t*)ix->s_ids, dv, (const uint32_t*)ix->pd_p[q],
-                                      (const uint64_t*)ix->pi_ids[qi], (const unsigned long long*)ab, *filter, d_out, d_out ? d_cap : 0, d_n);
-      else hipLaunchKernelGGL((k_ordered_filter<PredFilter>), dim3(fb), dim3(256), 0, ctx->stream, (const uint64_t*)ix->s_ids, (const unsigned long long*)ab, *filter, d_out, d_out ? d_cap : 0, d_n);
-    }
-    return;
-  }
-  if (!d_out || !d_cap) return;
-  // the match count is the device's: a grid for the most the caller can take, whose workgroups beyond the matches leave at once
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((std::min<uint64_t>(d_cap, ix->ord_n + ix->npi) + 2047) / 2048, 8192);
-  if (pending) {
-    if constexpr (POS) hipLaunchKernelGGL((k_ordered_copy_p<T, uint32_t>), dim3(blocks), dim3(256), 0, ctx->stream, sv, (const uint32_t*)ix->s_pos, (const uint32_t*)ix->s_pos, dv, (const uint32_t*)ix->pd_p[q],
-                                          (const uint32_t*)ix->pi_p[qi], (const unsigned long long*)ab, d_out, d_cap);
-    else hipLaunchKernelGGL((k_ordered_copy_p<T, uint64_t>), dim3(blocks), dim3(256), 0, ctx->stream, sv, (const uint32_t*)ix->s_pos, (const uint64_t*)ix->s_ids, dv, (const uint32_t*)ix->pd_p[q],
-                            (const uint64_t*)ix->pi_ids[qi], (const unsigned long long*)ab, d_out, d_cap);
-  } else {
-    if constexpr (POS) hipLaunchKernelGGL((k_ordered_copy<uint32_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t*)ix->s_pos, (const unsigned long long*)ab, d_out, d_cap);
-    else hipLaunchKernelGGL((k_ordered_copy<uint64_t>), dim3(blocks), dim3(256), 0, ctx->stream, (const uint64_t*)ix->s_ids, (const unsigned long long*)ab, d_out, d_cap);
-  }
-}
-template <bool POS, class OutT>
-void launch_ordered(bmx_ctx* ctx, const Index* ix, int64_t lo, int64_t hi, OutT* d_out, uint64_t d_cap, unsigned long long* d_n, const PredFilter* filter = nullptr) {
-  if (filter && !d_n) d_n = &ctx->ds->n_out;       // (the filter appends through a counter even when nobody asked for the count)
-  if (ix->ord_fits32) {     // the view was sorted from the 4-byte column: bounds clamped into int32 like the scans' (an empty range stays empty)
-    int64_t l = std::max<int64_t>(lo, (int64_t)INT32_MIN + 1), h = std::min<int64_t>(hi, INT32_MAX);
-    if (lo > INT32_MAX || hi < INT32_MIN) { l = 1; h = 0; }
-    launch_ordered_t<POS, OutT, int32_t>(ctx, ix, (int32_t)l, (int32_t)h, d_out, d_cap, d_n, filter);
-  } else launch_ordered_t<POS, OutT, int64_t>(ctx, ix, lo, hi, d_out, d_cap, d_n, filter);
+  return sorted();
 }
 
 template <bool POS, class Pred>
@@ -1795,10 +1443,7 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   } else { ctx->stg_tails = nullptr; (void)hipGetLastError(); }
   ctx->fixed_capacity = (flags & BMX_CTX_FIXED_CAPACITY) != 0;
   ctx->defer_enabled = !launches_are_serialized();
-  { const char* vp = std::getenv("BMX_VIEW_PATCH"); if (vp && vp[0] == '0' && !vp[1]) ctx->view_patching = false; }
-  { const char* vf = std::getenv("BMX_TEST_VIEW_FAIL"); if (vf && (vf[0] == '1' || vf[0] == '2') && !vf[1]) ctx->view_test_fail = vf[0] - '0'; }
-  { const char* vs = std::getenv("BMX_VIEW_SORT"); if (vs && std::strcmp(vs, "own") == 0) ctx->view_own_sort = true; }
-  { const char* vp = std::getenv("BMX_VIEW_PENDING"); if (vp && vp[0] == '0' && !vp[1]) ctx->view_pending = false; }
+  ctx->view.read_env();
   { const char* kw = std::getenv("BMX_K1_WAVES"); if (kw && kw[0] >= '3' && kw[0] <= '8' && kw[0] != '7' && !kw[1]) ctx->k1_waves = kw[0] - '0'; }
   CR(hipMemsetAsync(ctx->ds, 0, sizeof(DevScalars), ctx->stream));
   hipLaunchKernelGGL(k_init_slots, dim3(2048), dim3(256), 0, ctx->stream, ctx->slots, nslots);
@@ -1816,7 +1461,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   (void)hipGetLastError();
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); if (!ctx->side_is_callers) (void)hipStreamDestroy(ctx->side); ctx->side = nullptr; }
-  for (auto& ix : ctx->indexes) { dev_free(ix.ids); dev_free(ix.v64); dev_free(ix.v32); free_ordered_view(ix); }
+  for (auto& ix : ctx->indexes) { free_columns(ix); ix.view.release(); }
   dev_free(ctx->slots); dev_free(ctx->ds); dev_free(ctx->next); dev_free(ctx->blk_info); dev_free(ctx->blk_follow); dev_free(ctx->shard_ctr);
   for (uint32_t h = 0; h < bmx_ctx::WS_SETS; h++) { dev_free(ctx->wflag[h]); dev_free(ctx->slot_of[h]); dev_free(ctx->fld_ws[h]); }
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
@@ -1830,10 +1475,8 @@ void bmx_destroy(bmx_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->down_stream) { (void)hipStreamSynchronize(ctx->down_stream); (void)hipStreamDestroy(ctx->down_stream); }
   dev_free(ctx->slot_pos); dev_free(ctx->chg);
-  for (int i = 0; i < 2; i++) { if (ctx->vk_v[i]) (void)hipFree(ctx->vk_v[i]); dev_free(ctx->vk_p[i]); }
-  if (ctx->vk_sv) (void)hipFree(ctx->vk_sv); dev_free(ctx->vk_sp); dev_free(ctx->vk_d0); dev_free(ctx->vk_y0);
+  ctx->view.release();
   if (ctx->hres) (void)hipHostFree(const_cast<unsigned long long*>(ctx->hres));
-  if (ctx->view_err_host) (void)hipHostFree(ctx->view_err_host); if (ctx->view_ev) (void)hipEventDestroy(ctx->view_ev);
   if (ctx->host_rows) { (void)hipHostFree(ctx->host_rows); ctx->host_rows = nullptr; }
   if (ctx->stg_tails) { (void)hipHostFree(ctx->stg_tails); ctx->stg_tails = nullptr; ctx->stg[0].tail = ctx->stg[1].tail = nullptr; }
   if (ctx->pin_in) { (void)hipHostFree(ctx->pin_in); ctx->pin_in = nullptr; }
@@ -2093,7 +1736,7 @@ int bmx_index_drop(bmx_ctx* ctx, uint32_t field) {
   HIPCHK(hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < ctx->indexes.size(); i++)
     if (ctx->indexes[i].field == field) {
-      dev_free(ctx->indexes[i].ids); dev_free(ctx->indexes[i].v64); dev_free(ctx->indexes[i].v32); free_ordered_view(ctx->indexes[i]);
+      free_columns(ctx->indexes[i]); ctx->indexes[i].view.release();
       ctx->indexes.erase(ctx->indexes.begin() + (long)i);
       if (ctx->indexes.empty()) {   // nothing left to maintain: the merges stop logging and the maintenance memory goes back
         ctx->chg_valid = false; ctx->chg_ub = 0;
@@ -2128,18 +1771,19 @@ int bmx_index_set_ordered(bmx_ctx* ctx, uint32_t field, uint32_t after_queries) 
   Index* ix;
   int rc = fresh_index(ctx, field, &ix);      // (creates the index like a first query would)
   if (rc) return rc;
-  ix->ordered_after = after_queries;
-  ix->stale_queries = 0;
-  if (!after_queries) { HIPCHK(hipStreamSynchronize(ctx->stream)); free_ordered_view(*ix); }
+  ix->view.ordered_after = after_queries;
+  ix->view.stale_queries = 0;
+  if (!after_queries) { HIPCHK(hipStreamSynchronize(ctx->stream)); ix->view.release(); }
   return BMX_OK;
 }
 int bmx_index_ordered_info(bmx_ctx* ctx, uint32_t field, uint32_t* after_queries, int* valid_now, uint64_t* sorts) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   Index* ix = find_index(ctx, field);
   if (!ix) return fail(ctx, BMX_ERR_INVALID, "bmx_index_ordered_info: no index on this field");
-  if (after_queries) *after_queries = ix->ordered_after;
-  if (valid_now) *valid_now = ix->ordered_after && ix->s_val && ix->ord_content == ix->content && ix->version == ctx->version;
-  if (sorts) *sorts = ix->ord_sorts;
+  const OrderedView& v = ix->view;
+  if (after_queries) *after_queries = v.ordered_after;
+  if (valid_now) *valid_now = v.ordered_after && v.s_val && v.ord_content == ix->content && ix->version == ctx->version;
+  if (sorts) *sorts = v.ord_sorts;
   return BMX_OK;
 }
 
@@ -2147,13 +1791,14 @@ int bmx_index_ordered_stats(bmx_ctx* ctx, uint32_t field, uint64_t* sorts, uint6
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   Index* ix = find_index(ctx, field);
   if (!ix) return fail(ctx, BMX_ERR_INVALID, "bmx_index_ordered_stats: no index on this field");
-  if (sorts) *sorts = ix->ord_sorts;
-  if (patches) *patches = ix->ord_patches;
-  if (keys_patched) *keys_patched = ix->ord_patched_keys;
-  if (last_sort_us) *last_sort_us = ix->last_sort_us;
-  if (last_patch_us) *last_patch_us = ix->last_patch_us;
-  if (rewrites) *rewrites = ix->ord_merges;
-  if (pending_keys) *pending_keys = ix->npd + ix->npi;
+  const OrderedView& v = ix->view;
+  if (sorts) *sorts = v.ord_sorts;
+  if (patches) *patches = v.ord_patches;
+  if (keys_patched) *keys_patched = v.ord_patched_keys;
+  if (last_sort_us) *last_sort_us = v.last_sort_us;
+  if (last_patch_us) *last_patch_us = v.last_patch_us;
+  if (rewrites) *rewrites = v.ord_merges;
+  if (pending_keys) *pending_keys = v.npd + v.npi;
   return BMX_OK;
 }
 
