@@ -31,6 +31,9 @@ hipError_t sort_pairs_i64(void* tmp, size_t* tmp_bytes, const int64_t* kin, int6
 
 using namespace bmx;
 
+// count, stats and device status of one host batch, written by k_small_tail into mapped host memory
+struct SmallOut { unsigned long long n_applied; bmx_merge_stats stats; uint32_t status; uint32_t pad; };
+
 namespace {
 
 struct DevScalars {  // one small device allocation; zeroed at create
@@ -86,7 +89,7 @@ struct Index {
   uint64_t* ids = nullptr; int64_t* v64 = nullptr; int32_t* v32 = nullptr;   // the columns (free_columns)
   bool fits32 = false;
   uint64_t version = ~0ull;  // table version it was built from
-  bool has_pos = false;      // its rows' positions are in ctx->slot_pos (it can be maintained from the change log)
+  bool has_pos = false;      // its rows' positions are in ctx->chg.slot_pos (it can be maintained from the change log)
   uint64_t content = 0;      // counts the refreshes that really changed something in the columns (a value, a new row, a rebuild)
   OrderedView view;
 };
@@ -112,35 +115,80 @@ inline bool public_mode_ok(int insert_mode) {  // what bmx.h documents: BMX_INSE
   return (insert_mode & ~(BMX_INSERT_DELTA | BMX_MERGE_UNIQUE_KEYS | BMX_MERGE_STRICT_FLAGS | BMX_MERGE_MARK_CREATED)) == 0;
 }
 
-}  // namespace
+template <class T>
+void dev_free(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+// One all-or-nothing group of device buffers: what the pointers of the list hold goes back, then every one gets a new buffer, or none does (what was
+// allocated goes back, the HIP error is cleared and handed to `err`). dev_alloc_all is the same for a context's entry points.
+struct DevBuf { void** p; size_t bytes; template <class T> DevBuf(T*& q, size_t b) : p(reinterpret_cast<void**>(&q)), bytes(b) {} };
+bool alloc_all(std::initializer_list<DevBuf> bufs, hipError_t* err = nullptr) {
+  for (const DevBuf& b : bufs) dev_free(*b.p);
+  for (const DevBuf* b = bufs.begin(); b != bufs.end(); b++) {
+    const hipError_t e = hipMalloc(b->p, b->bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      *b->p = nullptr;
+      for (const DevBuf* f = bufs.begin(); f != b; f++) dev_free(*f->p);
+      if (err) *err = e;
+      return false;
+    }
+  }
+  return true;
+}
 
-// count, stats and device status of one host batch, written by k_small_tail into mapped host memory
-struct SmallOut { unsigned long long n_applied; bmx_merge_stats stats; uint32_t status; uint32_t pad; };
-struct bmx_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  Slot* slots = nullptr;
-  uint64_t nslots = 0, capacity_rows = 0;
-  uint32_t load_pct = 50;             // maximum load factor (percent) at capacity_rows: nslots = capacity_rows * 100 / load_pct
-  DevScalars* ds = nullptr;
-  // per-batch workspace (grown on demand)
-  uint32_t ws_cap = 0;
-  uint32_t* next = nullptr;
+// The merge's per-batch workspace (merge_core), grown on demand.
+struct MergeWs {
   // what the compaction (K3) reads is kept per batch PARITY, so that the compaction of batch b can run on a second stream while the probe
   // kernel of batch b + 1 fills the other set ("deferred compaction", merge_core): winner bytes, the claimers' slots, the deltas' field
   // hashes (for the index change log) and the sharded counters
   // THREE sets: while batch k is probed the compactions of batches k - 1 (just released) and k - 2 (not waited for yet) may both still be reading theirs
-  static constexpr uint32_t WS_SETS = 3, BLK_SEGS = 4;
-  uint8_t* wflag[WS_SETS] = {nullptr, nullptr, nullptr};
-  uint32_t* slot_of[WS_SETS] = {nullptr, nullptr, nullptr};
-  uint32_t* fld_ws[WS_SETS] = {nullptr, nullptr, nullptr};
-  uint32_t ws_par = 0;
-  uint32_t* blk_info = nullptr;       // 4 x (ws_cap/256 + 16) block summaries: batch k adds into segment k % 4 and k_probe_apply zeroes segment (k + 1) % 4 for batch k + 1;
+  static constexpr uint32_t SETS = 3, BLK_SEGS = 4;
+  uint32_t cap = 0;
+  uint32_t* next = nullptr;
+  uint8_t* wflag[SETS] = {nullptr, nullptr, nullptr};
+  uint32_t* slot_of[SETS] = {nullptr, nullptr, nullptr};
+  uint32_t* fld[SETS] = {nullptr, nullptr, nullptr};
+  uint32_t par = 0;
+  uint32_t* blk_info = nullptr;       // 4 x (cap/256 + 16) block summaries: batch k adds into segment k % 4 and k_probe_apply zeroes segment (k + 1) % 4 for batch k + 1;
                                       // four, because the compactions of batches k - 1 and k - 2 may still read theirs while batch k is probed
   uint32_t blk_half = 0, blk_seg = 0; bool blk_clean[BLK_SEGS] = {false, false, false, false};   // blk_clean[h]: segment h is known to be all zero
-  uint32_t* blk_follow = nullptr;     // ws_cap/256 epoch tags: a delta of the block got a follower on its row
-  unsigned long long* shard_ctr = nullptr;  // WS_SETS x CTR_SHARDS * CTR_STRIDE (one per workspace set)
-  // staging for BMX_MEM_HOST calls
+  uint32_t* blk_follow = nullptr;     // cap/256 epoch tags: a delta of the block got a follower on its row
+  unsigned long long* shard_ctr = nullptr;  // SETS x CTR_SHARDS * CTR_STRIDE (one per workspace set), allocated at create
+  int ensure(bmx_ctx* ctx, uint64_t n);     // room for a batch of n deltas
+  void release() {
+    dev_free(next); dev_free(blk_info); dev_free(blk_follow); dev_free(shard_ctr);
+    for (uint32_t h = 0; h < SETS; h++) { dev_free(wflag[h]); dev_free(slot_of[h]); dev_free(fld[h]); }
+    cap = 0;
+  }
+};
+
+// Deferred compaction (merge_core): the compaction of a device-resident batch is not launched with the batch. If the next call is another such
+// merge, it goes to a high-priority side stream behind a one-wave wait for that merge's probe kernel to START (= everything of this batch is
+// done), and runs under that probe kernel; anything else launches it on the context's stream first (flush_pending).
+struct Deferral {
+  struct PendingK3 {
+    bool on = false;
+    const uint8_t* wflag = nullptr; const uint32_t* blk = nullptr; uint32_t n = 0; uint32_t* applied = nullptr;
+    FinishMerge Fin{}; ChgLog L{}; uint32_t mark_created = 0; bool notify_after = false; uint64_t notify_seq = 0; uint64_t seq = 0;
+  } pend;
+  bool enabled = true;
+  hipStream_t side = nullptr;
+  bool side_is_callers = false;       // bmx_set_side_stream: the deferred compactions run on a stream the caller owns (the sharded pipeline's exchange stream)
+  uint64_t seq = 0;                   // deferred merges so far (the sequence numbers in ds->seqw)
+  uint64_t side_last = 0, side_prev = 0;   // sequence numbers of the last two compactions launched on the side stream (0: none this stream is not ordered behind already)
+  uint64_t n_deferred = 0, n_side = 0;   // merges whose compaction was deferred / actually ran on the side stream (bmx_get_deferred_counts)
+  void release() {                    // the side stream finishes; it is destroyed only if the library created it
+    if (!side) return;
+    (void)hipStreamSynchronize(side);
+    if (!side_is_callers) (void)hipStreamDestroy(side);
+    side = nullptr;
+  }
+};
+
+// What exists only for BMX_MEM_HOST calls (bmx_host.inc): staging, copy streams, mapped host memory, the point reads' columns.
+struct HostIO {
   // Two staging sets: batch b+1 is uploaded (copy stream) while batch b is merged (main stream); bmx_merge_submit / bmx_merge_collect
   struct Staging {
     uint32_t cap = 0;
@@ -151,27 +199,88 @@ struct bmx_ctx {
     hipEvent_t up = nullptr, done = nullptr;                                  // inputs uploaded / kernels of the batch finished
     uint64_t n = 0; bool want_flags = false; bool busy = false; uint64_t ticket = 0;
   } stg[2];
+  SmallOut* tails = nullptr;           // mapped host memory behind stg[i].tail
   // small host batches (<= SMALL_HOST_N deltas): inputs are packed into mapped host memory the kernels read directly, results are written
   // straight into mapped host memory: three launches and one stream synchronisation per call, no copies, no second stream
   uint8_t* pin_in = nullptr; uint8_t* pin_out = nullptr;
-  SmallOut* stg_tails = nullptr;       // mapped host memory behind stg[i].tail
   hipStream_t copy_stream = nullptr;   // uploads
   hipStream_t down_stream = nullptr;   // downloads (PCIe is full duplex: results of batch b come back while batch b+1 goes up)
   uint64_t next_ticket = 1;
+  volatile unsigned long long* hres = nullptr;   // mapped page-locked result words (HRES_*): counts the host waits for arrive without a download
   // persistent device buffers of the host-mode point reads and dumps (grow-only)
   uint64_t pr_cap = 0;
   uint64_t* pr_id = nullptr; uint32_t* pr_field = nullptr; int64_t* pr_ts = nullptr; int64_t* pr_val = nullptr; uint8_t* pr_found = nullptr;
-  uint64_t scan_cap = 0; uint64_t* scan_out = nullptr;
-  bool scan_defer = false; uint64_t scan_defer_cap = 0;   // host-mode scan split in two (bmx_comm_scan_*): enqueue now, scan_collect() later
-  uint32_t* block_counts = nullptr;   // SEL_MAX_BLOCKS
-  uint32_t* scan_mask = nullptr;      // scan scratch: one match bit per index row
-  uint32_t* scan_counts = nullptr;    // scan scratch: matches per 8192-row block (+ total)
-  uint64_t scan_blocks_cap = 0;
+  int create(bmx_ctx* ctx);            // at create: the staging sets' events, device words and mapped tails
+  void release();                      // (after the context's stream has finished)
+};
+
+// Scratch of the scans and selects, grown on demand.
+struct ScanScratch {
+  uint64_t out_cap = 0; uint64_t* out = nullptr;       // a host-mode answer on its way down
+  bool defer = false; uint64_t defer_cap = 0;          // host-mode scan split in two (bmx_comm_scan_*): enqueue now, scan_collect() later
+  uint32_t* block_counts = nullptr;   // SEL_MAX_BLOCKS, allocated at create
+  uint32_t* mask = nullptr;           // one match bit per index row
+  uint32_t* counts = nullptr;         // matches per 8192-row block (+ total)
+  uint64_t blocks_cap = 0;
+  int ensure(bmx_ctx* ctx, uint64_t rows, uint64_t out_n);
+  void release() { dev_free(out); dev_free(block_counts); dev_free(mask); dev_free(counts); out_cap = blocks_cap = 0; }
+};
+
+// incremental index maintenance (scan_kernels.h): slot -> position in its field's index, and the log of the winners' slots since the
+// indices were last brought up to date. valid: the log is complete (every merge since then was logged and nothing moved the slots).
+// Both exist from the first index build on (ensure_ix_maintenance).
+struct ChangeLog {
+  uint32_t* slot_pos = nullptr; uint64_t slot_pos_n = 0;
+  uint2* log = nullptr; uint64_t cap = 0, ub = 0;
+  bool valid = false; uint32_t par = 0;
+  uint64_t full_builds = 0, incremental = 0;
+  void release() { dev_free(slot_pos); slot_pos_n = 0; dev_free(log); cap = 0; ub = 0; valid = false; }
+};
+
+// Scratch of the partition kernels (partition_impl).
+struct PartScratch {
+  uint32_t* counts = nullptr;         // PART_MAX_SHARDS * PART_BLOCKS, allocated at create
+  uint8_t* owner = nullptr;           // owner shard of every delta of the batch being partitioned
+  uint64_t owner_cap = 0;
+  void release() { dev_free(counts); dev_free(owner); owner_cap = 0; }
+};
+
+// bmx_timer_* events and the optional per-kernel profiling (bmx_profile_enable).
+struct Profiling {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool on = false;
+  uint32_t n = 0;
+  std::vector<hipEvent_t> ev;         // 4 events per profiled call
+  std::vector<hipEvent_t> scan_ev;    // 3 events per profiled scan call (before the mask pass, after it, after the emit pass)
+  uint32_t scan_n = 0;
+  void release() {
+    for (auto e : ev) (void)hipEventDestroy(e);
+    for (auto e : scan_ev) (void)hipEventDestroy(e);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    ev.clear(); scan_ev.clear(); ev0 = ev1 = nullptr;
+  }
+};
+
+}  // namespace
+
+struct bmx_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  Slot* slots = nullptr;
+  uint64_t nslots = 0, capacity_rows = 0;
+  uint32_t load_pct = 50;             // maximum load factor (percent) at capacity_rows: nslots = capacity_rows * 100 / load_pct
+  DevScalars* ds = nullptr;
+  MergeWs ws;
+  Deferral defer;
+  HostIO host;
+  ScanScratch scan;
+  ChangeLog chg;
+  PartScratch part;
+  Profiling prof;
+  ViewShared view;                    // what the indexes' value-ordered views share
   bool fixed_capacity = false;
   uint64_t nbatch = 0;
-  uint32_t* part_counts = nullptr;    // PART_MAX_SHARDS * PART_BLOCKS
-  uint8_t* part_owner = nullptr;      // owner shard of every delta of the batch being partitioned
-  uint64_t part_owner_cap = 0;
   uint32_t epoch = 0;
   uint64_t version = 0;
   uint64_t rows_ub = 0;               // host-side upper bound of resident rows
@@ -181,44 +290,15 @@ struct bmx_ctx {
   uint64_t batch_seq = 0;
   std::deque<std::pair<uint64_t, uint64_t>> inflight;   // (sequence number, deltas) of batches whose row count the host has not seen yet
   std::vector<Index> indexes;
-  // incremental index maintenance (scan_kernels.h): slot -> position in its field's index, and the log of the winners' slots since the
-  // indices were last brought up to date. chg_valid: the log is complete (every merge since then was logged and nothing moved the slots).
-  uint32_t* slot_pos = nullptr; uint64_t slot_pos_n = 0;
-  uint2* chg = nullptr; uint64_t chg_cap = 0, chg_ub = 0;
-  bool chg_valid = false; uint32_t chg_par = 0;
-  uint64_t ix_full_builds = 0, ix_incremental = 0;
-  ViewShared view;                    // what the indexes' value-ordered views share
-  volatile unsigned long long* hres = nullptr;                            // mapped page-locked result words (HRES_*): counts the host waits for arrive without a download
   // bmx_merge_notify: words (possibly in other GPUs' memory) that every merge's last workgroup sets to the number of merges finished since
   SeqPtrs notify{}; uint32_t n_notify = 0; uint64_t notify_seq = 0;
   // bmx_merge_tail_wait: armed = the next default-path merge's resolve kernel polls these words before it ends; waited = a resolve kernel that did so has
   // been enqueued (the bmx_merge_records_after that asks for the same wait then launches no wait kernel)
   struct TailWait { const unsigned long long* words = nullptr; uint32_t n = 0; unsigned long long at_least = 0; } tail_armed, tail_waited;
   bool notify_armed = false;          // set by bmx_merge_records_after around ITS merge: only the merges of the slab protocol count up the peers' free words
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // Deferred compaction (merge_core): the compaction of a device-resident batch is not launched with the batch. If the next call is another such
-  // merge, it goes to a high-priority side stream behind a one-wave wait for that merge's probe kernel to START (= everything of this batch is
-  // done), and runs under that probe kernel; anything else launches it on the context's stream first (flush_pending).
-  struct PendingK3 {
-    bool on = false;
-    const uint8_t* wflag = nullptr; const uint32_t* blk = nullptr; uint32_t n = 0; uint32_t* applied = nullptr;
-    FinishMerge Fin{}; ChgLog L{}; uint32_t mark_created = 0; bool notify_after = false; uint64_t notify_seq = 0; uint64_t seq = 0;
-  } pend;
-  bool defer_enabled = true;
   uint32_t placement_tries = 0, placement_tries_asked = 0; float placement_us_best = 0, placement_us_worst = 0;   // what alloc_table_tuned saw for the current table
   uint64_t n_row_waits = 0;           // merges that waited for a batch in flight to report its row count (wait_for_row_reports)
   int k1_waves = 8;                   // BMX_K1_WAVES (8, 6 or 5): resident waves per SIMD of the probe kernel
-  hipStream_t side = nullptr;
-  bool side_is_callers = false;       // bmx_set_side_stream: the deferred compactions run on a stream the caller owns (the sharded pipeline's exchange stream)
-  uint64_t dseq = 0;                  // deferred merges so far (the sequence numbers in ds->seqw)
-  uint64_t side_last = 0, side_prev = 0;   // sequence numbers of the last two compactions launched on the side stream (0: none this stream is not ordered behind already)
-  uint64_t n_deferred = 0, n_side = 0;   // merges whose compaction was deferred / actually ran on the side stream (bmx_get_deferred_counts)
-  // optional per-kernel profiling (bmx_profile_enable)
-  bool prof_on = false;
-  uint32_t prof_n = 0;
-  std::vector<hipEvent_t> prof_ev;    // 4 events per profiled call
-  std::vector<hipEvent_t> scan_ev;    // 3 events per profiled scan call (before the mask pass, after it, after the emit pass)
-  uint32_t scan_prof_n = 0;
   std::string err;
 };
 
@@ -244,19 +324,13 @@ int fail_hip(bmx_ctx* c, hipError_t e, const char* what) {
     if (e__ != hipSuccess) return fail_hip(ctx, e__, "launch " name); \
   } while (0)
 
-template <class T>
-int dev_alloc(bmx_ctx* ctx, T** p, uint64_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-  if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BMX_ERR_NOMEM : BMX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  return BMX_OK;
+int dev_alloc_all(bmx_ctx* ctx, std::initializer_list<DevBuf> bufs) {   // (alloc_all) BMX_ERR_NOMEM on out-of-memory, BMX_ERR_HIP otherwise
+  hipError_t e = hipSuccess;
+  if (alloc_all(bufs, &e)) return BMX_OK;
+  return fail(ctx, e == hipErrorOutOfMemory ? BMX_ERR_NOMEM : BMX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
 template <class T>
-void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
+int dev_alloc(bmx_ctx* ctx, T** p, uint64_t count) { return dev_alloc_all(ctx, {{*p, std::max<uint64_t>(count, 1) * sizeof(T)}}); }
 void free_columns(Index& ix) { dev_free(ix.ids); dev_free(ix.v64); dev_free(ix.v32); ix.cap = 0; }
 
 // Pull the sticky device status; translate to an error code.
@@ -316,7 +390,7 @@ int wait_for_row_reports(bmx_ctx* ctx, uint64_t n) {
   if (!ctx->host_rows) return BMX_OK;
   const auto t0 = std::chrono::steady_clock::now();
   while ((ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) && !ctx->inflight.empty()) {
-    if (ctx->inflight.size() == 1 && ctx->pend.on) { if (int frc = flush_pending(ctx)) return frc; }   // the only report outstanding is that of a compaction not launched yet
+    if (ctx->inflight.size() == 1 && ctx->defer.pend.on) { if (int frc = flush_pending(ctx)) return frc; }   // the only report outstanding is that of a compaction not launched yet
     const uint64_t want = ctx->inflight.front().first;
     uint32_t spins = 0;
     while (__atomic_load_n(ctx->host_rows + 1, __ATOMIC_ACQUIRE) < want) {
@@ -330,68 +404,24 @@ int wait_for_row_reports(bmx_ctx* ctx, uint64_t n) {
   }
   return BMX_OK;
 }
-int ensure_workspace(bmx_ctx* ctx, uint64_t n) {
-  if (n <= ctx->ws_cap) return BMX_OK;
+int MergeWs::ensure(bmx_ctx* ctx, uint64_t n) {
+  if (n <= cap) return BMX_OK;
   if (int frc = flush_pending(ctx)) return frc;      // a compaction not launched yet reads the workspace this call frees
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>((uint64_t)ctx->ws_cap * 2, MAX_BATCH));
-  cap = std::max<uint64_t>(cap, 1u << 16);
-  cap = (cap + 255) & ~255ull;
-  dev_free(ctx->next); dev_free(ctx->blk_info); dev_free(ctx->blk_follow);
-  for (uint32_t h = 0; h < bmx_ctx::WS_SETS; h++) { dev_free(ctx->wflag[h]); dev_free(ctx->slot_of[h]); dev_free(ctx->fld_ws[h]); }
-  ctx->ws_cap = 0;
-  int rc;
-  if ((rc = dev_alloc(ctx, &ctx->next, cap))) return rc;
-  for (uint32_t h = 0; h < bmx_ctx::WS_SETS; h++)
-    if ((rc = dev_alloc(ctx, &ctx->wflag[h], cap + 16)) || (rc = dev_alloc(ctx, &ctx->slot_of[h], cap)) || (rc = dev_alloc(ctx, &ctx->fld_ws[h], cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->blk_info, bmx_ctx::BLK_SEGS * ((cap / 256 + 16 + 3) & ~3ull))) || (rc = dev_alloc(ctx, &ctx->blk_follow, cap / 256 + 16))) return rc;
-  HIPCHK(hipMemsetAsync(ctx->next, 0, cap * sizeof(uint32_t), ctx->stream));
-  HIPCHK(hipMemsetAsync(ctx->blk_follow, 0, (cap / 256 + 16) * sizeof(uint32_t), ctx->stream));
-  ctx->blk_half = (uint32_t)((cap / 256 + 16 + 3) & ~3ull);    // a multiple of four entries: every segment stays 16-byte aligned for the compaction's wide loads
-  HIPCHK(hipMemsetAsync(ctx->blk_info, 0, bmx_ctx::BLK_SEGS * (size_t)ctx->blk_half * sizeof(uint32_t), ctx->stream));
-  for (uint32_t h = 0; h < bmx_ctx::BLK_SEGS; h++) ctx->blk_clean[h] = true;
-  ctx->ws_cap = (uint32_t)cap;
-  return BMX_OK;
-}
-
-// The copy streams exist only once a host batch is submitted: HIP maps streams onto a few hardware queues, and a device-mode caller
-// that overlaps its own streams (the sharded pipeline: exchange beside merge) must not find them sharing a queue with idle ones of ours
-// (measured: with two extra streams per context the exchange kernel serialised behind the merge kernels, 164 vs 125 us per step).
-int ensure_copy_streams(bmx_ctx* ctx) {
-  if (!ctx->copy_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  if (!ctx->down_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
-  return BMX_OK;
-}
-
-int ensure_staging(bmx_ctx* ctx, int k, uint64_t n) {
-  bmx_ctx::Staging& S = ctx->stg[k];
-  if (n <= S.cap) return BMX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->copy_stream));
-  HIPCHK(hipStreamSynchronize(ctx->down_stream));
-  uint64_t cap = std::max<uint64_t>(n, 1u << 16);
-  cap = (cap + 255) & ~255ull;
-  dev_free(S.id); dev_free(S.field); dev_free(S.ts); dev_free(S.val); dev_free(S.applied); dev_free(S.flags);
-  S.cap = 0;
-  int rc;
-  if ((rc = dev_alloc(ctx, &S.id, cap)) || (rc = dev_alloc(ctx, &S.field, cap)) || (rc = dev_alloc(ctx, &S.ts, cap)) ||
-      (rc = dev_alloc(ctx, &S.val, cap)) || (rc = dev_alloc(ctx, &S.applied, cap)) || (rc = dev_alloc(ctx, &S.flags, cap)))
+  uint64_t c = std::max<uint64_t>(n, std::min<uint64_t>((uint64_t)cap * 2, MAX_BATCH));
+  c = std::max<uint64_t>(c, 1u << 16);
+  c = (c + 255) & ~255ull;
+  const uint64_t half = (c / 256 + 16 + 3) & ~3ull;   // a multiple of four entries: every segment stays 16-byte aligned for the compaction's wide loads
+  cap = 0;
+  if (int rc = dev_alloc_all(ctx, {{next, c * 4}, {wflag[0], c + 16}, {slot_of[0], c * 4}, {fld[0], c * 4}, {wflag[1], c + 16}, {slot_of[1], c * 4}, {fld[1], c * 4},
+                                   {wflag[2], c + 16}, {slot_of[2], c * 4}, {fld[2], c * 4}, {blk_info, BLK_SEGS * half * 4}, {blk_follow, (c / 256 + 16) * 4}}))
     return rc;
-  S.cap = (uint32_t)cap;
-  return BMX_OK;
-}
-
-int ensure_point_read(bmx_ctx* ctx, uint64_t n) {
-  if (n <= ctx->pr_cap) return BMX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->pr_id); dev_free(ctx->pr_field); dev_free(ctx->pr_ts); dev_free(ctx->pr_val); dev_free(ctx->pr_found);
-  ctx->pr_cap = 0;
-  const uint64_t cap = (std::max<uint64_t>(n + n / 4, 1u << 12) + 255) & ~255ull;
-  int rc;
-  if ((rc = dev_alloc(ctx, &ctx->pr_id, cap)) || (rc = dev_alloc(ctx, &ctx->pr_field, cap)) || (rc = dev_alloc(ctx, &ctx->pr_ts, cap)) ||
-      (rc = dev_alloc(ctx, &ctx->pr_val, cap)) || (rc = dev_alloc(ctx, &ctx->pr_found, cap)))
-    return rc;
-  ctx->pr_cap = cap;
+  HIPCHK(hipMemsetAsync(next, 0, c * sizeof(uint32_t), ctx->stream));
+  HIPCHK(hipMemsetAsync(blk_follow, 0, (c / 256 + 16) * sizeof(uint32_t), ctx->stream));
+  blk_half = (uint32_t)half;
+  HIPCHK(hipMemsetAsync(blk_info, 0, BLK_SEGS * (size_t)blk_half * sizeof(uint32_t), ctx->stream));
+  for (uint32_t h = 0; h < BLK_SEGS; h++) blk_clean[h] = true;
+  cap = (uint32_t)c;
   return BMX_OK;
 }
 
@@ -483,8 +513,8 @@ int grow_table(bmx_ctx* ctx, uint64_t capacity_rows) {
   ctx->slots = fresh; ctx->nslots = nslots; ctx->capacity_rows = capacity_rows;
   // the batch epoch keeps counting: next[] still holds links tagged with earlier epochs; the new heads are all 0
   ctx->version++;          // indices are rebuilt on their next use
-  ctx->chg_valid = false;  // every row moved: the recorded slot positions mean nothing any more
-  dev_free(ctx->slot_pos); ctx->slot_pos_n = 0;
+  ctx->chg.valid = false;  // every row moved: the recorded slot positions mean nothing any more
+  dev_free(ctx->chg.slot_pos); ctx->chg.slot_pos_n = 0;
   for (auto& ix : ctx->indexes) ix.has_pos = false;
   return check_status(ctx);
 }
@@ -498,10 +528,10 @@ int grow_table(bmx_ctx* ctx, uint64_t capacity_rows) {
 //   side stream:  k_seq_wait(seqw[0] >= q + 1)  ->  K3(q)  ->  k_seq_signal(seqw[1] = q)
 //   main stream:  K1(q + 1) [block 0 stores seqw[0] = q + 1 when it starts: K2(q) is done]  ->  K2(q + 1) [block 0 returns once seqw[1] >= q]
 // so K3(q) is complete before K1(q + 2) overwrites the workspace half it read, whatever the side stream's queue does. K3 is launched LATE: a
-// merge only records it (ctx->pend); the next deferring merge puts it on the side stream, anything else (bmx_sync, a scan, a host batch, a
+// merge only records it (ctx->defer.pend); the next deferring merge puts it on the side stream, anything else (bmx_sync, a scan, a host batch, a
 // merge on another path, ...) launches it on the context's own stream first (flush_pending, called by every entry point) — after which that
 // stream is ordered behind everything, because the K2 in front of it waited for the only compaction that could still be running on the side.
-void launch_k3(bmx_ctx* ctx, const bmx_ctx::PendingK3& P, hipStream_t ks) {
+void launch_k3(bmx_ctx* ctx, const Deferral::PendingK3& P, hipStream_t ks) {
   hipLaunchKernelGGL((k_compact_winners<FinishMerge>), dim3((uint32_t)(((uint64_t)P.n + 4095) / 4096)), dim3(SEL_THREADS), 0, ks, P.wflag, P.blk, P.n,
                      P.applied, P.Fin, P.L, P.mark_created);
   if (P.notify_after) hipLaunchKernelGGL(k_seq_signal_multi, dim3(1), dim3(64), 0, ks, ctx->notify, ctx->n_notify, (unsigned long long)P.notify_seq);
@@ -514,16 +544,16 @@ bool launches_are_serialized() {
   return on("ROCPROF_COUNTER_COLLECTION") || on("HIP_LAUNCH_BLOCKING") || on("AMD_SERIALIZE_KERNEL") || on("BMX_NO_DEFERRED_COMPACTION");
 }
 int flush_pending(bmx_ctx* ctx) {
-  if (ctx->side_last) {
+  if (ctx->defer.side_last) {
     // the resolve kernel at the end of this stream waited for the compaction launched on the side stream TWO batches ago only: the last one may still be
     // running there (it was released when the last probe kernel started, so this one-wave wait is a formality, and it cannot starve anything)
-    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)&ctx->ds->seqw[1], (unsigned long long)ctx->side_last, &ctx->ds->status, ctx->ds->seq_diag);
+    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)&ctx->ds->seqw[1], (unsigned long long)ctx->defer.side_last, &ctx->ds->status, ctx->ds->seq_diag);
     LAUNCHCHK("k_seq_wait");
-    ctx->side_last = ctx->side_prev = 0;
+    ctx->defer.side_last = ctx->defer.side_prev = 0;
   }
-  if (!ctx->pend.on) return BMX_OK;
-  ctx->pend.on = false;
-  launch_k3(ctx, ctx->pend, ctx->stream);
+  if (!ctx->defer.pend.on) return BMX_OK;
+  ctx->defer.pend.on = false;
+  launch_k3(ctx, ctx->defer.pend, ctx->stream);
   LAUNCHCHK("k_compact_winners");
   return BMX_OK;
 }
@@ -550,9 +580,9 @@ int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fie
   if (unique && strict) return fail(ctx, BMX_ERR_INVALID, "BMX_MERGE_STRICT_FLAGS cannot be combined with BMX_MERGE_UNIQUE_KEYS");
   if (insert_mode != BMX_INSERT_REFERENCE && insert_mode != BMX_INSERT_DELTA) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
   int rc;
-  hipEvent_t* pe = (ctx->prof_on && ctx->prof_n < PROF_MAX_CALLS) ? &ctx->prof_ev[4 * ctx->prof_n] : nullptr;
+  hipEvent_t* pe = (ctx->prof.on && ctx->prof.n < PROF_MAX_CALLS) ? &ctx->prof.ev[4 * ctx->prof.n] : nullptr;
   // the compaction of THIS batch is deferred iff the default path runs (K1 + K2) on a batch big enough to hide it behind; per-kernel profiling brackets every launch
-  const bool deferring = defer && ctx->defer_enabled && !strict && !unique && !pe && n >= DEFER_MIN_N;
+  const bool deferring = defer && ctx->defer.enabled && !strict && !unique && !pe && n >= DEFER_MIN_N;
   if (!deferring && (rc = flush_pending(ctx))) return rc;     // everything else sees the stream in order
   if (n == 0) {
     if ((rc = flush_pending(ctx))) return rc;
@@ -579,61 +609,61 @@ int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fie
       if ((rc = grow_table(ctx, want))) return rc;
     }
   }
-  rc = ensure_workspace(ctx, n);
+  rc = ctx->ws.ensure(ctx, n);
   if (rc) return rc;
-  if (deferring && !ctx->side) {
+  if (deferring && !ctx->defer.side) {
     int lo = 0, hi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));      // hi = the numerically smallest = highest priority: a hardware queue of its own
-    HIPCHK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, hi));
+    HIPCHK(hipStreamCreateWithPriority(&ctx->defer.side, hipStreamNonBlocking, hi));
   }
   if (++ctx->epoch > EPOCH_MAX) {  // tags wrap: forget every claim
     hipLaunchKernelGGL(k_sweep_heads, dim3(2048), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots);
     LAUNCHCHK("k_sweep_heads");
-    HIPCHK(hipMemsetAsync(ctx->next, 0, (size_t)ctx->ws_cap * sizeof(uint32_t), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->blk_follow, 0, ((size_t)ctx->ws_cap / 256 + 16) * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->ws.next, 0, (size_t)ctx->ws.cap * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->ws.blk_follow, 0, ((size_t)ctx->ws.cap / 256 + 16) * sizeof(uint32_t), ctx->stream));
     ctx->epoch = 1;
   }
   // this batch's workspace set and block-summary segment
-  const uint32_t par = (ctx->ws_par = (ctx->ws_par + 1u) % bmx_ctx::WS_SETS);
-  const uint32_t seg = ctx->blk_seg, seg_next = (seg + 1u) % bmx_ctx::BLK_SEGS;
-  ctx->blk_seg = seg_next;
-  uint8_t* wflag = ctx->wflag[par];
-  unsigned long long* ctr = ctx->shard_ctr + (size_t)par * CTR_SHARDS * CTR_STRIDE;
+  const uint32_t par = (ctx->ws.par = (ctx->ws.par + 1u) % MergeWs::SETS);
+  const uint32_t seg = ctx->ws.blk_seg, seg_next = (seg + 1u) % MergeWs::BLK_SEGS;
+  ctx->ws.blk_seg = seg_next;
+  uint8_t* wflag = ctx->ws.wflag[par];
+  unsigned long long* ctr = ctx->ws.shard_ctr + (size_t)par * CTR_SHARDS * CTR_STRIDE;
   MergeArgs A;
   A.slots = ctx->slots; A.nslots = ctx->nslots;
   A.id = id; A.field = field; A.ts = ts; A.val = val; A.recs = recs;
   A.n = (uint32_t)n; A.epoch = ctx->epoch;
-  A.next = ctx->next; A.wflag = wflag; A.flags = flags;
-  A.slot_of = ctx->slot_of[par]; A.blk_follow = ctx->blk_follow; A.shard_ctr = ctr; A.status = &ctx->ds->status;
-  A.blk_info = ctx->blk_info + (size_t)seg * ctx->blk_half; A.blk_next = ctx->blk_info + (size_t)seg_next * ctx->blk_half; A.blk_ents = ctx->blk_half;
+  A.next = ctx->ws.next; A.wflag = wflag; A.flags = flags;
+  A.slot_of = ctx->ws.slot_of[par]; A.blk_follow = ctx->ws.blk_follow; A.shard_ctr = ctr; A.status = &ctx->ds->status;
+  A.blk_info = ctx->ws.blk_info + (size_t)seg * ctx->ws.blk_half; A.blk_next = ctx->ws.blk_info + (size_t)seg_next * ctx->ws.blk_half; A.blk_ents = ctx->ws.blk_half;
   const bool wave_k1 = !strict;       // k_probe_apply: adds into its segment, zeroes the next one
-  if (wave_k1 && !ctx->blk_clean[seg]) HIPCHK(hipMemsetAsync(A.blk_info, 0, (size_t)ctx->blk_half * sizeof(uint32_t), ctx->stream));   // a batch on another path used this segment last
-  ctx->blk_clean[seg] = false; ctx->blk_clean[seg_next] = wave_k1;
+  if (wave_k1 && !ctx->ws.blk_clean[seg]) HIPCHK(hipMemsetAsync(A.blk_info, 0, (size_t)ctx->ws.blk_half * sizeof(uint32_t), ctx->stream));   // a batch on another path used this segment last
+  ctx->ws.blk_clean[seg] = false; ctx->ws.blk_clean[seg_next] = wave_k1;
   A.force = force ? 1u : 0u;
   // the index change log of this batch (written by its compaction): decided here because a deferred compaction reads the deltas' fields from a copy
   ChgLog L{};
-  if (ctx->chg_valid) {
-    if (!strict && (!unique || force) && ctx->chg_ub + n <= ctx->chg_cap && ctx->nslots < (1ull << 31)) {
-      L.chg = ctx->chg; L.base = &ctx->ds->chg_n[ctx->chg_par]; L.next = &ctx->ds->chg_n[ctx->chg_par ^ 1u];
-      L.slot_of = ctx->slot_of[par]; L.field = field; L.recs = recs; L.cap = ctx->chg_cap;
-      if (deferring) { A.fld_out = ctx->fld_ws[par]; L.field = ctx->fld_ws[par]; L.recs = nullptr; }   // the caller's columns need not outlive this call's kernels
-      ctx->chg_par ^= 1u; ctx->chg_ub += n;
+  if (ctx->chg.valid) {
+    if (!strict && (!unique || force) && ctx->chg.ub + n <= ctx->chg.cap && ctx->nslots < (1ull << 31)) {
+      L.chg = ctx->chg.log; L.base = &ctx->ds->chg_n[ctx->chg.par]; L.next = &ctx->ds->chg_n[ctx->chg.par ^ 1u];
+      L.slot_of = ctx->ws.slot_of[par]; L.field = field; L.recs = recs; L.cap = ctx->chg.cap;
+      if (deferring) { A.fld_out = ctx->ws.fld[par]; L.field = ctx->ws.fld[par]; L.recs = nullptr; }   // the caller's columns need not outlive this call's kernels
+      ctx->chg.par ^= 1u; ctx->chg.ub += n;
     } else {
-      ctx->chg_valid = false;   // this batch is not in the log (another merge path, or the log is full): the next scan rebuilds
+      ctx->chg.valid = false;   // this batch is not in the log (another merge path, or the log is full): the next scan rebuilds
     }
   }
   A.log_slots = (L.chg != nullptr) ? 1u : 0u;
-  const bool side_k3 = deferring && ctx->pend.on;     // the compaction of the batch before goes to the side stream, under this batch's probe kernel
+  const bool side_k3 = deferring && ctx->defer.pend.on;     // the compaction of the batch before goes to the side stream, under this batch's probe kernel
   if (deferring) {
-    ++ctx->dseq;
-    A.started = &ctx->ds->seqw[0]; A.started_val = ctx->dseq;
+    ++ctx->defer.seq;
+    A.started = &ctx->ds->seqw[0]; A.started_val = ctx->defer.seq;
     if (side_k3) {
       // this batch's resolve kernel ends only once the compaction launched on the side stream BEFORE the one that goes there now is done: the next probe
       // kernel then reuses nothing a compaction still reads (three workspace sets), and that compaction has had two probe kernels' time
-      if (ctx->side_last) { A.k3_done = &ctx->ds->seqw[1]; A.k3_wait = ctx->side_last; }
-      if (ctx->pend.Fin.n_notify) {   // the slab set of the batch before is free the moment this probe kernel starts: said there, not under it
-        A.notify = ctx->pend.Fin.notify; A.n_notify = ctx->pend.Fin.n_notify; A.notify_value = ctx->pend.Fin.notify_value;
-        ctx->pend.Fin.n_notify = 0;
+      if (ctx->defer.side_last) { A.k3_done = &ctx->ds->seqw[1]; A.k3_wait = ctx->defer.side_last; }
+      if (ctx->defer.pend.Fin.n_notify) {   // the slab set of the batch before is free the moment this probe kernel starts: said there, not under it
+        A.notify = ctx->defer.pend.Fin.notify; A.n_notify = ctx->defer.pend.Fin.n_notify; A.notify_value = ctx->defer.pend.Fin.notify_value;
+        ctx->defer.pend.Fin.n_notify = 0;
       }
     }
   }
@@ -666,12 +696,12 @@ int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fie
   LAUNCHCHK("k_probe_apply");
   if (side_k3) {
     // K1 of this batch is enqueued: the wait below cannot be left without its signal. K3 of the batch before, on the side stream.
-    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->side, (const unsigned long long*)&ctx->ds->seqw[0], (unsigned long long)ctx->dseq, &ctx->ds->status, ctx->ds->seq_diag);
-    launch_k3(ctx, ctx->pend, ctx->side);
-    hipLaunchKernelGGL(k_seq_signal, dim3(1), dim3(64), 0, ctx->side, &ctx->ds->seqw[1], (unsigned long long)ctx->pend.seq);
-    ctx->side_prev = ctx->side_last; ctx->side_last = ctx->pend.seq;
-    ctx->pend.on = false;
-    ctx->n_side++;
+    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->defer.side, (const unsigned long long*)&ctx->ds->seqw[0], (unsigned long long)ctx->defer.seq, &ctx->ds->status, ctx->ds->seq_diag);
+    launch_k3(ctx, ctx->defer.pend, ctx->defer.side);
+    hipLaunchKernelGGL(k_seq_signal, dim3(1), dim3(64), 0, ctx->defer.side, &ctx->ds->seqw[1], (unsigned long long)ctx->defer.pend.seq);
+    ctx->defer.side_prev = ctx->defer.side_last; ctx->defer.side_last = ctx->defer.pend.seq;
+    ctx->defer.pend.on = false;
+    ctx->defer.n_side++;
     LAUNCHCHK("deferred k_compact_winners");
   }
   if (pe) HIPCHK(hipEventRecord(pe[1], ctx->stream));
@@ -692,7 +722,7 @@ int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fie
   ctx->tail_armed = bmx_ctx::TailWait{};
   if (pe) HIPCHK(hipEventRecord(pe[2], ctx->stream));
   // K3: ordered compaction of the winner bytes (+ the index change log while an index is being maintained)
-  bmx_ctx::PendingK3 P;
+  Deferral::PendingK3 P;
   P.wflag = wflag; P.blk = A.blk_info; P.n = (uint32_t)n; P.applied = applied_idx; P.L = L; P.mark_created = mark_created;
   P.Fin = FinishMerge{reinterpret_cast<unsigned long long*>(n_applied), stats, ctr, &ctx->ds->row_count};
   if (ctx->host_rows) { P.Fin.host_mirror = ctx->host_rows; P.Fin.seq = ++ctx->batch_seq; ctx->inflight.emplace_back(P.Fin.seq, n); }
@@ -700,14 +730,14 @@ int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fie
   P.notify_after = notifying && L.chg && !deferring;   // a change log read from the caller's columns: the compaction's workgroups still read the batch, so the peers are told from a launch behind it
   if (notifying) { P.notify_seq = ++ctx->notify_seq; if (!P.notify_after) { P.Fin.notify = ctx->notify; P.Fin.n_notify = ctx->n_notify; P.Fin.notify_value = ctx->notify_seq; } }
   if (deferring) {
-    P.on = true; P.seq = ctx->dseq;
-    ctx->pend = P;
-    ctx->n_deferred++;
+    P.on = true; P.seq = ctx->defer.seq;
+    ctx->defer.pend = P;
+    ctx->defer.n_deferred++;
   } else {
     launch_k3(ctx, P, ctx->stream);
     LAUNCHCHK("k_compact_winners");
   }
-  if (pe) { HIPCHK(hipEventRecord(pe[3], ctx->stream)); ctx->prof_n++; }
+  if (pe) { HIPCHK(hipEventRecord(pe[3], ctx->stream)); ctx->prof.n++; }
   ctx->nbatch++;
   ctx->rows_ub += n;
   ctx->version++;
@@ -721,147 +751,7 @@ int merge_records_internal(bmx_ctx* ctx, uint64_t n, const bmx_delta_rec* recs, 
                           (insert_mode & MERGE_FORCE_INTERNAL) != 0);
 }
 
-// Host batches go through two staging sets. submit: upload on the copy stream, then the merge on the main stream behind an event;
-// collect: results back on the copy stream once the batch's kernels are done. While the host uploads batch b+1 (a pageable
-// hipMemcpyAsync keeps the calling thread busy for the whole transfer) the GPU merges batch b.
-__global__ void k_noop() {}
-__global__ void k_small_tail(const unsigned long long* n_applied, const bmx_merge_stats* stats, const uint32_t* status, SmallOut* out) {
-  if (threadIdx.x == 0) { out->n_applied = *n_applied; out->stats = *stats; out->status = *status; }
-}
-int submit_host(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-                int insert_mode, bool want_flags, uint64_t* ticket, bool inputs_free_on_return) {
-  int k = -1;
-  for (int i = 0; i < 2; i++) if (!ctx->stg[i].busy) { k = i; break; }
-  if (k < 0) return fail(ctx, BMX_ERR_INVALID, "two batches are already in flight: collect the oldest first (bmx_merge_collect)");
-  bmx_ctx::Staging& S = ctx->stg[k];
-  int rc = ensure_copy_streams(ctx);
-  if (rc) return rc;
-  if ((rc = ensure_staging(ctx, k, n))) return rc;
-  if (n) {
-    HIPCHK(hipMemcpyAsync(S.id, id, n * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIPCHK(hipMemcpyAsync(S.field, field, n * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIPCHK(hipMemcpyAsync(S.ts, ts, n * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIPCHK(hipMemcpyAsync(S.val, val, n * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIPCHK(hipEventRecord(S.up, ctx->copy_stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream, S.up, 0));
-    // a copy from page-locked memory (bmx_host_alloc) is truly asynchronous: bmx_merge_submit promises that the arrays may be reused on return
-    if (inputs_free_on_return) HIPCHK(hipEventSynchronize(S.up));
-  }
-  rc = merge_core<false>(ctx, n, S.id, S.field, S.ts, S.val, nullptr, insert_mode & ~MERGE_FORCE_INTERNAL, S.applied, reinterpret_cast<uint64_t*>(S.n_out),
-                         want_flags ? S.flags : nullptr, S.stats, false, (insert_mode & MERGE_FORCE_INTERNAL) != 0);
-  if (rc) return rc;
-  if (S.tail) {
-    hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)S.n_out, (const bmx_merge_stats*)S.stats, (const uint32_t*)&ctx->ds->status, S.tail);
-    LAUNCHCHK("k_small_tail");
-  }
-  HIPCHK(hipEventRecord(S.done, ctx->stream));
-  S.n = n; S.want_flags = want_flags; S.busy = true; S.ticket = ctx->next_ticket++;
-  *ticket = S.ticket;
-  return BMX_OK;
-}
-
-int collect_host(bmx_ctx* ctx, uint64_t ticket, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
-  int k = -1;
-  for (int i = 0; i < 2; i++) if (ctx->stg[i].busy && ctx->stg[i].ticket == ticket) k = i;
-  if (k < 0) return fail(ctx, BMX_ERR_INVALID, "unknown or already collected ticket");
-  if (ctx->stg[1 - k].busy && ctx->stg[1 - k].ticket < ticket) return fail(ctx, BMX_ERR_INVALID, "collect tickets in submission order");
-  bmx_ctx::Staging& S = ctx->stg[k];
-  S.busy = false;
-  bmx_merge_stats hs; std::memset(&hs, 0, sizeof(hs));
-  uint32_t st = 0;
-  if (S.tail) {                         // count, stats and status are in mapped host memory once the batch's last launch is done
-    HIPCHK(hipEventSynchronize(S.done));
-    hs = S.tail->stats; st = S.tail->status;
-  } else {
-    HIPCHK(hipStreamWaitEvent(ctx->down_stream, S.done, 0));
-    HIPCHK(hipMemcpyAsync(&hs, S.stats, sizeof(hs), hipMemcpyDeviceToHost, ctx->down_stream));
-    HIPCHK(hipMemcpyAsync(&st, &ctx->ds->status, sizeof(st), hipMemcpyDeviceToHost, ctx->down_stream));
-    HIPCHK(hipStreamSynchronize(ctx->down_stream));
-  }
-  if (st) return check_status(ctx);     // sticky device error of this (or an earlier, uncollected) batch
-  if (S.n == 0) std::memset(&hs, 0, sizeof(hs));
-  if (applied_idx && hs.n_applied) HIPCHK(hipMemcpyAsync(applied_idx, S.applied, hs.n_applied * 4, hipMemcpyDeviceToHost, ctx->down_stream));
-  if (flags && S.n && S.want_flags) HIPCHK(hipMemcpyAsync(flags, S.flags, S.n, hipMemcpyDeviceToHost, ctx->down_stream));
-  HIPCHK(hipStreamSynchronize(ctx->down_stream));
-  if (!ctx->stg[1 - k].busy && S.n) ctx->rows_ub = hs.n_rows;   // exact again once nothing else is in flight
-  if (n_applied) *n_applied = hs.n_applied;
-  if (stats) *stats = hs;
-  return BMX_OK;
-}
-
-// Small host batch (the reference's sync chunks hold 50 entries, src/bullet-network-sync.js:18): the general path costs ~115 us per call whatever
-// the size (four pageable uploads, two extra streams, three downloads); here the columns are packed into mapped host memory that the kernels read
-// over PCIe, and winners, count, stats and the device status come back through mapped host memory as well.
-constexpr uint64_t SMALL_HOST_N = 32768;
-constexpr int SMALL_PATH_UNAVAILABLE = 1;
-constexpr size_t SMALL_IN_BYTES = SMALL_HOST_N * 28, SMALL_OUT_APPLIED = 0, SMALL_OUT_FLAGS = SMALL_HOST_N * 4, SMALL_OUT_TAIL = SMALL_HOST_N * 5,
-                 SMALL_OUT_BYTES = SMALL_OUT_TAIL + sizeof(SmallOut);
-// result words in mapped host memory: a kernel's last workgroup (or one copy) writes them, the host reads them after the synchronisation it needs anyway
-constexpr int HRES_TOTALS = 0 /* 2 per maintained index */, HRES_RUN = PART_MAX_SHARDS /* one per index */, HRES_ERR = HRES_RUN + PART_MAX_SHARDS / 2, HRES_SPLIT = HRES_ERR + 1 /* 2 */,
-              HRES_SCAN_N = HRES_SPLIT + 2, HRES_WORDS = HRES_SCAN_N + 1;
-bool ensure_hres(bmx_ctx* ctx) {
-  if (ctx->hres) return true;
-  void* p = nullptr;
-  if (hipHostMalloc(&p, HRES_WORDS * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return false; }
-  std::memset(p, 0, HRES_WORDS * sizeof(unsigned long long));
-  ctx->hres = static_cast<volatile unsigned long long*>(p);
-  return true;
-}
-bool ensure_pinned(bmx_ctx* ctx) {   // the two mapped host buffers of the small-call paths (merge, point reads, scans); false = fall back to copies
-  if (ctx->pin_in) return true;
-  { const char* t = std::getenv("BMX_TEST_FAIL_PINNED"); if (t && t[0] == '1') return false; }   // test hook: as if the page-locked allocation had failed
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->pin_in), SMALL_IN_BYTES, hipHostMallocMapped) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&ctx->pin_out), SMALL_OUT_BYTES, hipHostMallocMapped) != hipSuccess) {
-    (void)hipGetLastError();
-    if (ctx->pin_in) { (void)hipHostFree(ctx->pin_in); ctx->pin_in = nullptr; }
-    ctx->pin_out = nullptr;
-    return false;
-  }
-  return true;
-}
-int merge_host_small(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-                     int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
-  if (!ensure_pinned(ctx)) return SMALL_PATH_UNAVAILABLE;
-  // the previous small batch's kernels are done (every call ends with a synchronisation): the buffers are free
-  uint64_t* p_id = reinterpret_cast<uint64_t*>(ctx->pin_in);
-  int64_t* p_ts = reinterpret_cast<int64_t*>(ctx->pin_in + n * 8);
-  int64_t* p_val = reinterpret_cast<int64_t*>(ctx->pin_in + n * 16);
-  uint32_t* p_field = reinterpret_cast<uint32_t*>(ctx->pin_in + n * 24);
-  std::memcpy(p_id, id, n * 8); std::memcpy(p_ts, ts, n * 8); std::memcpy(p_val, val, n * 8); std::memcpy(p_field, field, n * 4);
-  uint32_t* o_applied = reinterpret_cast<uint32_t*>(ctx->pin_out + SMALL_OUT_APPLIED);
-  uint8_t* o_flags = ctx->pin_out + SMALL_OUT_FLAGS;
-  SmallOut* o_tail = reinterpret_cast<SmallOut*>(ctx->pin_out + SMALL_OUT_TAIL);
-  // count and stats go through device scalars first (the merge's last workgroup read-modify-writes them), then one thread copies them out
-  int rc = merge_core<false>(ctx, n, p_id, p_field, p_ts, p_val, nullptr, insert_mode & ~MERGE_FORCE_INTERNAL, applied_idx ? o_applied : nullptr, reinterpret_cast<uint64_t*>(&ctx->ds->n_out),
-                             flags ? o_flags : nullptr, &ctx->ds->stats, false, (insert_mode & MERGE_FORCE_INTERNAL) != 0);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)&ctx->ds->n_out, (const bmx_merge_stats*)&ctx->ds->stats,
-                     (const uint32_t*)&ctx->ds->status, o_tail);
-  LAUNCHCHK("k_small_tail");
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (o_tail->status) return check_status(ctx);
-  const bmx_merge_stats hs = o_tail->stats;
-  if (applied_idx && hs.n_applied) std::memcpy(applied_idx, o_applied, hs.n_applied * 4);
-  if (flags) std::memcpy(flags, o_flags, n);
-  ctx->rows_ub = hs.n_rows; ctx->inflight.clear();
-  if (n_applied) *n_applied = hs.n_applied;
-  if (stats) *stats = hs;
-  return BMX_OK;
-}
-
-int merge_host(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-               int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
-  for (int i = 0; i < 2; i++)
-    if (ctx->stg[i].busy) return fail(ctx, BMX_ERR_INVALID, "a submitted batch is still in flight: collect it before a synchronous merge");
-  if (n && n <= SMALL_HOST_N) {
-    int src = merge_host_small(ctx, n, id, field, ts, val, insert_mode, applied_idx, n_applied, flags, stats);
-    if (src != SMALL_PATH_UNAVAILABLE) return src;
-  }
-  uint64_t ticket = 0;
-  int rc = submit_host(ctx, n, id, field, ts, val, insert_mode, flags != nullptr, &ticket, false);   // collect_host waits for the whole batch
-  if (rc) return rc;
-  return collect_host(ctx, ticket, applied_idx, n_applied, flags, stats);
-}
+#include "bmx_host.inc"
 
 Index* find_index(bmx_ctx* ctx, uint32_t field) {
   for (auto& ix : ctx->indexes)
@@ -874,23 +764,23 @@ constexpr size_t IX_MAINTAINED_MAX = PART_MAX_SHARDS / 2;   // two scratch words
 // slot -> index position map (4 B per slot) and the change log; both exist from the first index build on
 int ensure_ix_maintenance(bmx_ctx* ctx) {
   int rc;
-  if (ctx->slot_pos_n != ctx->nslots) {
+  if (ctx->chg.slot_pos_n != ctx->nslots) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->slot_pos); ctx->slot_pos_n = 0;
+    dev_free(ctx->chg.slot_pos); ctx->chg.slot_pos_n = 0;
     for (auto& ix : ctx->indexes) ix.has_pos = false;
-    ctx->chg_valid = false;
+    ctx->chg.valid = false;
     if (ctx->nslots >= (1ull << 31)) return BMX_OK;      // bit 31 of a log entry is the "created" mark: larger tables are rebuilt, not maintained
-    if ((rc = dev_alloc(ctx, &ctx->slot_pos, ctx->nslots))) { g_err.clear(); ctx->err.clear(); return BMX_OK; }   // no memory for it: fall back to rebuilds
-    ctx->slot_pos_n = ctx->nslots;
-    HIPCHK(hipMemsetAsync(ctx->slot_pos, 0xFF, ctx->nslots * sizeof(uint32_t), ctx->stream));
+    if ((rc = dev_alloc(ctx, &ctx->chg.slot_pos, ctx->nslots))) { g_err.clear(); ctx->err.clear(); return BMX_OK; }   // no memory for it: fall back to rebuilds
+    ctx->chg.slot_pos_n = ctx->nslots;
+    HIPCHK(hipMemsetAsync(ctx->chg.slot_pos, 0xFF, ctx->nslots * sizeof(uint32_t), ctx->stream));
   }
   // the log is only used while it is shorter than max(nslots/8, 1M) entries (fresh_index): size it for that, not for the largest table
   const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(ctx->nslots / 4, 1u << 20) + (1u << 16), 1u << 26);   // 1M .. 64M entries of 8 B
-  if (ctx->chg_cap < want) {
+  if (ctx->chg.cap < want) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->chg); ctx->chg_cap = 0; ctx->chg_valid = false;
-    if ((rc = dev_alloc(ctx, &ctx->chg, want))) { g_err.clear(); ctx->err.clear(); return BMX_OK; }
-    ctx->chg_cap = want;
+    ctx->chg.cap = 0; ctx->chg.valid = false;
+    if ((rc = dev_alloc(ctx, &ctx->chg.log, want))) { g_err.clear(); ctx->err.clear(); return BMX_OK; }
+    ctx->chg.cap = want;
   }
   return BMX_OK;
 }
@@ -898,7 +788,7 @@ int ensure_ix_maintenance(bmx_ctx* ctx) {
 // forget the log: every index is either fresh or about to be rebuilt
 int reset_chg_log(bmx_ctx* ctx) {
   HIPCHK(hipMemsetAsync(ctx->ds->chg_n, 0, sizeof(ctx->ds->chg_n), ctx->stream));
-  ctx->chg_par = 0; ctx->chg_ub = 0;
+  ctx->chg.par = 0; ctx->chg.ub = 0;
   return BMX_OK;
 }
 
@@ -908,9 +798,9 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   if (mrc) return mrc;
   PredSlotField P{ctx->slots, ix->field};
   SelGeom g = sel_geom<PredSlotField::E>(ctx->nslots);
-  hipLaunchKernelGGL((k_sel_count<PredSlotField>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ctx->nslots, g.tiles_per_block, ctx->block_counts);
+  hipLaunchKernelGGL((k_sel_count<PredSlotField>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ctx->nslots, g.tiles_per_block, ctx->scan.block_counts);
   LAUNCHCHK("k_sel_count(index)");
-  hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, ctx->block_counts, g.blocks, &ctx->ds->n_out);
+  hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.block_counts, g.blocks, &ctx->ds->n_out);
   LAUNCHCHK("k_sum_counts");
   unsigned long long n = 0;
   HIPCHK(hipMemcpyAsync(&n, &ctx->ds->n_out, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
@@ -918,15 +808,14 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   if (n + (n >> 4) + (1u << 16) > ix->cap) {   // too little head room left for appended rows: a new set of columns
     free_columns(*ix);
     uint64_t cap = (n + n / 8 + (1u << 16) + 1023) & ~1023ull;   // head room: rows created later are appended
-    int rc;
-    if ((rc = dev_alloc(ctx, &ix->ids, cap)) || (rc = dev_alloc(ctx, &ix->v64, cap)) || (rc = dev_alloc(ctx, &ix->v32, cap + 4))) return rc;
+    if (int rc = dev_alloc_all(ctx, {{ix->ids, cap * sizeof(uint64_t)}, {ix->v64, cap * sizeof(int64_t)}, {ix->v32, (cap + 4) * sizeof(int32_t)}})) return rc;
     ix->cap = cap;
   }
   HIPCHK(hipMemsetAsync(&ctx->ds->wide, 0, sizeof(uint32_t), ctx->stream));
-  EmitIndex Em{ctx->slots, ix->ids, ix->v64, ix->v32, &ctx->ds->wide, ctx->slot_pos};
+  EmitIndex Em{ctx->slots, ix->ids, ix->v64, ix->v32, &ctx->ds->wide, ctx->chg.slot_pos};
   FinishCount Fin{nullptr};
   hipLaunchKernelGGL((k_sel_write<PredSlotField, EmitIndex, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, Em, Fin, ctx->nslots,
-                     g.tiles_per_block, ctx->block_counts);
+                     g.tiles_per_block, ctx->scan.block_counts);
   LAUNCHCHK("k_sel_write(index)");
   uint32_t wide = 0;
   HIPCHK(hipMemcpyAsync(&wide, &ctx->ds->wide, sizeof(wide), hipMemcpyDeviceToHost, ctx->stream));
@@ -935,13 +824,13 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   ix->fits32 = wide == 0;
   ix->content++;             // every position may be another row's now
   ix->version = ctx->version;
-  ix->has_pos = ctx->slot_pos != nullptr;
-  ctx->ix_full_builds++;
+  ix->has_pos = ctx->chg.slot_pos != nullptr;
+  ctx->chg.full_builds++;
   // the log starts (or goes on) only if every index now knows its rows' positions and none is waiting for entries already logged
-  if (ctx->slot_pos && ctx->chg && !ctx->chg_valid && ctx->indexes.size() <= IX_MAINTAINED_MAX) {
+  if (ctx->chg.slot_pos && ctx->chg.log && !ctx->chg.valid && ctx->indexes.size() <= IX_MAINTAINED_MAX) {
     bool all = true;
     for (auto& o : ctx->indexes) all = all && o.has_pos && o.version == ctx->version;
-    if (all) { int rc = reset_chg_log(ctx); if (rc) return rc; ctx->chg_valid = true; }
+    if (all) { int rc = reset_chg_log(ctx); if (rc) return rc; ctx->chg.valid = true; }
   }
   return BMX_OK;
 }
@@ -955,8 +844,8 @@ int refresh_from_log(bmx_ctx* ctx) {
   const auto dbg_t0 = std::chrono::steady_clock::now();
   auto dbg_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - dbg_t0).count(); };
   double dbg_sync = 0;
-  const unsigned long long* n_dev = &ctx->ds->chg_n[ctx->chg_par];
-  const uint64_t ub = ctx->chg_ub;
+  const unsigned long long* n_dev = &ctx->ds->chg_n[ctx->chg.par];
+  const uint64_t ub = ctx->chg.ub;
   struct Res { unsigned long long added; uint32_t wide; uint32_t changed; unsigned long long run; };     // (wide, changed: the two halves of one result word)
   std::vector<Res> res(ctx->indexes.size());
   std::vector<char> capture(ctx->indexes.size(), 0);
@@ -964,7 +853,7 @@ int refresh_from_log(bmx_ctx* ctx) {
   if (ctx->indexes.size() > IX_MAINTAINED_MAX) return fail(ctx, BMX_ERR_INTERNAL, "index maintenance with more indexes than result words");
   if (ub) {
     if (!ensure_hres(ctx)) return fail(ctx, BMX_ERR_NOMEM, "index maintenance: no page-locked memory for the result words");
-    for (size_t k = 0; k < ctx->indexes.size(); k++) ctx->hres[HRES_RUN + k] = ~0ull;
+    for (size_t k = 0; k < ctx->indexes.size(); k++) ctx->host.hres[HRES_RUN + k] = ~0ull;
     for (size_t k = 0; k < ctx->indexes.size(); k++) {
       Index& ix = ctx->indexes[k];
       OrderedView& v = ix.view;
@@ -976,38 +865,38 @@ int refresh_from_log(bmx_ctx* ctx) {
       unsigned long long* d_added = &ctx->ds->part_totals[2 * k];
       uint32_t* d_wide = reinterpret_cast<uint32_t*>(&ctx->ds->part_totals[2 * k + 1]);
       HIPCHK(hipMemsetAsync(d_added, 0, 2 * sizeof(unsigned long long), ctx->stream));
-      PredLogCreated P{ctx->chg, n_dev, ix.field, ctx->slot_pos};
+      PredLogCreated P{ctx->chg.log, n_dev, ix.field, ctx->chg.slot_pos};
       SelGeom g = sel_geom<PredLogCreated::E>(ub);
-      hipLaunchKernelGGL((k_sel_count<PredLogCreated>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ub, g.tiles_per_block, ctx->block_counts);
+      hipLaunchKernelGGL((k_sel_count<PredLogCreated>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ub, g.tiles_per_block, ctx->scan.block_counts);
       LAUNCHCHK("k_sel_count(log)");
-      EmitAppend Em{ctx->chg, ctx->slots, ix.ids, ix.v64, ix.v32, d_wide, ctx->slot_pos, ix.n, ix.cap};
+      EmitAppend Em{ctx->chg.log, ctx->slots, ix.ids, ix.v64, ix.v32, d_wide, ctx->chg.slot_pos, ix.n, ix.cap};
       FinishCount Fin{d_added};
       hipLaunchKernelGGL((k_sel_write<PredLogCreated, EmitAppend, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, Em, Fin, ub, g.tiles_per_block,
-                         ctx->block_counts);
+                         ctx->scan.block_counts);
       LAUNCHCHK("k_sel_write(log)");
       const uint32_t ublocks = (uint32_t)std::min<uint64_t>((ub + 255) / 256, 4096);
-      hipLaunchKernelGGL(k_ix_update, dim3(ublocks), dim3(256), 0, ctx->stream, (const uint2*)ctx->chg, n_dev, (const Slot*)ctx->slots, ix.field, (const uint32_t*)ctx->slot_pos,
+      hipLaunchKernelGGL(k_ix_update, dim3(ublocks), dim3(256), 0, ctx->stream, (const uint2*)ctx->chg.log, n_dev, (const Slot*)ctx->slots, ix.field, (const uint32_t*)ctx->chg.slot_pos,
                          ix.v64, ix.v32, d_wide, capture[k] ? 2u : (v.ordered_after ? 1u : 0u), v.cl_pos, v.cl_old, (uint64_t)v.cl_cap);
       LAUNCHCHK("k_ix_update");
       if (capture[k]) {      // the change run without its holes, in log order (ordered select: no atomics), and its length
         PredChanged PC{v.cl_pos, n_dev};
         SelGeom gc = sel_geom<PredChanged::E>(ub);
-        hipLaunchKernelGGL((k_sel_count<PredChanged>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, ub, gc.tiles_per_block, ctx->block_counts);
+        hipLaunchKernelGGL((k_sel_count<PredChanged>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, ub, gc.tiles_per_block, ctx->scan.block_counts);
         EmitChanged EC{v.cl_pos, v.cl_old, v.cl2_pos, v.cl2_old};
-        FinishCount FC{const_cast<unsigned long long*>(&ctx->hres[HRES_RUN + k])};
-        hipLaunchKernelGGL((k_sel_write<PredChanged, EmitChanged, FinishCount>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, EC, FC, ub, gc.tiles_per_block, ctx->block_counts);
+        FinishCount FC{const_cast<unsigned long long*>(&ctx->host.hres[HRES_RUN + k])};
+        hipLaunchKernelGGL((k_sel_write<PredChanged, EmitChanged, FinishCount>), dim3(gc.blocks), dim3(SEL_THREADS), 0, ctx->stream, PC, EC, FC, ub, gc.tiles_per_block, ctx->scan.block_counts);
         LAUNCHCHK("k_sel_write(change run)");
       }
     }
     // one copy of the indexes' (added, wide | changed) words into the mapped result words; the change runs' lengths were written there by their selects
-    HIPCHK(hipMemcpyAsync(const_cast<unsigned long long*>(&ctx->hres[HRES_TOTALS]), ctx->ds->part_totals, 2 * ctx->indexes.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(const_cast<unsigned long long*>(&ctx->host.hres[HRES_TOTALS]), ctx->ds->part_totals, 2 * ctx->indexes.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     dbg_sync = dbg_us();
     for (size_t k = 0; k < ctx->indexes.size(); k++) {
-      res[k].added = ctx->hres[HRES_TOTALS + 2 * k];
-      const unsigned long long wc = ctx->hres[HRES_TOTALS + 2 * k + 1];
+      res[k].added = ctx->host.hres[HRES_TOTALS + 2 * k];
+      const unsigned long long wc = ctx->host.hres[HRES_TOTALS + 2 * k + 1];
       res[k].wide = (uint32_t)wc; res[k].changed = (uint32_t)(wc >> 32);
-      res[k].run = capture[k] ? ctx->hres[HRES_RUN + k] : 0;
+      res[k].run = capture[k] ? ctx->host.hres[HRES_RUN + k] : 0;
     }
   }
   int rc = reset_chg_log(ctx);
@@ -1017,7 +906,7 @@ int refresh_from_log(bmx_ctx* ctx) {
     if (ub && ix.n + res[k].added > ix.cap) {
       // The appended rows did not fit. The entries it missed are gone with the log, so this index must never be refreshed from a LATER log:
       // without its positions it can only come back through build_index(), and the log stops until every index is fresh again.
-      ix.version = ~0ull; ix.has_pos = false; ctx->chg_valid = false;
+      ix.version = ~0ull; ix.has_pos = false; ctx->chg.valid = false;
       continue;
     }
     if (ub) {
@@ -1032,7 +921,7 @@ int refresh_from_log(bmx_ctx* ctx) {
     }
     ix.version = ctx->version;
   }
-  ctx->ix_incremental++;
+  ctx->chg.incremental++;
   if (ctx->view.debug) std::fprintf(stderr, "bmx: refresh from the log: columns up to date after %.1f us, patches done after %.1f us\n", dbg_sync, dbg_us());
   return BMX_OK;
 }
@@ -1040,7 +929,7 @@ int refresh_from_log(bmx_ctx* ctx) {
 int fresh_index(bmx_ctx* ctx, uint32_t field, Index** out) {
   Index* ix = find_index(ctx, field);
   if (!ix) {  // equals()/range() auto-create a missing index: src/bullet-query.js:194-196, 230-232
-    if (ctx->indexes.size() >= IX_MAINTAINED_MAX) ctx->chg_valid = false;   // more indexes than the maintenance pass has result words for: they are rebuilt when stale
+    if (ctx->indexes.size() >= IX_MAINTAINED_MAX) ctx->chg.valid = false;   // more indexes than the maintenance pass has result words for: they are rebuilt when stale
     ctx->indexes.emplace_back();
     ix = &ctx->indexes.back();
     ix->field = field;
@@ -1048,14 +937,14 @@ int fresh_index(bmx_ctx* ctx, uint32_t field, Index** out) {
   if (ix->version != ctx->version) {
     // maintained: every index has its positions recorded, the log is complete, and it is shorter than a quarter of the table
     // (beyond that the rebuild's two sequential passes over the table are cheaper than the log's random accesses)
-    bool inc = ctx->chg_valid && ix->has_pos && ctx->chg_ub <= std::max<uint64_t>(ctx->nslots / 8, 1u << 20);
+    bool inc = ctx->chg.valid && ix->has_pos && ctx->chg.ub <= std::max<uint64_t>(ctx->nslots / 8, 1u << 20);
     if (inc) for (auto& o : ctx->indexes) inc = inc && (o.has_pos || &o == ix);
     if (inc) {
       int rc = refresh_from_log(ctx);
       if (rc) return rc;
     }
     if (ix->version != ctx->version) {   // not maintained (or its appended rows did not fit): rebuild from the table
-      ctx->chg_valid = false;
+      ctx->chg.valid = false;
       int rc = build_index(ctx, ix);
       if (rc) return rc;
     }
@@ -1064,28 +953,23 @@ int fresh_index(bmx_ctx* ctx, uint32_t field, Index** out) {
   return BMX_OK;
 }
 
-int ensure_scan_out(bmx_ctx* ctx, uint64_t n) {
-  if (n <= ctx->scan_cap) return BMX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->scan_out);
-  ctx->scan_cap = 0;
-  int rc = dev_alloc(ctx, &ctx->scan_out, n);
-  if (rc) return rc;
-  ctx->scan_cap = n;
-  return BMX_OK;
-}
-
-// scratch of the scans: one match bit per index row + one count per 8192-row block (+1 for the total)
-int ensure_scan_scratch(bmx_ctx* ctx, uint64_t n) {
-  uint64_t nb = (n + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS;
-  if (nb <= ctx->scan_blocks_cap) return BMX_OK;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->scan_mask); dev_free(ctx->scan_counts);
-  ctx->scan_blocks_cap = 0;
-  uint64_t cap = nb + nb / 4 + 16;
-  int rc;
-  if ((rc = dev_alloc(ctx, &ctx->scan_mask, cap * (SCAN_BLOCK_ELEMS / 32))) || (rc = dev_alloc(ctx, &ctx->scan_counts, cap + 1))) return rc;
-  ctx->scan_blocks_cap = cap;
+// scratch of the scans for an index of `rows` rows: one match bit per row + one count per 8192-row block (+1 for the total); `out_n` > 0: a device
+// buffer for that many ids of a host-mode answer on its way down
+int ScanScratch::ensure(bmx_ctx* ctx, uint64_t rows, uint64_t out_n) {
+  if (out_n > out_cap) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    out_cap = 0;
+    if (int rc = dev_alloc(ctx, &out, out_n)) return rc;
+    out_cap = out_n;
+  }
+  const uint64_t nb = (rows + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS;
+  if (nb > blocks_cap) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    blocks_cap = 0;
+    const uint64_t cap = nb + nb / 4 + 16;
+    if (int rc = dev_alloc_all(ctx, {{mask, cap * (SCAN_BLOCK_ELEMS / 32) * sizeof(uint32_t)}, {counts, (cap + 1) * sizeof(uint32_t)}})) return rc;
+    blocks_cap = cap;
+  }
   return BMX_OK;
 }
 
@@ -1196,28 +1080,28 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
   // small host-mode answers (count only, or room for at most SCAN_PIN_IDS ids) come back through mapped host memory: no download, one synchronisation
   constexpr uint64_t SCAN_PIN_IDS = 16384;
   static_assert(SCAN_PIN_IDS * 8 + 8 <= SMALL_OUT_BYTES, "pinned scan answer fits the small-call buffer");
-  const bool pinned = host && !ctx->scan_defer && (!out_ids || std::min<uint64_t>(cap, ix->n) <= SCAN_PIN_IDS) && ensure_pinned(ctx);
-  bool direct_host = false;
+  const bool pinned = host && !ctx->scan.defer && (!out_ids || std::min<uint64_t>(cap, ix->n) <= SCAN_PIN_IDS) && ensure_pinned(ctx);
+  bool direct_host = false, staged = false;
   if (host && out_ids) {
     d_cap = std::min<uint64_t>(cap, ix->n);
-    if (pinned) d_out = reinterpret_cast<OutT*>(ctx->pin_out);
+    if (pinned) d_out = reinterpret_cast<OutT*>(ctx->host.pin_out);
     else {
       // a caller's buffer in page-locked memory (bmx_host_alloc, hipHostMalloc, a registered range) is written by the kernels themselves: no staging copy behind the answer
       hipPointerAttribute_t at{};
-      if (!ctx->scan_defer && hipPointerGetAttributes(&at, out_ids) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) { d_out = static_cast<OutT*>(at.devicePointer); direct_host = true; }
+      if (!ctx->scan.defer && hipPointerGetAttributes(&at, out_ids) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) { d_out = static_cast<OutT*>(at.devicePointer); direct_host = true; }
       else {
         (void)hipGetLastError();
-        if ((rc = ensure_scan_out(ctx, std::max<uint64_t>(d_cap, 1)))) return rc;
-        d_out = reinterpret_cast<OutT*>(ctx->scan_out);
+        staged = true;
       }
     }
   }
-  if ((rc = ensure_scan_scratch(ctx, std::max<uint64_t>(ix->n, 1)))) return rc;
-  const bool hres_n = host && !pinned && !ctx->scan_defer && !(ordered && std::is_same<Pred, PredFilter>::value) /* (that one counts with atomics) */ && ensure_hres(ctx);       // the count of a larger host-mode answer: a mapped result word
-  unsigned long long* d_n = host ? (pinned ? reinterpret_cast<unsigned long long*>(ctx->pin_out + SCAN_PIN_IDS * 8) : hres_n ? const_cast<unsigned long long*>(&ctx->hres[HRES_SCAN_N]) : &ctx->ds->n_out)
+  if ((rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), staged ? std::max<uint64_t>(d_cap, 1) : 0))) return rc;
+  if (staged) d_out = reinterpret_cast<OutT*>(ctx->scan.out);
+  const bool hres_n = host && !pinned && !ctx->scan.defer && !(ordered && std::is_same<Pred, PredFilter>::value) /* (that one counts with atomics) */ && ensure_hres(ctx);       // the count of a larger host-mode answer: a mapped result word
+  unsigned long long* d_n = host ? (pinned ? reinterpret_cast<unsigned long long*>(ctx->host.pin_out + SCAN_PIN_IDS * 8) : hres_n ? const_cast<unsigned long long*>(&ctx->host.hres[HRES_SCAN_N]) : &ctx->ds->n_out)
                                  : reinterpret_cast<unsigned long long*>(n_out);
   const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
-  hipEvent_t* se = (ctx->prof_on && ctx->scan_prof_n < PROF_MAX_CALLS && !ctx->scan_ev.empty()) ? &ctx->scan_ev[3 * ctx->scan_prof_n] : nullptr;
+  hipEvent_t* se = (ctx->prof.on && ctx->prof.scan_n < PROF_MAX_CALLS && !ctx->prof.scan_ev.empty()) ? &ctx->prof.scan_ev[3 * ctx->prof.scan_n] : nullptr;
   if (se) HIPCHK(hipEventRecord(se[0], ctx->stream));
   if (ordered) {
     if constexpr (std::is_same<Pred, PredFilter>::value) launch_ordered<POS>(ctx, ix, olo, ohi, d_out, d_cap, d_n, &P);
@@ -1226,7 +1110,7 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     if (se) HIPCHK(hipEventRecord(se[1], ctx->stream));
   } else if (d_out) {
     // pass 1: one read of the column -> match mask + block counts; pass 2: ids / positions from the mask
-    hipLaunchKernelGGL((k_scan_mask<Pred, true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan_mask, ctx->scan_counts);
+    hipLaunchKernelGGL((k_scan_mask<Pred, true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
     LAUNCHCHK("k_scan_mask");
     if (se) HIPCHK(hipEventRecord(se[1], ctx->stream));
     typename std::conditional<POS, EmitPos, EmitIds>::type Em;
@@ -1239,21 +1123,21 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     using EmT = decltype(Em);
     FinishCount Fin{d_n};
     if (nb > SCAN_SUB8_BLOCKS)   // large column: an eighth of the workgroups, each sums the counts in front of it once (no offsets launch)
-      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan_mask, ctx->scan_counts, ix->n, nb, Em, Fin);
+      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
     else
-      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan_mask, ctx->scan_counts, ix->n, nb, Em, Fin);
+      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
     LAUNCHCHK("k_scan_emit");
   } else if (d_n) {
-    hipLaunchKernelGGL((k_scan_mask<Pred, false>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan_mask, ctx->scan_counts);
+    hipLaunchKernelGGL((k_scan_mask<Pred, false>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
     LAUNCHCHK("k_scan_mask(count)");
     if (se) HIPCHK(hipEventRecord(se[1], ctx->stream));
-    hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan_counts, nb, d_n);
+    hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.counts, nb, d_n);
     LAUNCHCHK("k_sum_counts");
   } else if (se) {
     HIPCHK(hipEventRecord(se[1], ctx->stream));
   }
-  if (se) { HIPCHK(hipEventRecord(se[2], ctx->stream)); ctx->scan_prof_n++; }
-  if (host && ctx->scan_defer) { ctx->scan_defer_cap = out_ids ? d_cap : 0; return BMX_OK; }   // the caller fetches with scan_collect()
+  if (se) { HIPCHK(hipEventRecord(se[2], ctx->stream)); ctx->prof.scan_n++; }
+  if (host && ctx->scan.defer) { ctx->scan.defer_cap = out_ids ? d_cap : 0; return BMX_OK; }   // the caller fetches with scan_collect()
   if (pinned) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const unsigned long long m = *d_n;
@@ -1265,25 +1149,21 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     unsigned long long m = 0;
     if (!hres_n) HIPCHK(hipMemcpyAsync(&m, &ctx->ds->n_out, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (hres_n) m = ctx->hres[HRES_SCAN_N];
-    if (out_ids && m && !direct_host) HIPCHK(hipMemcpy(out_ids, ctx->scan_out, std::min<uint64_t>(m, d_cap) * sizeof(OutT), hipMemcpyDeviceToHost));
+    if (hres_n) m = ctx->host.hres[HRES_SCAN_N];
+    if (out_ids && m && !direct_host) HIPCHK(hipMemcpy(out_ids, ctx->scan.out, std::min<uint64_t>(m, d_cap) * sizeof(OutT), hipMemcpyDeviceToHost));
     if (n_out) *n_out = m;
   }
   return BMX_OK;
 }
-template <class Pred>
-int run_scan(bmx_ctx* ctx, const Pred& P, const Index* ix, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem) {
-  return run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem);
-}
 
-// second half of a deferred host-mode scan: wait for the scan enqueued with ctx->scan_defer set, deliver the count and up to `cap` ids
+// second half of a deferred host-mode scan: wait for the scan enqueued with ctx->scan.defer set, deliver the count and up to `cap` ids
 int scan_collect(bmx_ctx* ctx, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
   if (int erc = enter(ctx)) return erc;
   unsigned long long m = 0;
   HIPCHK(hipMemcpyAsync(&m, &ctx->ds->n_out, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint64_t k = std::min<uint64_t>(std::min<uint64_t>(m, ctx->scan_defer_cap), cap);
-  if (out_ids && k) HIPCHK(hipMemcpy(out_ids, ctx->scan_out, k * 8, hipMemcpyDeviceToHost));
+  const uint64_t k = std::min<uint64_t>(std::min<uint64_t>(m, ctx->scan.defer_cap), cap);
+  if (out_ids && k) HIPCHK(hipMemcpy(out_ids, ctx->scan.out, k * 8, hipMemcpyDeviceToHost));
   if (n_out) *n_out = m;
   return BMX_OK;
 }
@@ -1301,17 +1181,54 @@ int scan_range_impl_t(bmx_ctx* ctx, uint32_t field, int64_t lo, int64_t hi, void
     int64_t l = std::max<int64_t>(lo, (int64_t)INT32_MIN + 1), h = std::min<int64_t>(hi, INT32_MAX);
     if (lo > INT32_MAX || hi < INT32_MIN) { l = 1; h = 0; }
     PredRange32 P{ix->v32, (int32_t)l, (int32_t)h, ix->n * sizeof(int32_t) > SCAN_NT_BYTES};
-    const int src = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, ordered, l, h);
-    if (ordered && !src) view_after_query(ctx, ix);
-    return src;
+    rc = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, ordered, l, h);
+  } else {
+    PredRange64 P{ix->v64, std::max<int64_t>(lo, -VAL_MAX), hi, ix->n * sizeof(int64_t) > SCAN_NT_BYTES};    // values live in +-(2^53-1): the clamp changes no answer and keeps tombstones (INT64_MIN) out
+    rc = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, ordered, P.lo, P.hi);
   }
-  PredRange64 P{ix->v64, std::max<int64_t>(lo, -VAL_MAX), hi, ix->n * sizeof(int64_t) > SCAN_NT_BYTES};    // values live in +-(2^53-1): the clamp changes no answer and keeps tombstones (INT64_MIN) out
-  const int src = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, ordered, P.lo, P.hi);
-  if (ordered && !src) view_after_query(ctx, ix);
-  return src;
+  if (ordered && !rc) view_after_query(ctx, ix);
+  return rc;
 }
 int scan_range_impl(bmx_ctx* ctx, uint32_t field, int64_t lo, int64_t hi, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem) {
   return scan_range_impl_t<false>(ctx, field, lo, hi, out_ids, cap, n_out, mem);
+}
+
+// bmx_load_rows / bmx_put_rows: chunks of 2^22 rows (force: bmx_put_rows, stored as given)
+int load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem, bool force) {
+  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
+  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
+  if (int erc = enter(ctx)) return erc;
+  const uint64_t chunk = 1u << 22;
+  for (uint64_t off = 0; off < n; off += chunk) {
+    const uint64_t m = std::min<uint64_t>(chunk, n - off);
+    int rc;
+    if (mem == BMX_MEM_DEVICE)
+      rc = merge_core<false>(ctx, m, id + off, field + off, ts + off, val + off, nullptr, BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr, false, force);
+    else
+      rc = merge_host(ctx, m, id + off, field + off, ts + off, val + off, force ? MERGE_FORCE_INTERNAL : BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  return mem == BMX_MEM_DEVICE ? BMX_OK : check_status(ctx);
+}
+
+// the mean time between consecutive events of the profiled calls: `per` events per call, per - 1 intervals
+int profile_means(bmx_ctx* ctx, bool scan, float* ms_out, uint32_t* n_calls) {
+  if (!ctx || !ms_out || !n_calls) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
+  if (int erc = enter(ctx)) return erc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const std::vector<hipEvent_t>& ev = scan ? ctx->prof.scan_ev : ctx->prof.ev;
+  const uint32_t per = scan ? 3 : 4, calls = scan ? ctx->prof.scan_n : ctx->prof.n;
+  double acc[3] = {0, 0, 0};
+  for (uint32_t i = 0; i < calls; i++)
+    for (uint32_t k = 0; k + 1 < per; k++) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev[per * i + k], ev[per * i + k + 1]));
+      acc[k] += ms;
+    }
+  for (uint32_t k = 0; k + 1 < per; k++) ms_out[k] = calls ? (float)(acc[k] / calls) : 0.f;
+  *n_calls = calls;
+  return BMX_OK;
 }
 
 }  // namespace
@@ -1414,9 +1331,9 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   CR(hipSetDevice(device));
   CR(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
   ctx->stream = ctx->own_stream;
-  CR(hipEventCreate(&ctx->ev0));
-  CR(hipEventCreate(&ctx->ev1));
-  for (int i = 0; i < 2; i++) { CR(hipEventCreateWithFlags(&ctx->stg[i].up, hipEventDisableTiming)); CR(hipEventCreateWithFlags(&ctx->stg[i].done, hipEventDisableTiming)); }
+  CR(hipEventCreate(&ctx->prof.ev0));
+  CR(hipEventCreate(&ctx->prof.ev1));
+  for (auto& S : ctx->host.stg) { CR(hipEventCreateWithFlags(&S.up, hipEventDisableTiming)); CR(hipEventCreateWithFlags(&S.done, hipEventDisableTiming)); }
   const uint64_t nslots = slots_for(capacity_rows, max_load_pct);
   ctx->nslots = nslots;
   ctx->placement_tries_asked = (flags >> 8) & 0xFu;         // BMX_CTX_PLACEMENT_TRIES(n): 0 = the default
@@ -1424,25 +1341,17 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   int rc;
   if ((rc = alloc_table_tuned(ctx, nslots, &ctx->slots))) return bail(rc);
   if ((rc = dev_alloc(ctx, &ctx->ds, 1))) return bail(rc);
-  for (int i = 0; i < 2; i++) {
-    if ((rc = dev_alloc(ctx, &ctx->stg[i].n_out, 1)) || (rc = dev_alloc(ctx, &ctx->stg[i].stats, 1))) return bail(rc);
-    CR(hipMemsetAsync(ctx->stg[i].n_out, 0, sizeof(unsigned long long), ctx->stream));
-    CR(hipMemsetAsync(ctx->stg[i].stats, 0, sizeof(bmx_merge_stats), ctx->stream));
-  }
-  if ((rc = dev_alloc(ctx, &ctx->block_counts, SEL_MAX_BLOCKS))) return bail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->part_counts, PART_MAX_SHARDS * PART_BLOCKS))) return bail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->shard_ctr, bmx_ctx::WS_SETS * CTR_SHARDS * CTR_STRIDE))) return bail(rc);
-  CR(hipMemsetAsync(ctx->shard_ctr, 0, bmx_ctx::WS_SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long), ctx->stream));
+  if ((rc = ctx->host.create(ctx))) return bail(rc);
+  if ((rc = dev_alloc_all(ctx, {{ctx->scan.block_counts, SEL_MAX_BLOCKS * sizeof(uint32_t)}, {ctx->part.counts, PART_MAX_SHARDS * PART_BLOCKS * sizeof(uint32_t)},
+                                {ctx->ws.shard_ctr, MergeWs::SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long)}})))
+    return bail(rc);
+  CR(hipMemsetAsync(ctx->ws.shard_ctr, 0, MergeWs::SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long), ctx->stream));
   // the row-count mirror is an optimisation: without mapped host memory the capacity guard simply synchronises as before
   if (hipHostMalloc(reinterpret_cast<void**>(&ctx->host_rows), 2 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
     ctx->host_rows[0] = 0; ctx->host_rows[1] = 0;
   } else { ctx->host_rows = nullptr; (void)hipGetLastError(); }
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->stg_tails), 2 * sizeof(SmallOut), hipHostMallocMapped) == hipSuccess) {
-    std::memset(ctx->stg_tails, 0, 2 * sizeof(SmallOut));
-    for (int i = 0; i < 2; i++) ctx->stg[i].tail = ctx->stg_tails + i;
-  } else { ctx->stg_tails = nullptr; (void)hipGetLastError(); }
   ctx->fixed_capacity = (flags & BMX_CTX_FIXED_CAPACITY) != 0;
-  ctx->defer_enabled = !launches_are_serialized();
+  ctx->defer.enabled = !launches_are_serialized();
   ctx->view.read_env();
   { const char* kw = std::getenv("BMX_K1_WAVES"); if (kw && kw[0] >= '3' && kw[0] <= '8' && kw[0] != '7' && !kw[1]) ctx->k1_waves = kw[0] - '0'; }
   CR(hipMemsetAsync(ctx->ds, 0, sizeof(DevScalars), ctx->stream));
@@ -1460,32 +1369,17 @@ void bmx_destroy(bmx_ctx* ctx) {
   (void)flush_pending(ctx); // a compaction that was only recorded writes the CALLER's winner list and count: it runs before anything is freed
   (void)hipGetLastError();
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->side) { (void)hipStreamSynchronize(ctx->side); if (!ctx->side_is_callers) (void)hipStreamDestroy(ctx->side); ctx->side = nullptr; }
+  ctx->defer.release();
   for (auto& ix : ctx->indexes) { free_columns(ix); ix.view.release(); }
-  dev_free(ctx->slots); dev_free(ctx->ds); dev_free(ctx->next); dev_free(ctx->blk_info); dev_free(ctx->blk_follow); dev_free(ctx->shard_ctr);
-  for (uint32_t h = 0; h < bmx_ctx::WS_SETS; h++) { dev_free(ctx->wflag[h]); dev_free(ctx->slot_of[h]); dev_free(ctx->fld_ws[h]); }
-  if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-  for (int i = 0; i < 2; i++) {
-    bmx_ctx::Staging& S = ctx->stg[i];
-    dev_free(S.id); dev_free(S.field); dev_free(S.ts); dev_free(S.val); dev_free(S.applied); dev_free(S.flags); dev_free(S.n_out); dev_free(S.stats);
-    if (S.up) (void)hipEventDestroy(S.up);
-    if (S.done) (void)hipEventDestroy(S.done);
-  }
-  dev_free(ctx->pr_id); dev_free(ctx->pr_field); dev_free(ctx->pr_ts); dev_free(ctx->pr_val); dev_free(ctx->pr_found);
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  if (ctx->down_stream) { (void)hipStreamSynchronize(ctx->down_stream); (void)hipStreamDestroy(ctx->down_stream); }
-  dev_free(ctx->slot_pos); dev_free(ctx->chg);
+  dev_free(ctx->slots); dev_free(ctx->ds);
+  ctx->ws.release();
+  ctx->host.release();     // (the copy and download streams finish before the staging goes back)
+  ctx->chg.release();
   ctx->view.release();
-  if (ctx->hres) (void)hipHostFree(const_cast<unsigned long long*>(ctx->hres));
-  if (ctx->host_rows) { (void)hipHostFree(ctx->host_rows); ctx->host_rows = nullptr; }
-  if (ctx->stg_tails) { (void)hipHostFree(ctx->stg_tails); ctx->stg_tails = nullptr; ctx->stg[0].tail = ctx->stg[1].tail = nullptr; }
-  if (ctx->pin_in) { (void)hipHostFree(ctx->pin_in); ctx->pin_in = nullptr; }
-  if (ctx->pin_out) { (void)hipHostFree(ctx->pin_out); ctx->pin_out = nullptr; }
-  dev_free(ctx->scan_out); dev_free(ctx->block_counts); dev_free(ctx->part_counts); dev_free(ctx->part_owner); dev_free(ctx->scan_mask); dev_free(ctx->scan_counts);
-  for (auto ev : ctx->prof_ev) (void)hipEventDestroy(ev);
-  for (auto ev : ctx->scan_ev) (void)hipEventDestroy(ev);
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+  ctx->scan.release();
+  ctx->part.release();
+  ctx->prof.release();
+  if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
@@ -1604,39 +1498,10 @@ int bmx_merge_records_after(bmx_ctx* ctx, const uint64_t* wait_words_dev, uint32
 }
 
 int bmx_load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) {
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (int erc = enter(ctx)) return erc;
-  const uint64_t chunk = 1u << 22;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    uint64_t m = std::min<uint64_t>(chunk, n - off);
-    int rc;
-    if (mem == BMX_MEM_DEVICE)
-      rc = merge_core<false>(ctx, m, id + off, field + off, ts + off, val + off, nullptr, BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr);
-    else
-      rc = merge_host(ctx, m, id + off, field + off, ts + off, val + off, BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return mem == BMX_MEM_DEVICE ? BMX_OK : check_status(ctx);
+  return load_rows(ctx, n, id, field, ts, val, mem, false);
 }
-
 int bmx_put_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) {
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (int erc = enter(ctx)) return erc;
-  const uint64_t chunk = 1u << 22;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - off);
-    int rc;
-    if (mem == BMX_MEM_DEVICE)
-      rc = merge_core<false>(ctx, m, id + off, field + off, ts + off, val + off, nullptr, BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr, false, /*force=*/true);
-    else
-      rc = merge_host(ctx, m, id + off, field + off, ts + off, val + off, MERGE_FORCE_INTERNAL, nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return mem == BMX_MEM_DEVICE ? BMX_OK : check_status(ctx);
+  return load_rows(ctx, n, id, field, ts, val, mem, true);
 }
 
 int bmx_get_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, int64_t* ts, int64_t* val, uint8_t* found, int mem) {
@@ -1652,11 +1517,11 @@ int bmx_get_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* f
   }
   if (mem != BMX_MEM_HOST) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
   if (n <= 8192 && ensure_pinned(ctx)) {   // few keys: keys and answers through mapped host memory, one launch and one synchronisation (25 us instead of 67)
-    uint64_t* p_id = reinterpret_cast<uint64_t*>(ctx->pin_in);
-    uint32_t* p_f = reinterpret_cast<uint32_t*>(ctx->pin_in + n * 8);
-    int64_t* o_ts = reinterpret_cast<int64_t*>(ctx->pin_out);
-    int64_t* o_val = reinterpret_cast<int64_t*>(ctx->pin_out + n * 8);
-    uint8_t* o_found = ctx->pin_out + n * 16;
+    uint64_t* p_id = reinterpret_cast<uint64_t*>(ctx->host.pin_in);
+    uint32_t* p_f = reinterpret_cast<uint32_t*>(ctx->host.pin_in + n * 8);
+    int64_t* o_ts = reinterpret_cast<int64_t*>(ctx->host.pin_out);
+    int64_t* o_val = reinterpret_cast<int64_t*>(ctx->host.pin_out + n * 8);
+    uint8_t* o_found = ctx->host.pin_out + n * 16;
     std::memcpy(p_id, id, n * 8); std::memcpy(p_f, field, n * 4);
     hipLaunchKernelGGL(k_get_rows, dim3(blocks), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots, (uint32_t)n, (const uint64_t*)p_id, (const uint32_t*)p_f, o_ts, o_val, o_found);
     LAUNCHCHK("k_get_rows");
@@ -1666,13 +1531,13 @@ int bmx_get_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* f
   }
   int rc = ensure_point_read(ctx, n);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(ctx->pr_id, id, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->pr_field, field, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_get_rows, dim3(blocks), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots, (uint32_t)n, ctx->pr_id, ctx->pr_field, ctx->pr_ts, ctx->pr_val, ctx->pr_found);
+  HIPCHK(hipMemcpyAsync(ctx->host.pr_id, id, n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->host.pr_field, field, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_get_rows, dim3(blocks), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots, (uint32_t)n, ctx->host.pr_id, ctx->host.pr_field, ctx->host.pr_ts, ctx->host.pr_val, ctx->host.pr_found);
   LAUNCHCHK("k_get_rows");
-  HIPCHK(hipMemcpyAsync(ts, ctx->pr_ts, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(val, ctx->pr_val, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(found, ctx->pr_found, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ts, ctx->host.pr_ts, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(val, ctx->host.pr_val, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(found, ctx->host.pr_found, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return BMX_OK;
 }
@@ -1696,15 +1561,15 @@ int bmx_dump_rows(bmx_ctx* ctx, uint64_t cap, uint64_t* id, uint32_t* field, int
   int rc = BMX_OK;
   if (host && cap) {   // persistent (grow-only) device columns: no allocation per call
     if ((rc = ensure_point_read(ctx, cap))) return rc;
-    d_id = ctx->pr_id; d_f = ctx->pr_field; d_ts = ctx->pr_ts; d_val = ctx->pr_val;
+    d_id = ctx->host.pr_id; d_f = ctx->host.pr_field; d_ts = ctx->host.pr_ts; d_val = ctx->host.pr_val;
   }
   PredSlotAny P{ctx->slots};
   EmitRows Em{ctx->slots, cap, d_id, d_f, d_ts, d_val};
   FinishCount Fin{host ? &ctx->ds->n_out : reinterpret_cast<unsigned long long*>(n_out)};
   SelGeom g = sel_geom<PredSlotAny::E>(ctx->nslots);
-  hipLaunchKernelGGL((k_sel_count<PredSlotAny>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ctx->nslots, g.tiles_per_block, ctx->block_counts);
+  hipLaunchKernelGGL((k_sel_count<PredSlotAny>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, ctx->nslots, g.tiles_per_block, ctx->scan.block_counts);
   hipLaunchKernelGGL((k_sel_write<PredSlotAny, EmitRows, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, ctx->stream, P, Em, Fin, ctx->nslots,
-                     g.tiles_per_block, ctx->block_counts);
+                     g.tiles_per_block, ctx->scan.block_counts);
   hipError_t e = hipGetLastError();
   if (host) {
     unsigned long long m = 0;
@@ -1738,11 +1603,7 @@ int bmx_index_drop(bmx_ctx* ctx, uint32_t field) {
     if (ctx->indexes[i].field == field) {
       free_columns(ctx->indexes[i]); ctx->indexes[i].view.release();
       ctx->indexes.erase(ctx->indexes.begin() + (long)i);
-      if (ctx->indexes.empty()) {   // nothing left to maintain: the merges stop logging and the maintenance memory goes back
-        ctx->chg_valid = false; ctx->chg_ub = 0;
-        dev_free(ctx->chg); ctx->chg_cap = 0;
-        dev_free(ctx->slot_pos); ctx->slot_pos_n = 0;
-      }
+      if (ctx->indexes.empty()) ctx->chg.release();   // nothing left to maintain: the merges stop logging and the maintenance memory goes back
       return BMX_OK;
     }
   return fail(ctx, BMX_ERR_NO_INDEX, "no index on that field");
@@ -1760,8 +1621,8 @@ int bmx_index_size(bmx_ctx* ctx, uint32_t field, uint64_t* n_out) {
 
 int bmx_index_refresh_counts(bmx_ctx* ctx, uint64_t* full_builds, uint64_t* incremental_updates) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (full_builds) *full_builds = ctx->ix_full_builds;
-  if (incremental_updates) *incremental_updates = ctx->ix_incremental;
+  if (full_builds) *full_builds = ctx->chg.full_builds;
+  if (incremental_updates) *incremental_updates = ctx->chg.incremental;
   return BMX_OK;
 }
 
@@ -1852,7 +1713,7 @@ int bmx_scan_filter(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint64
     if (!src) view_after_query(ctx, ix);
     return src;
   }
-  return run_scan(ctx, P, ix, out_ids, cap, n_out, mem);
+  return run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem);
 }
 
 static int partition_impl(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
@@ -1867,16 +1728,16 @@ static int partition_impl(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const ui
   if (int erc = enter(ctx)) return erc;
   uint32_t per_block = (uint32_t)((n + PART_BLOCKS - 1) / PART_BLOCKS);
   per_block = std::max<uint32_t>(PART_TILE, (per_block + PART_TILE - 1) / PART_TILE * PART_TILE);
-  if (n > ctx->part_owner_cap) {
+  if (n > ctx->part.owner_cap) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->part_owner); ctx->part_owner_cap = 0;
-    int rc = dev_alloc(ctx, &ctx->part_owner, n + 256);
+    ctx->part.owner_cap = 0;
+    int rc = dev_alloc(ctx, &ctx->part.owner, n + 256);
     if (rc) return rc;
-    ctx->part_owner_cap = n;
+    ctx->part.owner_cap = n;
   }
-  hipLaunchKernelGGL(k_part_count, dim3(PART_BLOCKS), dim3(256), 0, ctx->stream, id, (uint32_t)n, nshards, per_block, ctx->part_counts, ctx->part_owner);
+  hipLaunchKernelGGL(k_part_count, dim3(PART_BLOCKS), dim3(256), 0, ctx->stream, id, (uint32_t)n, nshards, per_block, ctx->part.counts, ctx->part.owner);
   LAUNCHCHK("k_part_count");
-  hipLaunchKernelGGL(k_part_scatter, dim3(PART_BLOCKS), dim3(256), 0, ctx->stream, id, field, ts, val, (const uint8_t*)ctx->part_owner, (uint32_t)n, nshards, per_block, ctx->part_counts,
+  hipLaunchKernelGGL(k_part_scatter, dim3(PART_BLOCKS), dim3(256), 0, ctx->stream, id, field, ts, val, (const uint8_t*)ctx->part.owner, (uint32_t)n, nshards, per_block, ctx->part.counts,
                      recs_out, reinterpret_cast<unsigned long long*>(counts_out_dev), (uint32_t)slab, &ctx->ds->status, po);
   LAUNCHCHK("k_part_scatter");
   return BMX_OK;
@@ -2018,7 +1879,7 @@ int bmx_merge_notify(bmx_ctx* ctx, uint64_t* const* words, uint32_t nwords) {
 int bmx_set_deferred_compaction(bmx_ctx* ctx, int on) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int erc = enter(ctx)) return erc;
-  ctx->defer_enabled = on != 0 && !launches_are_serialized();    // (never where kernels run one at a time: see launches_are_serialized)
+  ctx->defer.enabled = on != 0 && !launches_are_serialized();    // (never where kernels run one at a time: see launches_are_serialized)
   return BMX_OK;
 }
 int bmx_set_wait_limit(bmx_ctx* ctx, double seconds) {
@@ -2032,9 +1893,9 @@ int bmx_set_side_stream(bmx_ctx* ctx, void* hip_stream) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int erc = enter(ctx)) return erc;            // whatever is recorded or still on the old side stream is ordered into the context's stream first
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (ctx->side) { HIPCHK(hipStreamSynchronize(ctx->side)); if (!ctx->side_is_callers) (void)hipStreamDestroy(ctx->side); }
-  ctx->side = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : nullptr;    // nullptr: the next deferring merge creates the context's own again
-  ctx->side_is_callers = hip_stream != nullptr;
+  if (ctx->defer.side) { HIPCHK(hipStreamSynchronize(ctx->defer.side)); if (!ctx->defer.side_is_callers) (void)hipStreamDestroy(ctx->defer.side); }
+  ctx->defer.side = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : nullptr;    // nullptr: the next deferring merge creates the context's own again
+  ctx->defer.side_is_callers = hip_stream != nullptr;
   return BMX_OK;
 }
 int bmx_merge_fence(bmx_ctx* ctx) {
@@ -2043,8 +1904,8 @@ int bmx_merge_fence(bmx_ctx* ctx) {
 }
 int bmx_get_deferred_counts(bmx_ctx* ctx, uint64_t* deferred, uint64_t* on_side_stream) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (deferred) *deferred = ctx->n_deferred;
-  if (on_side_stream) *on_side_stream = ctx->n_side;
+  if (deferred) *deferred = ctx->defer.n_deferred;
+  if (on_side_stream) *on_side_stream = ctx->defer.n_side;
   return BMX_OK;
 }
 
@@ -2065,79 +1926,47 @@ int bmx_get_placement(bmx_ctx* ctx, uint32_t* candidates, float* probe_us_chosen
 int bmx_timer_start(bmx_ctx* ctx) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int erc = enter(ctx)) return erc;
-  HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-  return BMX_OK;
-}
-int bmx_timer_stop(bmx_ctx* ctx, float* ms_out) {
-  if (!ctx || !ms_out) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
-  if (int erc = enter(ctx)) return erc;          // the last batch's compaction is part of what is timed
-  HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(hipEventSynchronize(ctx->ev1));
-  HIPCHK(hipEventElapsedTime(ms_out, ctx->ev0, ctx->ev1));
+  HIPCHK(hipEventRecord(ctx->prof.ev0, ctx->stream));
   return BMX_OK;
 }
 
 int bmx_timer_mark(bmx_ctx* ctx) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int erc = enter(ctx)) return erc;          // the last batch's compaction is part of what is timed
-  HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->prof.ev1, ctx->stream));
   return BMX_OK;
 }
 int bmx_timer_elapsed(bmx_ctx* ctx, float* ms_out) {
   if (!ctx || !ms_out) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
   HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipEventSynchronize(ctx->ev1));
-  HIPCHK(hipEventElapsedTime(ms_out, ctx->ev0, ctx->ev1));
+  HIPCHK(hipEventSynchronize(ctx->prof.ev1));
+  HIPCHK(hipEventElapsedTime(ms_out, ctx->prof.ev0, ctx->prof.ev1));
   return BMX_OK;
+}
+int bmx_timer_stop(bmx_ctx* ctx, float* ms_out) {
+  if (!ctx || !ms_out) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
+  if (int rc = bmx_timer_mark(ctx)) return rc;
+  return bmx_timer_elapsed(ctx, ms_out);
 }
 
 int bmx_profile_enable(bmx_ctx* ctx, int on) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int erc = enter(ctx)) return erc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (on && ctx->prof_ev.empty()) {
-    ctx->prof_ev.resize(4 * PROF_MAX_CALLS, nullptr);
-    for (auto& ev : ctx->prof_ev) HIPCHK(hipEventCreate(&ev));
-    ctx->scan_ev.resize(3 * PROF_MAX_CALLS, nullptr);
-    for (auto& ev : ctx->scan_ev) HIPCHK(hipEventCreate(&ev));
+  if (on && ctx->prof.ev.empty()) {
+    ctx->prof.ev.resize(4 * PROF_MAX_CALLS, nullptr);
+    for (auto& ev : ctx->prof.ev) HIPCHK(hipEventCreate(&ev));
+    ctx->prof.scan_ev.resize(3 * PROF_MAX_CALLS, nullptr);
+    for (auto& ev : ctx->prof.scan_ev) HIPCHK(hipEventCreate(&ev));
   }
-  ctx->prof_on = on != 0;
-  ctx->prof_n = 0;
-  ctx->scan_prof_n = 0;
+  ctx->prof.on = on != 0;
+  ctx->prof.n = 0;
+  ctx->prof.scan_n = 0;
   return BMX_OK;
 }
 
-int bmx_profile_read(bmx_ctx* ctx, float ms_out[3], uint32_t* n_calls) {
-  if (!ctx || !ms_out || !n_calls) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
-  if (int erc = enter(ctx)) return erc;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  double acc[3] = {0, 0, 0};
-  for (uint32_t i = 0; i < ctx->prof_n; i++)
-    for (int k = 0; k < 3; k++) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ctx->prof_ev[4 * i + k], ctx->prof_ev[4 * i + k + 1]));
-      acc[k] += ms;
-    }
-  for (int k = 0; k < 3; k++) ms_out[k] = ctx->prof_n ? (float)(acc[k] / ctx->prof_n) : 0.f;
-  *n_calls = ctx->prof_n;
-  return BMX_OK;
-}
-
-int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) {
-  if (!ctx || !ms_out || !n_calls) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
-  if (int erc = enter(ctx)) return erc;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  double acc[2] = {0, 0};
-  for (uint32_t i = 0; i < ctx->scan_prof_n; i++)
-    for (int k = 0; k < 2; k++) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ctx->scan_ev[3 * i + k], ctx->scan_ev[3 * i + k + 1]));
-      acc[k] += ms;
-    }
-  for (int k = 0; k < 2; k++) ms_out[k] = ctx->scan_prof_n ? (float)(acc[k] / ctx->scan_prof_n) : 0.f;
-  *n_calls = ctx->scan_prof_n;
-  return BMX_OK;
-}
+int bmx_profile_read(bmx_ctx* ctx, float ms_out[3], uint32_t* n_calls) { return profile_means(ctx, false, ms_out, n_calls); }
+int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { return profile_means(ctx, true, ms_out, n_calls); }
 
 }  // extern "C"
 

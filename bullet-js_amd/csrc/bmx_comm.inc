@@ -275,7 +275,7 @@ int bmx_comm_create(uint32_t nshards, const int* devices, uint64_t capacity_rows
   for (uint32_t g = 0; g < nshards; g++) {
     int rc = bmx_create(devices[g], capacity_rows_per_shard, flags, &c->sh[g]);
     if (rc) { c->err = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(nullptr); return bail(rc); }
-    c->sh[g]->defer_enabled = false;   // the communicator orders its shards' streams with events right behind their merges: every compaction stays on its stream
+    c->sh[g]->defer.enabled = false;   // the communicator orders its shards' streams with events right behind their merges: every compaction stays on its stream
     bmx_comm::Shard& S = c->s[g];
     if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&S.counts), PART_MAX_SHARDS * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&S.n_applied), sizeof(unsigned long long)) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&S.stats), sizeof(bmx_merge_stats)) != hipSuccess ||
@@ -482,9 +482,9 @@ static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32
   uint64_t* want = (out_ids && cap) ? out_ids : nullptr;
   for (uint32_t g = 0; g < c->N; g++) {
     bmx_ctx* x = c->sh[g];
-    x->scan_defer = true;
+    x->scan.defer = true;
     const int rc = terms ? bmx_scan_filter(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST) : bmx_scan_range(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST);
-    x->scan_defer = false;
+    x->scan.defer = false;
     if (rc) {   // nothing of the shards before g is delivered; their scans finish on their own streams
       return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));
     }

@@ -25,18 +25,6 @@ void OrderedView::release() {
   ord_cap = 0; ord_n = 0; ord_content = ~0ull; ord_cap2 = 0; cl_cap = 0;
 }
 
-// One all-or-nothing group of device buffers: every pointer of the list gets its buffer, or none does (what was allocated goes back, the HIP error is cleared).
-struct DevBuf { void** p; size_t bytes; template <class T> DevBuf(T*& q, size_t b) : p(reinterpret_cast<void**>(&q)), bytes(b) {} };
-bool alloc_all(std::initializer_list<DevBuf> bufs) {
-  for (const DevBuf* b = bufs.begin(); b != bufs.end(); b++)
-    if (hipMalloc(b->p, b->bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      *b->p = nullptr;
-      for (const DevBuf* f = bufs.begin(); f != b; f++) dev_free(*f->p);
-      return false;
-    }
-  return true;
-}
 // the page-locked error word and the event through which a background rewrite reports (false: not to be had, no rewrite runs behind an answer)
 bool ensure_rewrite_report(ViewShared& sh) {
   if (!sh.err_host && hipHostMalloc(reinterpret_cast<void**>(&sh.err_host), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); sh.err_host = nullptr; }
@@ -50,7 +38,7 @@ constexpr uint64_t VIEW_PATCH_MAX_LOG = 1ull << 24;     // a longer change log i
 int ensure_change_run(bmx_ctx* ctx, OrderedView& v, uint64_t ub) {
   if (v.cl_cap >= ub) return BMX_OK;
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  dev_free(v.cl_pos); dev_free(v.cl_old); dev_free(v.cl2_pos); dev_free(v.cl2_old); v.cl_cap = 0;
+  v.cl_cap = 0;
   const uint64_t cap = (ub + ub / 2 + (1u << 16) + 255) & ~255ull;
   if (alloc_all({{v.cl_pos, cap * sizeof(uint32_t)}, {v.cl_old, cap * sizeof(int64_t)}, {v.cl2_pos, cap * sizeof(uint32_t)}, {v.cl2_old, cap * sizeof(int64_t)}})) v.cl_cap = cap;
   return BMX_OK;
@@ -59,7 +47,6 @@ int ensure_view_scratch(bmx_ctx* ctx, uint64_t keys, uint64_t tiles) {
   ViewShared& sh = ctx->view;
   if (keys > sh.vk_cap) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; i++) { dev_free(sh.vk_v[i]); dev_free(sh.vk_p[i]); }
     sh.vk_cap = 0;
     const uint64_t cap = (keys + keys / 4 + (1u << 16) + 255) & ~255ull;
     if (!alloc_all({{sh.vk_v[0], cap * 8}, {sh.vk_p[0], cap * 4}, {sh.vk_v[1], cap * 8}, {sh.vk_p[1], cap * 4}})) return fail(ctx, BMX_ERR_NOMEM, "view patch: out of device memory");
@@ -67,7 +54,7 @@ int ensure_view_scratch(bmx_ctx* ctx, uint64_t keys, uint64_t tiles) {
   }
   if (tiles + 1 > sh.vk_tiles_cap) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(sh.vk_sv); dev_free(sh.vk_sp); dev_free(sh.vk_d0); dev_free(sh.vk_y0); sh.vk_tiles_cap = 0;
+    sh.vk_tiles_cap = 0;
     const uint64_t cap = tiles + tiles / 4 + 1024;
     if (!alloc_all({{sh.vk_sv, cap * 8}, {sh.vk_sp, cap * 4}, {sh.vk_d0, cap * 4}, {sh.vk_y0, cap * 4}})) return fail(ctx, BMX_ERR_NOMEM, "view patch: out of device memory");
     sh.vk_tiles_cap = cap;
@@ -132,7 +119,7 @@ template <class T>
 bool ensure_view_spare(bmx_ctx* ctx, OrderedView& v, uint64_t nz) {
   if (nz <= v.ord_cap2 && v.s_val2) return true;
   if (v.s_val2) (void)hipStreamSynchronize(ctx->stream);
-  dev_free(v.s_val2); dev_free(v.s_pos2); dev_free(v.s_ids2); v.ord_cap2 = 0;
+  v.ord_cap2 = 0;
   const uint64_t cap = std::max<uint64_t>(v.ord_cap, nz + nz / 8 + 1024);
   if (!alloc_all({{v.s_val2, cap * sizeof(T)}, {v.s_pos2, cap * sizeof(uint32_t)}, {v.s_ids2, cap * sizeof(uint64_t)}})) return false;
   v.ord_cap2 = cap;
@@ -219,10 +206,10 @@ int patch_view_t(bmx_ctx* ctx, Index& ix, uint64_t c, uint64_t n0, uint64_t adde
   ViewRun<T> X{static_cast<T*>(v.s_val), v.s_pos, v.s_ids};
   auto finish = [&]() -> int {       // the error word comes back; 0 = everything enqueued above did what it should
     hipError_t e = hipGetLastError();
-    ctx->hres[HRES_ERR] = 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<unsigned long long*>(&ctx->hres[HRES_ERR]), &ctx->ds->view_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    ctx->host.hres[HRES_ERR] = 1;
+    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<unsigned long long*>(&ctx->host.hres[HRES_ERR]), &ctx->ds->view_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return (e != hipSuccess || (uint32_t)ctx->hres[HRES_ERR]) ? 1 : 0;
+    return (e != hipSuccess || (uint32_t)ctx->host.hres[HRES_ERR]) ? 1 : 0;
   };
   auto rewrite_main = [&](const T* dv, const uint32_t* dp, uint64_t nd, const T* yv, const uint32_t* yp, uint64_t ny) -> bool {   // step 3
     const uint64_t nz = nx - nd + ny;
@@ -266,19 +253,19 @@ int patch_view_t(bmx_ctx* ctx, Index& ix, uint64_t c, uint64_t n0, uint64_t adde
       const int dc = v.pcur, ic = v.icur;
       unsigned long long hc[2] = {0, 0};
       if (c) {
-        ctx->hres[HRES_SPLIT] = ctx->hres[HRES_SPLIT + 1] = ~0ull;
+        ctx->host.hres[HRES_SPLIT] = ctx->host.hres[HRES_SPLIT + 1] = ~0ull;
         (void)hipMemsetAsync(v.pi_dead, 0, v.npi, st);
         hipLaunchKernelGGL((k_view_flag_in<T>), dim3((uint32_t)((c + 255) / 256)), dim3(256), 0, st, Dv, Dp, (uint32_t)c, (const T*)piv[ic], (const uint32_t*)v.pi_p[ic], (uint32_t)v.npi, flag, v.pi_dead);
         SelGeom g = sel_geom<1>(c);
         for (uint32_t want = 0; want < 2; want++) {
           PredFlag PF{flag, want};
           EmitKeys<T> EK{Dv, Dp, sel_v + (want ? c : 0), sel_p + (want ? c : 0)};
-          FinishCount FC{const_cast<unsigned long long*>(&ctx->hres[HRES_SPLIT + want])};
-          hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, c, g.tiles_per_block, ctx->block_counts);
-          hipLaunchKernelGGL((k_sel_write<PredFlag, EmitKeys<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, EK, FC, c, g.tiles_per_block, ctx->block_counts);
+          FinishCount FC{const_cast<unsigned long long*>(&ctx->host.hres[HRES_SPLIT + want])};
+          hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, c, g.tiles_per_block, ctx->scan.block_counts);
+          hipLaunchKernelGGL((k_sel_write<PredFlag, EmitKeys<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PF, EK, FC, c, g.tiles_per_block, ctx->scan.block_counts);
         }
         if (hipStreamSynchronize(st) != hipSuccess) return soft(__LINE__);
-        hc[0] = ctx->hres[HRES_SPLIT]; hc[1] = ctx->hres[HRES_SPLIT + 1];
+        hc[0] = ctx->host.hres[HRES_SPLIT]; hc[1] = ctx->host.hres[HRES_SPLIT + 1];
         if (hc[0] + hc[1] != c || hc[1] > v.npi) return soft(__LINE__);
       }
       const uint64_t cX = hc[0], cI = hc[1];
@@ -289,8 +276,8 @@ int patch_view_t(bmx_ctx* ctx, Index& ix, uint64_t c, uint64_t n0, uint64_t adde
         EmitRun<T> ER{(const T*)piv[ic], (const uint32_t*)v.pi_p[ic], (const uint64_t*)v.pi_ids[ic], piv[ic ^ 1], v.pi_p[ic ^ 1], v.pi_ids[ic ^ 1]};
         FinishCount FC{&ctx->ds->view_tmp[0]};
         SelGeom g = sel_geom<1>(v.npi);
-        hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, v.npi, g.tiles_per_block, ctx->block_counts);
-        hipLaunchKernelGGL((k_sel_write<PredFlag, EmitRun<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, ER, FC, v.npi, g.tiles_per_block, ctx->block_counts);
+        hipLaunchKernelGGL((k_sel_count<PredFlag>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, v.npi, g.tiles_per_block, ctx->scan.block_counts);
+        hipLaunchKernelGGL((k_sel_write<PredFlag, EmitRun<T>, FinishCount>), dim3(g.blocks), dim3(SEL_THREADS), 0, st, PN, ER, FC, v.npi, g.tiles_per_block, ctx->scan.block_counts);
         ia = ic ^ 1; na = v.npi - cI;
       }
       ViewRun<T> Ai{piv[ia], v.pi_p[ia], v.pi_ids[ia]}, Zi{piv[ia ^ 1], v.pi_p[ia ^ 1], v.pi_ids[ia ^ 1]};
