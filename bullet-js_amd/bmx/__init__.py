@@ -24,6 +24,7 @@ MERGE_STRICT_FLAGS = 0x200
 CTX_FIXED_CAPACITY = 2
 FLAG_INCOMING, FLAG_CURRENT, FLAG_HISTORICAL = 1, 2, 4
 MAX_BATCH = 1 << 24
+SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
     "bmx_create", "bmx_create_ex", "bmx_destroy", "bmx_last_error", "bmx_abi_version", "bmx_selfcheck", "bmx_set_deferred_compaction", "bmx_set_side_stream", "bmx_set_wait_limit", "bmx_merge_fence", "bmx_get_deferred_counts", "bmx_get_info", "bmx_get_placement", "bmx_set_probe_waves", "bmx_sync", "bmx_set_stream", "bmx_get_stream", "bmx_seq_signal", "bmx_seq_wait",
@@ -35,6 +36,7 @@ EXPORTS = [
     "bmx_comm_scan_range", "bmx_comm_scan_equals", "bmx_comm_scan_count", "bmx_comm_scan_filter",
     "bmx_vc_create", "bmx_vc_destroy", "bmx_vc_last_error", "bmx_vc_load_rows", "bmx_vc_merge_batch", "bmx_vc_get_rows", "bmx_vc_row_count", "bmx_vc_scan_range", "bmx_vc_merge_batch_dev", "bmx_vc_set_stream", "bmx_vc_sync",
     "bmx_vc_load_rows_ks", "bmx_vc_merge_batch_ks", "bmx_vc_get_rows_ks", "bmx_vc_merge_batch_ks_dev", "bmx_vc_keyset", "bmx_vc_keyset_dense",
+    "bmx_key_bucket", "bmx_digest", "bmx_export_rows", "bmx_comm_digest", "bmx_comm_export_rows",
 ]
 
 
@@ -128,6 +130,11 @@ def load_library():
     L.bmx_scan_range_pos.argtypes = [vp, u32, i64, i64, vp, u64, vp, i32]; L.bmx_scan_range_pos.restype = i32
     L.bmx_index_ids.argtypes = [vp, u32, u64, u64, vp, i32]; L.bmx_index_ids.restype = i32
     L.bmx_owner_of.argtypes = [u64, u32]; L.bmx_owner_of.restype = u32
+    L.bmx_key_bucket.argtypes = [u64, u32, u32]; L.bmx_key_bucket.restype = u32
+    L.bmx_digest.argtypes = [vp, u32, u32, vp, vp, i32]; L.bmx_digest.restype = i32
+    L.bmx_export_rows.argtypes = [vp, i64, u32, vp, u32, vp, u64, vp, i32]; L.bmx_export_rows.restype = i32
+    L.bmx_comm_digest.argtypes = [vp, u32, u32, vp, vp]; L.bmx_comm_digest.restype = i32
+    L.bmx_comm_export_rows.argtypes = [vp, i64, u32, vp, u32, vp, u64, vp]; L.bmx_comm_export_rows.restype = i32
     L.bmx_partition_by_owner.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp]; L.bmx_partition_by_owner.restype = i32
     L.bmx_partition_by_owner_slabs.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp]; L.bmx_partition_by_owner_slabs.restype = i32
     L.bmx_partition_scatter.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, u32, u64]; L.bmx_partition_scatter.restype = i32
@@ -354,6 +361,42 @@ class Engine:
         assert m.value <= n       # tombstones hold a slot (row_count) but are not dumped
         k = m.value
         return id[:k], field[:k], ts[:k], val[:k]
+
+    # ---- replica reconciliation (include/bmx.h; bmx/replica.py drives it) ----
+    def digest(self, log2_buckets=10, tombstones=False):
+        """-> (sums u64[2^L], counts u64[2^L]): per-bucket sum of the row digests and number of rows; sums.sum() (mod 2^64) is the digest of
+        dump_rows(). tombstones=True: tombstoned keys take part, hashed with val = VAL_DELETED."""
+        B = 1 << int(log2_buckets)
+        sums = np.zeros(B, np.uint64); counts = np.zeros(B, np.uint64)
+        self._chk(self.L.bmx_digest(self.h, int(log2_buckets), SYNC_TOMBSTONES if tombstones else 0, _ptr(sums), _ptr(counts), MEM_HOST))
+        return sums, counts
+
+    def digest_dev(self, log2_buckets, sums, counts, tombstones=False):
+        """same into device memory (u64[2^L] each); enqueue-only"""
+        self._chk(self.L.bmx_digest(self.h, int(log2_buckets), SYNC_TOMBSTONES if tombstones else 0, _ptr(sums), _ptr(counts), MEM_DEVICE))
+
+    def export_rows(self, since=0, log2_buckets=0, bucket_bits=None, only_tombstones=False, cap=None, out=None):
+        """-> (records, n): the keys with clock >= since whose bucket's bit is set (bucket_bits: u64 words, None = every bucket) as DELTA_REC_DTYPE
+        records in table order; n = number of matches, len(records) = min(n, cap). cap=None: everything (one counting call first).
+        out: a DELTA_REC_DTYPE array to fill (e.g. in a HostBuffer) — its length is the cap and the result a view of it."""
+        bits = _bucket_words(bucket_bits, log2_buckets)
+        fl = EXPORT_ONLY_TOMBSTONES if only_tombstones else 0
+        m = C.c_uint64()
+        if out is not None:
+            if out.dtype != DELTA_REC_DTYPE or not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a contiguous DELTA_REC_DTYPE array")
+            cap = len(out)
+        elif cap is None:
+            self._chk(self.L.bmx_export_rows(self.h, int(since), int(log2_buckets), _ptr(bits), fl, None, 0, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+            cap = m.value
+        recs = out if out is not None else np.zeros(int(cap), DELTA_REC_DTYPE)
+        self._chk(self.L.bmx_export_rows(self.h, int(since), int(log2_buckets), _ptr(bits), fl, _ptr(recs) if cap else None, int(cap), C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+        return recs[:min(m.value, int(cap))], m.value
+
+    def export_rows_dev(self, out, cap, n_out, since=0, log2_buckets=0, bucket_bits=None, only_tombstones=False):
+        """same with device memory: out = room for cap 32-byte records (None: count only), n_out = one u64, bucket_bits = device u64 words or None; enqueue-only"""
+        self._chk(self.L.bmx_export_rows(self.h, int(since), int(log2_buckets), _ptr(bucket_bits), EXPORT_ONLY_TOMBSTONES if only_tombstones else 0,
+                                         _ptr(out), int(cap), _ptr(n_out), MEM_DEVICE))
 
     def index_build(self, field):
         self._chk(self.L.bmx_index_build(self.h, int(field)))
@@ -695,6 +738,24 @@ class Comm:
         k = m.value
         return id[:k], field[:k], ts[:k], val[:k]
 
+    def digest(self, log2_buckets=10, tombstones=False):
+        """Engine.digest over all shards: the vectors one engine holding the same rows gives"""
+        B = 1 << int(log2_buckets)
+        sums = np.zeros(B, np.uint64); counts = np.zeros(B, np.uint64)
+        self._chk(self.L.bmx_comm_digest(self.h, int(log2_buckets), SYNC_TOMBSTONES if tombstones else 0, _ptr(sums), _ptr(counts)))
+        return sums, counts
+
+    def export_rows(self, since=0, log2_buckets=0, bucket_bits=None, only_tombstones=False):
+        """Engine.export_rows over all shards, shard after shard -> (records, n)"""
+        bits = _bucket_words(bucket_bits, log2_buckets)
+        fl = EXPORT_ONLY_TOMBSTONES if only_tombstones else 0
+        m = C.c_uint64()
+        self._chk(self.L.bmx_comm_export_rows(self.h, int(since), int(log2_buckets), _ptr(bits), fl, None, 0, C.byref(m)))
+        recs = np.zeros(m.value, DELTA_REC_DTYPE)
+        if m.value:
+            self._chk(self.L.bmx_comm_export_rows(self.h, int(since), int(log2_buckets), _ptr(bits), fl, _ptr(recs), len(recs), C.byref(m)))
+        return recs[:min(m.value, len(recs))], m.value
+
     def index_build(self, field):
         self._chk(self.L.bmx_comm_index_build(self.h, int(field)))
 
@@ -848,3 +909,40 @@ def keyset_writers(ks):
 def owner_of(ids, nshards):
     L = load_library()
     return np.array([L.bmx_owner_of(int(i), int(nshards)) for i in np.asarray(ids, dtype=np.uint64)], dtype=np.uint32)
+
+
+def _mix64(x):
+    x = x ^ (x >> np.uint64(33)); x = x * np.uint64(0xff51afd7ed558ccd)
+    x = x ^ (x >> np.uint64(33)); x = x * np.uint64(0xc4ceb9fe1a85ec53)
+    return x ^ (x >> np.uint64(33))
+
+
+def key_bucket(ids, fields, log2_buckets):
+    """Bucket of every key (id, field) among 2^log2_buckets (0..16): the formula of include/bmx.h bmx_key_bucket, restated in numpy. u32 array."""
+    L = int(log2_buckets)
+    if not 0 <= L <= 16:
+        raise ValueError("log2_buckets must be 0..16")
+    ids = np.asarray(ids, np.uint64); fields = np.asarray(fields, np.uint32).astype(np.uint64)
+    if L == 0:
+        return np.zeros(np.broadcast(ids, fields).shape, np.uint32)
+    with np.errstate(over="ignore"):
+        h = _mix64(_mix64(ids ^ np.uint64(0xA0761D6478BD642F)) + fields * np.uint64(0xE7037ED1A0B428DB) + np.uint64(0x8EBC6AF09C88C6E3))
+    return (h >> np.uint64(64 - L)).astype(np.uint32)
+
+
+def _bucket_words(bucket_bits, log2_buckets):
+    """None, or the bucket set as the contiguous u64 words bmx_export_rows reads (at least 2^L bits)"""
+    if bucket_bits is None:
+        return None
+    bits = _np(bucket_bits, np.uint64)
+    if len(bits) < max(1, (1 << int(log2_buckets)) // 64):
+        raise ValueError("bucket_bits needs 2^log2_buckets bits (at least one u64 word)")
+    return bits
+
+
+def bucket_bits_of(buckets, log2_buckets):
+    """bucket numbers -> the bit words export_rows takes"""
+    w = np.zeros(max(1, (1 << int(log2_buckets)) // 64), np.uint64)
+    for b in np.unique(np.asarray(buckets, np.int64)):
+        w[int(b) >> 6] |= np.uint64(1 << (int(b) & 63))
+    return w

@@ -22,6 +22,7 @@
 #include "scan_kernels.h"
 #include "select.h"
 #include "slot.h"
+#include "sync_kernels.h"
 #include "view_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
@@ -245,6 +246,15 @@ struct PartScratch {
   void release() { dev_free(counts); dev_free(owner); owner_cap = 0; }
 };
 
+// Scratch of the reconciliation sweeps (bmx_sync.inc): what a BMX_MEM_HOST caller's digest vectors, bucket set and records pass through. Grow-only.
+struct SyncScratch {
+  unsigned long long* dig = nullptr;      // 2 x 2^16 words: sums and counts
+  unsigned long long* bits = nullptr;     // 2^16 bits
+  bmx_delta_rec* recs = nullptr; uint64_t recs_cap = 0;
+  int cus = 0;                            // compute units of the context's device (the digest's grid)
+  void release() { dev_free(dig); dev_free(bits); dev_free(recs); recs_cap = 0; }
+};
+
 // bmx_timer_* events and the optional per-kernel profiling (bmx_profile_enable).
 struct Profiling {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -277,6 +287,7 @@ struct bmx_ctx {
   ScanScratch scan;
   ChangeLog chg;
   PartScratch part;
+  SyncScratch sync;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
   bool fixed_capacity = false;
@@ -1378,6 +1389,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->view.release();
   ctx->scan.release();
   ctx->part.release();
+  ctx->sync.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1970,5 +1982,6 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 
 }  // extern "C"
 
+#include "bmx_sync.inc"
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"

@@ -517,4 +517,36 @@ int bmx_comm_scan_filter(bmx_comm* c, uint32_t nterms, const bmx_term* terms, ui
   return comm_scan(c, 0, 0, 0, nterms, terms, out_ids, cap, n_out);
 }
 
+// Replica reconciliation over the shards (bmx.h). The shards' key sets are disjoint and the digest is a sum, so the digest of the sharded graph is the
+// element-wise sum of the shards' vectors — the same vectors one context holding all the rows would give. Host memory.
+int bmx_comm_digest(bmx_comm* c, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts) {
+  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (log2_buckets > 16 || !sums || !counts) return cfail(c, BMX_ERR_INVALID, "bmx_comm_digest: log2_buckets > 16 or null output");
+  DevGuard guard;
+  const uint64_t B = 1ull << log2_buckets;
+  std::vector<uint64_t> s(B), n(B);
+  std::memset(sums, 0, B * sizeof(uint64_t)); std::memset(counts, 0, B * sizeof(uint64_t));
+  for (uint32_t g = 0; g < c->N; g++) {
+    CSH(g, bmx_digest(c->sh[g], log2_buckets, flags, s.data(), n.data(), BMX_MEM_HOST));
+    for (uint64_t b = 0; b < B; b++) { sums[b] += s[b]; counts[b] += n[b]; }
+  }
+  return BMX_OK;
+}
+
+// bmx_export_rows shard after shard into one host array (like bmx_comm_dump_rows): shard order, table order inside a shard
+int bmx_comm_export_rows(bmx_comm* c, int64_t since_ts, uint32_t log2_buckets, const uint64_t* bucket_bits, uint32_t flags, bmx_delta_rec* out, uint64_t cap,
+                         uint64_t* n_out) {
+  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  DevGuard guard;
+  uint64_t tot = 0;
+  for (uint32_t g = 0; g < c->N; g++) {
+    uint64_t m = 0;
+    const uint64_t room = (out && cap > tot) ? cap - tot : 0;
+    CSH(g, bmx_export_rows(c->sh[g], since_ts, log2_buckets, bucket_bits, flags, room ? out + tot : nullptr, room, &m, BMX_MEM_HOST));
+    tot += m;
+  }
+  if (n_out) *n_out = tot;
+  return BMX_OK;
+}
+
 }  // extern "C"

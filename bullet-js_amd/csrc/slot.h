@@ -48,6 +48,15 @@ __host__ __device__ inline uint64_t mix64(uint64_t x) {
 // owner shard of a node id; independent of node_hash (below) so every shard sees uniformly hashed lines
 __host__ __device__ inline uint64_t owner_hash(uint64_t id) { return mix64(id * 0xD6E8FEB86659FD93ULL + 0x2545F4914F6CDD1DULL); }
 
+// Key bucket of the replica reconciliation (bmx.h bmx_key_bucket): the top L bits of a 64-bit mix of (id, field) that shares no constant with
+// owner_hash or node_hash and sees nothing of the table — neither its size nor its shard count —, so two replicas of any shape agree on it.
+__host__ __device__ inline uint64_t key_mix(uint64_t id, uint32_t field) {
+  return mix64(mix64(id ^ 0xA0761D6478BD642FULL) + (uint64_t)field * 0xE7037ED1A0B428DBULL + 0x8EBC6AF09C88C6E3ULL);
+}
+__host__ __device__ inline uint32_t key_bucket(uint64_t id, uint32_t field, uint32_t log2_buckets) {
+  return log2_buckets ? (uint32_t)(key_mix(id, field) >> (64u - log2_buckets)) : 0u;
+}
+
 // Probe sequence of a key. A 128-byte line is a bucket (SPL slots: 4 rows of 32 B, or 2 vector-clock rows of 64 B): the line comes from
 // the NODE id alone, the start inside the line from the field, and the line's slots are tried cyclically before the next line is.
 // So the fields of one node share a line while it has room — a sync chunk that carries several fields of a node costs one fill, and one

@@ -67,6 +67,18 @@ class DeviceGraph {
   getRows(id, field) { if (this.preOp) this.preOp(); return this.comm ? this.native.commGetRows(this.comm, id, field) : this.native.getRows(this.handle, id, field); }
   rowCount() { if (this.preOp) this.preOp(); return this.comm ? this.native.commRowCount(this.comm) : this.native.rowCount(this.handle); }
   dumpRows() { if (this.preOp) this.preOp(); return this.comm ? this.native.commDumpRows(this.comm) : this.native.dumpRows(this.handle); }
+  /* Replica reconciliation (bmx_digest / bmx_export_rows, include/bmx.h). digest: per-bucket sums of the row digests and row counts over 2^L key buckets
+   * ({tombstones: true}: tombstoned keys take part). exportRows: the keys with clock >= since whose bucket's bit is set in bucketBits (BigUint64Array of
+   * 2^log2Buckets bits, null = every bucket) as columns ready for a peer's mergeBatch(cols, BMX_INSERT_DELTA); {onlyTombstones: true}: the tombstoned keys instead. */
+  digest(log2Buckets = 10, opts = {}) {
+    if (this.preOp) this.preOp();
+    return this.comm ? this.native.commDigest(this.comm, log2Buckets >>> 0, !!opts.tombstones) : this.native.digest(this.handle, log2Buckets >>> 0, !!opts.tombstones);
+  }
+  exportRows(opts = {}) {
+    if (this.preOp) this.preOp();
+    const since = opts.since === undefined ? 0 : opts.since, L = (opts.log2Buckets || 0) >>> 0, bits = opts.bucketBits || null, tomb = !!opts.onlyTombstones;
+    return this.comm ? this.native.commExportRows(this.comm, since, L, bits, tomb) : this.native.exportRows(this.handle, since, L, bits, tomb);
+  }
   indexBuild(f) { if (this.preOp) this.preOp(); return this.comm ? this.native.commIndexBuild(this.comm, f) : this.native.indexBuild(this.handle, f); }
   indexDrop(f) { return this.comm ? this.native.commIndexDrop(this.comm, f) : this.native.indexDrop(this.handle, f); }
   /* value-ordered view of the index on field f (bmx_index_set_ordered): equals / range answer in O(log R + matches) while the field is not written;

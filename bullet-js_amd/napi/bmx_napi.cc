@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
+#include <algorithm>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -928,6 +929,78 @@ napi_value CommDumpRows(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, out, "ts", c); napi_set_named_property(env, out, "val", d);
   return out;
 }
+/* Replica reconciliation (bmx.h): thin bindings, no logic.
+ * digest(handle, log2Buckets, tombstones) / commDigest(comm, ...) -> {sums: BigUint64Array, counts: BigUint64Array}
+ * exportRows(handle, since, log2Buckets, bucketBits: BigUint64Array | null, onlyTombstones) / commExportRows(comm, ...) -> {id, field, ts, val, n} */
+template <class H>
+napi_value digest_impl(napi_env env, napi_value* argv, H* h, bmx_ctx* ctx, bmx_comm* comm) {
+  uint32_t L; NAPI_OK(napi_get_value_uint32(env, argv[1], &L));
+  bool tomb = false; NAPI_OK(napi_get_value_bool(env, argv[2], &tomb));
+  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
+  void *ps, *pc;
+  napi_value a = make_ta(env, napi_biguint64_array, 8, (size_t)1 << L, &ps), b = make_ta(env, napi_biguint64_array, 8, (size_t)1 << L, &pc);
+  const uint32_t fl = tomb ? BMX_SYNC_TOMBSTONES : 0u;
+  const int rc = ctx ? bmx_digest(ctx, L, fl, (uint64_t*)ps, (uint64_t*)pc, BMX_MEM_HOST) : bmx_comm_digest(comm, L, fl, (uint64_t*)ps, (uint64_t*)pc);
+  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
+  napi_value out; NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "sums", a); napi_set_named_property(env, out, "counts", b);
+  return out;
+}
+napi_value export_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
+  int64_t since; if (!get_i64(env, argv[1], &since)) return nullptr;
+  uint32_t L; NAPI_OK(napi_get_value_uint32(env, argv[2], &L));
+  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
+  napi_valuetype bt; napi_typeof(env, argv[3], &bt);
+  const uint64_t* bits = nullptr;
+  if (bt != napi_null && bt != napi_undefined) {
+    void* p; size_t words;
+    if (!get_ta(env, argv[3], napi_biguint64_array, &p, &words)) return nullptr;
+    if (words < std::max<size_t>(1, ((size_t)1 << L) / 64)) { napi_throw_range_error(env, nullptr, "bmx: bucketBits needs 2^log2Buckets bits"); return nullptr; }
+    bits = (const uint64_t*)p;
+  }
+  bool only_tomb = false; NAPI_OK(napi_get_value_bool(env, argv[4], &only_tomb));
+  const uint32_t fl = only_tomb ? BMX_EXPORT_ONLY_TOMBSTONES : 0u;
+  uint64_t n = 0;
+  int rc = ctx ? bmx_export_rows(ctx, since, L, bits, fl, nullptr, 0, &n, BMX_MEM_HOST) : bmx_comm_export_rows(comm, since, L, bits, fl, nullptr, 0, &n);
+  std::vector<bmx_delta_rec> recs(n ? n : 1);
+  uint64_t m = 0;
+  if (!rc && n) rc = ctx ? bmx_export_rows(ctx, since, L, bits, fl, recs.data(), n, &m, BMX_MEM_HOST) : bmx_comm_export_rows(comm, since, L, bits, fl, recs.data(), n, &m);
+  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
+  if (m > n) m = n;
+  void *pi, *pf, *pt, *pv;
+  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_uint32_array, 4, m, &pf),
+             c = make_ta(env, napi_bigint64_array, 8, m, &pt), d = make_ta(env, napi_bigint64_array, 8, m, &pv);
+  for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((uint32_t*)pf)[i] = recs[i].field; ((int64_t*)pt)[i] = recs[i].ts; ((int64_t*)pv)[i] = recs[i].val; }
+  napi_value out; NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "id", a); napi_set_named_property(env, out, "field", b);
+  napi_set_named_property(env, out, "ts", c); napi_set_named_property(env, out, "val", d);
+  set_num(env, out, "n", (double)m);
+  return out;
+}
+napi_value Digest(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
+  Turn turn(h);   // runs in issue order with the asynchronous merges
+  return digest_impl(env, argv, h, h->ctx, nullptr);
+}
+napi_value ExportRows(napi_env env, napi_callback_info info) {
+  ARGS(5);
+  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
+  Turn turn(h);
+  return export_impl(env, argv, h->ctx, nullptr);
+}
+napi_value CommDigest(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
+  std::lock_guard<std::mutex> g(h->mu);
+  return digest_impl(env, argv, h, nullptr, h->c);
+}
+napi_value CommExportRows(napi_env env, napi_callback_info info) {
+  ARGS(5);
+  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
+  std::lock_guard<std::mutex> g(h->mu);
+  return export_impl(env, argv, nullptr, h->c);
+}
 napi_value CommIndexSetOrdered(napi_env env, napi_callback_info info) {
   ARGS(3);
   CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
@@ -1018,7 +1091,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"indexSize", IndexSize}, {"indexRefreshCounts", IndexRefreshCounts}, {"scanRange", ScanRange}, {"scanCount", ScanCount}, {"scanFilter", ScanFilter}, {"info", Info},
       {"vcCreate", VcCreate}, {"vcDestroy", VcDestroy}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows}, {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}, {"ownersOf", OwnersOf},
       {"commCreate", CommCreate}, {"commDestroy", CommDestroy}, {"commMergeBatch", CommMergeBatch}, {"commLoadRows", CommLoadRows}, {"commGetRows", CommGetRows},
-      {"commRowCount", CommRowCount}, {"commDumpRows", CommDumpRows}, {"commIndexBuild", CommIndexBuild}, {"commIndexSetOrdered", CommIndexSetOrdered}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize},
+      {"commRowCount", CommRowCount}, {"commDumpRows", CommDumpRows}, {"digest", Digest}, {"exportRows", ExportRows}, {"commDigest", CommDigest}, {"commExportRows", CommExportRows}, {"commIndexBuild", CommIndexBuild}, {"commIndexSetOrdered", CommIndexSetOrdered}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize},
       {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}};
   for (auto& f : fns) {
     napi_value v;

@@ -267,8 +267,8 @@ int bmx_put_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* f
 int bmx_get_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, int64_t* ts, int64_t* val,
                  uint8_t* found, int mem);
 int bmx_get_row(bmx_ctx* ctx, uint64_t id, uint32_t field, int64_t* ts, int64_t* val); /* 1 found, 0 absent, <0 error */
-/* all resident rows that hold data (tombstones are left out), unordered; *n_out = their number even if cap is smaller (checkpoint hook:
- * src/bullet-network-sync.js:592-664 _collectFullSyncData, which skips deleted entries the same way) */
+/* all resident rows that hold data (tombstones are left out), unordered; *n_out = their number even if cap is smaller (checkpoint hook). It is NOT the
+ * reference's sync producer: _collectFullSyncData (src/bullet-network-sync.js:592-664) also sends every deleted entry (:651-661) — see bmx_export_rows below. */
 int bmx_dump_rows(bmx_ctx* ctx, uint64_t cap, uint64_t* id, uint32_t* field, int64_t* ts, int64_t* val,
                   uint64_t* n_out, int mem);
 int bmx_row_count(bmx_ctx* ctx, uint64_t* n_out);   /* keys holding a slot: rows + tombstones (what counts against capacity_rows) */
@@ -276,6 +276,44 @@ int bmx_row_count(bmx_ctx* ctx, uint64_t* n_out);   /* keys holding a slot: rows
  * row on the device, frees the old one. Synchronous. The reference's store is a JS object that simply grows
  * (src/bullet.js:28); this is the device-side equivalent. */
 int bmx_reserve(bmx_ctx* ctx, uint64_t capacity_rows);
+
+/* ---- replica reconciliation --------------------------------------------------------------------
+ * The producing half of the sync loop. The reference answers a peer's requestSync (src/bullet-network-sync.js:84) with _collectFullSyncData(since)
+ * (:592-664): every entry modified at or after `since` (:602, :633) PLUS every deleted entry (:651-661), in chunks. Here two replicas first compare
+ * per-bucket digests of their state and then ship only the rows of the buckets that differ, as the 32-byte bmx_delta_rec every receiving path speaks
+ * (bmx_merge_records, the exchange slabs). Both calls are read-only sweeps of the table and ordinary entry points: they order behind a deferred
+ * compaction, see the last merge and work after a growth. The device keeps clocks, not wall time: `since_ts` filters on the row's CLOCK, not on the
+ * reference's lastModified (which stays with the host).
+ *
+ * bmx_key_bucket: bucket of a key among B = 2^L buckets, L = log2_buckets in 0..16 (pure function, no GPU needed):
+ *     mix64(x) = x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33           (all mod 2^64)
+ *     h        = mix64(mix64(id ^ 0xA0761D6478BD642F) + field * 0xE7037ED1A0B428DB + 0x8EBC6AF09C88C6E3)
+ *     bucket   = L ? h >> (64 - L) : 0
+ *   It depends on (id, field) alone — not on the table size, the load factor, the shard count or bmx_owner_of's modulus — so replicas of any shape
+ *   agree on it, and buckets nest: bucket at L = bucket at L + 1 >> 1.
+ *
+ * bmx_digest: sums[b] = sum mod 2^64 of the row digest over the rows of bucket b, counts[b] = their number (B words each; zeroed by the call, in
+ *   stream order). Row digest = four chained splitmix64 over val, ts, field, id:
+ *     sm(x) = z = x + 0x9e3779b97f4a7c15; z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9; z = (z ^ z >> 27) * 0x94d049bb133111eb; z ^ z >> 31
+ *     digest = sm(sm(sm(sm(val) ^ ts) ^ field) ^ id)
+ *   Without flags tombstones are skipped: the sum over all buckets is the digest of what bmx_dump_rows returns. With BMX_SYNC_TOMBSTONES a tombstoned
+ *   key takes part, hashed with val = BMX_VAL_DELETED, so a deletion changes its bucket. One sweep of the table (n_slots x 32 bytes). L <= 10:
+ *   accumulated in LDS, at most 2 x B memory-side atomics per workgroup. L = 11..16 is the SLOW form: one pair of global atomics per row (measured:
+ *   DESIGN.md "Replica reconciliation").
+ *
+ * bmx_export_rows: every key with clock >= since_ts whose bucket's bit is set in bucket_bits (bit b = word b / 64, bit b % 64; B bits, at least one
+ *   word; NULL = every bucket) as one record {id, field, aux = 0, ts, val}. By default the keys that hold data; with BMX_EXPORT_ONLY_TOMBSTONES the
+ *   tombstoned keys instead (val = BMX_VAL_DELETED). Two separate calls on purpose: data records go straight into the peer's
+ *   bmx_merge_records(..., BMX_INSERT_DELTA); the merge refuses BMX_VAL_DELETED as a value, so the receiver resolves the (few) tombstones itself:
+ *   bmx_get_rows, keep those with a strictly larger clock than its own row, bmx_put_rows. Output order = table order (deterministic for a given
+ *   table); *n_out = number of matches even when cap is smaller; nothing is written at or beyond out[cap]; out == NULL counts only. `mem` covers out,
+ *   n_out and bucket_bits alike (host: staged; an `out` in bmx_host_alloc memory is written by the kernel itself). The table is read twice (count, write). */
+#define BMX_SYNC_TOMBSTONES        1u   /* bmx_digest: tombstoned keys take part, hashed with val = BMX_VAL_DELETED */
+#define BMX_EXPORT_ONLY_TOMBSTONES 2u   /* bmx_export_rows: the tombstoned keys instead of the keys that hold data */
+uint32_t bmx_key_bucket(uint64_t id, uint32_t field, uint32_t log2_buckets);
+int bmx_digest(bmx_ctx* ctx, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts, int mem);
+int bmx_export_rows(bmx_ctx* ctx, int64_t since_ts, uint32_t log2_buckets, const uint64_t* bucket_bits, uint32_t flags, bmx_delta_rec* out, uint64_t cap,
+                    uint64_t* n_out, int mem);
 
 /* ---- index + scans --------------------------------------------------------------------------
  * bmx_index_build replaces BulletQuery.index(path, field) / _buildIndex (src/bullet-query.js:30-73):
@@ -423,6 +461,11 @@ int bmx_comm_shard_result(bmx_comm* comm, uint32_t shard, const bmx_delta_rec** 
 int bmx_comm_row_count(bmx_comm* comm, uint64_t* n_out);
 int bmx_comm_get_rows(bmx_comm* comm, uint64_t n, const uint64_t* id, const uint32_t* field, int64_t* ts, int64_t* val, uint8_t* found);
 int bmx_comm_dump_rows(bmx_comm* comm, uint64_t cap, uint64_t* id, uint32_t* field, int64_t* ts, int64_t* val, uint64_t* n_out);
+/* bmx_digest / bmx_export_rows over the shards (host memory): the shards' keys are disjoint and the digest is a sum, so the vectors are the element-wise sum
+ * of the shards' — equal to those of one context holding the same rows; the export goes shard after shard like bmx_comm_dump_rows. */
+int bmx_comm_digest(bmx_comm* comm, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts);
+int bmx_comm_export_rows(bmx_comm* comm, int64_t since_ts, uint32_t log2_buckets, const uint64_t* bucket_bits, uint32_t flags, bmx_delta_rec* out, uint64_t cap,
+                         uint64_t* n_out);
 int bmx_comm_index_build(bmx_comm* comm, uint32_t field);
 int bmx_comm_index_set_ordered(bmx_comm* comm, uint32_t field, uint32_t after_queries);   /* bmx_index_set_ordered on every shard (results: shard by shard, each in (value, position) order) */
 int bmx_comm_scan_range(bmx_comm* comm, uint32_t field, int64_t lo, int64_t hi, uint64_t* out_ids, uint64_t cap, uint64_t* n_out);
