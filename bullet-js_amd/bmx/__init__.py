@@ -24,6 +24,7 @@ MERGE_STRICT_FLAGS = 0x200
 CTX_FIXED_CAPACITY = 2
 FLAG_INCOMING, FLAG_CURRENT, FLAG_HISTORICAL = 1, 2, 4
 MAX_BATCH = 1 << 24
+AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
@@ -37,6 +38,7 @@ EXPORTS = [
     "bmx_vc_create", "bmx_vc_destroy", "bmx_vc_last_error", "bmx_vc_load_rows", "bmx_vc_merge_batch", "bmx_vc_get_rows", "bmx_vc_row_count", "bmx_vc_scan_range", "bmx_vc_merge_batch_dev", "bmx_vc_set_stream", "bmx_vc_sync",
     "bmx_vc_load_rows_ks", "bmx_vc_merge_batch_ks", "bmx_vc_get_rows_ks", "bmx_vc_merge_batch_ks_dev", "bmx_vc_keyset", "bmx_vc_keyset_dense",
     "bmx_key_bucket", "bmx_digest", "bmx_export_rows", "bmx_comm_digest", "bmx_comm_export_rows",
+    "bmx_scan_aggregate", "bmx_comm_scan_aggregate",
 ]
 
 
@@ -52,6 +54,43 @@ class MergeStats(C.Structure):
 
 class Term(C.Structure):
     _fields_ = [("field", C.c_uint32), ("reserved", C.c_uint32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+class Agg(C.Structure):
+    """bmx_agg: one record of bmx_scan_aggregate (48 bytes); the sum is a two's-complement 128-bit number in two words"""
+    _fields_ = [("n_match", C.c_uint64), ("n", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64)]
+
+
+AGG_DTYPE = np.dtype([("n_match", "<u8"), ("n", "<u8"), ("min", "<i8"), ("max", "<i8"), ("sum_lo", "<u8"), ("sum_hi", "<i8")])
+
+
+class AggResult:
+    """One group's aggregate: n_match nodes satisfy every term, n of them hold the measure; sum (a Python int, exact), min and max are over those n
+    (min and max are None when nothing was measured: n == 0, or no measure field)."""
+    __slots__ = ("n_match", "n", "min", "max", "sum")
+
+    def __init__(self, rec):
+        self.n_match = int(rec["n_match"]); self.n = int(rec["n"])
+        self.sum = (int(rec["sum_hi"]) << 64) + int(rec["sum_lo"])
+        measured = self.n and int(rec["min"]) <= int(rec["max"])      # (without a measure field n == n_match and min / max keep their empty values)
+        self.min = int(rec["min"]) if measured else None
+        self.max = int(rec["max"]) if measured else None
+
+    def __eq__(self, o):
+        return isinstance(o, AggResult) and all(getattr(self, k) == getattr(o, k) for k in self.__slots__)
+
+    def __repr__(self):
+        return "AggResult(n_match=%d, n=%d, min=%r, max=%r, sum=%d)" % (self.n_match, self.n, self.min, self.max, self.sum)
+
+
+def agg_results(recs, ngroups):
+    """records of one bmx_scan_aggregate call (AGG_DTYPE) -> one AggResult (ngroups == 0) or the list of ngroups + 1"""
+    return AggResult(recs[0]) if not ngroups else [AggResult(r) for r in recs[:ngroups + 1]]
+
+
+def _agg_args(terms, measure, group, group_lo, ngroups):
+    arr = (Term * max(len(terms), 1))(*[Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])
+    return (len(terms), arr, AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group), int(group_lo), int(ngroups))
 
 
 class Info(C.Structure):
@@ -135,6 +174,8 @@ def load_library():
     L.bmx_export_rows.argtypes = [vp, i64, u32, vp, u32, vp, u64, vp, i32]; L.bmx_export_rows.restype = i32
     L.bmx_comm_digest.argtypes = [vp, u32, u32, vp, vp]; L.bmx_comm_digest.restype = i32
     L.bmx_comm_export_rows.argtypes = [vp, i64, u32, vp, u32, vp, u64, vp]; L.bmx_comm_export_rows.restype = i32
+    L.bmx_scan_aggregate.argtypes = [vp, u32, C.POINTER(Term), u32, u32, i64, u32, vp, i32]; L.bmx_scan_aggregate.restype = i32
+    L.bmx_comm_scan_aggregate.argtypes = [vp, u32, C.POINTER(Term), u32, u32, i64, u32, vp]; L.bmx_comm_scan_aggregate.restype = i32
     L.bmx_partition_by_owner.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp]; L.bmx_partition_by_owner.restype = i32
     L.bmx_partition_by_owner_slabs.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp]; L.bmx_partition_by_owner_slabs.restype = i32
     L.bmx_partition_scatter.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, u32, u64]; L.bmx_partition_scatter.restype = i32
@@ -476,6 +517,13 @@ class Engine:
         self._chk(self.L.bmx_scan_filter(self.h, len(terms), arr, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
         return out[:min(m.value, cap)].copy()
 
+    def scan_aggregate(self, terms, measure=None, group=None, group_lo=0, ngroups=0):
+        """count / sum / min / max of field `measure` over the nodes that satisfy every (field, lo, hi) of `terms`, without fetching an id. ngroups == 0:
+        one AggResult; otherwise the list of ngroups + 1: entry g for value(group) == group_lo + g, the last for the nodes outside the window."""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        self._chk(self.L.bmx_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out), MEM_HOST))
+        return agg_results(out, int(ngroups))
+
     def info(self):
         i = Info()
         self._chk(self.L.bmx_get_info(self.h, C.byref(i)))
@@ -600,6 +648,11 @@ class Engine:
 
     def scan_range_dev(self, field, lo, hi, out_ids, cap, n_out):
         self._chk(self.L.bmx_scan_range(self.h, int(field), int(lo), int(hi), _ptr(out_ids), int(cap), _ptr(n_out), MEM_DEVICE))
+
+    def scan_aggregate_dev(self, terms, out, measure=None, group=None, group_lo=0, ngroups=0):
+        """scan_aggregate into device memory (`out`: room for ngroups + 1 records of 48 bytes, or 1 with ngroups == 0); enqueue-only — after sync(),
+        agg_results(out.cpu().numpy().view(AGG_DTYPE), ngroups) reads it"""
+        self._chk(self.L.bmx_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out), MEM_DEVICE))
 
     def scan_range_pos_dev(self, field, lo, hi, out_pos, cap, n_out):
         self._chk(self.L.bmx_scan_range_pos(self.h, int(field), int(lo), int(hi), _ptr(out_pos), int(cap), _ptr(n_out), MEM_DEVICE))
@@ -776,6 +829,12 @@ class Comm:
 
     def scan_equals(self, field, value):
         return self.scan_range(field, value, value)
+
+    def scan_aggregate(self, terms, measure=None, group=None, group_lo=0, ngroups=0):
+        """Engine.scan_aggregate over all shards: the records one engine holding the same rows gives"""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        self._chk(self.L.bmx_comm_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out)))
+        return agg_results(out, int(ngroups))
 
     def scan_filter(self, terms):
         arr = (Term * len(terms))(*[Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])

@@ -24,6 +24,7 @@
 #include "slot.h"
 #include "sync_kernels.h"
 #include "view_kernels.h"
+#include "agg_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -255,6 +256,15 @@ struct SyncScratch {
   void release() { dev_free(dig); dev_free(bits); dev_free(recs); recs_cap = 0; }
 };
 
+// Scratch of the aggregate queries (bmx_agg.inc): one accumulator per group, which every query's last kernel leaves empty again (clean), and the records of a
+// BMX_MEM_HOST answer on their way down. Grow-only: 1025 records at first, 65537 with the first query that has more groups.
+struct AggScratch {
+  AggRaw* raw = nullptr; bmx_agg* stage = nullptr; uint32_t cap = 0;
+  bool clean = false;
+  int cus = 0;                            // compute units of the context's device (the sweep's grid)
+  void release() { dev_free(raw); dev_free(stage); cap = 0; clean = false; }
+};
+
 // bmx_timer_* events and the optional per-kernel profiling (bmx_profile_enable).
 struct Profiling {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -288,6 +298,7 @@ struct bmx_ctx {
   ChangeLog chg;
   PartScratch part;
   SyncScratch sync;
+  AggScratch agg;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
   bool fixed_capacity = false;
@@ -1390,6 +1401,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->scan.release();
   ctx->part.release();
   ctx->sync.release();
+  ctx->agg.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1983,5 +1995,6 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 }  // extern "C"
 
 #include "bmx_sync.inc"
+#include "bmx_agg.inc"
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"

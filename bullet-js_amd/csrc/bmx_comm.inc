@@ -517,6 +517,41 @@ int bmx_comm_scan_filter(bmx_comm* c, uint32_t nterms, const bmx_term* terms, ui
   return comm_scan(c, 0, 0, 0, nterms, terms, out_ids, cap, n_out);
 }
 
+// bmx_scan_aggregate over the shards (host memory). A node's rows all live on the shard that owns its id, so a node is selected, measured and grouped by one
+// shard alone and the shards' records combine exactly: the counts and the 128-bit sums add, the minima and maxima fold. Every shard's query is enqueued
+// before the first shard's records are fetched.
+int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups,
+                            bmx_agg* out) {
+  if (const char* bad = agg_bad_args(nterms, terms, group_field, ngroups, out)) return cfail(c, BMX_ERR_INVALID, bad);
+  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  DevGuard guard;
+  const uint32_t nrec = agg_records(ngroups);
+  for (uint32_t g = 0; g < c->N; g++) {
+    bmx_ctx* x = c->sh[g];
+    int rc = enter(x);
+    if (!rc) rc = agg_enqueue(x, nterms, terms, measure_field, group_field, group_lo, ngroups, nullptr);
+    if (rc) return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));   // (the queries of the shards before g finish on their own streams)
+  }
+  std::vector<bmx_agg> part(nrec);
+  int first = BMX_OK; std::string msg;
+  for (uint32_t g = 0; g < c->N; g++) {
+    bmx_ctx* x = c->sh[g];
+    int rc = enter(x);
+    if (!rc) rc = agg_collect(x, nrec, g == 0 ? out : part.data());    // every shard is collected, also after an error
+    if (rc) { if (!first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x); } continue; }
+    if (g == 0) continue;
+    for (uint32_t r = 0; r < nrec; r++) {
+      bmx_agg& o = out[r]; const bmx_agg& p = part[r];
+      o.n_match += p.n_match; o.n += p.n;
+      o.min = std::min(o.min, p.min); o.max = std::max(o.max, p.max);
+      const unsigned __int128 s = (((unsigned __int128)(uint64_t)o.sum_hi << 64) | o.sum_lo) + (((unsigned __int128)(uint64_t)p.sum_hi << 64) | p.sum_lo);
+      o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
+    }
+  }
+  if (first) return cfail(c, first, msg);
+  return BMX_OK;
+}
+
 // Replica reconciliation over the shards (bmx.h). The shards' key sets are disjoint and the digest is a sum, so the digest of the sharded graph is the
 // element-wise sum of the shards' vectors — the same vectors one context holding all the rows would give. Host memory.
 int bmx_comm_digest(bmx_comm* c, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts) {

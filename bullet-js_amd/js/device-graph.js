@@ -98,6 +98,25 @@ class DeviceGraph {
   indexIds(f, first, count) { if (this.preOp) this.preOp(); return this.native.indexIds(this.handle, f, first, count); }
   scanCount(f, lo, hi) { if (this.preOp) this.preOp(); return this.comm ? this.native.commScanCount(this.comm, f, lo, hi) : this.native.scanCount(this.handle, f, lo, hi); }
   scanFilter(terms) { if (this.preOp) this.preOp(); return this.comm ? this.native.commScanFilter(this.comm, terms) : this.native.scanFilter(this.handle, terms); }
+  /* Aggregate query (bmx_scan_aggregate, include/bmx.h): count / sum / min / max of field `measure` over the nodes that satisfy every [field, lo, hi] of terms,
+   * answered on the device without fetching an id. Without nGroups one record {nMatch, n, sum, min, max}; with {group, groupLo, nGroups} the array of
+   * nGroups + 1 records: entry g for value(group) === groupLo + g, the last for the nodes outside the window. sum is a Number while it is a safe integer,
+   * a BigInt otherwise; min and max are null when nothing was measured (n === 0, or no measure). */
+  scanAggregate(terms, opts = {}) {
+    if (this.preOp) this.preOp();
+    const measure = opts.measure === undefined ? null : opts.measure, group = opts.group === undefined ? null : opts.group;
+    const groupLo = opts.groupLo || 0, nGroups = (opts.nGroups || 0) >>> 0;
+    const r = this.comm ? this.native.commScanAggregate(this.comm, terms, measure, group, groupLo, nGroups) : this.native.scanAggregate(this.handle, terms, measure, group, groupLo, nGroups);
+    const recs = new Array(r.nMatch.length);
+    for (let i = 0; i < recs.length; i++) {
+      const n = Number(r.n[i]);
+      const big = (r.sumHi[i] << 64n) + r.sumLo[i];
+      const sum = big >= BigInt(Number.MIN_SAFE_INTEGER) && big <= BigInt(Number.MAX_SAFE_INTEGER) ? Number(big) : big;
+      const measured = n > 0 && r.min[i] <= r.max[i];        // (without a measure field n === nMatch and min / max keep their empty values)
+      recs[i] = { nMatch: Number(r.nMatch[i]), n, sum, min: measured ? Number(r.min[i]) : null, max: measured ? Number(r.max[i]) : null };
+    }
+    return nGroups ? recs : recs[0];
+  }
   info() { return this.comm ? { nShards: this.nShards, devices: this.devices, nRows: this.rowCount() } : this.native.info(this.handle); }
   close() {
     if (this.handle) { this.native.destroy(this.handle); this.handle = null; }

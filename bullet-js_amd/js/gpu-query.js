@@ -350,6 +350,48 @@ class GpuQuery {
     return this._nodes(ixs[0], this._ordinals(ixs[0], ids).sort((a, b) => a - b));
   }
 
+  /* device indexes of the fields an aggregate names, or BMX_NOT_DEVICE_INDEX exactly where filterWhere throws it */
+  _deviceIndexes(path, fields, what) {
+    const ixs = fields.map((f) => this._fresh(path, f));
+    if (!ixs.every((ix) => ix.kind === "device")) {
+      const err = new Error(`bmx: ${what} needs integer-valued fields on every term`);
+      err.code = "BMX_NOT_DEVICE_INDEX";
+      throw err;
+    }
+    return ixs;
+  }
+
+  /**
+   * Aggregate on the device (the reduction that query.map(path, fn).reduce(...) does on the host, src/bullet-query.js:322-333): over the children of path
+   * that satisfy every term [{field, min, max}], the number matched, and count / sum / min / max of `field` over those that carry it.
+   * -> {matched, count, sum, min, max}; sum is a Number while it is a safe integer, a BigInt otherwise; min and max are null when count === 0.
+   */
+  aggregateWhere(path, terms, field) {
+    if (!terms || terms.length === 0) return { matched: 0, count: 0, sum: 0, min: null, max: null };
+    const ixs = this._deviceIndexes(path, terms.map((t) => t.field).concat(field === undefined || field === null ? [] : [field]), "aggregateWhere");
+    this.lastPath = "device";
+    const native = terms.map((t, k) => [ixs[k].deviceField, Math.ceil(t.min), Math.floor(t.max)]);
+    const r = this.graph.scanAggregate(native, { measure: ixs.length > terms.length ? ixs[terms.length].deviceField : null });
+    return { matched: r.nMatch, count: r.n, sum: r.sum, min: r.min, max: r.max };
+  }
+
+  /**
+   * "count users by role" in one call (the reference: one count(path, field, value) per distinct value, src/bullet-query.js:293-313): a Map from each
+   * integer value of `field` in [min, max] that occurs among the children of path to the number of children that carry it.
+   */
+  countBy(path, field, min, max) {
+    const [ix] = this._deviceIndexes(path, [field], "countBy");
+    this.lastPath = "device";
+    const out = new Map();
+    const lo = Math.ceil(min), hi = Math.floor(max);
+    for (let base = lo; base <= hi; base += 65536) {          // windows of BMX_AGG_MAX_GROUPS values
+      const n = Math.min(65536, hi - base + 1);
+      const recs = this.graph.scanAggregate([[ix.deviceField, base, base + n - 1]], { group: ix.deviceField, groupLo: base, nGroups: n });
+      for (let g = 0; g < n; g++) if (recs[g].nMatch) out.set(base + g, recs[g].nMatch);
+    }
+    return out;
+  }
+
   filter(path, fn) {
     const base = this.bullet._getData(path);
     const out = [];

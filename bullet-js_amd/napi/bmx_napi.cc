@@ -1084,6 +1084,58 @@ napi_value CommScanFilter(napi_env env, napi_callback_info info) {
   return ta;
 }
 
+/* Aggregate queries (bmx.h bmx_scan_aggregate): thin bindings, no logic.
+ * scanAggregate(handle, [[field, lo, hi], ...], measure | null, group | null, groupLo, nGroups) / commScanAggregate(comm, ...) ->
+ * {nMatch, n: BigUint64Array, min, max: BigInt64Array, sumLo: BigUint64Array, sumHi: BigInt64Array}, one entry per record (nGroups + 1, or 1 without groups) */
+napi_value aggregate_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
+  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
+  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: aggregate needs 1..8 terms"); return nullptr; }
+  bmx_term terms[8];
+  for (uint32_t k = 0; k < nt; k++) {
+    napi_value t, e0, e1, e2;
+    NAPI_OK(napi_get_element(env, argv[1], k, &t));
+    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
+    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
+    terms[k].reserved = 0;
+    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
+  }
+  uint32_t fld[2] = {BMX_AGG_NO_FIELD, BMX_AGG_NO_FIELD};
+  for (int k = 0; k < 2; k++) {
+    napi_valuetype vt; napi_typeof(env, argv[2 + k], &vt);
+    if (vt != napi_null && vt != napi_undefined) NAPI_OK(napi_get_value_uint32(env, argv[2 + k], &fld[k]));
+  }
+  int64_t glo; if (!get_i64(env, argv[4], &glo)) return nullptr;
+  uint32_t ng; NAPI_OK(napi_get_value_uint32(env, argv[5], &ng));
+  if (ng > BMX_AGG_MAX_GROUPS || (ng && fld[1] == BMX_AGG_NO_FIELD)) { napi_throw_range_error(env, nullptr, "bmx: nGroups is 0..65536 and needs a group field"); return nullptr; }
+  const size_t nrec = ng ? (size_t)ng + 1 : 1;
+  std::vector<bmx_agg> recs(nrec);
+  const int rc = ctx ? bmx_scan_aggregate(ctx, nt, terms, fld[0], fld[1], glo, ng, recs.data(), BMX_MEM_HOST) : bmx_comm_scan_aggregate(comm, nt, terms, fld[0], fld[1], glo, ng, recs.data());
+  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
+  void *pm, *pn, *plo, *phi, *psl, *psh;
+  napi_value a = make_ta(env, napi_biguint64_array, 8, nrec, &pm), b = make_ta(env, napi_biguint64_array, 8, nrec, &pn), c = make_ta(env, napi_bigint64_array, 8, nrec, &plo),
+             d = make_ta(env, napi_bigint64_array, 8, nrec, &phi), e = make_ta(env, napi_biguint64_array, 8, nrec, &psl), f = make_ta(env, napi_bigint64_array, 8, nrec, &psh);
+  for (size_t i = 0; i < nrec; i++) {
+    ((uint64_t*)pm)[i] = recs[i].n_match; ((uint64_t*)pn)[i] = recs[i].n; ((int64_t*)plo)[i] = recs[i].min; ((int64_t*)phi)[i] = recs[i].max;
+    ((uint64_t*)psl)[i] = recs[i].sum_lo; ((int64_t*)psh)[i] = recs[i].sum_hi;
+  }
+  napi_value out; NAPI_OK(napi_create_object(env, &out));
+  napi_set_named_property(env, out, "nMatch", a); napi_set_named_property(env, out, "n", b); napi_set_named_property(env, out, "min", c);
+  napi_set_named_property(env, out, "max", d); napi_set_named_property(env, out, "sumLo", e); napi_set_named_property(env, out, "sumHi", f);
+  return out;
+}
+napi_value ScanAggregate(napi_env env, napi_callback_info info) {
+  ARGS(6);
+  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
+  Turn turn(h);   // runs in issue order with the asynchronous merges
+  return aggregate_impl(env, argv, h->ctx, nullptr);
+}
+napi_value CommScanAggregate(napi_env env, napi_callback_info info) {
+  ARGS(6);
+  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
+  std::lock_guard<std::mutex> g(h->mu);
+  return aggregate_impl(env, argv, nullptr, h->c);
+}
+
 napi_value Init(napi_env env, napi_value exports) {
   struct { const char* name; napi_callback fn; } fns[] = {
       {"abiVersion", AbiVersion}, {"create", Create}, {"destroy", Destroy}, {"mergeBatch", MergeBatch}, {"mergeBatchAsync", MergeBatchAsync}, {"reserve", Reserve}, {"loadRows", LoadRows}, {"putRows", PutRows}, {"hostColumns", HostColumns}, {"scanRangePos", ScanRangePos}, {"indexIds", IndexIds}, {"commPutRows", CommPutRows},
@@ -1092,7 +1144,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"vcCreate", VcCreate}, {"vcDestroy", VcDestroy}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows}, {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}, {"ownersOf", OwnersOf},
       {"commCreate", CommCreate}, {"commDestroy", CommDestroy}, {"commMergeBatch", CommMergeBatch}, {"commLoadRows", CommLoadRows}, {"commGetRows", CommGetRows},
       {"commRowCount", CommRowCount}, {"commDumpRows", CommDumpRows}, {"digest", Digest}, {"exportRows", ExportRows}, {"commDigest", CommDigest}, {"commExportRows", CommExportRows}, {"commIndexBuild", CommIndexBuild}, {"commIndexSetOrdered", CommIndexSetOrdered}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize},
-      {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}};
+      {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}, {"scanAggregate", ScanAggregate}, {"commScanAggregate", CommScanAggregate}};
   for (auto& f : fns) {
     napi_value v;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v) != napi_ok) return nullptr;

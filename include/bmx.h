@@ -398,6 +398,39 @@ int bmx_index_ids(bmx_ctx* ctx, uint32_t field, uint64_t first, uint64_t count, 
 int bmx_scan_filter(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap,
                     uint64_t* n_out, int mem);
 
+/* ---- aggregate queries ----------------------------------------------------------------------------
+ * What the reference's users ask next about the nodes a query selects (docs/querying.md "Count Operations", "Map Operations"): "count users by role" is one
+ * count(path, field, value) per distinct value (src/bullet-query.js:293-313), "total inventory value" is query.map(path, fn).reduce(...) (:322-333) — both walk
+ * every child object on the host. bmx_scan_aggregate answers them on the device without delivering a single id: nothing proportional to the match count is
+ * written anywhere, the whole answer is one 48-byte record per group.
+ *
+ * Selection: exactly bmx_scan_filter's — an AND of 1..8 inclusive range terms over fields of the same node; term 0 runs on the index of terms[0].field (built
+ *   or refreshed like any scan), the other terms are probed in the table; tombstones match no term; lo > hi matches nothing.
+ * Measure: the value of measure_field on each matching node (taken from the index column when it is terms[0].field, from the term's own probe when it is another
+ *   term's field). A matching node whose measure row is absent or tombstoned counts in n_match but not in n. BMX_AGG_NO_FIELD: no measure — n = n_match, the sum
+ *   is 0, min and max keep their empty values.
+ * Sum: exact (|val| <= 2^53 - 1 and fewer than 2^32 rows: below 2^85), as a two's-complement 128-bit number. Integer adds: the answer is bit-reproducible.
+ * Grouping: ngroups == 0 writes one record, out[0]. ngroups in 1..BMX_AGG_MAX_GROUPS writes ngroups + 1 records: out[g] aggregates the matching nodes with
+ *   value(group_field) == group_lo + g, out[ngroups] those whose group value is absent, tombstoned or outside the window; the n_match of all records add up
+ *   to the ungrouped n_match. Up to 1024 groups are accumulated in the workgroups' LDS (a histogram: "count by age" over one term reads the value column and
+ *   nothing else); 1025..65536 groups are the SLOW form, one set of global atomics per matching row.
+ * BMX_ERR_INVALID, before any device work: nterms outside 1..8, terms or out NULL, ngroups > BMX_AGG_MAX_GROUPS, ngroups > 0 without a group field, a bad mem.
+ * mem: BMX_MEM_HOST is synchronous. BMX_MEM_DEVICE takes out as a device pointer and only enqueues; the call writes every record in stream order (the caller
+ *   does not zero it). An ordinary entry point: it orders behind a deferred compaction, sees the last merge, works after a growth and on an index that has
+ *   switched to its int64 column. With a current value-ordered view on terms[0].field the candidates are the view's run for term 0's range — O(log R +
+ *   candidates) — and the answer is the same. bmx_comm_scan_aggregate (below) combines the shards' records. */
+typedef struct bmx_agg {
+  uint64_t n_match;   /* nodes that satisfy every term */
+  uint64_t n;         /* of those, nodes whose measure field holds data (== n_match with BMX_AGG_NO_FIELD) */
+  int64_t  min, max;  /* over the n measure values; INT64_MAX / INT64_MIN when n == 0 */
+  uint64_t sum_lo;    /* exact two's-complement 128-bit sum of the n measure values */
+  int64_t  sum_hi;
+} bmx_agg;            /* 48 bytes */
+#define BMX_AGG_NO_FIELD 0xFFFFFFFFu   /* the reserved field hash: "no measure" / "no grouping" */
+#define BMX_AGG_MAX_GROUPS 65536u
+int bmx_scan_aggregate(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint32_t measure_field,
+                       uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* out, int mem);
+
 /* ---- sharding (one context per GPU; rows owned by bmx_owner_of(id, nshards)) -----------------
  * Replaces the gossip fan-out of src/bullet-network.js:378-418 inside one node: instead of every
  * peer merging every delta, each delta is routed to the shard that owns its node id.
@@ -472,6 +505,10 @@ int bmx_comm_scan_range(bmx_comm* comm, uint32_t field, int64_t lo, int64_t hi, 
 int bmx_comm_scan_equals(bmx_comm* comm, uint32_t field, int64_t value, uint64_t* out_ids, uint64_t cap, uint64_t* n_out);
 int bmx_comm_scan_count(bmx_comm* comm, uint32_t field, int64_t lo, int64_t hi, uint64_t* n_out);
 int bmx_comm_scan_filter(bmx_comm* comm, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out);
+/* bmx_scan_aggregate over the shards (host memory): a node's rows all live on the shard that owns its id, so the shards' records combine exactly — the counts
+ * and the 128-bit sums add, the minima and maxima fold. Every shard's query is enqueued before the first shard's records are fetched. */
+int bmx_comm_scan_aggregate(bmx_comm* comm, uint32_t nterms, const bmx_term* terms, uint32_t measure_field,
+                            uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* out);
 
 /* ---- N4: fixed-K multi-writer vector clocks -------------------------------------
  * A second kind of table for rows whose clocks have up to 8 writers: {writer_0: c0, ..., writer_{K-1}: c_{K-1}} with small
