@@ -112,10 +112,6 @@ struct ViewShared {
 
 thread_local std::string g_err;
 constexpr uint32_t PROF_MAX_CALLS = 64;
-constexpr int MERGE_FORCE_INTERNAL = 0x4000;   // marker carried by the INTERNAL host-batch helpers (merge_host, submit_host) for bmx_put_rows; never accepted from a caller
-inline bool public_mode_ok(int insert_mode) {  // what bmx.h documents: BMX_INSERT_* plus the three optional bits
-  return (insert_mode & ~(BMX_INSERT_DELTA | BMX_MERGE_UNIQUE_KEYS | BMX_MERGE_STRICT_FLAGS | BMX_MERGE_MARK_CREATED)) == 0;
-}
 
 template <class T>
 void dev_free(T*& p) {
@@ -379,400 +375,7 @@ int check_status(bmx_ctx* ctx) {
   return fail(ctx, BMX_ERR_RANGE, "delta out of domain: reserved key, ts outside [0, 2^53-1] or |val| > 2^53-1");
 }
 
-int refresh_rows(bmx_ctx* ctx) {
-  unsigned long long r = 0;
-  if (ctx->host_rows && ctx->batch_seq > 0) {      // every change of the row count went through a merge, whose last workgroup mirrored it to the host
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    r = __atomic_load_n(ctx->host_rows, __ATOMIC_ACQUIRE);
-  } else {
-    HIPCHK(hipMemcpyAsync(&r, &ctx->ds->row_count, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  ctx->rows_ub = r;
-  ctx->inflight.clear();
-  return BMX_OK;
-}
-
-// rows_ub from the mirror the merges write, no sync: rows the host has seen + every delta of the batches enqueued after that one
-void tighten_rows_ub(bmx_ctx* ctx) {
-  if (!ctx->host_rows) return;
-  const uint64_t seen_seq = __atomic_load_n(ctx->host_rows + 1, __ATOMIC_ACQUIRE);
-  const uint64_t seen_rows = __atomic_load_n(ctx->host_rows, __ATOMIC_RELAXED);   // this count, or a later one: still an upper bound with the sum below
-  if (seen_seq == 0) return;
-  while (!ctx->inflight.empty() && ctx->inflight.front().first <= seen_seq) ctx->inflight.pop_front();
-  uint64_t pending = 0;
-  for (const auto& b : ctx->inflight) pending += b.second;
-  ctx->rows_ub = std::min<uint64_t>(ctx->rows_ub, seen_rows + pending);
-}
-
-int flush_pending(bmx_ctx* ctx);
-// (merge_core's capacity guard) Blocks the CALLER, not the device: until the row reports of enough batches in flight have arrived for the bound to clear,
-// or none is left. A report that does not come within two seconds (a wedged queue) leaves the decision to the synchronising path.
-int wait_for_row_reports(bmx_ctx* ctx, uint64_t n) {
-  if (!ctx->host_rows) return BMX_OK;
-  const auto t0 = std::chrono::steady_clock::now();
-  while ((ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) && !ctx->inflight.empty()) {
-    if (ctx->inflight.size() == 1 && ctx->defer.pend.on) { if (int frc = flush_pending(ctx)) return frc; }   // the only report outstanding is that of a compaction not launched yet
-    const uint64_t want = ctx->inflight.front().first;
-    uint32_t spins = 0;
-    while (__atomic_load_n(ctx->host_rows + 1, __ATOMIC_ACQUIRE) < want) {
-      if ((++spins & 1023u) == 0) {
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return BMX_OK;
-        std::this_thread::yield();
-      }
-    }
-    tighten_rows_ub(ctx);
-    ctx->n_row_waits++;
-  }
-  return BMX_OK;
-}
-int MergeWs::ensure(bmx_ctx* ctx, uint64_t n) {
-  if (n <= cap) return BMX_OK;
-  if (int frc = flush_pending(ctx)) return frc;      // a compaction not launched yet reads the workspace this call frees
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  uint64_t c = std::max<uint64_t>(n, std::min<uint64_t>((uint64_t)cap * 2, MAX_BATCH));
-  c = std::max<uint64_t>(c, 1u << 16);
-  c = (c + 255) & ~255ull;
-  const uint64_t half = (c / 256 + 16 + 3) & ~3ull;   // a multiple of four entries: every segment stays 16-byte aligned for the compaction's wide loads
-  cap = 0;
-  if (int rc = dev_alloc_all(ctx, {{next, c * 4}, {wflag[0], c + 16}, {slot_of[0], c * 4}, {fld[0], c * 4}, {wflag[1], c + 16}, {slot_of[1], c * 4}, {fld[1], c * 4},
-                                   {wflag[2], c + 16}, {slot_of[2], c * 4}, {fld[2], c * 4}, {blk_info, BLK_SEGS * half * 4}, {blk_follow, (c / 256 + 16) * 4}}))
-    return rc;
-  HIPCHK(hipMemsetAsync(next, 0, c * sizeof(uint32_t), ctx->stream));
-  HIPCHK(hipMemsetAsync(blk_follow, 0, (c / 256 + 16) * sizeof(uint32_t), ctx->stream));
-  blk_half = (uint32_t)half;
-  HIPCHK(hipMemsetAsync(blk_info, 0, BLK_SEGS * (size_t)blk_half * sizeof(uint32_t), ctx->stream));
-  for (uint32_t h = 0; h < BLK_SEGS; h++) blk_clean[h] = true;
-  cap = (uint32_t)c;
-  return BMX_OK;
-}
-
-// Slots of a table that holds `capacity_rows` rows at load factor <= load_pct %. 0 = does not fit the 32-bit slot indices the
-// per-delta workspace (slot_of[]) carries: 2^32 slots x 32 B = 137 GB would fit the 288 GB of HBM, so it is refused explicitly.
-uint64_t slots_for(uint64_t capacity_rows, uint32_t load_pct) {
-  if (capacity_rows > (1ull << 40)) return 0;
-  uint64_t nslots = std::max<uint64_t>(4096, (capacity_rows * 100 + load_pct - 1) / load_pct);
-  nslots = (nslots + 3) & ~3ull;
-  return nslots >= (1ull << 32) ? 0 : nslots;   // the last 32-bit value is a sentinel (STRICT_NO_ROW)
-}
-
-// Where a table lands matters: the same kernels on the same rows take 68-72 us per 1M-delta launch on some allocations of a 1.4 GB table and 77-80 us on
-// others made in the same process minutes apart — a property of the allocation that stays for its lifetime (profiles/r04_placement_probe.log: six tables alive at
-// once, three passes; which ones are fast changes from run to run). So a large table is allocated up to PLACEMENT_TRIES times (fewer once a clearly faster candidate has turned up), every candidate is timed with
-// the probe kernel's own request mix (k_placement_probe: 2^20 random slot reads + head exchanges + 16-byte stores, best of three launches, ~0.25 ms per
-// candidate), the fastest is kept and the others are freed. Candidates stay allocated while the next one is made (otherwise the allocator hands the same range
-// back); tables too large for that many copies get fewer tries. BMX_TABLE_PLACEMENT_TRIES=1 switches it off. -> the chosen allocation (uninitialised)
-constexpr int PLACEMENT_TRIES = 4;   // at create (BMX_CTX_PLACEMENT_TRIES(n) in bmx_create_ex's flags, then BMX_TABLE_PLACEMENT_TRIES in the environment, override: 1..8);
-                                     // round 4 tried up to eight: the transient footprint (8 x 1.4 GB) bought ~1 us over four (profiles/r04_placement_probe.log)
-constexpr int PLACEMENT_TRIES_GROW = 3;  // while the old table is alive as well: old + 3 candidates = 4 x the table at the peak
-constexpr uint64_t PLACEMENT_MIN_BYTES = 256ull << 20;     // below the Infinity Cache's size a table's lines are served on-die wherever they live
-int alloc_table_tuned(bmx_ctx* ctx, uint64_t nslots, Slot** out, bool growing = false) {
-  *out = nullptr;
-  int tries = growing ? PLACEMENT_TRIES_GROW : PLACEMENT_TRIES;
-  if (ctx->placement_tries_asked) tries = growing ? std::min<int>(ctx->placement_tries_asked, PLACEMENT_TRIES_GROW) : (int)ctx->placement_tries_asked;
-  if (const char* t = std::getenv("BMX_TABLE_PLACEMENT_TRIES")) { const int v = std::atoi(t); if (v >= 1 && v <= 8) tries = v; }
-  const uint64_t bytes = nslots * sizeof(Slot);
-  if (bytes < PLACEMENT_MIN_BYTES) tries = 1;
-  else {
-    // never more than HALF of what is free right now for the candidates together (other contexts, torch's allocator and other processes share the
-    // device: ADVICE r4), and never without 2 GB to spare
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) { while (tries > 1 && ((uint64_t)tries * bytes > free_b / 2 || (uint64_t)tries * bytes + (2ull << 30) > free_b)) tries--; } else (void)hipGetLastError();
-  }
-  int rc;
-  if (tries == 1) return dev_alloc(ctx, out, nslots);
-  std::vector<Slot*> cand;
-  std::vector<float> us;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); if (e0) (void)hipEventDestroy(e0); return dev_alloc(ctx, out, nslots); }
-  constexpr uint32_t PN = 1u << 20;
-  const char* cenv = std::getenv("BMX_TABLE_CONTIGUOUS");
-  const int n_contig = cenv ? std::atoi(cenv) : 0;         // measurement switch: the first n candidates are asked for as physically contiguous memory
-  for (int k = 0; k < tries; k++) {
-    Slot* p = nullptr;
-    if (k < n_contig) {
-      if (hipExtMallocWithFlags(reinterpret_cast<void**>(&p), bytes, hipDeviceMallocContiguous) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
-      if (std::getenv("BMX_PLACEMENT_DEBUG")) fprintf(stderr, "bmx placement: candidate %d: contiguous allocation %s\n", k, p ? "granted" : "refused");
-    }
-    if (!p && (rc = dev_alloc(ctx, &p, nslots))) { if (cand.empty()) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; } break; }
-    float best = 1e30f;
-    for (int rep = 0; rep < 4; rep++) {                    // (the first launch on a fresh allocation also pays its page-table walk misses: not counted)
-      (void)hipEventRecord(e0, ctx->stream);
-      hipLaunchKernelGGL(k_placement_probe, dim3(PN / 64), dim3(64), 0, ctx->stream, p, nslots, PN, (uint32_t)(k * 16 + rep));
-      (void)hipEventRecord(e1, ctx->stream);
-      float ms = 0;
-      if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); ms = 1e9f; }
-      if (rep > 0) best = std::min(best, ms * 1000.f);
-    }
-    cand.push_back(p); us.push_back(best);
-    if (std::getenv("BMX_PLACEMENT_DEBUG")) fprintf(stderr, "bmx placement: candidate %d at %p (%llu MB): probe %.2f us\n", k, (void*)p, (unsigned long long)(bytes >> 20), best);
-  }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  size_t pick = 0;
-  for (size_t k = 1; k < cand.size(); k++) if (us[k] < us[pick]) pick = k;
-  for (size_t k = 0; k < cand.size(); k++) if (k != pick) (void)hipFree(cand[k]);
-  ctx->placement_tries = (uint32_t)cand.size(); ctx->placement_us_best = us[pick];
-  ctx->placement_us_worst = *std::max_element(us.begin(), us.end());
-  *out = cand[pick];
-  return BMX_OK;
-}
-
-// Rehash into a table for `capacity_rows` rows. Synchronous.
-int grow_table(bmx_ctx* ctx, uint64_t capacity_rows) {
-  if (capacity_rows <= ctx->capacity_rows) return BMX_OK;
-  int rc;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint64_t nslots = slots_for(capacity_rows, ctx->load_pct);
-  if (!nslots) return fail(ctx, BMX_ERR_INVALID, "table would need more than 2^32 slots (slot indices are 32-bit): shard the graph over more contexts");
-  Slot* fresh = nullptr;
-  if ((rc = alloc_table_tuned(ctx, nslots, &fresh, /*growing=*/true))) return rc;
-  hipLaunchKernelGGL(k_init_slots, dim3(2048), dim3(256), 0, ctx->stream, fresh, nslots);
-  hipLaunchKernelGGL(k_rehash, dim3(2048), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots, fresh, nslots, &ctx->ds->status);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) { dev_free(fresh); return fail_hip(ctx, e, "grow_table"); }
-  dev_free(ctx->slots);
-  ctx->slots = fresh; ctx->nslots = nslots; ctx->capacity_rows = capacity_rows;
-  // the batch epoch keeps counting: next[] still holds links tagged with earlier epochs; the new heads are all 0
-  ctx->version++;          // indices are rebuilt on their next use
-  ctx->chg.valid = false;  // every row moved: the recorded slot positions mean nothing any more
-  dev_free(ctx->chg.slot_pos); ctx->chg.slot_pos_n = 0;
-  for (auto& ix : ctx->indexes) ix.has_pos = false;
-  return check_status(ctx);
-}
-
-// ---- deferred compaction ---------------------------------------------------------------------------------------------------------------
-// K3 (k_compact_winners) reads only per-batch workspace — winner bytes, block counts, the claimers' slots — and writes what the CALLER reads
-// after bmx_sync(): applied_idx, n_applied, stats. Nothing the next batch's probe kernel needs. So for a stream of device-resident batches the
-// compaction of batch b runs on a second, high-priority stream UNDER the probe kernel of batch b + 1 (which is bound by memory-side requests in
-// flight, not by CUs), and the context's stream carries K1 -> K2 -> K1 -> K2 ... only. Ordering without command-processor markers (an event
-// record between two kernels holds a stream ~10 us, bmx.h "bmx_seq_signal"):
-//   side stream:  k_seq_wait(seqw[0] >= q + 1)  ->  K3(q)  ->  k_seq_signal(seqw[1] = q)
-//   main stream:  K1(q + 1) [block 0 stores seqw[0] = q + 1 when it starts: K2(q) is done]  ->  K2(q + 1) [block 0 returns once seqw[1] >= q]
-// so K3(q) is complete before K1(q + 2) overwrites the workspace half it read, whatever the side stream's queue does. K3 is launched LATE: a
-// merge only records it (ctx->defer.pend); the next deferring merge puts it on the side stream, anything else (bmx_sync, a scan, a host batch, a
-// merge on another path, ...) launches it on the context's own stream first (flush_pending, called by every entry point) — after which that
-// stream is ordered behind everything, because the K2 in front of it waited for the only compaction that could still be running on the side.
-void launch_k3(bmx_ctx* ctx, const Deferral::PendingK3& P, hipStream_t ks) {
-  hipLaunchKernelGGL((k_compact_winners<FinishMerge>), dim3((uint32_t)(((uint64_t)P.n + 4095) / 4096)), dim3(SEL_THREADS), 0, ks, P.wflag, P.blk, P.n,
-                     P.applied, P.Fin, P.L, P.mark_created);
-  if (P.notify_after) hipLaunchKernelGGL(k_seq_signal_multi, dim3(1), dim3(64), 0, ks, ctx->notify, ctx->n_notify, (unsigned long long)P.notify_seq);
-}
-// The deferral protocol lets a one-wave kernel on the side stream wait for a kernel on the context's stream to START. Where the runtime or a tool runs
-// kernels strictly one at a time — rocprofv3 counter collection (--pmc serialises every dispatch of the device), HIP_LAUNCH_BLOCKING,
-// AMD_SERIALIZE_KERNEL — that wait would never end (it expires after ~60 s and raises BMX_ERR_INTERNAL). Such processes keep every launch in stream order.
-bool launches_are_serialized() {
-  auto on = [](const char* name) { const char* v = std::getenv(name); return v && v[0] && !(v[0] == '0' && !v[1]) && std::strcmp(v, "False") && std::strcmp(v, "false"); };
-  return on("ROCPROF_COUNTER_COLLECTION") || on("HIP_LAUNCH_BLOCKING") || on("AMD_SERIALIZE_KERNEL") || on("BMX_NO_DEFERRED_COMPACTION");
-}
-int flush_pending(bmx_ctx* ctx) {
-  if (ctx->defer.side_last) {
-    // the resolve kernel at the end of this stream waited for the compaction launched on the side stream TWO batches ago only: the last one may still be
-    // running there (it was released when the last probe kernel started, so this one-wave wait is a formality, and it cannot starve anything)
-    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)&ctx->ds->seqw[1], (unsigned long long)ctx->defer.side_last, &ctx->ds->status, ctx->ds->seq_diag);
-    LAUNCHCHK("k_seq_wait");
-    ctx->defer.side_last = ctx->defer.side_prev = 0;
-  }
-  if (!ctx->defer.pend.on) return BMX_OK;
-  ctx->defer.pend.on = false;
-  launch_k3(ctx, ctx->defer.pend, ctx->stream);
-  LAUNCHCHK("k_compact_winners");
-  return BMX_OK;
-}
-// every entry point that is not a deferring merge: bind the device, launch a compaction that is still only recorded
-int enter(bmx_ctx* ctx) {
-  HIPCHK(hipSetDevice(ctx->device));
-  return flush_pending(ctx);
-}
-constexpr uint64_t DEFER_MIN_N = 1u << 16;   // below this a batch is launch-bound: the side stream's three extra launches would cost more than the compaction
-
-// The merge proper: all pointers are device pointers; only enqueues work. `defer`: the caller reads applied_idx / n_applied / stats only after
-// bmx_sync() or another bmx_* call on this context (the BMX_MEM_DEVICE contract), so the compaction may be deferred (above).
-template <bool AOS>
-int merge_core(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-               const bmx_delta_rec* recs, int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags,
-               bmx_merge_stats* stats, bool defer = false, bool force = false) {
-  if (n > MAX_BATCH) return fail(ctx, BMX_ERR_INVALID, "batch larger than 2^24 deltas: split it (sequential semantics are preserved)");
-  const uint32_t mark_created = (insert_mode & BMX_MERGE_MARK_CREATED) ? 1u : 0u;
-  const bool unique = (insert_mode & BMX_MERGE_UNIQUE_KEYS) != 0 || force;      // force = bmx_put_rows: unique keys, stored as given
-  const bool strict = (insert_mode & BMX_MERGE_STRICT_FLAGS) != 0;
-  if (insert_mode & ~(BMX_INSERT_DELTA | BMX_MERGE_UNIQUE_KEYS | BMX_MERGE_STRICT_FLAGS | BMX_MERGE_MARK_CREATED)) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
-  insert_mode &= ~(BMX_MERGE_UNIQUE_KEYS | BMX_MERGE_STRICT_FLAGS | BMX_MERGE_MARK_CREATED);
-  if (force) insert_mode = BMX_INSERT_DELTA;
-  if (unique && strict) return fail(ctx, BMX_ERR_INVALID, "BMX_MERGE_STRICT_FLAGS cannot be combined with BMX_MERGE_UNIQUE_KEYS");
-  if (insert_mode != BMX_INSERT_REFERENCE && insert_mode != BMX_INSERT_DELTA) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
-  int rc;
-  hipEvent_t* pe = (ctx->prof.on && ctx->prof.n < PROF_MAX_CALLS) ? &ctx->prof.ev[4 * ctx->prof.n] : nullptr;
-  // the compaction of THIS batch is deferred iff the default path runs (K1 + K2) on a batch big enough to hide it behind; per-kernel profiling brackets every launch
-  const bool deferring = defer && ctx->defer.enabled && !strict && !unique && !pe && n >= DEFER_MIN_N;
-  if (!deferring && (rc = flush_pending(ctx))) return rc;     // everything else sees the stream in order
-  if (n == 0) {
-    if ((rc = flush_pending(ctx))) return rc;
-    if (n_applied) HIPCHK(hipMemsetAsync(n_applied, 0, sizeof(uint64_t), ctx->stream));
-    if (stats) HIPCHK(hipMemsetAsync(stats, 0, sizeof(bmx_merge_stats), ctx->stream));
-    return BMX_OK;
-  }
-  // capacity guards: physical (never let probing run out of empty slots) and logical (capacity_rows)
-  if (ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) tighten_rows_ub(ctx);
-  if (ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) {
-    // The bound counts every delta of every batch still in flight as a new row. A host that runs many batches ahead of the device (a stream of
-    // device batches: ~10 us per call against ~80 us per batch) reaches it long before the table is full: wait for the OLDEST batch in flight to
-    // report its row count (its compaction writes the host-visible mirror) and look again — the device keeps its queue, nothing drains. Only when
-    // nothing is left in flight does the exact count decide (below).
-    if ((rc = wait_for_row_reports(ctx, n))) return rc;
-  }
-  if (ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) {
-    if ((rc = flush_pending(ctx))) return rc;                 // the exact row count is the last compaction's
-    rc = refresh_rows(ctx);
-    if (rc) return rc;
-    if (ctx->rows_ub + n >= ctx->nslots || ctx->rows_ub > ctx->capacity_rows) {
-      if (ctx->fixed_capacity) return fail(ctx, BMX_ERR_FULL, "resident table is full (capacity_rows exceeded)");
-      uint64_t want = std::max<uint64_t>(ctx->capacity_rows * 2, ctx->rows_ub + n + n / 2);   // amortised doubling
-      if ((rc = grow_table(ctx, want))) return rc;
-    }
-  }
-  rc = ctx->ws.ensure(ctx, n);
-  if (rc) return rc;
-  if (deferring && !ctx->defer.side) {
-    int lo = 0, hi = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));      // hi = the numerically smallest = highest priority: a hardware queue of its own
-    HIPCHK(hipStreamCreateWithPriority(&ctx->defer.side, hipStreamNonBlocking, hi));
-  }
-  if (++ctx->epoch > EPOCH_MAX) {  // tags wrap: forget every claim
-    hipLaunchKernelGGL(k_sweep_heads, dim3(2048), dim3(256), 0, ctx->stream, ctx->slots, ctx->nslots);
-    LAUNCHCHK("k_sweep_heads");
-    HIPCHK(hipMemsetAsync(ctx->ws.next, 0, (size_t)ctx->ws.cap * sizeof(uint32_t), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->ws.blk_follow, 0, ((size_t)ctx->ws.cap / 256 + 16) * sizeof(uint32_t), ctx->stream));
-    ctx->epoch = 1;
-  }
-  // this batch's workspace set and block-summary segment
-  const uint32_t par = (ctx->ws.par = (ctx->ws.par + 1u) % MergeWs::SETS);
-  const uint32_t seg = ctx->ws.blk_seg, seg_next = (seg + 1u) % MergeWs::BLK_SEGS;
-  ctx->ws.blk_seg = seg_next;
-  uint8_t* wflag = ctx->ws.wflag[par];
-  unsigned long long* ctr = ctx->ws.shard_ctr + (size_t)par * CTR_SHARDS * CTR_STRIDE;
-  MergeArgs A;
-  A.slots = ctx->slots; A.nslots = ctx->nslots;
-  A.id = id; A.field = field; A.ts = ts; A.val = val; A.recs = recs;
-  A.n = (uint32_t)n; A.epoch = ctx->epoch;
-  A.next = ctx->ws.next; A.wflag = wflag; A.flags = flags;
-  A.slot_of = ctx->ws.slot_of[par]; A.blk_follow = ctx->ws.blk_follow; A.shard_ctr = ctr; A.status = &ctx->ds->status;
-  A.blk_info = ctx->ws.blk_info + (size_t)seg * ctx->ws.blk_half; A.blk_next = ctx->ws.blk_info + (size_t)seg_next * ctx->ws.blk_half; A.blk_ents = ctx->ws.blk_half;
-  const bool wave_k1 = !strict;       // k_probe_apply: adds into its segment, zeroes the next one
-  if (wave_k1 && !ctx->ws.blk_clean[seg]) HIPCHK(hipMemsetAsync(A.blk_info, 0, (size_t)ctx->ws.blk_half * sizeof(uint32_t), ctx->stream));   // a batch on another path used this segment last
-  ctx->ws.blk_clean[seg] = false; ctx->ws.blk_clean[seg_next] = wave_k1;
-  A.force = force ? 1u : 0u;
-  // the index change log of this batch (written by its compaction): decided here because a deferred compaction reads the deltas' fields from a copy
-  ChgLog L{};
-  if (ctx->chg.valid) {
-    if (!strict && (!unique || force) && ctx->chg.ub + n <= ctx->chg.cap && ctx->nslots < (1ull << 31)) {
-      L.chg = ctx->chg.log; L.base = &ctx->ds->chg_n[ctx->chg.par]; L.next = &ctx->ds->chg_n[ctx->chg.par ^ 1u];
-      L.slot_of = ctx->ws.slot_of[par]; L.field = field; L.recs = recs; L.cap = ctx->chg.cap;
-      if (deferring) { A.fld_out = ctx->ws.fld[par]; L.field = ctx->ws.fld[par]; L.recs = nullptr; }   // the caller's columns need not outlive this call's kernels
-      ctx->chg.par ^= 1u; ctx->chg.ub += n;
-    } else {
-      ctx->chg.valid = false;   // this batch is not in the log (another merge path, or the log is full): the next scan rebuilds
-    }
-  }
-  A.log_slots = (L.chg != nullptr) ? 1u : 0u;
-  const bool side_k3 = deferring && ctx->defer.pend.on;     // the compaction of the batch before goes to the side stream, under this batch's probe kernel
-  if (deferring) {
-    ++ctx->defer.seq;
-    A.started = &ctx->ds->seqw[0]; A.started_val = ctx->defer.seq;
-    if (side_k3) {
-      // this batch's resolve kernel ends only once the compaction launched on the side stream BEFORE the one that goes there now is done: the next probe
-      // kernel then reuses nothing a compaction still reads (three workspace sets), and that compaction has had two probe kernels' time
-      if (ctx->defer.side_last) { A.k3_done = &ctx->ds->seqw[1]; A.k3_wait = ctx->defer.side_last; }
-      if (ctx->defer.pend.Fin.n_notify) {   // the slab set of the batch before is free the moment this probe kernel starts: said there, not under it
-        A.notify = ctx->defer.pend.Fin.notify; A.n_notify = ctx->defer.pend.Fin.n_notify; A.notify_value = ctx->defer.pend.Fin.notify_value;
-        ctx->defer.pend.Fin.n_notify = 0;
-      }
-    }
-  }
-  bool tail_used = false;
-  if (ctx->tail_armed.n && !strict && !unique) {     // (paths without a resolve kernel leave it armed for nobody: the later wait launch is then not skipped)
-    A.tail_words = ctx->tail_armed.words; A.tail_n = ctx->tail_armed.n; A.tail_at_least = ctx->tail_armed.at_least; A.tail_diag = ctx->ds->seq_diag;
-    tail_used = true;
-  }
-  const uint32_t blocks = (uint32_t)((n + 255) / 256);
-  const uint32_t rblocks = blocks;   // one lane per delta
-  if (pe) HIPCHK(hipEventRecord(pe[0], ctx->stream));
-  if (strict) {
-    hipLaunchKernelGGL((k_probe_link_strict<AOS>), dim3(blocks), dim3(256), 0, ctx->stream, A);
-  } else {
-    constexpr int NT = 64;    // every wave its own workgroup (profiles/r03_ab_inserts.log)
-    const dim3 grid((uint32_t)((n + NT - 1) / NT));
-    const int kw = ctx->k1_waves;   // resident waves per SIMD the probe kernel may take (8 = all; 6 / 5 leave room for the kernels that run beside it)
-#define BMX_LAUNCH_K1(KERN) do { \
-      if (insert_mode == BMX_INSERT_REFERENCE) { \
-        if (unique) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_REFERENCE, true, NT>), grid, dim3(NT), 0, ctx->stream, A); \
-        else hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_REFERENCE, false, NT>), grid, dim3(NT), 0, ctx->stream, A); \
-      } else { \
-        if (unique) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_DELTA, true, NT>), grid, dim3(NT), 0, ctx->stream, A); \
-        else hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_DELTA, false, NT>), grid, dim3(NT), 0, ctx->stream, A); \
-      } } while (0)
-    if (kw == 6) BMX_LAUNCH_K1(k_probe_apply_w6); else if (kw == 5) BMX_LAUNCH_K1(k_probe_apply_w5); else if (kw == 4) BMX_LAUNCH_K1(k_probe_apply_w4);
-    else if (kw == 3) BMX_LAUNCH_K1(k_probe_apply_w3); else BMX_LAUNCH_K1(k_probe_apply);
-#undef BMX_LAUNCH_K1
-  }
-  LAUNCHCHK("k_probe_apply");
-  if (side_k3) {
-    // K1 of this batch is enqueued: the wait below cannot be left without its signal. K3 of the batch before, on the side stream.
-    hipLaunchKernelGGL(k_seq_wait, dim3(1), dim3(64), 0, ctx->defer.side, (const unsigned long long*)&ctx->ds->seqw[0], (unsigned long long)ctx->defer.seq, &ctx->ds->status, ctx->ds->seq_diag);
-    launch_k3(ctx, ctx->defer.pend, ctx->defer.side);
-    hipLaunchKernelGGL(k_seq_signal, dim3(1), dim3(64), 0, ctx->defer.side, &ctx->ds->seqw[1], (unsigned long long)ctx->defer.pend.seq);
-    ctx->defer.side_prev = ctx->defer.side_last; ctx->defer.side_last = ctx->defer.pend.seq;
-    ctx->defer.pend.on = false;
-    ctx->defer.n_side++;
-    LAUNCHCHK("deferred k_compact_winners");
-  }
-  if (pe) HIPCHK(hipEventRecord(pe[1], ctx->stream));
-  if (strict) {   // flags for every delta against the untouched rows, then the final state by the last claimers
-    if (insert_mode == BMX_INSERT_REFERENCE) {
-      if (flags) hipLaunchKernelGGL((k_resolve_strict<AOS, BMX_INSERT_REFERENCE, false>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-      hipLaunchKernelGGL((k_resolve_strict<AOS, BMX_INSERT_REFERENCE, true>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-    } else {
-      if (flags) hipLaunchKernelGGL((k_resolve_strict<AOS, BMX_INSERT_DELTA, false>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-      hipLaunchKernelGGL((k_resolve_strict<AOS, BMX_INSERT_DELTA, true>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-    }
-  } else if (!unique) {  // duplicate keys can only exist without the caller's guarantee
-    if (insert_mode == BMX_INSERT_REFERENCE) hipLaunchKernelGGL((k_resolve_lists<AOS, BMX_INSERT_REFERENCE>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-    else hipLaunchKernelGGL((k_resolve_lists<AOS, BMX_INSERT_DELTA>), dim3(rblocks), dim3(256), 0, ctx->stream, A);
-  }
-  LAUNCHCHK("k_resolve_lists");
-  if (tail_used) { ctx->tail_waited = ctx->tail_armed; }
-  ctx->tail_armed = bmx_ctx::TailWait{};
-  if (pe) HIPCHK(hipEventRecord(pe[2], ctx->stream));
-  // K3: ordered compaction of the winner bytes (+ the index change log while an index is being maintained)
-  Deferral::PendingK3 P;
-  P.wflag = wflag; P.blk = A.blk_info; P.n = (uint32_t)n; P.applied = applied_idx; P.L = L; P.mark_created = mark_created;
-  P.Fin = FinishMerge{reinterpret_cast<unsigned long long*>(n_applied), stats, ctr, &ctx->ds->row_count};
-  if (ctx->host_rows) { P.Fin.host_mirror = ctx->host_rows; P.Fin.seq = ++ctx->batch_seq; ctx->inflight.emplace_back(P.Fin.seq, n); }
-  const bool notifying = ctx->n_notify && ctx->notify_armed;
-  P.notify_after = notifying && L.chg && !deferring;   // a change log read from the caller's columns: the compaction's workgroups still read the batch, so the peers are told from a launch behind it
-  if (notifying) { P.notify_seq = ++ctx->notify_seq; if (!P.notify_after) { P.Fin.notify = ctx->notify; P.Fin.n_notify = ctx->n_notify; P.Fin.notify_value = ctx->notify_seq; } }
-  if (deferring) {
-    P.on = true; P.seq = ctx->defer.seq;
-    ctx->defer.pend = P;
-    ctx->defer.n_deferred++;
-  } else {
-    launch_k3(ctx, P, ctx->stream);
-    LAUNCHCHK("k_compact_winners");
-  }
-  if (pe) { HIPCHK(hipEventRecord(pe[3], ctx->stream)); ctx->prof.n++; }
-  ctx->nbatch++;
-  ctx->rows_ub += n;
-  ctx->version++;
-  return BMX_OK;
-}
-
-// records already on the device, for callers INSIDE the library (the communicator): the put marker is honoured, the compaction is never deferred
-int merge_records_internal(bmx_ctx* ctx, uint64_t n, const bmx_delta_rec* recs, int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
-  HIPCHK(hipSetDevice(ctx->device));
-  return merge_core<true>(ctx, n, nullptr, nullptr, nullptr, nullptr, recs, insert_mode & ~MERGE_FORCE_INTERNAL, applied_idx, n_applied, nullptr, stats, false,
-                          (insert_mode & MERGE_FORCE_INTERNAL) != 0);
-}
-
+#include "bmx_merge.inc"
 #include "bmx_host.inc"
 
 Index* find_index(bmx_ctx* ctx, uint32_t field) {
@@ -1215,25 +818,6 @@ int scan_range_impl(bmx_ctx* ctx, uint32_t field, int64_t lo, int64_t hi, uint64
   return scan_range_impl_t<false>(ctx, field, lo, hi, out_ids, cap, n_out, mem);
 }
 
-// bmx_load_rows / bmx_put_rows: chunks of 2^22 rows (force: bmx_put_rows, stored as given)
-int load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem, bool force) {
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (int erc = enter(ctx)) return erc;
-  const uint64_t chunk = 1u << 22;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - off);
-    int rc;
-    if (mem == BMX_MEM_DEVICE)
-      rc = merge_core<false>(ctx, m, id + off, field + off, ts + off, val + off, nullptr, BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr, false, force);
-    else
-      rc = merge_host(ctx, m, id + off, field + off, ts + off, val + off, force ? MERGE_FORCE_INTERNAL : BMX_INSERT_DELTA, nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return mem == BMX_MEM_DEVICE ? BMX_OK : check_status(ctx);
-}
-
 // the mean time between consecutive events of the profiled calls: `per` events per call, per - 1 intervals
 int profile_means(bmx_ctx* ctx, bool scan, float* ms_out, uint32_t* n_calls) {
   if (!ctx || !ms_out || !n_calls) return fail(ctx, BMX_ERR_INVALID, "bad arguments");
@@ -1474,22 +1058,23 @@ int bmx_merge_batch(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t
                     int insert_mode, int mem, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
-  if (!public_mode_ok(insert_mode)) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return fail(ctx, BMX_ERR_INVALID, bad);
   HIPCHK(hipSetDevice(ctx->device));
-  if (mem == BMX_MEM_DEVICE) return merge_core<false>(ctx, n, id, field, ts, val, nullptr, insert_mode, applied_idx, n_applied, flags, stats, /*defer=*/true);
+  const MergeIn in{n, id, field, ts, val, nullptr}; const MergeOut out{applied_idx, n_applied, flags, stats};
+  if (mem == BMX_MEM_DEVICE) return merge_core(ctx, in, out, mode, /*defer=*/true);
   if (mem != BMX_MEM_HOST) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (n > MAX_BATCH) return fail(ctx, BMX_ERR_INVALID, "batch larger than 2^24 deltas: split it (sequential semantics are preserved)");
-  return merge_host(ctx, n, id, field, ts, val, insert_mode, applied_idx, n_applied, flags, stats);
+  if (n > MAX_BATCH) return fail(ctx, BMX_ERR_INVALID, BATCH_TOO_LARGE);   // before staging memory is sized
+  return merge_host(ctx, in, mode, out);
 }
 
 int bmx_merge_submit(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int insert_mode,
                      int want_flags, uint64_t* ticket) {
   if (!ctx || !ticket) return fail(ctx, BMX_ERR_INVALID, "bmx_merge_submit: null context or ticket");
   if (n && (!id || !field || !ts || !val)) return fail(ctx, BMX_ERR_INVALID, "null input column");
-  if (n > MAX_BATCH) return fail(ctx, BMX_ERR_INVALID, "batch larger than 2^24 deltas: split it (sequential semantics are preserved)");
-  if (!public_mode_ok(insert_mode)) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
+  if (n > MAX_BATCH) return fail(ctx, BMX_ERR_INVALID, BATCH_TOO_LARGE);   // before staging memory is sized
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (int erc = enter(ctx)) return erc;
-  return submit_host(ctx, n, id, field, ts, val, insert_mode, want_flags != 0, ticket, true);
+  return submit_host(ctx, MergeIn{n, id, field, ts, val, nullptr}, mode, want_flags != 0, ticket, true);
 }
 
 int bmx_merge_collect(bmx_ctx* ctx, uint64_t ticket, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
@@ -1502,9 +1087,9 @@ int bmx_merge_records(bmx_ctx* ctx, uint64_t n, const bmx_delta_rec* recs, int i
                       uint8_t* flags, bmx_merge_stats* stats) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (n && !recs) return fail(ctx, BMX_ERR_INVALID, "null records");
-  if (!public_mode_ok(insert_mode)) return fail(ctx, BMX_ERR_INVALID, "bad insert_mode");
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return fail(ctx, BMX_ERR_INVALID, bad);
   HIPCHK(hipSetDevice(ctx->device));
-  return merge_core<true>(ctx, n, nullptr, nullptr, nullptr, nullptr, recs, insert_mode, applied_idx, n_applied, flags, stats, /*defer=*/true);
+  return merge_core(ctx, MergeIn{n, nullptr, nullptr, nullptr, nullptr, recs}, MergeOut{applied_idx, n_applied, flags, stats}, mode, /*defer=*/true);
 }
 
 int bmx_merge_records_after(bmx_ctx* ctx, const uint64_t* wait_words_dev, uint32_t n_wait, uint64_t wait_at_least, uint64_t n, const bmx_delta_rec* recs,
@@ -1521,12 +1106,8 @@ int bmx_merge_records_after(bmx_ctx* ctx, const uint64_t* wait_words_dev, uint32
   return rc;
 }
 
-int bmx_load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) {
-  return load_rows(ctx, n, id, field, ts, val, mem, false);
-}
-int bmx_put_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) {
-  return load_rows(ctx, n, id, field, ts, val, mem, true);
-}
+int bmx_load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) { return load_rows(ctx, n, id, field, ts, val, mem, MODE_LOAD); }
+int bmx_put_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int mem) { return load_rows(ctx, n, id, field, ts, val, mem, MODE_PUT); }
 
 int bmx_get_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, int64_t* ts, int64_t* val, uint8_t* found, int mem) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");

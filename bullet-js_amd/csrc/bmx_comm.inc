@@ -112,7 +112,7 @@ int comm_ensure_recv(bmx_comm* c, uint32_t g, uint64_t n) {
 // through each shard's small-batch path (mapped host memory, ~30 us per shard that got anything). Keys never straddle shards and the split keeps
 // the batch order inside a shard, so the sequential semantics hold as in the device-routed path, which costs 1.2-2.3 ms per call whatever the size.
 constexpr uint64_t COMM_SMALL_N = 32768;
-int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int insert_mode,
+int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, const MergeMode& mode,
                     uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
   const uint32_t N = c->N;
   if (c->dev_step_pending) { int rc = bmx_comm_sync(c); if (rc) return rc; }
@@ -129,7 +129,7 @@ int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
     for (size_t x = 0; x < m; x++) { const uint32_t j = back[g][x]; gi[x] = id[j]; gf[x] = field[j]; gt[x] = ts[j]; gv[x] = val[j]; }
     uint64_t na = 0;
     CHIP(hipSetDevice(c->dev[g]));
-    CSH(g, merge_host(c->sh[g], m, gi.data(), gf.data(), gt.data(), gv.data(), insert_mode, applied_idx ? ga.data() : nullptr, &na, nullptr, &st));
+    CSH(g, merge_host(c->sh[g], MergeIn{m, gi.data(), gf.data(), gt.data(), gv.data(), nullptr}, mode, MergeOut{applied_idx ? ga.data() : nullptr, &na, nullptr, &st}));
     if (applied_idx) for (uint64_t x = 0; x < na; x++) winners.push_back(back[g][ga[x]]);
     tot.n_applied += st.n_applied; tot.n_conflicts += st.n_conflicts; tot.n_rows += st.n_rows;
   }
@@ -143,20 +143,20 @@ int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
 }
 
 // One host batch through the shards. want = winners wanted (merge) or not (load).
-int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int insert_mode,
+int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, const MergeMode& mode,
                     uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
   const uint32_t N = c->N;
-  if (n > MAX_BATCH) return cfail(c, BMX_ERR_INVALID, "batch larger than 2^24 deltas: split it (sequential semantics are preserved)");
+  if (n > MAX_BATCH) return cfail(c, BMX_ERR_INVALID, BATCH_TOO_LARGE);   // before a partition is launched
   if (n_applied) *n_applied = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (n && (!id || !field || !ts || !val)) return cfail(c, BMX_ERR_INVALID, "null input column");
-  if (n && n <= COMM_SMALL_N) return comm_host_small(c, n, id, field, ts, val, insert_mode, applied_idx, n_applied, stats);
+  if (n && n <= COMM_SMALL_N) return comm_host_small(c, n, id, field, ts, val, mode, applied_idx, n_applied, stats);
   if (c->dev_step_pending) { int rc0 = bmx_comm_sync(c); if (rc0) return rc0; }
   if (N == 1 && n) {   // one shard owns everything: nothing to route, no winner map to build — the context's own host-batch path (two staging sets, three streams)
     CHIP(hipSetDevice(c->dev[0]));
     bmx_merge_stats st; std::memset(&st, 0, sizeof(st));
     uint64_t na = 0;
-    int rc = merge_host(c->sh[0], n, id, field, ts, val, insert_mode, applied_idx, &na, nullptr, &st);
+    int rc = merge_host(c->sh[0], MergeIn{n, id, field, ts, val, nullptr}, mode, MergeOut{applied_idx, &na, nullptr, &st});
     if (rc) return cfail(c, rc, std::string("shard 0: ") + bmx_last_error(c->sh[0]));
     if (n_applied) *n_applied = na;
     if (stats) *stats = st;
@@ -212,7 +212,7 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
     hipStream_t st = reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[g]));
     if (g) CHIP(hipStreamWaitEvent(st, routed0, 0));
     if (m[g]) {
-      CSH(g, merge_records_internal(c->sh[g], slab, G.recv, insert_mode, applied_idx ? G.applied : nullptr, reinterpret_cast<uint64_t*>(G.n_applied), G.stats));
+      CSH(g, merge_records_internal(c->sh[g], slab, G.recv, mode, applied_idx ? G.applied : nullptr, reinterpret_cast<uint64_t*>(G.n_applied), G.stats));
       if (applied_idx) {
         hipLaunchKernelGGL(k_mark_aux, dim3(256), dim3(256), 0, st, (const bmx_delta_rec*)G.recv, (const uint32_t*)G.applied, (const unsigned long long*)G.n_applied, c->g_flag);
         CHIP(hipGetLastError());
@@ -254,6 +254,12 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
   if (n_applied) *n_applied = total;
   if (stats) *stats = tot;
   return BMX_OK;
+}
+// bmx_comm_load_rows (MODE_LOAD) / bmx_comm_put_rows (MODE_PUT)
+int comm_load_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, const MergeMode& mode) {
+  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  DevGuard guard;
+  return in_load_chunks(n, id, field, ts, val, [&](const MergeIn& p) { return comm_host_batch(c, p.n, p.id, p.field, p.ts, p.val, mode, nullptr, nullptr, nullptr); });
 }
 }  // namespace
 
@@ -333,43 +339,22 @@ int bmx_comm_sync(bmx_comm* c) {
   return first ? cfail(c, first, msg) : BMX_OK;
 }
 
-int bmx_comm_load_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
-  DevGuard guard;
-  const uint64_t chunk = 1u << 22;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - off);
-    int rc = comm_host_batch(c, m, id + off, field + off, ts + off, val + off, BMX_INSERT_DELTA, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return BMX_OK;
-}
-
-int bmx_comm_put_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
-  DevGuard guard;
-  const uint64_t chunk = 1u << 22;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = std::min<uint64_t>(chunk, n - off);
-    int rc = comm_host_batch(c, m, id + off, field + off, ts + off, val + off, MERGE_FORCE_INTERNAL, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return BMX_OK;
-}
+int bmx_comm_load_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) { return comm_load_rows(c, n, id, field, ts, val, MODE_LOAD); }
+int bmx_comm_put_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) { return comm_load_rows(c, n, id, field, ts, val, MODE_PUT); }
 
 int bmx_comm_merge(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int insert_mode,
                    uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
   if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
-  if (!public_mode_ok(insert_mode)) return cfail(c, BMX_ERR_INVALID, "bad insert_mode");
-  if (insert_mode & BMX_MERGE_STRICT_FLAGS) return cfail(c, BMX_ERR_INVALID, "bmx_comm_merge: per-delta flags are not collected across shards");
-  return comm_host_batch(c, n, id, field, ts, val, insert_mode, applied_idx, n_applied, stats);
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return cfail(c, BMX_ERR_INVALID, bad);
+  if (mode.strict) return cfail(c, BMX_ERR_INVALID, "bmx_comm_merge: per-delta flags are not collected across shards");
+  return comm_host_batch(c, n, id, field, ts, val, mode, applied_idx, n_applied, stats);
 }
 
 int bmx_comm_merge_dev(bmx_comm* c, const uint64_t* n, const uint64_t* const* id, const uint32_t* const* field, const int64_t* const* ts,
                        const int64_t* const* val, int insert_mode, uint64_t slab_records) {
   if (!c || !n || !id || !field || !ts || !val) return cfail(c, BMX_ERR_INVALID, "bmx_comm_merge_dev: null argument");
-  if (!public_mode_ok(insert_mode)) return cfail(c, BMX_ERR_INVALID, "bad insert_mode");
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return cfail(c, BMX_ERR_INVALID, bad);   // before anything is routed; the shards' bmx_merge_records take insert_mode as it is
   DevGuard guard;
   const uint32_t N = c->N;
   uint64_t nmax = 0;

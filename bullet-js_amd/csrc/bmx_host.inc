@@ -75,8 +75,8 @@ __global__ void k_noop() {}
 __global__ void k_small_tail(const unsigned long long* n_applied, const bmx_merge_stats* stats, const uint32_t* status, SmallOut* out) {
   if (threadIdx.x == 0) { out->n_applied = *n_applied; out->stats = *stats; out->status = *status; }
 }
-int submit_host(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-                int insert_mode, bool want_flags, uint64_t* ticket, bool inputs_free_on_return) {
+int submit_host(bmx_ctx* ctx, const MergeIn& in, const MergeMode& mode, bool want_flags, uint64_t* ticket, bool inputs_free_on_return) {
+  const uint64_t n = in.n;
   int k = -1;
   for (int i = 0; i < 2; i++) if (!ctx->host.stg[i].busy) { k = i; break; }
   if (k < 0) return fail(ctx, BMX_ERR_INVALID, "two batches are already in flight: collect the oldest first (bmx_merge_collect)");
@@ -84,17 +84,16 @@ int submit_host(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fi
   int rc = ensure_staging(ctx, k, n);
   if (rc) return rc;
   if (n) {
-    HIPCHK(hipMemcpyAsync(S.id, id, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
-    HIPCHK(hipMemcpyAsync(S.field, field, n * 4, hipMemcpyHostToDevice, ctx->host.copy_stream));
-    HIPCHK(hipMemcpyAsync(S.ts, ts, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
-    HIPCHK(hipMemcpyAsync(S.val, val, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
+    HIPCHK(hipMemcpyAsync(S.id, in.id, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
+    HIPCHK(hipMemcpyAsync(S.field, in.field, n * 4, hipMemcpyHostToDevice, ctx->host.copy_stream));
+    HIPCHK(hipMemcpyAsync(S.ts, in.ts, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
+    HIPCHK(hipMemcpyAsync(S.val, in.val, n * 8, hipMemcpyHostToDevice, ctx->host.copy_stream));
     HIPCHK(hipEventRecord(S.up, ctx->host.copy_stream));
     HIPCHK(hipStreamWaitEvent(ctx->stream, S.up, 0));
     // a copy from page-locked memory (bmx_host_alloc) is truly asynchronous: bmx_merge_submit promises that the arrays may be reused on return
     if (inputs_free_on_return) HIPCHK(hipEventSynchronize(S.up));
   }
-  rc = merge_core<false>(ctx, n, S.id, S.field, S.ts, S.val, nullptr, insert_mode & ~MERGE_FORCE_INTERNAL, S.applied, reinterpret_cast<uint64_t*>(S.n_out),
-                         want_flags ? S.flags : nullptr, S.stats, false, (insert_mode & MERGE_FORCE_INTERNAL) != 0);
+  rc = merge_core(ctx, MergeIn{n, S.id, S.field, S.ts, S.val, nullptr}, MergeOut{S.applied, reinterpret_cast<uint64_t*>(S.n_out), want_flags ? S.flags : nullptr, S.stats}, mode);
   if (rc) return rc;
   if (S.tail) {
     hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)S.n_out, (const bmx_merge_stats*)S.stats, (const uint32_t*)&ctx->ds->status, S.tail);
@@ -165,21 +164,21 @@ bool ensure_pinned(bmx_ctx* ctx) {   // the two mapped host buffers of the small
   }
   return true;
 }
-int merge_host_small(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-                     int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
+int merge_host_small(bmx_ctx* ctx, const MergeIn& in, const MergeMode& mode, const MergeOut& out) {
   if (!ensure_pinned(ctx)) return SMALL_PATH_UNAVAILABLE;
+  const uint64_t n = in.n;
   // the previous small batch's kernels are done (every call ends with a synchronisation): the buffers are free
   uint64_t* p_id = reinterpret_cast<uint64_t*>(ctx->host.pin_in);
   int64_t* p_ts = reinterpret_cast<int64_t*>(ctx->host.pin_in + n * 8);
   int64_t* p_val = reinterpret_cast<int64_t*>(ctx->host.pin_in + n * 16);
   uint32_t* p_field = reinterpret_cast<uint32_t*>(ctx->host.pin_in + n * 24);
-  std::memcpy(p_id, id, n * 8); std::memcpy(p_ts, ts, n * 8); std::memcpy(p_val, val, n * 8); std::memcpy(p_field, field, n * 4);
+  std::memcpy(p_id, in.id, n * 8); std::memcpy(p_ts, in.ts, n * 8); std::memcpy(p_val, in.val, n * 8); std::memcpy(p_field, in.field, n * 4);
   uint32_t* o_applied = reinterpret_cast<uint32_t*>(ctx->host.pin_out + SMALL_OUT_APPLIED);
   uint8_t* o_flags = ctx->host.pin_out + SMALL_OUT_FLAGS;
   SmallOut* o_tail = reinterpret_cast<SmallOut*>(ctx->host.pin_out + SMALL_OUT_TAIL);
   // count and stats go through device scalars first (the merge's last workgroup read-modify-writes them), then one thread copies them out
-  int rc = merge_core<false>(ctx, n, p_id, p_field, p_ts, p_val, nullptr, insert_mode & ~MERGE_FORCE_INTERNAL, applied_idx ? o_applied : nullptr, reinterpret_cast<uint64_t*>(&ctx->ds->n_out),
-                             flags ? o_flags : nullptr, &ctx->ds->stats, false, (insert_mode & MERGE_FORCE_INTERNAL) != 0);
+  int rc = merge_core(ctx, MergeIn{n, p_id, p_field, p_ts, p_val, nullptr},
+                      MergeOut{out.applied_idx ? o_applied : nullptr, reinterpret_cast<uint64_t*>(&ctx->ds->n_out), out.flags ? o_flags : nullptr, &ctx->ds->stats}, mode);
   if (rc) return rc;
   hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)&ctx->ds->n_out, (const bmx_merge_stats*)&ctx->ds->stats,
                      (const uint32_t*)&ctx->ds->status, o_tail);
@@ -187,25 +186,24 @@ int merge_host_small(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (o_tail->status) return check_status(ctx);
   const bmx_merge_stats hs = o_tail->stats;
-  if (applied_idx && hs.n_applied) std::memcpy(applied_idx, o_applied, hs.n_applied * 4);
-  if (flags) std::memcpy(flags, o_flags, n);
+  if (out.applied_idx && hs.n_applied) std::memcpy(out.applied_idx, o_applied, hs.n_applied * 4);
+  if (out.flags) std::memcpy(out.flags, o_flags, n);
   ctx->rows_ub = hs.n_rows; ctx->inflight.clear();
-  if (n_applied) *n_applied = hs.n_applied;
-  if (stats) *stats = hs;
+  if (out.n_applied) *out.n_applied = hs.n_applied;
+  if (out.stats) *out.stats = hs;
   return BMX_OK;
 }
 
-int merge_host(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val,
-               int insert_mode, uint32_t* applied_idx, uint64_t* n_applied, uint8_t* flags, bmx_merge_stats* stats) {
+int merge_host(bmx_ctx* ctx, const MergeIn& in, const MergeMode& mode, const MergeOut& out) {
   for (int i = 0; i < 2; i++)
     if (ctx->host.stg[i].busy) return fail(ctx, BMX_ERR_INVALID, "a submitted batch is still in flight: collect it before a synchronous merge");
-  if (n && n <= SMALL_HOST_N) {
-    int src = merge_host_small(ctx, n, id, field, ts, val, insert_mode, applied_idx, n_applied, flags, stats);
+  if (in.n && in.n <= SMALL_HOST_N) {
+    int src = merge_host_small(ctx, in, mode, out);
     if (src != SMALL_PATH_UNAVAILABLE) return src;
   }
   uint64_t ticket = 0;
-  int rc = submit_host(ctx, n, id, field, ts, val, insert_mode, flags != nullptr, &ticket, false);   // collect_host waits for the whole batch
+  int rc = submit_host(ctx, in, mode, out.flags != nullptr, &ticket, false);   // collect_host waits for the whole batch
   if (rc) return rc;
-  return collect_host(ctx, ticket, applied_idx, n_applied, flags, stats);
+  return collect_host(ctx, ticket, out.applied_idx, out.n_applied, out.flags, out.stats);
 }
 

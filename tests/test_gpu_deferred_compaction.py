@@ -151,6 +151,51 @@ def test_anything_between_two_merges_sees_the_finished_batch():
         assert e.deferred_counts()[0] >= 16
 
 
+def _record_batch(n, R, b):
+    """about 60 % distinct resident rows, 30 % repeats of 97 hot rows, 10 % rows nothing has seen yet; clocks around the resident rows' (some win, some lose)"""
+    rng = np.random.default_rng(8100 + b)
+    u = rng.integers(0, 100, n)
+    rows = np.empty(n, dtype=np.int64)
+    hit, hot, ins = u >= 40, (u >= 10) & (u < 40), u < 10
+    rows[hit] = rng.permutation(R)[:int(hit.sum())]
+    rows[hot] = rng.integers(0, 97, int(hot.sum()))
+    rows[ins] = R + b * n + np.nonzero(ins)[0]
+    ids, fld = synth.rows_to_keys(rows)
+    return ids, fld, 1_000_000 + b * 40_000 + rng.integers(0, 2_000_000, n), rng.integers(-(1 << 31), 1 << 31, n)
+
+
+@pytest.mark.parametrize("n", [65_536, 65_535])
+def test_record_batches_at_the_deferral_threshold_log_from_the_workspace_copy_of_the_fields(n):
+    """records (AOS) back to back at DEFER_MIN_N, the smallest batch that defers, and one below it, with an index maintained from the change log: a deferred
+    compaction logs the fields from the workspace copy the probe kernel made. Five batches: the three workspace sets and four block-summary segments wrap once."""
+    dev = torch.device("cuda", 0)
+    R, NB = 50_000, 5
+    F = streams.field_hash(0)
+    res = synth.big_resident(R, seed=81)
+    o = Oracle(); o.load_rows(*res)
+    hb = [_record_batch(n, R, b) for b in range(NB)]
+    recs = torch.zeros((NB, n, 4), dtype=torch.int64, device=dev)
+    counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    applied = torch.zeros((NB, n), dtype=torch.int32, device=dev)
+    n_applied = torch.zeros(NB, dtype=torch.int64, device=dev)
+    with bmx.Engine(2 * (R + NB * n)) as e:
+        e.load_rows(*res)
+        e.index_build(F)
+        for b in range(NB):
+            e.partition_by_owner_dev(n, *_dev(hb[b], dev), 1, recs[b], counts)     # one shard: the batch as records, in batch order
+        e.sync()
+        for b in range(NB):
+            e.merge_records_dev(n, recs[b], INSERT_REFERENCE, applied=applied[b], n_applied=n_applied[b:b + 1])
+        e.sync()
+        assert e.deferred_counts() == ((NB, NB - 1) if n >= 65_536 else (0, 0))
+        _check_batches(o, hb, applied, n_applied)
+        for lo, hi in ((-(1 << 27), 1 << 27), (-(1 << 40), 1 << 40)):
+            assert np.array_equal(np.sort(e.scan_range(F, lo, hi)), np.sort(o.scan_range(F, lo, hi)))
+        full, inc = e.index_refresh_counts()
+        assert full == 1 and inc >= 1, (full, inc)                                 # the log stayed valid through all five
+        assert e.row_count() == len(o) and rows_digest(*e.dump_rows()) == o.digest()
+
+
 def test_inputs_may_be_overwritten_in_stream_order_and_the_fence_orders_the_outputs():
     """the engine runs on the CALLER's stream: the batch columns are overwritten by the caller's next kernel on that stream (an index is being
     maintained, so the compaction wants the deltas' fields — from its own copy), and the outputs are read on that stream behind bmx_merge_fence"""
