@@ -467,9 +467,7 @@ static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32
   uint64_t* want = (out_ids && cap) ? out_ids : nullptr;
   for (uint32_t g = 0; g < c->N; g++) {
     bmx_ctx* x = c->sh[g];
-    x->scan.defer = true;
-    const int rc = terms ? bmx_scan_filter(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST) : bmx_scan_range(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST);
-    x->scan.defer = false;
+    const int rc = terms ? scan_filter_impl(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true) : scan_range_impl(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
     if (rc) {   // nothing of the shards before g is delivered; their scans finish on their own streams
       return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));
     }

@@ -1,6 +1,8 @@
 // bmx_host.inc — the paths of BMX_MEM_HOST calls: copy streams, the two staging sets (bmx_merge_submit / bmx_merge_collect), the small-batch path through
 // mapped host memory, merge_host, the mapped result words and the point reads' columns. Included by bmx.hip (one translation unit), which keeps their
 // state (HostIO).
+namespace {
+
 int HostIO::create(bmx_ctx* ctx) {
   int rc;
   if ((rc = dev_alloc_all(ctx, {{stg[0].n_out, sizeof(unsigned long long)}, {stg[0].stats, sizeof(bmx_merge_stats)},
@@ -152,6 +154,13 @@ bool ensure_hres(bmx_ctx* ctx) {
   ctx->host.hres = static_cast<volatile unsigned long long*>(p);
   return true;
 }
+// a caller's host buffer that the device can write itself (bmx_host_alloc, hipHostMalloc, a registered range): its device address, or nullptr
+void* mapped_host(void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) return at.devicePointer;
+  (void)hipGetLastError();
+  return nullptr;
+}
 bool ensure_pinned(bmx_ctx* ctx) {   // the two mapped host buffers of the small-call paths (merge, point reads, scans); false = fall back to copies
   if (ctx->host.pin_in) return true;
   { const char* t = std::getenv("BMX_TEST_FAIL_PINNED"); if (t && t[0] == '1') return false; }   // test hook: as if the page-locked allocation had failed
@@ -207,3 +216,4 @@ int merge_host(bmx_ctx* ctx, const MergeIn& in, const MergeMode& mode, const Mer
   return collect_host(ctx, ticket, out.applied_idx, out.n_applied, out.flags, out.stats);
 }
 
+}  // namespace

@@ -1,6 +1,8 @@
 // bmx_merge.inc — the host side of the merge: workspace and table (MergeWs::ensure, alloc_table_tuned, grow_table), the row-count bound, the deferred compaction, merge_core
 // as a list of named steps, the row loads. Included by bmx.hip (one translation unit), which keeps its state (MergeWs, Deferral, bmx_ctx), where this code always sat: the
-// code object lays kernel templates out in the order the source first uses them (bmx.hip, "the view's sort").
+// code object lays kernel templates out in the order the source first uses them (bmx.hip, the include list).
+namespace {
+
 int refresh_rows(bmx_ctx* ctx) {
   unsigned long long r = 0;
   if (ctx->host_rows && ctx->batch_seq > 0) {      // every change of the row count went through a merge, whose last workgroup mirrored it to the host
@@ -178,7 +180,7 @@ int grow_table(bmx_ctx* ctx, uint64_t capacity_rows) {
 void launch_k3(bmx_ctx* ctx, const Deferral::PendingK3& P, hipStream_t ks) {
   hipLaunchKernelGGL((k_compact_winners<FinishMerge>), dim3((uint32_t)(((uint64_t)P.n + 4095) / 4096)), dim3(SEL_THREADS), 0, ks, P.wflag, P.blk, P.n,
                      P.applied, P.Fin, P.L, P.mark_created);
-  if (P.notify_after) hipLaunchKernelGGL(k_seq_signal_multi, dim3(1), dim3(64), 0, ks, ctx->notify, ctx->n_notify, (unsigned long long)P.notify_seq);
+  if (P.notify_after) hipLaunchKernelGGL(k_seq_signal_multi, dim3(1), dim3(64), 0, ks, ctx->slab.notify, ctx->slab.n_notify, (unsigned long long)P.notify_seq);
 }
 // The deferral protocol lets a one-wave kernel on the side stream wait for a kernel on the context's stream to START. Where the runtime or a tool runs
 // kernels strictly one at a time — rocprofv3 counter collection (--pmc serialises every dispatch of the device), HIP_LAUNCH_BLOCKING,
@@ -299,8 +301,8 @@ bool arm_deferral(bmx_ctx* ctx, const MergeMode& mode, bool deferring, bool side
       if (PF.n_notify) { A.notify = PF.notify; A.n_notify = PF.n_notify; A.notify_value = PF.notify_value; PF.n_notify = 0; }   // the slab set of the batch before is free the moment this probe kernel starts: said there, not under it
     }
   }
-  if (!ctx->tail_armed.n || mode.strict || mode.unique) return false;     // (paths without a resolve kernel leave it armed for nobody: the later wait launch is then not skipped)
-  A.tail_words = ctx->tail_armed.words; A.tail_n = ctx->tail_armed.n; A.tail_at_least = ctx->tail_armed.at_least; A.tail_diag = ctx->ds->seq_diag;
+  if (!ctx->slab.tail_armed.n || mode.strict || mode.unique) return false;     // (paths without a resolve kernel leave it armed for nobody: the later wait launch is then not skipped)
+  A.tail_words = ctx->slab.tail_armed.words; A.tail_n = ctx->slab.tail_armed.n; A.tail_at_least = ctx->slab.tail_armed.at_least; A.tail_diag = ctx->ds->seq_diag;
   return true;
 }
 // K1 on the context's stream: the strict path's link kernel, or k_probe_apply for this rule / unique at the occupancy BMX_K1_WAVES asks for. Owns nothing.
@@ -364,9 +366,9 @@ int finish_batch(bmx_ctx* ctx, const MergeArgs& A, const MergeOut& out, const Ch
   P.wflag = A.wflag; P.blk = A.blk_info; P.n = A.n; P.applied = out.applied_idx; P.L = L; P.mark_created = mode.mark_created ? 1u : 0u;
   P.Fin = FinishMerge{reinterpret_cast<unsigned long long*>(out.n_applied), out.stats, A.shard_ctr, &ctx->ds->row_count};
   if (ctx->host_rows) { P.Fin.host_mirror = ctx->host_rows; P.Fin.seq = ++ctx->batch_seq; ctx->inflight.emplace_back(P.Fin.seq, A.n); }
-  const bool notifying = ctx->n_notify && ctx->notify_armed;
+  const bool notifying = ctx->slab.n_notify && ctx->slab.notify_armed;
   P.notify_after = notifying && L.chg && !deferring;   // a change log read from the caller's columns: the compaction's workgroups still read the batch, so the peers are told from a launch behind it
-  if (notifying) { P.notify_seq = ++ctx->notify_seq; if (!P.notify_after) { P.Fin.notify = ctx->notify; P.Fin.n_notify = ctx->n_notify; P.Fin.notify_value = ctx->notify_seq; } }
+  if (notifying) { P.notify_seq = ++ctx->slab.notify_seq; if (!P.notify_after) { P.Fin.notify = ctx->slab.notify; P.Fin.n_notify = ctx->slab.n_notify; P.Fin.notify_value = ctx->slab.notify_seq; } }
   if (deferring) { P.on = true; P.seq = ctx->defer.seq; ctx->defer.pend = P; ctx->defer.n_deferred++; }
   else { launch_k3(ctx, P, ctx->stream); LAUNCHCHK("k_compact_winners"); }
   ctx->nbatch++; ctx->rows_ub += A.n; ctx->version++;
@@ -400,8 +402,8 @@ int merge_steps(bmx_ctx* ctx, const MergeIn& in, const MergeOut& out, const Merg
   if (side_k3 && (rc = launch_side_compaction(ctx))) return rc;
   if (pe) HIPCHK(hipEventRecord(pe[1], ctx->stream));
   if ((rc = launch_resolve<AOS>(ctx, A, mode))) return rc;
-  if (tail_used) ctx->tail_waited = ctx->tail_armed;
-  ctx->tail_armed = bmx_ctx::TailWait{};       // (armed for the next default-path merge only)
+  if (tail_used) ctx->slab.tail_waited = ctx->slab.tail_armed;
+  ctx->slab.tail_armed = SlabProtocol::TailWait{};       // (armed for the next default-path merge only)
   if (pe) HIPCHK(hipEventRecord(pe[2], ctx->stream));
   if ((rc = finish_batch(ctx, A, out, L, mode, deferring))) return rc;
   if (pe) { HIPCHK(hipEventRecord(pe[3], ctx->stream)); ctx->prof.n++; }
@@ -434,3 +436,5 @@ int load_rows(bmx_ctx* ctx, uint64_t n, const uint64_t* id, const uint32_t* fiel
   if (int rc = in_load_chunks(n, id, field, ts, val, one)) return rc;
   return mem == BMX_MEM_DEVICE ? BMX_OK : check_status(ctx);
 }
+
+}  // namespace

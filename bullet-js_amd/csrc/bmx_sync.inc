@@ -16,14 +16,6 @@ int digest_grid(bmx_ctx* ctx, uint32_t* blocks) {
   return BMX_OK;
 }
 
-// a caller's host buffer that the device can write itself (bmx_host_alloc, hipHostMalloc, a registered range): its device address, or nullptr
-void* mapped_host(void* p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) return at.devicePointer;
-  (void)hipGetLastError();
-  return nullptr;
-}
-
 }  // namespace
 
 extern "C" {

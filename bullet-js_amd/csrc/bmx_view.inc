@@ -1,6 +1,9 @@
 // bmx_view.inc — host side of the value-ordered index view (include/bmx.h bmx_index_set_ordered; kernels: view_kernels.h, csrc/ordered_sort.hip):
 // the patch under writes with its pending runs and the rewrite of main behind the answer, and the ordered queries. Included by bmx.hip (one
-// translation unit), which keeps the view's state (OrderedView per index, ViewShared per context) and its sort (ensure_ordered_view).
+// translation unit), which keeps the view's state (OrderedView per index, ViewShared per context). The view's sort and the bmx_index_*ordered* entry points are
+// bmx_view_sort.inc, behind the index refresh that calls the patch here (bmx.hip, the include list).
+namespace {
+
 void ViewShared::read_env() {   // at create: the A/B switches, the test hook and the diagnostic prints
   { const char* vp = std::getenv("BMX_VIEW_PATCH"); if (vp && vp[0] == '0' && !vp[1]) patching = false; }
   { const char* vf = std::getenv("BMX_TEST_VIEW_FAIL"); if (vf && (vf[0] == '1' || vf[0] == '2') && !vf[1]) test_fail = vf[0] - '0'; }
@@ -339,3 +342,5 @@ void launch_ordered(bmx_ctx* ctx, const Index* ix, int64_t lo, int64_t hi, OutT*
     launch_ordered_t<POS, OutT, int32_t>(ctx, v, (int32_t)l, (int32_t)h, d_out, d_cap, d_n, filter);
   } else launch_ordered_t<POS, OutT, int64_t>(ctx, v, lo, hi, d_out, d_cap, d_n, filter);
 }
+
+}  // namespace

@@ -211,3 +211,122 @@ def test_positions_on_small_and_maintained_indexes():
         with pytest.raises(bmx.BmxError):
             e.index_ids(FA, e.index_size(FA) - 1, 5)
     o.close()
+
+
+PIN_IDS = 16384          # the small-answer limit (bmx_scan.inc SCAN_PIN_IDS): host answers of at most this many ids come back through mapped host memory
+ROUTE_RANGES = [(0, 49), (10, 19), (7, 7)]
+ROUTE_FILTER = [(FA, 10, 19), (FS, -500, 500)]
+
+
+def _route_rows(n):
+    rng = np.random.default_rng(20261017)
+    ids = streams.splitmix64_np(np.arange(1, n + 1, dtype=np.uint64))
+    return ids, rng.integers(0, 50, n).astype(np.int64), rng.integers(-1000, 1001, n).astype(np.int64)
+
+
+def _route_load(x, ids, ages, scores):
+    n = len(ids)
+    x.load_rows(np.concatenate([ids, ids]), np.concatenate([np.full(n, FA, np.uint32), np.full(n, FS, np.uint32)]), np.full(2 * n, 5, np.int64),
+                np.concatenate([ages, scores]))
+
+
+def _scan_raw(e, lo, hi, out, cap):
+    """bmx_scan_range into `out` (host) -> (the ids delivered, the count reported): the count is the full one whatever the cap"""
+    import ctypes as C
+    m = C.c_uint64()
+    e._chk(e.L.bmx_scan_range(e.h, int(FA), int(lo), int(hi), bmx._ptr(out), int(cap), C.cast(C.byref(m), C.c_void_p), bmx.MEM_HOST))
+    return out[:min(m.value, cap)], m.value
+
+
+def _filter_raw(e, terms, cap):
+    import ctypes as C
+    arr = (bmx.Term * len(terms))(*[bmx.Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])
+    out = np.zeros(max(cap, 1), np.uint64); m = C.c_uint64()
+    e._chk(e.L.bmx_scan_filter(e.h, len(terms), arr, bmx._ptr(out), int(cap), C.cast(C.byref(m), C.c_void_p), bmx.MEM_HOST))
+    return out[:min(m.value, cap)], m.value
+
+
+def _is_part_of(got, want_sorted, k):
+    """`got` holds k different ids, all of them matches"""
+    return len(got) == k and len(np.unique(got)) == k and bool(np.all(np.isin(got, want_sorted)))
+
+
+@pytest.mark.parametrize("n", [PIN_IDS + 1, PIN_IDS])
+def test_every_delivery_route_at_its_boundary(n):
+    """How an answer leaves the device, at the sizes where the route changes: an index of 16,385 rows (one more than the small-answer limit: three 8192-row scan
+    blocks, the last one ragged) and one of 16,384. Count only; the mapped small answer at cap 16,384; the staged download at cap 16,385 into a pageable array; the
+    caller's own page-locked buffer, whole and sliced to 100 entries (back on the small-answer route, full count); a device buffer (nothing written past cap);
+    positions at both caps; a two-term filter (with the view on its count is built by atomics and must not sit in the mapped count word); and, at 16,385 rows,
+    two logical shards behind bmx.Comm — the deferred route and its collect — followed by ordinary scans of the same rows: no mode survives. Every answer is
+    numpy's as a sorted id set with the exact count, with the value-ordered view off and on."""
+    import torch
+    ids, ages, scores = _route_rows(n)
+    want = {r: _expected_ids(ids, ages, *r) for r in ROUTE_RANGES}
+    assert len(want[(0, 49)]) == n and all(0 < len(w) for w in want.values())
+    fsel = (ages >= 10) & (ages <= 19) & (scores >= -500) & (scores <= 500)
+    fwant = np.sort(ids[fsel])
+    assert 0 < len(fwant) < PIN_IDS
+    dev = torch.device("cuda", 0)
+    hb = bmx.HostBuffer(8 * (PIN_IDS + 1))
+    locked = hb.array(np.uint64, PIN_IDS + 1)
+    with bmx.Engine(4 * n) as e:
+        _route_load(e, ids, ages, scores)
+        assert e.index_size(FA) == n
+        col = e.index_ids(FA)
+        for view in (False, True):
+            if view:
+                e.index_set_ordered(FA, 1)
+            for (lo, hi), w in want.items():
+                k = len(w)
+                assert e.scan_count(FA, lo, hi) == k, (view, lo, hi)
+                if view:
+                    assert e.index_ordered_info(FA)[1], "the view answers from here on"
+                # the small answer at its limit, the staged download one past it (at 16,384 rows both are small answers)
+                for cap in (PIN_IDS, PIN_IDS + 1):
+                    got, m = _scan_raw(e, lo, hi, np.zeros(PIN_IDS + 1, np.uint64), cap)
+                    assert m == k and _is_part_of(got, w, min(k, cap)), (view, lo, hi, cap)
+                    if k <= cap:
+                        assert np.array_equal(np.sort(got), w), (view, lo, hi, cap)
+                assert np.array_equal(np.sort(e.scan_range(FA, lo, hi)), w), (view, lo, hi, "default cap")
+                # the caller's page-locked buffer: whole (written by the kernels when it has more than 16,384 entries to take), then 100 entries of it
+                locked[:] = 0
+                got, m = _scan_raw(e, lo, hi, locked, len(locked))
+                assert m == k and np.array_equal(np.sort(got), w), (view, lo, hi, "page-locked")
+                locked[:] = 0
+                got, m = _scan_raw(e, lo, hi, locked[:100], 100)
+                assert m == k and _is_part_of(got, w, min(k, 100)) and not locked[100:].any(), (view, lo, hi, "page-locked, 100 entries")
+                # a device buffer, whole and truncated
+                for cap in (n, 1000):
+                    buf = torch.zeros(n + 8, dtype=torch.int64, device=dev); n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+                    torch.cuda.synchronize()
+                    e.scan_range_dev(FA, lo, hi, buf, cap, n_out)
+                    e.sync()
+                    assert int(n_out.item()) == k, (view, lo, hi, cap)
+                    assert _is_part_of(buf[:min(k, cap)].cpu().numpy().view(np.uint64), w, min(k, cap)), (view, lo, hi, cap)
+                    assert int(buf[min(k, cap):].abs().sum().item()) == 0, "nothing is written past the matches or past cap"
+                # positions at both caps name the rows of the id-mode answer, in its order
+                for cap in (PIN_IDS, PIN_IDS + 1):
+                    pos = e.scan_range_pos(FA, lo, hi, cap=cap)
+                    assert np.array_equal(col[pos], e.scan_range(FA, lo, hi, cap=cap)) and len(pos) == min(k, cap), (view, lo, hi, cap)
+            for cap in (PIN_IDS, PIN_IDS + 1, 100):
+                got, m = _filter_raw(e, ROUTE_FILTER, cap)
+                assert m == len(fwant) and _is_part_of(got, fwant, min(len(fwant), cap)), (view, cap)
+            assert np.array_equal(np.sort(e.scan_filter(ROUTE_FILTER)), fwant), view
+        if n > PIN_IDS:
+            with bmx.Comm([0, 0], 4 * n) as c:
+                _route_load(c, ids, ages, scores)
+                for view in (False, True):
+                    if view:
+                        c.index_set_ordered(FA, 1)
+                    for rep in range(2):
+                        for (lo, hi), w in want.items():
+                            assert c.scan_count(FA, lo, hi) == len(w), (view, rep, lo, hi)
+                            assert np.array_equal(np.sort(c.scan_range(FA, lo, hi)), w), (view, rep, lo, hi)
+                        assert np.array_equal(np.sort(c.scan_filter(ROUTE_FILTER)), fwant), (view, rep)
+            # ordinary scans of the same rows behind the communicator's: every route again
+            for (lo, hi), w in want.items():
+                assert e.scan_count(FA, lo, hi) == len(w)
+                assert np.array_equal(np.sort(e.scan_range(FA, lo, hi)), w)
+                got, m = _scan_raw(e, lo, hi, locked, len(locked))
+                assert m == len(w) and np.array_equal(np.sort(got), w)
+    hb.close()
