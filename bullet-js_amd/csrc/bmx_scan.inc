@@ -140,6 +140,8 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     LAUNCHCHK("k_scan_mask");
     if (se) HIPCHK(hipEventRecord(se[1], ctx->stream));
     typename std::conditional<POS, EmitPos, EmitIds>::type Em;
+    const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");       // measurement / test switch: blocks beyond which the emit pass takes eight per workgroup
+    const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
     if constexpr (POS) Em = EmitPos{d_out, d_cap};
     else {
       const char* sm = std::getenv("BMX_SCAN_STREAM_MIN");      // measurement switch: matches per block from which the id column is streamed (0xFFFFFFFF: never)
@@ -148,7 +150,7 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     }
     using EmT = decltype(Em);
     FinishCount Fin{d_n};
-    if (nb > SCAN_SUB8_BLOCKS)   // large column: an eighth of the workgroups, each sums the counts in front of it once (no offsets launch)
+    if (nb > sub8_blocks)   // large column: an eighth of the workgroups, each sums the counts in front of it once (no offsets launch)
       hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
     else
       hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
