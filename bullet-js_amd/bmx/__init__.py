@@ -25,6 +25,7 @@ CTX_FIXED_CAPACITY = 2
 FLAG_INCOMING, FLAG_CURRENT, FLAG_HISTORICAL = 1, 2, 4
 MAX_BATCH = 1 << 24
 AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
+TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
@@ -40,6 +41,9 @@ EXPORTS = [
     "bmx_key_bucket", "bmx_digest", "bmx_export_rows", "bmx_comm_digest", "bmx_comm_export_rows",
     "bmx_scan_aggregate", "bmx_comm_scan_aggregate",
 ]
+
+# include/bmx_top.h: additions to the ABI that bmx.h does not declare
+EXPORTS_TOP = ["bmx_scan_top", "bmx_comm_scan_top"]
 
 
 class BmxError(RuntimeError):
@@ -91,6 +95,33 @@ def agg_results(recs, ngroups):
 def _agg_args(terms, measure, group, group_lo, ngroups):
     arr = (Term * max(len(terms), 1))(*[Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])
     return (len(terms), arr, AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group), int(group_lo), int(ngroups))
+
+
+class TopRec(C.Structure):
+    """bmx_top_rec: one record of bmx_scan_top (16 bytes), also its cursor"""
+    _fields_ = [("id", C.c_uint64), ("val", C.c_int64)]
+
+
+TOP_DTYPE = np.dtype([("id", "<u8"), ("val", "<i8")])
+
+
+def _top_args(terms, k, desc, after):
+    arr = (Term * max(len(terms), 1))(*[Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])
+    cur = None
+    if after is not None:
+        cur = TopRec(int(after["id"]), int(after["val"])) if isinstance(after, (np.void, dict)) else TopRec(int(after[0]), int(after[1]))
+    return (len(terms), arr, TOP_DESC if desc else 0, C.byref(cur) if cur is not None else None, int(k))
+
+
+def top_merge(lists, k, desc=False):
+    """The merge bmx_comm_scan_top does with its shards' answers: `lists` are record arrays (TOP_DTYPE), each ordered by (val, id) — val descending with
+    desc, id ascending either way; -> the first k records of their union in that order. Pure numpy: no library, no GPU."""
+    parts = [np.asarray(x, TOP_DTYPE) for x in lists if len(x)]
+    if not parts:
+        return np.zeros(0, TOP_DTYPE)
+    a = np.concatenate(parts)
+    order = np.lexsort((a["id"], -a["val"] if desc else a["val"]))     # (|val| <= 2^53 - 1: the negation is exact)
+    return a[order[:int(k)]]
 
 
 class Info(C.Structure):
@@ -176,6 +207,8 @@ def load_library():
     L.bmx_comm_export_rows.argtypes = [vp, i64, u32, vp, u32, vp, u64, vp]; L.bmx_comm_export_rows.restype = i32
     L.bmx_scan_aggregate.argtypes = [vp, u32, C.POINTER(Term), u32, u32, i64, u32, vp, i32]; L.bmx_scan_aggregate.restype = i32
     L.bmx_comm_scan_aggregate.argtypes = [vp, u32, C.POINTER(Term), u32, u32, i64, u32, vp]; L.bmx_comm_scan_aggregate.restype = i32
+    L.bmx_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp, i32]; L.bmx_scan_top.restype = i32
+    L.bmx_comm_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp]; L.bmx_comm_scan_top.restype = i32
     L.bmx_partition_by_owner.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp]; L.bmx_partition_by_owner.restype = i32
     L.bmx_partition_by_owner_slabs.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp]; L.bmx_partition_by_owner_slabs.restype = i32
     L.bmx_partition_scatter.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, u32, u64]; L.bmx_partition_scatter.restype = i32
@@ -524,6 +557,15 @@ class Engine:
         self._chk(self.L.bmx_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out), MEM_HOST))
         return agg_results(out, int(ngroups))
 
+    def scan_top(self, terms, k, desc=False, after=None):
+        """The first k nodes, ordered by (value of terms[0]'s field, id) — value descending with desc — of the nodes that satisfy every (field, lo, hi) of
+        `terms` and come strictly after the cursor `after` (a record of an earlier answer, or (id, val); None: from the beginning).
+        -> (records: ndarray of TOP_DTYPE, n_eligible)"""
+        out = np.zeros(max(int(k), 1), TOP_DTYPE)
+        m, ne = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.bmx_scan_top(self.h, *_top_args(terms, k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p), C.cast(C.byref(ne), C.c_void_p), MEM_HOST))
+        return out[:m.value].copy(), ne.value
+
     def info(self):
         i = Info()
         self._chk(self.L.bmx_get_info(self.h, C.byref(i)))
@@ -653,6 +695,11 @@ class Engine:
         """scan_aggregate into device memory (`out`: room for ngroups + 1 records of 48 bytes, or 1 with ngroups == 0); enqueue-only — after sync(),
         agg_results(out.cpu().numpy().view(AGG_DTYPE), ngroups) reads it"""
         self._chk(self.L.bmx_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out), MEM_DEVICE))
+
+    def scan_top_dev(self, terms, k, out, n_out=None, n_eligible=None, desc=False, after=None):
+        """scan_top into device memory (`out`: room for k records of 16 bytes; n_out, n_eligible: one uint64 each, or None); enqueue-only. The cursor is
+        host data either way."""
+        self._chk(self.L.bmx_scan_top(self.h, *_top_args(terms, k, desc, after), _ptr(out), _ptr(n_out), _ptr(n_eligible), MEM_DEVICE))
 
     def scan_range_pos_dev(self, field, lo, hi, out_pos, cap, n_out):
         self._chk(self.L.bmx_scan_range_pos(self.h, int(field), int(lo), int(hi), _ptr(out_pos), int(cap), _ptr(n_out), MEM_DEVICE))
@@ -835,6 +882,13 @@ class Comm:
         out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
         self._chk(self.L.bmx_comm_scan_aggregate(self.h, *_agg_args(terms, measure, group, group_lo, ngroups), _ptr(out)))
         return agg_results(out, int(ngroups))
+
+    def scan_top(self, terms, k, desc=False, after=None):
+        """Engine.scan_top over all shards: every shard answers with its first k, the library merges them as top_merge does and adds up the n_eligible"""
+        out = np.zeros(max(int(k), 1), TOP_DTYPE)
+        m, ne = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.bmx_comm_scan_top(self.h, *_top_args(terms, k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p), C.cast(C.byref(ne), C.c_void_p)))
+        return out[:m.value].copy(), ne.value
 
     def scan_filter(self, terms):
         arr = (Term * len(terms))(*[Term(int(f), 0, int(lo), int(hi)) for f, lo, hi in terms])

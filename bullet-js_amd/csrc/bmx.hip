@@ -27,6 +27,7 @@
 #include "sync_kernels.h"
 #include "view_kernels.h"
 #include "agg_kernels.h"
+#include "top_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -289,6 +290,15 @@ struct AggScratch {
   void release() { dev_free(raw); dev_free(stage); cap = 0; clean = false; }
 };
 
+// Scratch of the ordered top-k queries (bmx_top.inc): the select's state record, which every query's last kernel leaves ready for the next (clean), the
+// candidate list, and the counts + records of a BMX_MEM_HOST answer on their way down. Allocated by the first query.
+struct TopScratch {
+  TopState* state = nullptr; unsigned long long* cand_u = nullptr; unsigned long long* cand_id = nullptr; uint8_t* stage = nullptr;
+  bool clean = false;
+  int cus = 0;                            // compute units of the context's device (the sweeps' grid)
+  void release() { dev_free(state); dev_free(cand_u); dev_free(cand_id); dev_free(stage); clean = false; }
+};
+
 // bmx_timer_* events and the optional per-kernel profiling (bmx_profile_enable).
 struct Profiling {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -323,6 +333,7 @@ struct bmx_ctx {
   PartScratch part;
   SyncScratch sync;
   AggScratch agg;
+  TopScratch top;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
   bool fixed_capacity = false;
@@ -584,6 +595,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->part.release();
   ctx->sync.release();
   ctx->agg.release();
+  ctx->top.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -867,5 +879,6 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_scan_filter.inc"
 #include "bmx_sync.inc"
 #include "bmx_agg.inc"
+#include "bmx_top.inc"
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"

@@ -535,6 +535,44 @@ int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms,
   return BMX_OK;
 }
 
+// bmx_scan_top over the shards (bmx_top.h, host memory). A node lives on one shard and the order (value, id) is total, so the first k of the whole graph are
+// the first k of the shards' first k: every shard's query is enqueued before the first answer is fetched, the answers (each ordered, <= k records) are merged
+// on the host and the shards' n_eligible add up.
+int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t flags, const bmx_top_rec* after, uint32_t k, bmx_top_rec* out, uint64_t* n_out,
+                      uint64_t* n_eligible) {
+  if (const char* bad = top_bad_args(nterms, terms, flags, k, out)) return cfail(c, BMX_ERR_INVALID, bad);
+  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  DevGuard guard;
+  for (uint32_t g = 0; g < c->N; g++) {
+    bmx_ctx* x = c->sh[g];
+    int rc = enter(x);
+    if (!rc) rc = top_enqueue(x, nterms, terms, flags, after, k, nullptr, nullptr, nullptr);
+    if (rc) return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));   // (the queries of the shards before g finish on their own streams)
+  }
+  const bool desc = (flags & BMX_TOP_DESC) != 0;
+  auto before = [desc](const bmx_top_rec& a, const bmx_top_rec& b) { return a.val != b.val ? (desc ? a.val > b.val : a.val < b.val) : a.id < b.id; };
+  std::vector<bmx_top_rec> all, part, tmp;
+  uint64_t tot = 0;
+  int first = BMX_OK; std::string msg;
+  for (uint32_t g = 0; g < c->N; g++) {
+    bmx_ctx* x = c->sh[g];
+    uint64_t ne = 0;
+    int rc = enter(x);
+    if (!rc) rc = top_collect(x, k, part, &ne);    // every shard is collected, also after an error
+    if (rc) { if (!first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x); } continue; }
+    tot += ne;
+    tmp.resize(all.size() + part.size());
+    std::merge(all.begin(), all.end(), part.begin(), part.end(), tmp.begin(), before);
+    if (tmp.size() > k) tmp.resize(k);
+    all.swap(tmp);
+  }
+  if (first) return cfail(c, first, msg);
+  if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(bmx_top_rec));
+  if (n_out) *n_out = all.size();
+  if (n_eligible) *n_eligible = tot;
+  return BMX_OK;
+}
+
 // Replica reconciliation over the shards (bmx.h). The shards' key sets are disjoint and the digest is a sum, so the digest of the sharded graph is the
 // element-wise sum of the shards' vectors — the same vectors one context holding all the rows would give. Host memory.
 int bmx_comm_digest(bmx_comm* c, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts) {

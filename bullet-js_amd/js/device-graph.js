@@ -117,6 +117,14 @@ class DeviceGraph {
     }
     return nGroups ? recs : recs[0];
   }
+  /* Ordered top-k query (bmx_scan_top, include/bmx_top.h): the first k nodes, ordered by (value of terms[0]'s field, id) — value descending with opts.desc —, of
+   * the nodes that satisfy every [field, lo, hi] of terms and come strictly after the cursor opts.after = [id (BigInt), value] (a record of an earlier page).
+   * -> {ids: BigUint64Array, vals: BigInt64Array, nEligible}; no match list is built on the device or fetched. */
+  scanTop(terms, k, opts = {}) {
+    if (this.preOp) this.preOp();
+    const after = opts.after === undefined ? null : opts.after;
+    return this.comm ? this.native.commScanTop(this.comm, terms, !!opts.desc, after, k >>> 0) : this.native.scanTop(this.handle, terms, !!opts.desc, after, k >>> 0);
+  }
   info() { return this.comm ? { nShards: this.nShards, devices: this.devices, nRows: this.rowCount() } : this.native.info(this.handle); }
   close() {
     if (this.handle) { this.native.destroy(this.handle); this.handle = null; }

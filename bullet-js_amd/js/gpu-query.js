@@ -23,7 +23,7 @@
  * differ from a fresh build (a child left the index or the integer domain, a child that existed without the field
  * gained it, an integer-like new key, a write at or above the indexed path) the index is rebuilt from the store.
  */
-const { Columns, fieldId, isDeviceInt } = require("./hash");
+const { Columns, fieldId, isDeviceInt, pathId } = require("./hash");
 
 function bucketKey(v) { return (typeof v === "object" && v !== null) ? JSON.stringify(v) : String(v); }
 
@@ -390,6 +390,64 @@ class GpuQuery {
       for (let g = 0; g < n; g++) if (recs[g].nMatch) out.set(base + g, recs[g].nMatch);
     }
     return out;
+  }
+
+  /**
+   * "The 20 highest scores", "the next page of products by price between 10 and 50" (docs/querying.md: fields used for sorting are the first reason to index;
+   * the reference answers with range() and a sort of every match on the host): the first k children of path ordered by `field`, then by the 64-bit hash of
+   * their path (js/hash.js pathId, the device's node id) — a total order, so pages never overlap.
+   * opts: desc (value descending, hash still ascending), min / max (bounds on `field`), where ([{field, min, max}]: further terms, as filterWhere takes them),
+   * after (the .cursor of the page before). -> the BulletNodes in order, as an array that also carries .cursor ([id, value] of its last record, null when
+   * empty: the next page's `after`), .values and .nEligible (children that satisfy the terms and lie behind `after`).
+   * An integer index answers on the device (bmx_scan_top); an index that lives on the host (non-integer values) applies the same order in JS.
+   */
+  top(path, field, k, opts = {}) {
+    const ix = this._fresh(path, field);
+    this.lastPath = ix.kind;
+    const where = opts.where || [];
+    const desc = !!opts.desc, after = opts.after || null;
+    const done = (nodes, values, cursor, nEligible) => { nodes.values = values; nodes.cursor = cursor; nodes.nEligible = nEligible; return nodes; };
+    if (ix.kind === "device") {
+      const ixs = this._deviceIndexes(path, where.map((t) => t.field), "top");
+      const lo = opts.min === undefined ? -Infinity : Math.ceil(opts.min), hi = opts.max === undefined ? Infinity : Math.floor(opts.max);
+      const native = [[ix.deviceField, lo, hi]].concat(where.map((t, j) => [ixs[j].deviceField, Math.ceil(t.min), Math.floor(t.max)]));
+      const r = this.graph.scanTop(native, k, { desc, after });
+      const n = r.ids.length;
+      const values = Array.from(r.vals, Number);
+      let nodes;
+      if (ix.source === "device") {
+        const u32 = new Uint32Array(r.ids.buffer, r.ids.byteOffset, n * 2);
+        nodes = [];
+        for (let i = 0; i < n; i++) nodes.push(this.bullet.get(this.graph.keys.pathOf(u32[2 * i], u32[2 * i + 1])));
+      } else nodes = this._nodes(ix, this._ordinals(ix, r.ids));
+      return done(nodes, values, n ? [r.ids[n - 1], values[n - 1]] : null, r.nEligible);
+    }
+    // host index: the same total order in JS. Numbers compare as numbers and come before everything else, which compares by its bucket key
+    const cmpVal = (a, b) => {
+      const na = typeof a === "number", nb = typeof b === "number";
+      if (na && nb) return a < b ? -1 : a > b ? 1 : 0;
+      if (na !== nb) return na ? -1 : 1;
+      const ka = bucketKey(a), kb = bucketKey(b);
+      return ka < kb ? -1 : ka > kb ? 1 : 0;
+    };
+    const base = this.bullet._getData(path);
+    const rows = [];
+    ix.values.forEach((v, i) => {
+      if (opts.min !== undefined && !(v >= opts.min)) return;
+      if (opts.max !== undefined && !(v <= opts.max)) return;
+      if (where.length) {
+        const child = base[ix.paths[i].slice(path.length + 1)];
+        for (const t of where) { const x = child && child[t.field]; if (x === null || x === undefined || !(x >= t.min && x <= t.max)) return; }
+      }
+      const [l, h] = pathId(ix.paths[i]);
+      rows.push({ i, v, id: (BigInt(h) << 32n) | BigInt(l) });
+    });
+    const cmp = (a, b) => (desc ? cmpVal(b.v, a.v) : cmpVal(a.v, b.v)) || (a.id < b.id ? -1 : a.id > b.id ? 1 : 0);
+    const eligible = after ? rows.filter((r) => cmp(r, { v: after[1], id: BigInt(after[0]) }) > 0) : rows;
+    eligible.sort(cmp);
+    const page = eligible.slice(0, k);
+    const last = page.length ? page[page.length - 1] : null;
+    return done(this._nodes(ix, page.map((r) => r.i)), page.map((r) => r.v), last ? [last.id, last.v] : null, eligible.length);
   }
 
   filter(path, fn) {

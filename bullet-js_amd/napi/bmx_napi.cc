@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "bmx.h"
+#include "bmx_top.h"
 
 namespace {
 
@@ -1136,6 +1137,59 @@ napi_value CommScanAggregate(napi_env env, napi_callback_info info) {
   return aggregate_impl(env, argv, nullptr, h->c);
 }
 
+/* Ordered top-k queries (bmx_top.h bmx_scan_top): thin bindings, no logic.
+ * scanTop(handle, [[field, lo, hi], ...], desc, after | null, k) / commScanTop(comm, ...) -> {ids: BigUint64Array, vals: BigInt64Array, nEligible}: the first k
+ * eligible nodes in (value, id) order; after = [id (BigInt), value] is the cursor. Ids are BigUint64Array entries, as scanFilter delivers them. */
+napi_value top_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
+  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
+  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: top needs 1..8 terms"); return nullptr; }
+  bmx_term terms[8];
+  for (uint32_t k = 0; k < nt; k++) {
+    napi_value t, e0, e1, e2;
+    NAPI_OK(napi_get_element(env, argv[1], k, &t));
+    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
+    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
+    terms[k].reserved = 0;
+    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
+  }
+  bool desc = false; NAPI_OK(napi_get_value_bool(env, argv[2], &desc));
+  bmx_top_rec cur{0, 0}; bool have_cur = false;
+  napi_valuetype vt; napi_typeof(env, argv[3], &vt);
+  if (vt != napi_null && vt != napi_undefined) {
+    napi_value e0, e1; bool lossless = false;
+    NAPI_OK(napi_get_element(env, argv[3], 0, &e0)); NAPI_OK(napi_get_element(env, argv[3], 1, &e1));
+    NAPI_OK(napi_get_value_bigint_uint64(env, e0, &cur.id, &lossless));
+    if (!get_i64(env, e1, &cur.val)) return nullptr;
+    have_cur = true;
+  }
+  uint32_t k; NAPI_OK(napi_get_value_uint32(env, argv[4], &k));
+  if (k == 0 || k > BMX_TOP_MAX_K) { napi_throw_range_error(env, nullptr, "bmx: k is 1..4096"); return nullptr; }
+  std::vector<bmx_top_rec> recs(k);
+  uint64_t m = 0, ne = 0;
+  const uint32_t flags = desc ? BMX_TOP_DESC : 0u;
+  const int rc = ctx ? bmx_scan_top(ctx, nt, terms, flags, have_cur ? &cur : nullptr, k, recs.data(), &m, &ne, BMX_MEM_HOST)
+                     : bmx_comm_scan_top(comm, nt, terms, flags, have_cur ? &cur : nullptr, k, recs.data(), &m, &ne);
+  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
+  void *pi, *pv;
+  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_bigint64_array, 8, m, &pv);
+  for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((int64_t*)pv)[i] = recs[i].val; }
+  napi_value out, nev; NAPI_OK(napi_create_object(env, &out)); napi_create_double(env, (double)ne, &nev);
+  napi_set_named_property(env, out, "ids", a); napi_set_named_property(env, out, "vals", b); napi_set_named_property(env, out, "nEligible", nev);
+  return out;
+}
+napi_value ScanTop(napi_env env, napi_callback_info info) {
+  ARGS(5);
+  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
+  Turn turn(h);   // runs in issue order with the asynchronous merges
+  return top_impl(env, argv, h->ctx, nullptr);
+}
+napi_value CommScanTop(napi_env env, napi_callback_info info) {
+  ARGS(5);
+  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
+  std::lock_guard<std::mutex> g(h->mu);
+  return top_impl(env, argv, nullptr, h->c);
+}
+
 napi_value Init(napi_env env, napi_value exports) {
   struct { const char* name; napi_callback fn; } fns[] = {
       {"abiVersion", AbiVersion}, {"create", Create}, {"destroy", Destroy}, {"mergeBatch", MergeBatch}, {"mergeBatchAsync", MergeBatchAsync}, {"reserve", Reserve}, {"loadRows", LoadRows}, {"putRows", PutRows}, {"hostColumns", HostColumns}, {"scanRangePos", ScanRangePos}, {"indexIds", IndexIds}, {"commPutRows", CommPutRows},
@@ -1144,7 +1198,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"vcCreate", VcCreate}, {"vcDestroy", VcDestroy}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows}, {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}, {"ownersOf", OwnersOf},
       {"commCreate", CommCreate}, {"commDestroy", CommDestroy}, {"commMergeBatch", CommMergeBatch}, {"commLoadRows", CommLoadRows}, {"commGetRows", CommGetRows},
       {"commRowCount", CommRowCount}, {"commDumpRows", CommDumpRows}, {"digest", Digest}, {"exportRows", ExportRows}, {"commDigest", CommDigest}, {"commExportRows", CommExportRows}, {"commIndexBuild", CommIndexBuild}, {"commIndexSetOrdered", CommIndexSetOrdered}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize},
-      {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}, {"scanAggregate", ScanAggregate}, {"commScanAggregate", CommScanAggregate}};
+      {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}, {"scanAggregate", ScanAggregate}, {"commScanAggregate", CommScanAggregate}, {"scanTop", ScanTop}, {"commScanTop", CommScanTop}};
   for (auto& f : fns) {
     napi_value v;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v) != napi_ok) return nullptr;

@@ -397,6 +397,8 @@ int bmx_index_ids(bmx_ctx* ctx, uint32_t field, uint64_t first, uint64_t count, 
  * fields of the same node. Arbitrary JS predicates stay on the host. */
 int bmx_scan_filter(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap,
                     uint64_t* n_out, int mem);
+/* Ordered, limited queries — the first k nodes by (value, id) of a filter's selection, paged with a keyset cursor — are declared in bmx_top.h (include it next to
+ * this header): an addition to ABI 4 with a header of its own. */
 
 /* ---- aggregate queries ----------------------------------------------------------------------------
  * What the reference's users ask next about the nodes a query selects (docs/querying.md "Count Operations", "Map Operations"): "count users by role" is one
