@@ -257,6 +257,23 @@ class OracleVC:
             return None
         return (c.tolist(), v.value, bool(sp.value), int(ks[0])) if with_keyset else (c.tolist(), v.value, bool(sp.value))
 
+    def get_rows(self, id, field):
+        """-> (clocks (n,K) u32, val i64[n], state u8[n], keysets u32[n]) in the layout of bmx.EngineVC.get_rows(with_keysets=True):
+        state 0 = absent (clock 0, val 0, key set 0xFFFFFFFF), 1 = dense, 2 = sparse"""
+        id = np.ascontiguousarray(id, np.uint64); field = np.ascontiguousarray(field, np.uint32)
+        n = len(id)
+        clocks = np.zeros((n, self.K), np.uint32); val = np.zeros(n, np.int64); st = np.zeros(n, np.uint8); ks = np.full(n, 0xFFFFFFFF, np.uint32)
+        get, h = self._L.orc_vc_get_row_ks, self._h
+        cp, kp, vp = _p(clocks, C.c_uint32), _p(ks, C.c_uint32), _p(val, C.c_int64)
+        cb, kb, vb = C.addressof(cp.contents), C.addressof(kp.contents), C.addressof(vp.contents)
+        u32p, i64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+        sp = C.c_int()
+        ids = id.tolist(); fs = field.tolist()
+        for k in range(n):
+            if get(h, ids[k], fs[k], C.cast(cb + 4 * self.K * k, u32p), C.cast(kb + 4 * k, u32p), C.cast(vb + 8 * k, i64p), C.byref(sp)):
+                st[k] = 2 if sp.value else 1
+        return clocks, val, st, ks
+
     def dump_rows(self):
         n = len(self)
         id = np.zeros(n, np.uint64); field = np.zeros(n, np.uint32); clocks = np.zeros((n, self.K), np.uint32); val = np.zeros(n, np.int64)

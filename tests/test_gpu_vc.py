@@ -1,7 +1,9 @@
 """GPU parity, N4: K-writer vector-clock rows on the device (bmx_vc_* through the C ABI) vs
  - the golden vectors made by the real reference (tests/golden/g6_vc_*.json, oracle/gen_golden.js runVcStream), and
  - oracle/bmx_oracle.c orc_vc_* on seeded random batches (hot keys, inserts, many batches, epoch wrap).
-Bit-exact: flags per delta, the ascending list of last-updating deltas, and every row's (clock, value, sparse/dense)."""
+Bit-exact: flags per delta, the ascending list of last-updating deltas, and every row's (clock, value, sparse/dense).
+The shapes here are whatever the seeds draw; the kernels' own edges (lists of 16 / 17 deltas, the 256-delta chunks and the bitmap of k_vc_resolve_long, the
+queue of 64 workgroups, where a row's winner sits, workspace regrowth, preload lists) are built one by one in tests/test_gpu_vc_kernel_edges.py."""
 import base64
 
 import numpy as np
