@@ -169,6 +169,8 @@ def test_export_filters_and_capacity():
         # everything
         recs, n = e.export_rows()
         assert n == len(id) == len(recs) and np.array_equal(_rec_tuples(recs), _tuples(id, f, ts, val))
+        # "in table order" (bmx.h): record for record the order of dump_rows, which walks the same slots
+        assert np.array_equal(recs["id"], id) and np.array_equal(recs["field"], f) and np.array_equal(recs["ts"], ts) and np.array_equal(recs["val"], val)
         # since = median clock
         since = int(np.median(ts))
         m = ts >= since
