@@ -1,7 +1,9 @@
 // bmx.hip — C ABI (include/bmx.h) over the gfx950 kernels. One context = one GPU + one HIP stream.
 // No CPU fallback exists: every entry point fails with BMX_ERR_NO_DEVICE / BMX_ERR_HIP when there is no GPU.
-// This file: the state (bmx_ctx and its owned parts), the error plumbing, check_status, bmx_selfcheck, create / destroy, the merge entry points, the point reads and
-// the dump, the setters, timers and profiling. Everything else of the translation unit is the .inc files, by subject, in the two include lists below.
+// This file: the state (bmx_ctx and its owned parts), the error and allocation helpers of all three handles (fail, HIPCHK_ON, dev_alloc_all: bmx_ctx here, bmx_vc in
+// bmx_vc.inc, bmx_comm in bmx_comm.inc, each with its own last-error channel), check_status, bmx_selfcheck, create / destroy, the merge entry points, the point reads
+// and the dump, the setters, timers and profiling. Everything else of the translation unit is the .inc files, by subject, in the two include lists below; what the
+// queries set up alike in front of their launches (term checks and clamps, the int32 range clamp, the sweep grid) is bmx_query.inc, at the head of the first list.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -113,7 +115,12 @@ struct ViewShared {
   void release();
 };
 
-thread_local std::string g_err;
+// Each handle type keeps its own thread-local last-error word for the calls that have no handle to leave the text in:
+// bmx_last_error(NULL), bmx_vc_last_error(NULL) and bmx_comm_last_error(NULL) are separate channels.
+thread_local std::string g_err, g_vc_err, g_comm_err;
+inline std::string& tls_err(const bmx_ctx*) { return g_err; }
+inline std::string& tls_err(const bmx_vc*) { return g_vc_err; }
+inline std::string& tls_err(const bmx_comm*) { return g_comm_err; }
 constexpr uint32_t PROF_MAX_CALLS = 64;
 
 template <class T>
@@ -277,7 +284,6 @@ struct SyncScratch {
   unsigned long long* dig = nullptr;      // 2 x 2^16 words: sums and counts
   unsigned long long* bits = nullptr;     // 2^16 bits
   bmx_delta_rec* recs = nullptr; uint64_t recs_cap = 0;
-  int cus = 0;                            // compute units of the context's device (the digest's grid)
   void release() { dev_free(dig); dev_free(bits); dev_free(recs); recs_cap = 0; }
 };
 
@@ -286,7 +292,6 @@ struct SyncScratch {
 struct AggScratch {
   AggRaw* raw = nullptr; bmx_agg* stage = nullptr; uint32_t cap = 0;
   bool clean = false;
-  int cus = 0;                            // compute units of the context's device (the sweep's grid)
   void release() { dev_free(raw); dev_free(stage); cap = 0; clean = false; }
 };
 
@@ -295,7 +300,6 @@ struct AggScratch {
 struct TopScratch {
   TopState* state = nullptr; unsigned long long* cand_u = nullptr; unsigned long long* cand_id = nullptr; uint8_t* stage = nullptr;
   bool clean = false;
-  int cus = 0;                            // compute units of the context's device (the sweeps' grid)
   void release() { dev_free(state); dev_free(cand_u); dev_free(cand_id); dev_free(stage); clean = false; }
 };
 
@@ -320,6 +324,7 @@ struct Profiling {
 
 struct bmx_ctx {
   int device = 0;
+  int cus = 1;                        // compute units of the device, looked up at create (sweep_grid)
   hipStream_t own_stream = nullptr, stream = nullptr;
   Slot* slots = nullptr;
   uint64_t nslots = 0, capacity_rows = 0;
@@ -356,33 +361,39 @@ struct bmx_ctx {
 
 namespace {
 
-int fail(bmx_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  g_err = msg;
+// The error and allocation helpers of all three handles (bmx_ctx here, bmx_vc in bmx_vc.inc, bmx_comm in bmx_comm.inc): the text goes to the handle, if there
+// is one, and to the handle type's own thread-local word. A bare nullptr means "no context".
+template <class H>
+int fail(H* h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  tls_err(h) = msg;
   return code;
 }
+inline int fail(std::nullptr_t, int code, const std::string& msg) { return fail(static_cast<bmx_ctx*>(nullptr), code, msg); }
 inline hipMemcpyKind host_or_dev(int mem) { return mem == BMX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice; }
-int fail_hip(bmx_ctx* c, hipError_t e, const char* what) {
-  return fail(c, BMX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+template <class H>
+int fail_hip(H* h, hipError_t e, const char* what) {
+  return fail(h, BMX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define HIPCHK(call)                                                  \
-  do {                                                                \
-    hipError_t e__ = (call);                                          \
-    if (e__ != hipSuccess) return fail_hip(ctx, e__, #call);          \
-  } while (0)
+// HIPCHK_ON(handle, call) returns BMX_ERR_HIP with the call's text from the enclosing function; HIPCHK(call) is the same for a function whose handle is `ctx`.
+// HIPCHK_BAIL is for the create functions, which leave through their `bail` lambda (it destroys the half-built handle and keeps the text).
+#define HIPCHK_ON(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail_hip(h, e__, #call); } while (0)
+#define HIPCHK(call) HIPCHK_ON(ctx, call)
+#define HIPCHK_BAIL(h, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return bail(fail_hip(h, e__, #call)); } while (0)
 #define LAUNCHCHK(name)                                               \
   do {                                                                \
     hipError_t e__ = hipGetLastError();                               \
     if (e__ != hipSuccess) return fail_hip(ctx, e__, "launch " name); \
   } while (0)
 
-int dev_alloc_all(bmx_ctx* ctx, std::initializer_list<DevBuf> bufs) {   // (alloc_all) BMX_ERR_NOMEM on out-of-memory, BMX_ERR_HIP otherwise
+template <class H>
+int dev_alloc_all(H* h, std::initializer_list<DevBuf> bufs) {   // (alloc_all) BMX_ERR_NOMEM on out-of-memory, BMX_ERR_HIP otherwise
   hipError_t e = hipSuccess;
   if (alloc_all(bufs, &e)) return BMX_OK;
-  return fail(ctx, e == hipErrorOutOfMemory ? BMX_ERR_NOMEM : BMX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+  return fail(h, e == hipErrorOutOfMemory ? BMX_ERR_NOMEM : BMX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
 }
-template <class T>
-int dev_alloc(bmx_ctx* ctx, T** p, uint64_t count) { return dev_alloc_all(ctx, {{*p, std::max<uint64_t>(count, 1) * sizeof(T)}}); }
+template <class H, class T>
+int dev_alloc(H* h, T** p, uint64_t count) { return dev_alloc_all(h, {{*p, std::max<uint64_t>(count, 1) * sizeof(T)}}); }
 void free_columns(Index& ix) { dev_free(ix.ids); dev_free(ix.v64); dev_free(ix.v32); ix.cap = 0; }
 
 // Pull the sticky device status; translate to an error code.
@@ -416,6 +427,7 @@ int check_status(bmx_ctx* ctx) {
 // the code object is held byte-identical across refactors of the host side. So every file sits where its code always sat, which is why two subjects come in two
 // files each: the index build in front of the view's patch and the refresh (which calls the patch) behind it, with the view's sort behind the refresh; the range
 // scans in front of this file's own entry points (bmx_selfcheck and bmx_dump_rows launch kernel templates) and the position scan and the filter behind them.
+#include "bmx_query.inc"   // (host arithmetic only: it launches nothing, so it has no place to keep)
 #include "bmx_merge.inc"
 #include "bmx_host.inc"
 #include "bmx_index.inc"
@@ -482,7 +494,7 @@ int bmx_selfcheck(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t*
   if (e == hipSuccess) e = hipStreamSynchronize(cs);
   if (cs) (void)hipStreamDestroy(cs);
   (void)hipFree(slots); (void)hipFree(d);
-  if (e != hipSuccess) return fail_hip(nullptr, e, "bmx_selfcheck");
+  if (e != hipSuccess) return fail_hip(ctx, e, "bmx_selfcheck");
   if (reads_out) *reads_out = h[1];
   if (torn_out) *torn_out = h[0];
   if (control_torn_out) *control_torn_out = h[2];
@@ -542,13 +554,14 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   ctx->capacity_rows = capacity_rows;
   ctx->load_pct = max_load_pct;
   auto bail = [&](int rc) { std::string m = ctx->err; bmx_destroy(ctx); g_err = m; return rc; };
-#define CR(call) do { hipError_t e2 = (call); if (e2 != hipSuccess) { fail_hip(ctx, e2, #call); return bail(BMX_ERR_HIP); } } while (0)
-  CR(hipSetDevice(device));
-  CR(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+  HIPCHK_BAIL(ctx, hipSetDevice(device));
+  HIPCHK_BAIL(ctx, hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device));
+  ctx->cus = std::max(ctx->cus, 1);
+  HIPCHK_BAIL(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
   ctx->stream = ctx->own_stream;
-  CR(hipEventCreate(&ctx->prof.ev0));
-  CR(hipEventCreate(&ctx->prof.ev1));
-  for (auto& S : ctx->host.stg) { CR(hipEventCreateWithFlags(&S.up, hipEventDisableTiming)); CR(hipEventCreateWithFlags(&S.done, hipEventDisableTiming)); }
+  HIPCHK_BAIL(ctx, hipEventCreate(&ctx->prof.ev0));
+  HIPCHK_BAIL(ctx, hipEventCreate(&ctx->prof.ev1));
+  for (auto& S : ctx->host.stg) { HIPCHK_BAIL(ctx, hipEventCreateWithFlags(&S.up, hipEventDisableTiming)); HIPCHK_BAIL(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming)); }
   const uint64_t nslots = slots_for(capacity_rows, max_load_pct);
   ctx->nslots = nslots;
   ctx->placement_tries_asked = (flags >> 8) & 0xFu;         // BMX_CTX_PLACEMENT_TRIES(n): 0 = the default
@@ -560,7 +573,7 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   if ((rc = dev_alloc_all(ctx, {{ctx->scan.block_counts, SEL_MAX_BLOCKS * sizeof(uint32_t)}, {ctx->part.counts, PART_MAX_SHARDS * PART_BLOCKS * sizeof(uint32_t)},
                                 {ctx->ws.shard_ctr, MergeWs::SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long)}})))
     return bail(rc);
-  CR(hipMemsetAsync(ctx->ws.shard_ctr, 0, MergeWs::SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long), ctx->stream));
+  HIPCHK_BAIL(ctx, hipMemsetAsync(ctx->ws.shard_ctr, 0, MergeWs::SETS * CTR_SHARDS * CTR_STRIDE * sizeof(unsigned long long), ctx->stream));
   // the row-count mirror is an optimisation: without mapped host memory the capacity guard simply synchronises as before
   if (hipHostMalloc(reinterpret_cast<void**>(&ctx->host_rows), 2 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
     ctx->host_rows[0] = 0; ctx->host_rows[1] = 0;
@@ -569,11 +582,10 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   ctx->defer.enabled = !launches_are_serialized();
   ctx->view.read_env();
   { const char* kw = std::getenv("BMX_K1_WAVES"); if (kw && kw[0] >= '3' && kw[0] <= '8' && kw[0] != '7' && !kw[1]) ctx->k1_waves = kw[0] - '0'; }
-  CR(hipMemsetAsync(ctx->ds, 0, sizeof(DevScalars), ctx->stream));
+  HIPCHK_BAIL(ctx, hipMemsetAsync(ctx->ds, 0, sizeof(DevScalars), ctx->stream));
   hipLaunchKernelGGL(k_init_slots, dim3(2048), dim3(256), 0, ctx->stream, ctx->slots, nslots);
-  CR(hipGetLastError());
-  CR(hipStreamSynchronize(ctx->stream));
-#undef CR
+  HIPCHK_BAIL(ctx, hipGetLastError());
+  HIPCHK_BAIL(ctx, hipStreamSynchronize(ctx->stream));
   *out = ctx;
   return BMX_OK;
 }

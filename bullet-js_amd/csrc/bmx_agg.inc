@@ -5,7 +5,7 @@ namespace {
 
 // what every caller's arguments must satisfy before anything touches a device (bmx_comm_scan_aggregate asks the same)
 const char* agg_bad_args(uint32_t nterms, const bmx_term* terms, uint32_t group_field, uint32_t ngroups, const bmx_agg* out) {
-  if (nterms == 0 || nterms > (uint32_t)MAX_TERMS || !terms) return "aggregate needs 1..8 terms";
+  if (const char* bad = bad_terms(nterms, terms, "aggregate needs 1..8 terms")) return bad;
   if (!out) return "bmx_scan_aggregate: null output";
   if (ngroups > BMX_AGG_MAX_GROUPS) return "bmx_scan_aggregate: more than BMX_AGG_MAX_GROUPS groups";
   if (ngroups && group_field == BMX_AGG_NO_FIELD) return "bmx_scan_aggregate: groups without a group field";
@@ -22,11 +22,6 @@ uint32_t agg_source(uint32_t field, uint32_t nterms, const bmx_term* terms) {
 
 int agg_scratch(bmx_ctx* ctx, uint32_t nrec) {
   AggScratch& s = ctx->agg;
-  if (!s.cus) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    s.cus = std::max(cus, 1);
-  }
   if (nrec > s.cap) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     s.cap = 0;
@@ -45,9 +40,8 @@ template <class T, int G>
 void agg_launch_sweep(bmx_ctx* ctx, const Index* ix, T lo, T hi, bool probe, const AggArgs& A) {
   const T* col = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
   const uint32_t nt = ix->n * sizeof(T) > SCAN_NT_BYTES ? 1u : 0u;
-  // two workgroups per CU, and none with fewer than four rounds of loads to spread its one flush over
-  const uint64_t per_round = (uint64_t)AGG_THREADS * AGG_U * (16 / sizeof(T));
-  const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ix->n + 4 * per_round - 1) / (4 * per_round), 2ull * (uint64_t)ctx->agg.cus));
+  // no workgroup with fewer than four rounds of loads to spread its one flush over
+  const uint32_t blocks = sweep_grid(ctx, ix->n, 4ull * AGG_THREADS * AGG_U * (16 / sizeof(T)));
   if (probe) hipLaunchKernelGGL((k_agg_sweep<T, true, G>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, col, (const uint64_t*)ix->ids, ix->n, lo, hi, nt, A);
   else hipLaunchKernelGGL((k_agg_sweep<T, false, G>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, col, (const uint64_t*)ix->ids, ix->n, lo, hi, nt, A);
 }
@@ -62,7 +56,7 @@ void agg_launch_view(bmx_ctx* ctx, const OrderedView& v, T lo, T hi, bool need_i
   if (pending) hipLaunchKernelGGL((k_ordered_bounds_p<T>), dim3(1), dim3(384), 0, ctx->stream, sv, v.ord_n, dv, v.npd, iv, v.npi, lo, hi, ab, (unsigned long long*)nullptr, 1u);
   else hipLaunchKernelGGL((k_ordered_bounds<T>), dim3(1), dim3(128), 0, ctx->stream, sv, v.ord_n, lo, hi, ab, (unsigned long long*)nullptr, 1u);
   // the run's length is the device's: a grid for the whole view, whose workgroups beyond the run leave at once
-  const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((v.ord_n + v.npi + 4ull * AGG_THREADS - 1) / (4ull * AGG_THREADS), 2ull * (uint64_t)ctx->agg.cus));
+  const uint32_t blocks = sweep_grid(ctx, v.ord_n + v.npi, 4ull * AGG_THREADS);
   hipLaunchKernelGGL((k_agg_view<T, G>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, sv, (const uint32_t*)v.s_pos, (const uint64_t*)v.s_ids, dv, (const uint32_t*)v.pd_p[q], iv,
                      (const uint64_t*)v.pi_ids[qi], (const unsigned long long*)ab, pending ? 1u : 0u, need_id ? 1u : 0u, A);
 }
@@ -90,15 +84,14 @@ int agg_enqueue(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint32_t m
   A.group_lo = group_lo; A.ngroups = ngroups; A.measure = measure_field; A.group = group_field;
   A.m_src = agg_source(measure_field, nterms, terms); A.g_src = ngroups ? agg_source(group_field, nterms, terms) : AGG_SRC_NONE;
   A.nterms = nterms;
-  for (uint32_t k = 0; k < nterms; k++) { A.t[k] = terms[k]; A.t[k].lo = std::max<int64_t>(terms[k].lo, -VAL_MAX); }   // tombstones (INT64_MIN) match no term
+  copy_terms(A.t, terms, nterms);
   const bool probe = nterms > 1 || A.m_src == AGG_SRC_PROBE || A.g_src == AGG_SRC_PROBE;
   const bool ordered = ensure_ordered_view(ctx, ix);
   const bool fits32 = ordered ? ix->view.ord_fits32 : ix->fits32;
   ctx->agg.clean = false;
-  if (fits32) {   // the 4-byte column, bounds clamped into int32 like the scans' (INT32_MIN is what a tombstone looks like there; an empty range stays empty)
-    int64_t l = std::max<int64_t>(A.t[0].lo, (int64_t)INT32_MIN + 1), h = std::min<int64_t>(A.t[0].hi, INT32_MAX);
-    if (A.t[0].lo > INT32_MAX || A.t[0].hi < INT32_MIN) { l = 1; h = 0; }
-    agg_launch<int32_t>(ctx, ix, ordered, l, h, probe, A);
+  if (fits32) {   // the 4-byte column
+    const Range32 r = clamp_i32(A.t[0].lo, A.t[0].hi);
+    agg_launch<int32_t>(ctx, ix, ordered, r.lo, r.hi, probe, A);
   } else agg_launch<int64_t>(ctx, ix, ordered, A.t[0].lo, A.t[0].hi, probe, A);
   LAUNCHCHK("k_agg_sweep / k_agg_view");
   hipLaunchKernelGGL(k_agg_finish, dim3(std::min<uint32_t>((nrec + 255) / 256, 64)), dim3(256), 0, ctx->stream, ctx->agg.raw, d_out ? d_out : ctx->agg.stage, nrec,

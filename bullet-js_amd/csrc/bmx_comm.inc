@@ -27,18 +27,31 @@ struct bmx_comm {
     uint64_t recv_cap = 0;
     bmx_delta_rec* recv = nullptr;               // what this shard merges
     uint32_t* applied = nullptr;                 // winners: positions in recv
-        unsigned long long* n_applied = nullptr;     // device
+    unsigned long long* n_applied = nullptr;     // device
     bmx_merge_stats* stats = nullptr;            // device
     hipEvent_t routed = nullptr;                 // this shard's partition (and scatter) of the current step is done
     hipEvent_t merged = nullptr;                 // this shard's merge of the previous step is done (its receive buffer may be overwritten)
     uint64_t slab = 0;                           // device path: records per (origin, owner) slab
+    void release() {                             // (with the shard's device current and idle)
+      dev_free(id); dev_free(field); dev_free(ts); dev_free(val); dev_free(counts); dev_free(recv); dev_free(applied); dev_free(n_applied); dev_free(stats);
+      if (routed) (void)hipEventDestroy(routed);
+      if (merged) (void)hipEventDestroy(merged);
+      routed = merged = nullptr; in_cap = recv_cap = 0;
+    }
   };
   std::vector<Shard> s;
   // winners of a host batch in the caller's index space: every shard marks its winners' batch indices in ONE byte map on shard 0's GPU
   // (peer stores), shard 0 compacts the map in order (k_count_winners + k_compact_winners): no host-side merge of N sorted lists
-  uint64_t g_cap = 0;
-  uint8_t* g_flag = nullptr; uint32_t* g_blk = nullptr; uint32_t* g_applied = nullptr; unsigned long long* g_n = nullptr;
-  hipEvent_t g_zeroed = nullptr;
+  struct WinnerMap {
+    uint64_t cap = 0;
+    uint8_t* flag = nullptr; uint32_t* blk = nullptr; uint32_t* applied = nullptr; unsigned long long* n = nullptr;
+    hipEvent_t zeroed = nullptr;
+    void release() {                             // (with shard 0's device current and idle)
+      dev_free(flag); dev_free(blk); dev_free(applied); dev_free(n);
+      if (zeroed) (void)hipEventDestroy(zeroed);
+      zeroed = nullptr; cap = 0;
+    }
+  } win;
   bool dev_step_pending = false;
   std::string err;
 };
@@ -50,62 +63,56 @@ struct DevGuard {
   DevGuard() { if (hipGetDevice(&d) != hipSuccess) { d = -1; (void)hipGetLastError(); } }
   ~DevGuard() { if (d >= 0) (void)hipSetDevice(d); }
 };
-thread_local std::string g_comm_err;
-int cfail(bmx_comm* c, int code, const std::string& m) { if (c) c->err = m; g_comm_err = m; return code; }
-#define CHIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return cfail(c, BMX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); } while (0)
-#define CSH(g, call) do { int rc__ = (call); if (rc__) return cfail(c, rc__, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(c->sh[g])); } while (0)
-template <class T> int calloc_dev(bmx_comm* c, T** p, uint64_t n) {
-  *p = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<uint64_t>(n, 1) * sizeof(T));
-  return e == hipSuccess ? BMX_OK : cfail(c, e == hipErrorOutOfMemory ? BMX_ERR_NOMEM : BMX_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-}
+// the one place that words a shard's error for the communicator's caller (a shard that could not be created left its text in bmx_last_error(NULL))
+std::string shard_msg(const bmx_comm* c, uint32_t g) { return std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(c->sh[g]); }
+#define CSH(g, call) do { int rc__ = (call); if (rc__) return fail(c, rc__, shard_msg(c, g)); } while (0)
 
 __global__ void k_mark_aux(const bmx_delta_rec* recs, const uint32_t* applied, const unsigned long long* n_applied, uint8_t* flag) {
   const uint64_t n = *n_applied;
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) flag[recs[applied[i]].aux] = 1;
 }
 
-int comm_ensure_global(bmx_comm* c, uint64_t n) {
-  if (n <= c->g_cap) return BMX_OK;
-  CHIP(hipSetDevice(c->dev[0]));
-  for (uint32_t i = 0; i < c->N; i++) { CHIP(hipSetDevice(c->dev[i])); CHIP(hipDeviceSynchronize()); }
-  CHIP(hipSetDevice(c->dev[0]));
-  (void)hipFree(c->g_flag); (void)hipFree(c->g_blk); (void)hipFree(c->g_applied);
-  c->g_flag = nullptr; c->g_blk = nullptr; c->g_applied = nullptr; c->g_cap = 0;
-  const uint64_t cap = (std::max<uint64_t>(n, 1u << 16) + 4095) & ~4095ull;
-  int rc;
-  if ((rc = calloc_dev(c, &c->g_flag, cap + 16)) || (rc = calloc_dev(c, &c->g_blk, cap / 256 + 16)) || (rc = calloc_dev(c, &c->g_applied, cap))) return rc;
-  c->g_cap = cap;
+// Buffers that the shards' kernels read and write across devices are regrown only when every shard's device is idle (peers may still be writing the old ones):
+// one all-or-nothing group from device `d`, which is the current device afterwards.
+int comm_regrow(bmx_comm* c, int d, uint64_t* cap_word, uint64_t cap, std::initializer_list<DevBuf> bufs) {
+  *cap_word = 0;
+  for (uint32_t i = 0; i < c->N; i++) { HIPCHK_ON(c, hipSetDevice(c->dev[i])); HIPCHK_ON(c, hipDeviceSynchronize()); }
+  HIPCHK_ON(c, hipSetDevice(d));
+  if (int rc = dev_alloc_all(c, bufs)) return rc;
+  *cap_word = cap;
   return BMX_OK;
 }
-
+int comm_ensure_global(bmx_comm* c, uint64_t n) {
+  bmx_comm::WinnerMap& W = c->win;
+  if (n <= W.cap) return BMX_OK;
+  const uint64_t cap = (std::max<uint64_t>(n, 1u << 16) + 4095) & ~4095ull;
+  return comm_regrow(c, c->dev[0], &W.cap, cap, {{W.flag, cap + 16}, {W.blk, (cap / 256 + 16) * sizeof(uint32_t)}, {W.applied, cap * sizeof(uint32_t)}});
+}
 int comm_ensure_in(bmx_comm* c, uint32_t g, uint64_t n) {
   bmx_comm::Shard& S = c->s[g];
   if (n <= S.in_cap) return BMX_OK;
-  CHIP(hipSetDevice(c->dev[g]));
-  CHIP(hipDeviceSynchronize());
-  (void)hipFree(S.id); (void)hipFree(S.field); (void)hipFree(S.ts); (void)hipFree(S.val);
-  S.id = nullptr; S.field = nullptr; S.ts = nullptr; S.val = nullptr; S.in_cap = 0;
   const uint64_t cap = (std::max<uint64_t>(n, 1u << 12) + 255) & ~255ull;
-  int rc;
-  if ((rc = calloc_dev(c, &S.id, cap)) || (rc = calloc_dev(c, &S.field, cap)) || (rc = calloc_dev(c, &S.ts, cap)) || (rc = calloc_dev(c, &S.val, cap)))
-    return rc;
-  S.in_cap = cap;
-  return BMX_OK;
+  return comm_regrow(c, c->dev[g], &S.in_cap, cap, {{S.id, cap * 8}, {S.field, cap * 4}, {S.ts, cap * 8}, {S.val, cap * 8}});
 }
 int comm_ensure_recv(bmx_comm* c, uint32_t g, uint64_t n) {
   bmx_comm::Shard& S = c->s[g];
   if (n <= S.recv_cap) return BMX_OK;
-  CHIP(hipSetDevice(c->dev[g]));
-  for (uint32_t i = 0; i < c->N; i++) { CHIP(hipSetDevice(c->dev[i])); CHIP(hipDeviceSynchronize()); }   // peers may still be writing the old buffer
-  CHIP(hipSetDevice(c->dev[g]));
-  (void)hipFree(S.recv); (void)hipFree(S.applied);
-  S.recv = nullptr; S.applied = nullptr; S.recv_cap = 0;
   const uint64_t cap = (std::max<uint64_t>(n + n / 4, 1u << 12) + 255) & ~255ull;
-  int rc;
-  if ((rc = calloc_dev(c, &S.recv, cap)) || (rc = calloc_dev(c, &S.applied, cap))) return rc;
-  S.recv_cap = cap;
-  return BMX_OK;
+  return comm_regrow(c, c->dev[g], &S.recv_cap, cap, {{S.recv, cap * sizeof(bmx_delta_rec)}, {S.applied, cap * sizeof(uint32_t)}});
+}
+
+// The sharded queries' two phases. `enqueue(g, shard)` runs on shards 0..N-1 and the first error ends the call (what the shards before it were given finishes on
+// their own streams); then `collect(g, shard)` runs on EVERY shard, also after an error, and the first error is the call's: N GPUs work at the same time, and
+// the host waits once per shard for work that is already running.
+template <class Enqueue, class Collect>
+int comm_two_phase(bmx_comm* c, Enqueue enqueue, Collect collect) {
+  for (uint32_t g = 0; g < c->N; g++) CSH(g, enqueue(g, c->sh[g]));
+  int first = BMX_OK; std::string msg;
+  for (uint32_t g = 0; g < c->N; g++) {
+    const int rc = collect(g, c->sh[g]);
+    if (rc && !first) { first = rc; msg = shard_msg(c, g); }
+  }
+  return first ? fail(c, first, msg) : BMX_OK;
 }
 
 // A small host batch (<= COMM_SMALL_N deltas): routed on the HOST — owner of every delta, stable split into per-shard sub-batches — and merged
@@ -128,7 +135,7 @@ int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
     gi.resize(m); gf.resize(m); gt.resize(m); gv.resize(m); ga.resize(m);
     for (size_t x = 0; x < m; x++) { const uint32_t j = back[g][x]; gi[x] = id[j]; gf[x] = field[j]; gt[x] = ts[j]; gv[x] = val[j]; }
     uint64_t na = 0;
-    CHIP(hipSetDevice(c->dev[g]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[g]));
     CSH(g, merge_host(c->sh[g], MergeIn{m, gi.data(), gf.data(), gt.data(), gv.data(), nullptr}, mode, MergeOut{applied_idx ? ga.data() : nullptr, &na, nullptr, &st}));
     if (applied_idx) for (uint64_t x = 0; x < na; x++) winners.push_back(back[g][ga[x]]);
     tot.n_applied += st.n_applied; tot.n_conflicts += st.n_conflicts; tot.n_rows += st.n_rows;
@@ -146,18 +153,17 @@ int comm_host_small(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
 int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, const MergeMode& mode,
                     uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
   const uint32_t N = c->N;
-  if (n > MAX_BATCH) return cfail(c, BMX_ERR_INVALID, BATCH_TOO_LARGE);   // before a partition is launched
+  if (n > MAX_BATCH) return fail(c, BMX_ERR_INVALID, BATCH_TOO_LARGE);   // before a partition is launched
   if (n_applied) *n_applied = 0;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (n && (!id || !field || !ts || !val)) return cfail(c, BMX_ERR_INVALID, "null input column");
+  if (n && (!id || !field || !ts || !val)) return fail(c, BMX_ERR_INVALID, "null input column");
   if (n && n <= COMM_SMALL_N) return comm_host_small(c, n, id, field, ts, val, mode, applied_idx, n_applied, stats);
   if (c->dev_step_pending) { int rc0 = bmx_comm_sync(c); if (rc0) return rc0; }
   if (N == 1 && n) {   // one shard owns everything: nothing to route, no winner map to build — the context's own host-batch path (two staging sets, three streams)
-    CHIP(hipSetDevice(c->dev[0]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[0]));
     bmx_merge_stats st; std::memset(&st, 0, sizeof(st));
     uint64_t na = 0;
-    int rc = merge_host(c->sh[0], MergeIn{n, id, field, ts, val, nullptr}, mode, MergeOut{applied_idx, &na, nullptr, &st});
-    if (rc) return cfail(c, rc, std::string("shard 0: ") + bmx_last_error(c->sh[0]));
+    CSH(0, merge_host(c->sh[0], MergeIn{n, id, field, ts, val, nullptr}, mode, MergeOut{applied_idx, &na, nullptr, &st}));
     if (n_applied) *n_applied = na;
     if (stats) *stats = st;
     return BMX_OK;
@@ -169,65 +175,64 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
   int rc;
   if ((rc = comm_ensure_in(c, 0, n))) return rc;
   bmx_comm::Shard& S0 = c->s[0];
-  CHIP(hipSetDevice(c->dev[0]));
+  HIPCHK_ON(c, hipSetDevice(c->dev[0]));
   hipStream_t s0 = reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[0]));
-  CHIP(hipMemcpyAsync(S0.id, id, n * 8, hipMemcpyHostToDevice, s0));
-  CHIP(hipMemcpyAsync(S0.field, field, n * 4, hipMemcpyHostToDevice, s0));
-  CHIP(hipMemcpyAsync(S0.ts, ts, n * 8, hipMemcpyHostToDevice, s0));
-  CHIP(hipMemcpyAsync(S0.val, val, n * 8, hipMemcpyHostToDevice, s0));
+  HIPCHK_ON(c, hipMemcpyAsync(S0.id, id, n * 8, hipMemcpyHostToDevice, s0));
+  HIPCHK_ON(c, hipMemcpyAsync(S0.field, field, n * 4, hipMemcpyHostToDevice, s0));
+  HIPCHK_ON(c, hipMemcpyAsync(S0.ts, ts, n * 8, hipMemcpyHostToDevice, s0));
+  HIPCHK_ON(c, hipMemcpyAsync(S0.val, val, n * 8, hipMemcpyHostToDevice, s0));
   if (applied_idx) {   // the byte map of this batch's winners, zeroed before any shard marks it
     if ((rc = comm_ensure_global(c, n))) return rc;
-    CHIP(hipSetDevice(c->dev[0]));
-    CHIP(hipMemsetAsync(c->g_flag, 0, n, s0));
+    HIPCHK_ON(c, hipSetDevice(c->dev[0]));
+    HIPCHK_ON(c, hipMemsetAsync(c->win.flag, 0, n, s0));
   }
   // 2. slab size: the mean run plus six standard deviations of a uniform owner hash; the exact counts come back with the partition, and a batch
   //    that does not fit (skewed node ids) is partitioned once more into slabs of the largest run — nothing has been merged by then
   std::vector<unsigned long long> cnt(N, 0);
   uint64_t slab = n / N + 6 * (uint64_t)std::sqrt((double)(n / N + 1)) + 64;
   for (int attempt = 0; attempt < 2; attempt++) {
-    if (slab > 0xFFFFFFFFull / N) return cfail(c, BMX_ERR_INVALID, "batch too large for one exchange slab per shard");
+    if (slab > 0xFFFFFFFFull / N) return fail(c, BMX_ERR_INVALID, "batch too large for one exchange slab per shard");
     for (uint32_t g = 0; g < N; g++) if ((rc = comm_ensure_recv(c, g, slab))) return rc;
-    CHIP(hipSetDevice(c->dev[0]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[0]));
     PartOut po; std::memset(&po, 0, sizeof(po));
     for (uint32_t g = 0; g < N; g++) po.base[g] = c->s[g].recv;
-    if (int prc = partition_impl(c->sh[0], n, S0.id, S0.field, S0.ts, S0.val, N, slab, nullptr, reinterpret_cast<uint64_t*>(S0.counts), &po, 0))
-      return cfail(c, prc, std::string("shard 0: ") + bmx_last_error(c->sh[0]));
-    CHIP(hipMemcpyAsync(cnt.data(), S0.counts, N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s0));
-    CHIP(hipStreamSynchronize(s0));
+    CSH(0, partition_impl(c->sh[0], n, S0.id, S0.field, S0.ts, S0.val, N, slab, nullptr, reinterpret_cast<uint64_t*>(S0.counts), &po, 0));
+    HIPCHK_ON(c, hipMemcpyAsync(cnt.data(), S0.counts, N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s0));
+    HIPCHK_ON(c, hipStreamSynchronize(s0));
     uint64_t mx = 0;
     for (uint32_t g = 0; g < N; g++) mx = std::max<uint64_t>(mx, cnt[g]);
     if (mx <= slab) break;
     (void)bmx_sync(c->sh[0]);            // clears the sticky "slab too small" status of the first attempt
-    if (attempt == 1) return cfail(c, BMX_ERR_INTERNAL, "owner partition overflowed a slab sized from its own counts");
+    if (attempt == 1) return fail(c, BMX_ERR_INTERNAL, "owner partition overflowed a slab sized from its own counts");
     slab = mx;
   }
-  CHIP(hipEventRecord(S0.routed, s0));    // the slabs are in place (and the winner map is zeroed)
+  HIPCHK_ON(c, hipEventRecord(S0.routed, s0));    // the slabs are in place (and the winner map is zeroed)
   // 3. every owner merges its slab and marks its winners in the map; all on the owner's stream
   std::vector<uint64_t> m(N, 0);
   hipEvent_t routed0 = S0.routed;
   for (uint32_t g = 0; g < N; g++) {
     m[g] = cnt[g];
     bmx_comm::Shard& G = c->s[g];
-    CHIP(hipSetDevice(c->dev[g]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[g]));
     hipStream_t st = reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[g]));
-    if (g) CHIP(hipStreamWaitEvent(st, routed0, 0));
+    if (g) HIPCHK_ON(c, hipStreamWaitEvent(st, routed0, 0));
     if (m[g]) {
       CSH(g, merge_records_internal(c->sh[g], slab, G.recv, mode, applied_idx ? G.applied : nullptr, reinterpret_cast<uint64_t*>(G.n_applied), G.stats));
       if (applied_idx) {
-        hipLaunchKernelGGL(k_mark_aux, dim3(256), dim3(256), 0, st, (const bmx_delta_rec*)G.recv, (const uint32_t*)G.applied, (const unsigned long long*)G.n_applied, c->g_flag);
-        CHIP(hipGetLastError());
+        hipLaunchKernelGGL(k_mark_aux, dim3(256), dim3(256), 0, st, (const bmx_delta_rec*)G.recv, (const uint32_t*)G.applied, (const unsigned long long*)G.n_applied, c->win.flag);
+        HIPCHK_ON(c, hipGetLastError());
       }
     }
-    if (g) CHIP(hipEventRecord(G.merged, st));       // "this shard's part of the host batch is done" (shard 0 orders itself)
+    if (g) HIPCHK_ON(c, hipEventRecord(G.merged, st));       // "this shard's part of the host batch is done" (shard 0 orders itself)
   }
   if (applied_idx && n) {   // shard 0 compacts the byte map once every shard has marked
-    CHIP(hipSetDevice(c->dev[0]));
-    for (uint32_t g = 1; g < N; g++) CHIP(hipStreamWaitEvent(s0, c->s[g].merged, 0));
-    hipLaunchKernelGGL(k_count_winners, dim3((uint32_t)((n + 4095) / 4096)), dim3(256), 0, s0, (const uint8_t*)c->g_flag, (uint32_t)n, c->g_blk);
-    FinishCount Fin{c->g_n};
-    hipLaunchKernelGGL((k_compact_winners<FinishCount>), dim3((uint32_t)((n + 4095) / 4096)), dim3(SEL_THREADS), 0, s0, (const uint8_t*)c->g_flag, (const uint32_t*)c->g_blk,
-                       (uint32_t)n, c->g_applied, Fin, ChgLog{});
-    CHIP(hipGetLastError());
+    HIPCHK_ON(c, hipSetDevice(c->dev[0]));
+    for (uint32_t g = 1; g < N; g++) HIPCHK_ON(c, hipStreamWaitEvent(s0, c->s[g].merged, 0));
+    hipLaunchKernelGGL(k_count_winners, dim3((uint32_t)((n + 4095) / 4096)), dim3(256), 0, s0, (const uint8_t*)c->win.flag, (uint32_t)n, c->win.blk);
+    FinishCount Fin{c->win.n};
+    hipLaunchKernelGGL((k_compact_winners<FinishCount>), dim3((uint32_t)((n + 4095) / 4096)), dim3(SEL_THREADS), 0, s0, (const uint8_t*)c->win.flag, (const uint32_t*)c->win.blk,
+                       (uint32_t)n, c->win.applied, Fin, ChgLog{});
+    HIPCHK_ON(c, hipGetLastError());
   }
   // 5. results: one wait per shard, then the winners (already in ascending batch order) from shard 0
   uint64_t total = 0;
@@ -235,8 +240,8 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
   std::vector<bmx_merge_stats> hs(N);
   for (uint32_t g = 0; g < N; g++) {
     std::memset(&hs[g], 0, sizeof(bmx_merge_stats));
-    CHIP(hipSetDevice(c->dev[g]));
-    CHIP(hipMemcpyAsync(&hs[g], c->s[g].stats, sizeof(bmx_merge_stats), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[g]))));
+    HIPCHK_ON(c, hipSetDevice(c->dev[g]));
+    HIPCHK_ON(c, hipMemcpyAsync(&hs[g], c->s[g].stats, sizeof(bmx_merge_stats), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[g]))));
   }
   for (uint32_t g = 0; g < N; g++) {
     CSH(g, bmx_sync(c->sh[g]));             // waits for the shard's stream and reports its sticky device errors
@@ -245,10 +250,10 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
   }
   if (applied_idx && n) {
     unsigned long long w = 0;
-    CHIP(hipSetDevice(c->dev[0]));
-    CHIP(hipMemcpy(&w, c->g_n, sizeof(w), hipMemcpyDeviceToHost));
-    if (w != tot.n_applied) return cfail(c, BMX_ERR_INTERNAL, "winner map and per-shard winner counts disagree");
-    if (w) CHIP(hipMemcpy(applied_idx, c->g_applied, w * 4, hipMemcpyDeviceToHost));
+    HIPCHK_ON(c, hipSetDevice(c->dev[0]));
+    HIPCHK_ON(c, hipMemcpy(&w, c->win.n, sizeof(w), hipMemcpyDeviceToHost));
+    if (w != tot.n_applied) return fail(c, BMX_ERR_INTERNAL, "winner map and per-shard winner counts disagree");
+    if (w) HIPCHK_ON(c, hipMemcpy(applied_idx, c->win.applied, w * 4, hipMemcpyDeviceToHost));
   }
   total = tot.n_applied;
   if (n_applied) *n_applied = total;
@@ -257,7 +262,7 @@ int comm_host_batch(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t*
 }
 // bmx_comm_load_rows (MODE_LOAD) / bmx_comm_put_rows (MODE_PUT)
 int comm_load_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, const MergeMode& mode) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   return in_load_chunks(n, id, field, ts, val, [&](const MergeIn& p) { return comm_host_batch(c, p.n, p.id, p.field, p.ts, p.val, mode, nullptr, nullptr, nullptr); });
 }
@@ -271,37 +276,36 @@ bmx_ctx* bmx_comm_shard(bmx_comm* c, uint32_t i) { return (c && i < c->N) ? c->s
 
 int bmx_comm_create(uint32_t nshards, const int* devices, uint64_t capacity_rows_per_shard, uint32_t flags, bmx_comm** out) {
   if (!out || nshards == 0 || nshards > PART_MAX_SHARDS || !devices || capacity_rows_per_shard == 0)
-    return cfail(nullptr, BMX_ERR_INVALID, "bmx_comm_create: bad arguments (1..16 shards)");
+    return fail<bmx_comm>(nullptr, BMX_ERR_INVALID, "bmx_comm_create: bad arguments (1..16 shards)");
   *out = nullptr;
   DevGuard guard;
   bmx_comm* c = new (std::nothrow) bmx_comm();
-  if (!c) return cfail(nullptr, BMX_ERR_NOMEM, "out of host memory");
+  if (!c) return fail<bmx_comm>(nullptr, BMX_ERR_NOMEM, "out of host memory");
   c->N = nshards; c->dev.assign(devices, devices + nshards); c->sh.assign(nshards, nullptr); c->s.resize(nshards);
   auto bail = [&](int rc) { std::string m = c->err; bmx_comm_destroy(c); g_comm_err = m; return rc; };
   for (uint32_t g = 0; g < nshards; g++) {
-    int rc = bmx_create(devices[g], capacity_rows_per_shard, flags, &c->sh[g]);
-    if (rc) { c->err = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(nullptr); return bail(rc); }
+    if (int rc = bmx_create(devices[g], capacity_rows_per_shard, flags, &c->sh[g])) return bail(fail(c, rc, shard_msg(c, g)));
     c->sh[g]->defer.enabled = false;   // the communicator orders its shards' streams with events right behind their merges: every compaction stays on its stream
     bmx_comm::Shard& S = c->s[g];
-    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&S.counts), PART_MAX_SHARDS * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&S.n_applied), sizeof(unsigned long long)) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&S.stats), sizeof(bmx_merge_stats)) != hipSuccess ||
-        hipMemset(S.n_applied, 0, sizeof(unsigned long long)) != hipSuccess || hipMemset(S.stats, 0, sizeof(bmx_merge_stats)) != hipSuccess ||
-        hipEventCreateWithFlags(&S.routed, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&S.merged, hipEventDisableTiming) != hipSuccess) {
-      c->err = "bmx_comm_create: device allocation failed";
-      return bail(BMX_ERR_HIP);
-    }
+    HIPCHK_BAIL(c, hipSetDevice(devices[g]));
+    if (int rc = dev_alloc_all(c, {{S.counts, PART_MAX_SHARDS * sizeof(unsigned long long)}, {S.n_applied, sizeof(unsigned long long)}, {S.stats, sizeof(bmx_merge_stats)}})) return bail(rc);
+    HIPCHK_BAIL(c, hipMemset(S.n_applied, 0, sizeof(unsigned long long)));
+    HIPCHK_BAIL(c, hipMemset(S.stats, 0, sizeof(bmx_merge_stats)));
+    HIPCHK_BAIL(c, hipEventCreateWithFlags(&S.routed, hipEventDisableTiming));
+    HIPCHK_BAIL(c, hipEventCreateWithFlags(&S.merged, hipEventDisableTiming));
   }
-  if (hipSetDevice(devices[0]) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&c->g_n), sizeof(unsigned long long)) != hipSuccess ||
-      hipEventCreateWithFlags(&c->g_zeroed, hipEventDisableTiming) != hipSuccess) { c->err = "bmx_comm_create: device allocation failed"; return bail(BMX_ERR_HIP); }
+  HIPCHK_BAIL(c, hipSetDevice(devices[0]));
+  if (int rc = dev_alloc(c, &c->win.n, 1)) return bail(rc);
+  HIPCHK_BAIL(c, hipEventCreateWithFlags(&c->win.zeroed, hipEventDisableTiming));
   // peer access between distinct devices (the device path stores straight into the owners' receive buffers)
   for (uint32_t a = 0; a < nshards; a++)
     for (uint32_t b = 0; b < nshards; b++)
       if (devices[a] != devices[b]) {
         int can = 0;
-        if (hipDeviceCanAccessPeer(&can, devices[a], devices[b]) != hipSuccess || !can) { c->err = "bmx_comm_create: GPUs of one communicator must be peer-accessible"; return bail(BMX_ERR_HIP); }
+        if (hipDeviceCanAccessPeer(&can, devices[a], devices[b]) != hipSuccess || !can) return bail(fail(c, BMX_ERR_HIP, "bmx_comm_create: GPUs of one communicator must be peer-accessible"));
         (void)hipSetDevice(devices[a]);
         hipError_t e = hipDeviceEnablePeerAccess(devices[b], 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { c->err = std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e); return bail(BMX_ERR_HIP); }
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return bail(fail(c, BMX_ERR_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e)));
         (void)hipGetLastError();
       }
   *out = c;
@@ -313,30 +317,25 @@ void bmx_comm_destroy(bmx_comm* c) {
   DevGuard guard;
   for (uint32_t g = 0; g < c->N; g++) { if (c->sh[g]) { (void)hipSetDevice(c->dev[g]); (void)hipDeviceSynchronize(); } }
   for (uint32_t g = 0; g < c->N; g++) {
-    bmx_comm::Shard& S = c->s[g];
     (void)hipSetDevice(c->dev[g]);
-    (void)hipFree(S.id); (void)hipFree(S.field); (void)hipFree(S.ts); (void)hipFree(S.val); (void)hipFree(S.counts);
-    (void)hipFree(S.recv); (void)hipFree(S.applied); (void)hipFree(S.n_applied); (void)hipFree(S.stats);
-    if (S.routed) (void)hipEventDestroy(S.routed);
-    if (S.merged) (void)hipEventDestroy(S.merged);
+    c->s[g].release();
     if (c->sh[g]) bmx_destroy(c->sh[g]);
   }
   if (c->N) (void)hipSetDevice(c->dev[0]);
-  (void)hipFree(c->g_flag); (void)hipFree(c->g_blk); (void)hipFree(c->g_applied); (void)hipFree(c->g_n);
-  if (c->g_zeroed) (void)hipEventDestroy(c->g_zeroed);
+  c->win.release();
   delete c;
 }
 
 int bmx_comm_sync(bmx_comm* c) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   int first = BMX_OK; std::string msg;
   for (uint32_t g = 0; g < c->N; g++) {
     int rc = bmx_sync(c->sh[g]);
-    if (rc && !first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(c->sh[g]); }
+    if (rc && !first) { first = rc; msg = shard_msg(c, g); }
   }
   c->dev_step_pending = false;
-  return first ? cfail(c, first, msg) : BMX_OK;
+  return first ? fail(c, first, msg) : BMX_OK;
 }
 
 int bmx_comm_load_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) { return comm_load_rows(c, n, id, field, ts, val, MODE_LOAD); }
@@ -344,23 +343,23 @@ int bmx_comm_put_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_
 
 int bmx_comm_merge(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val, int insert_mode,
                    uint32_t* applied_idx, uint64_t* n_applied, bmx_merge_stats* stats) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
-  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return cfail(c, BMX_ERR_INVALID, bad);
-  if (mode.strict) return cfail(c, BMX_ERR_INVALID, "bmx_comm_merge: per-delta flags are not collected across shards");
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return fail(c, BMX_ERR_INVALID, bad);
+  if (mode.strict) return fail(c, BMX_ERR_INVALID, "bmx_comm_merge: per-delta flags are not collected across shards");
   return comm_host_batch(c, n, id, field, ts, val, mode, applied_idx, n_applied, stats);
 }
 
 int bmx_comm_merge_dev(bmx_comm* c, const uint64_t* n, const uint64_t* const* id, const uint32_t* const* field, const int64_t* const* ts,
                        const int64_t* const* val, int insert_mode, uint64_t slab_records) {
-  if (!c || !n || !id || !field || !ts || !val) return cfail(c, BMX_ERR_INVALID, "bmx_comm_merge_dev: null argument");
-  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return cfail(c, BMX_ERR_INVALID, bad);   // before anything is routed; the shards' bmx_merge_records take insert_mode as it is
+  if (!c || !n || !id || !field || !ts || !val) return fail(c, BMX_ERR_INVALID, "bmx_comm_merge_dev: null argument");
+  MergeMode mode; if (const char* bad = merge_mode_of(insert_mode, &mode)) return fail(c, BMX_ERR_INVALID, bad);   // before anything is routed; the shards' bmx_merge_records take insert_mode as it is
   DevGuard guard;
   const uint32_t N = c->N;
   uint64_t nmax = 0;
-  for (uint32_t i = 0; i < N; i++) { if (n[i] > MAX_BATCH) return cfail(c, BMX_ERR_INVALID, "batch larger than 2^24 deltas"); nmax = std::max(nmax, n[i]); }
+  for (uint32_t i = 0; i < N; i++) { if (n[i] > MAX_BATCH) return fail(c, BMX_ERR_INVALID, "batch larger than 2^24 deltas"); nmax = std::max(nmax, n[i]); }
   if (slab_records == 0) slab_records = nmax / N + nmax / (8 * N) + 64;          // 12.5 % head room over the mean run
-  if (slab_records * N > 0xFFFFFFFFull) return cfail(c, BMX_ERR_INVALID, "slab too large");
+  if (slab_records * N > 0xFFFFFFFFull) return fail(c, BMX_ERR_INVALID, "slab too large");
   int rc;
   for (uint32_t g = 0; g < N; g++) {
     if ((rc = comm_ensure_recv(c, g, (uint64_t)N * slab_records))) return rc;
@@ -369,22 +368,21 @@ int bmx_comm_merge_dev(bmx_comm* c, const uint64_t* n, const uint64_t* const* id
   // 1. every origin scatters straight into its owners' receive slabs (slab i of every receive buffer belongs to origin i); the owners'
   //    previous merges must have finished reading those buffers
   for (uint32_t i = 0; i < N; i++) {
-    CHIP(hipSetDevice(c->dev[i]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[i]));
     hipStream_t st = reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[i]));
-    for (uint32_t g = 0; g < N; g++) if (g != i) CHIP(hipStreamWaitEvent(st, c->s[g].merged, 0));
+    for (uint32_t g = 0; g < N; g++) if (g != i) HIPCHK_ON(c, hipStreamWaitEvent(st, c->s[g].merged, 0));
     PartOut po; std::memset(&po, 0, sizeof(po));
     for (uint32_t g = 0; g < N; g++) po.base[g] = c->s[g].recv + (size_t)i * slab_records;
-    if (int prc = partition_impl(c->sh[i], n[i], id[i], field[i], ts[i], val[i], N, slab_records, nullptr, reinterpret_cast<uint64_t*>(c->s[i].counts), &po, 0))
-      return cfail(c, prc, std::string("shard ") + std::to_string(i) + ": " + bmx_last_error(c->sh[i]));
-    CHIP(hipEventRecord(c->s[i].routed, st));
+    CSH(i, partition_impl(c->sh[i], n[i], id[i], field[i], ts[i], val[i], N, slab_records, nullptr, reinterpret_cast<uint64_t*>(c->s[i].counts), &po, 0));
+    HIPCHK_ON(c, hipEventRecord(c->s[i].routed, st));
   }
   // 2. every owner merges its N slabs once all origins have scattered
   for (uint32_t g = 0; g < N; g++) {
-    CHIP(hipSetDevice(c->dev[g]));
+    HIPCHK_ON(c, hipSetDevice(c->dev[g]));
     hipStream_t st = reinterpret_cast<hipStream_t>(bmx_get_stream(c->sh[g]));
-    for (uint32_t i = 0; i < N; i++) if (i != g) CHIP(hipStreamWaitEvent(st, c->s[i].routed, 0));
+    for (uint32_t i = 0; i < N; i++) if (i != g) HIPCHK_ON(c, hipStreamWaitEvent(st, c->s[i].routed, 0));
     CSH(g, bmx_merge_records(c->sh[g], (uint64_t)N * slab_records, c->s[g].recv, insert_mode, c->s[g].applied, reinterpret_cast<uint64_t*>(c->s[g].n_applied), nullptr, c->s[g].stats));
-    CHIP(hipEventRecord(c->s[g].merged, st));
+    HIPCHK_ON(c, hipEventRecord(c->s[g].merged, st));
   }
   c->dev_step_pending = true;
   return BMX_OK;
@@ -392,7 +390,7 @@ int bmx_comm_merge_dev(bmx_comm* c, const uint64_t* n, const uint64_t* const* id
 
 int bmx_comm_shard_result(bmx_comm* c, uint32_t shard, const bmx_delta_rec** recs_dev, const uint32_t** applied_dev, const uint64_t** n_applied_dev,
                           const bmx_merge_stats** stats_dev, uint64_t* n_records) {
-  if (!c || shard >= c->N) return cfail(c, BMX_ERR_INVALID, "bad shard");
+  if (!c || shard >= c->N) return fail(c, BMX_ERR_INVALID, "bad shard");
   const bmx_comm::Shard& S = c->s[shard];
   if (recs_dev) *recs_dev = S.recv;
   if (applied_dev) *applied_dev = S.applied;
@@ -403,7 +401,7 @@ int bmx_comm_shard_result(bmx_comm* c, uint32_t shard, const bmx_delta_rec** rec
 }
 
 int bmx_comm_row_count(bmx_comm* c, uint64_t* n_out) {
-  if (!c || !n_out) return cfail(c, BMX_ERR_INVALID, "bad arguments");
+  if (!c || !n_out) return fail(c, BMX_ERR_INVALID, "bad arguments");
   DevGuard guard;
   uint64_t tot = 0;
   for (uint32_t g = 0; g < c->N; g++) { uint64_t r = 0; CSH(g, bmx_row_count(c->sh[g], &r)); tot += r; }
@@ -412,10 +410,10 @@ int bmx_comm_row_count(bmx_comm* c, uint64_t* n_out) {
 }
 
 int bmx_comm_get_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_t* field, int64_t* ts, int64_t* val, uint8_t* found) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   if (n == 0) return BMX_OK;
-  if (!id || !field || !ts || !val || !found) return cfail(c, BMX_ERR_INVALID, "null pointer");
+  if (!id || !field || !ts || !val || !found) return fail(c, BMX_ERR_INVALID, "null pointer");
   std::vector<std::vector<uint64_t>> pos(c->N);
   for (uint64_t j = 0; j < n; j++) pos[bmx_owner_of(id[j], c->N)].push_back(j);
   for (uint32_t g = 0; g < c->N; g++) {
@@ -430,7 +428,7 @@ int bmx_comm_get_rows(bmx_comm* c, uint64_t n, const uint64_t* id, const uint32_
 }
 
 int bmx_comm_dump_rows(bmx_comm* c, uint64_t cap, uint64_t* id, uint32_t* field, int64_t* ts, int64_t* val, uint64_t* n_out) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   uint64_t tot = 0;
   for (uint32_t g = 0; g < c->N; g++) {
@@ -444,7 +442,7 @@ int bmx_comm_dump_rows(bmx_comm* c, uint64_t cap, uint64_t* id, uint32_t* field,
 }
 
 int bmx_comm_index_build(bmx_comm* c, uint32_t field) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   for (uint32_t g = 0; g < c->N; g++) CSH(g, bmx_index_build(c->sh[g], field));
   return BMX_OK;
@@ -452,7 +450,7 @@ int bmx_comm_index_build(bmx_comm* c, uint32_t field) {
 
 // value-ordered views on every shard's index of `field` (bmx.h bmx_index_set_ordered): each shard answers from its own sorted copy, concatenated as ever
 int bmx_comm_index_set_ordered(bmx_comm* c, uint32_t field, uint32_t after_queries) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   for (uint32_t g = 0; g < c->N; g++) CSH(g, bmx_index_set_ordered(c->sh[g], field, after_queries));
   return BMX_OK;
@@ -462,26 +460,22 @@ int bmx_comm_index_set_ordered(bmx_comm* c, uint32_t field, uint32_t after_queri
 // concatenated in shard order. Two phases: the scans of ALL shards are enqueued first (each into its context's own result buffer), then the
 // results are fetched shard by shard — N GPUs scan at the same time, and the host waits once per shard for work that is already running.
 static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   uint64_t* want = (out_ids && cap) ? out_ids : nullptr;
-  for (uint32_t g = 0; g < c->N; g++) {
-    bmx_ctx* x = c->sh[g];
-    const int rc = terms ? scan_filter_impl(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true) : scan_range_impl(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
-    if (rc) {   // nothing of the shards before g is delivered; their scans finish on their own streams
-      return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));
-    }
-  }
   uint64_t tot = 0;
-  int first = BMX_OK; std::string msg;
-  for (uint32_t g = 0; g < c->N; g++) {
-    uint64_t m = 0;
-    const uint64_t room = (want && cap > tot) ? cap - tot : 0;
-    const int rc = scan_collect(c->sh[g], room ? out_ids + tot : nullptr, room, &m);    // every shard is collected, also after an error
-    if (rc && !first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(c->sh[g]); }
-    tot += m;
-  }
-  if (first) return cfail(c, first, msg);
+  const int rc = comm_two_phase(c,
+    [&](uint32_t, bmx_ctx* x) {
+      return terms ? scan_filter_impl(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true) : scan_range_impl(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
+    },
+    [&](uint32_t, bmx_ctx* x) {
+      uint64_t m = 0;
+      const uint64_t room = (want && cap > tot) ? cap - tot : 0;
+      const int crc = scan_collect(x, room ? out_ids + tot : nullptr, room, &m);
+      tot += m;
+      return crc;
+    });
+  if (rc) return rc;
   if (n_out) *n_out = tot;
   return BMX_OK;
 }
@@ -495,8 +489,8 @@ int bmx_comm_scan_count(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uin
   return comm_scan(c, field, lo, hi, 0, nullptr, nullptr, 0, n_out);
 }
 int bmx_comm_scan_filter(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
-  if (nterms == 0 || !terms) return cfail(c, BMX_ERR_INVALID, "filter needs 1..8 terms");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (nterms == 0 || !terms) return fail(c, BMX_ERR_INVALID, "filter needs 1..8 terms");
   return comm_scan(c, 0, 0, 0, nterms, terms, out_ids, cap, n_out);
 }
 
@@ -505,34 +499,26 @@ int bmx_comm_scan_filter(bmx_comm* c, uint32_t nterms, const bmx_term* terms, ui
 // before the first shard's records are fetched.
 int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups,
                             bmx_agg* out) {
-  if (const char* bad = agg_bad_args(nterms, terms, group_field, ngroups, out)) return cfail(c, BMX_ERR_INVALID, bad);
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (const char* bad = agg_bad_args(nterms, terms, group_field, ngroups, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   const uint32_t nrec = agg_records(ngroups);
-  for (uint32_t g = 0; g < c->N; g++) {
-    bmx_ctx* x = c->sh[g];
-    int rc = enter(x);
-    if (!rc) rc = agg_enqueue(x, nterms, terms, measure_field, group_field, group_lo, ngroups, nullptr);
-    if (rc) return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));   // (the queries of the shards before g finish on their own streams)
-  }
   std::vector<bmx_agg> part(nrec);
-  int first = BMX_OK; std::string msg;
-  for (uint32_t g = 0; g < c->N; g++) {
-    bmx_ctx* x = c->sh[g];
-    int rc = enter(x);
-    if (!rc) rc = agg_collect(x, nrec, g == 0 ? out : part.data());    // every shard is collected, also after an error
-    if (rc) { if (!first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x); } continue; }
-    if (g == 0) continue;
-    for (uint32_t r = 0; r < nrec; r++) {
-      bmx_agg& o = out[r]; const bmx_agg& p = part[r];
-      o.n_match += p.n_match; o.n += p.n;
-      o.min = std::min(o.min, p.min); o.max = std::max(o.max, p.max);
-      const unsigned __int128 s = (((unsigned __int128)(uint64_t)o.sum_hi << 64) | o.sum_lo) + (((unsigned __int128)(uint64_t)p.sum_hi << 64) | p.sum_lo);
-      o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
-    }
-  }
-  if (first) return cfail(c, first, msg);
-  return BMX_OK;
+  return comm_two_phase(c,
+    [&](uint32_t, bmx_ctx* x) { const int rc = enter(x); return rc ? rc : agg_enqueue(x, nterms, terms, measure_field, group_field, group_lo, ngroups, nullptr); },
+    [&](uint32_t g, bmx_ctx* x) {
+      int rc = enter(x);
+      if (!rc) rc = agg_collect(x, nrec, g == 0 ? out : part.data());
+      if (rc || g == 0) return rc;
+      for (uint32_t r = 0; r < nrec; r++) {
+        bmx_agg& o = out[r]; const bmx_agg& p = part[r];
+        o.n_match += p.n_match; o.n += p.n;
+        o.min = std::min(o.min, p.min); o.max = std::max(o.max, p.max);
+        const unsigned __int128 s = (((unsigned __int128)(uint64_t)o.sum_hi << 64) | o.sum_lo) + (((unsigned __int128)(uint64_t)p.sum_hi << 64) | p.sum_lo);
+        o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
+      }
+      return BMX_OK;
+    });
 }
 
 // bmx_scan_top over the shards (bmx_top.h, host memory). A node lives on one shard and the order (value, id) is total, so the first k of the whole graph are
@@ -540,33 +526,28 @@ int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms,
 // on the host and the shards' n_eligible add up.
 int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t flags, const bmx_top_rec* after, uint32_t k, bmx_top_rec* out, uint64_t* n_out,
                       uint64_t* n_eligible) {
-  if (const char* bad = top_bad_args(nterms, terms, flags, k, out)) return cfail(c, BMX_ERR_INVALID, bad);
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (const char* bad = top_bad_args(nterms, terms, flags, k, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
-  for (uint32_t g = 0; g < c->N; g++) {
-    bmx_ctx* x = c->sh[g];
-    int rc = enter(x);
-    if (!rc) rc = top_enqueue(x, nterms, terms, flags, after, k, nullptr, nullptr, nullptr);
-    if (rc) return cfail(c, rc, std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x));   // (the queries of the shards before g finish on their own streams)
-  }
   const bool desc = (flags & BMX_TOP_DESC) != 0;
   auto before = [desc](const bmx_top_rec& a, const bmx_top_rec& b) { return a.val != b.val ? (desc ? a.val > b.val : a.val < b.val) : a.id < b.id; };
   std::vector<bmx_top_rec> all, part, tmp;
   uint64_t tot = 0;
-  int first = BMX_OK; std::string msg;
-  for (uint32_t g = 0; g < c->N; g++) {
-    bmx_ctx* x = c->sh[g];
-    uint64_t ne = 0;
-    int rc = enter(x);
-    if (!rc) rc = top_collect(x, k, part, &ne);    // every shard is collected, also after an error
-    if (rc) { if (!first) { first = rc; msg = std::string("shard ") + std::to_string(g) + ": " + bmx_last_error(x); } continue; }
-    tot += ne;
-    tmp.resize(all.size() + part.size());
-    std::merge(all.begin(), all.end(), part.begin(), part.end(), tmp.begin(), before);
-    if (tmp.size() > k) tmp.resize(k);
-    all.swap(tmp);
-  }
-  if (first) return cfail(c, first, msg);
+  const int rc = comm_two_phase(c,
+    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : top_enqueue(x, nterms, terms, flags, after, k, nullptr, nullptr, nullptr); },
+    [&](uint32_t, bmx_ctx* x) {
+      uint64_t ne = 0;
+      int crc = enter(x);
+      if (!crc) crc = top_collect(x, k, part, &ne);
+      if (crc) return crc;
+      tot += ne;
+      tmp.resize(all.size() + part.size());
+      std::merge(all.begin(), all.end(), part.begin(), part.end(), tmp.begin(), before);
+      if (tmp.size() > k) tmp.resize(k);
+      all.swap(tmp);
+      return BMX_OK;
+    });
+  if (rc) return rc;
   if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(bmx_top_rec));
   if (n_out) *n_out = all.size();
   if (n_eligible) *n_eligible = tot;
@@ -576,8 +557,8 @@ int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint3
 // Replica reconciliation over the shards (bmx.h). The shards' key sets are disjoint and the digest is a sum, so the digest of the sharded graph is the
 // element-wise sum of the shards' vectors — the same vectors one context holding all the rows would give. Host memory.
 int bmx_comm_digest(bmx_comm* c, uint32_t log2_buckets, uint32_t flags, uint64_t* sums, uint64_t* counts) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
-  if (log2_buckets > 16 || !sums || !counts) return cfail(c, BMX_ERR_INVALID, "bmx_comm_digest: log2_buckets > 16 or null output");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (log2_buckets > 16 || !sums || !counts) return fail(c, BMX_ERR_INVALID, "bmx_comm_digest: log2_buckets > 16 or null output");
   DevGuard guard;
   const uint64_t B = 1ull << log2_buckets;
   std::vector<uint64_t> s(B), n(B);
@@ -592,7 +573,7 @@ int bmx_comm_digest(bmx_comm* c, uint32_t log2_buckets, uint32_t flags, uint64_t
 // bmx_export_rows shard after shard into one host array (like bmx_comm_dump_rows): shard order, table order inside a shard
 int bmx_comm_export_rows(bmx_comm* c, int64_t since_ts, uint32_t log2_buckets, const uint64_t* bucket_bits, uint32_t flags, bmx_delta_rec* out, uint64_t cap,
                          uint64_t* n_out) {
-  if (!c) return cfail(nullptr, BMX_ERR_INVALID, "null communicator");
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   uint64_t tot = 0;
   for (uint32_t g = 0; g < c->N; g++) {

@@ -176,14 +176,11 @@ int scan_range_impl_t(bmx_ctx* ctx, uint32_t field, int64_t lo, int64_t hi, void
   if (rc) return rc;
   const bool ordered = (n_out || out) && ensure_ordered_view(ctx, ix);     // (it was sorted from columns of the width they have now: a widened index has a new `content`)
   if (ix->fits32) {
-    // every value fits int32: scan the 4-byte column with bounds clamped into int32 (an empty range stays empty). INT32_MIN itself is what a
-    // tombstone looks like in this column and is never matched (a real -2^31 makes the index wide: scan_kernels.h v32_of)
-    int64_t l = std::max<int64_t>(lo, (int64_t)INT32_MIN + 1), h = std::min<int64_t>(hi, INT32_MAX);
-    if (lo > INT32_MAX || hi < INT32_MIN) { l = 1; h = 0; }
-    PredRange32 P{ix->v32, (int32_t)l, (int32_t)h, ix->n * sizeof(int32_t) > SCAN_NT_BYTES};
-    rc = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, deferred, ordered, l, h);
+    const Range32 r = clamp_i32(lo, hi);     // every value fits int32: scan the 4-byte column
+    PredRange32 P{ix->v32, (int32_t)r.lo, (int32_t)r.hi, ix->n * sizeof(int32_t) > SCAN_NT_BYTES};
+    rc = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, deferred, ordered, r.lo, r.hi);
   } else {
-    PredRange64 P{ix->v64, std::max<int64_t>(lo, -VAL_MAX), hi, ix->n * sizeof(int64_t) > SCAN_NT_BYTES};    // values live in +-(2^53-1): the clamp changes no answer and keeps tombstones (INT64_MIN) out
+    PredRange64 P{ix->v64, above_tombstones(lo), hi, ix->n * sizeof(int64_t) > SCAN_NT_BYTES};
     rc = run_scan_t<POS>(ctx, P, ix, out, cap, n_out, mem, deferred, ordered, P.lo, P.hi);
   }
   if (ordered && !rc) view_after_query(ctx, ix);

@@ -15,7 +15,7 @@ namespace {
 // bmx_scan_filter and the first half of bmx_comm_scan_filter
 int scan_filter_impl(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred = false) {
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (nterms == 0 || nterms > MAX_TERMS || !terms) return fail(ctx, BMX_ERR_INVALID, "filter needs 1..8 terms");
+  if (const char* bad = bad_terms(nterms, terms, "filter needs 1..8 terms")) return fail(ctx, BMX_ERR_INVALID, bad);
   if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
   if (int erc = enter(ctx)) return erc;
   Index* ix;
@@ -23,7 +23,7 @@ int scan_filter_impl(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint6
   if (rc) return rc;
   PredFilter P;
   P.v = ix->v64; P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nterms = nterms;
-  for (uint32_t k = 0; k < nterms; k++) { P.t[k] = terms[k]; P.t[k].lo = std::max<int64_t>(terms[k].lo, -VAL_MAX); }   // tombstones (INT64_MIN) match no term
+  copy_terms(P.t, terms, nterms);
   // with a value-ordered view of the first term's index: its run is the candidate list, the other terms are probed for those ids only (no order)
   if ((n_out || out_ids) && ensure_ordered_view(ctx, ix)) {
     const int src = run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem, deferred, true, P.t[0].lo, P.t[0].hi);

@@ -5,15 +5,9 @@ namespace {
 constexpr uint32_t SYNC_MAX_LOG2 = 16;
 
 // the workgroups of one digest sweep: two per CU, never more than the table has chunks for
-int digest_grid(bmx_ctx* ctx, uint32_t* blocks) {
-  if (!ctx->sync.cus) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    ctx->sync.cus = std::max(cus, 1);
-  }
+uint32_t digest_grid(const bmx_ctx* ctx) {
   const uint64_t chunks = (ctx->nslots + 64ull * DIG_U - 1) / (64ull * DIG_U);
-  *blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((chunks + DIG_WAVES - 1) / DIG_WAVES, 2ull * (uint64_t)ctx->sync.cus));
-  return BMX_OK;
+  return sweep_grid(ctx, chunks, DIG_WAVES);
 }
 
 }  // namespace
@@ -39,8 +33,7 @@ int bmx_digest(bmx_ctx* ctx, uint32_t log2_buckets, uint32_t flags, uint64_t* su
   }
   HIPCHK(hipMemsetAsync(d_s, 0, B * sizeof(unsigned long long), ctx->stream));
   HIPCHK(hipMemsetAsync(d_c, 0, B * sizeof(unsigned long long), ctx->stream));
-  uint32_t blocks = 1;
-  if (int rc = digest_grid(ctx, &blocks)) return rc;
+  const uint32_t blocks = digest_grid(ctx);
   const bool nt = ctx->nslots * sizeof(Slot) > SCAN_NT_BYTES;
   const bool lds = log2_buckets <= DIG_LDS_LOG2;
   const uint32_t tomb = (flags & BMX_SYNC_TOMBSTONES) ? 1u : 0u;

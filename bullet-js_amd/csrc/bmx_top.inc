@@ -5,7 +5,7 @@ namespace {
 
 // what every caller's arguments must satisfy before anything touches a device (bmx_comm_scan_top asks the same)
 const char* top_bad_args(uint32_t nterms, const bmx_term* terms, uint32_t flags, uint32_t k, const bmx_top_rec* out) {
-  if (nterms == 0 || nterms > (uint32_t)MAX_TERMS || !terms) return "bmx_scan_top needs 1..8 terms";
+  if (const char* bad = bad_terms(nterms, terms, "bmx_scan_top needs 1..8 terms")) return bad;
   if (!out) return "bmx_scan_top: null output";
   if (k == 0 || k > BMX_TOP_MAX_K) return "bmx_scan_top: k outside 1..BMX_TOP_MAX_K";
   if (flags & ~BMX_TOP_DESC) return "bmx_scan_top: unknown flag bits";
@@ -14,11 +14,6 @@ const char* top_bad_args(uint32_t nterms, const bmx_term* terms, uint32_t flags,
 
 int top_scratch(bmx_ctx* ctx) {
   TopScratch& s = ctx->top;
-  if (!s.cus) {
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    s.cus = std::max(cus, 1);
-  }
   if (!s.state) {
     if (int rc = dev_alloc_all(ctx, {{s.state, sizeof(TopState)}, {s.cand_u, TOP_CAND * sizeof(unsigned long long)}, {s.cand_id, TOP_CAND * sizeof(unsigned long long)},
                                      {s.stage, 2 * sizeof(unsigned long long) + BMX_TOP_MAX_K * sizeof(bmx_top_rec)}})) return rc;
@@ -36,9 +31,8 @@ template <class T, bool PROBE>
 int top_launch(bmx_ctx* ctx, const Index* ix, const TopArgs& A, uint32_t k) {
   const T* col = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
   const uint32_t nt = ix->n * sizeof(T) > SCAN_NT_BYTES ? 1u : 0u;
-  // two workgroups per CU, and none with fewer than four rounds of loads to spread its one flush over
-  const uint64_t per_round = (uint64_t)TOP_THREADS * TOP_U * (16 / sizeof(T));
-  const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ix->n + 4 * per_round - 1) / (4 * per_round), 2ull * (uint64_t)ctx->top.cus));
+  // no workgroup with fewer than four rounds of loads to spread its one flush over
+  const uint32_t blocks = sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T)));
   hipLaunchKernelGGL((k_top_sweep0<T, PROBE>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, col, ix->n, nt, A);
   LAUNCHCHK("k_top_sweep0");
   hipLaunchKernelGGL(k_top_init, dim3(1), dim3(64), 0, ctx->stream, A.S, k);
@@ -67,12 +61,9 @@ int top_enqueue(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint32_t f
   TopArgs A{};
   A.ids = ix->ids; A.mask = ctx->scan.mask; A.slots = ctx->slots; A.nslots = ctx->nslots; A.S = ctx->top.state;
   A.desc = flags & BMX_TOP_DESC; A.nterms = nterms;
-  for (uint32_t t = 0; t < nterms; t++) { A.t[t] = terms[t]; A.t[t].lo = std::max<int64_t>(terms[t].lo, -VAL_MAX); }   // tombstones (INT64_MIN) match no term
+  copy_terms(A.t, terms, nterms);
   A.lo = A.t[0].lo; A.hi = A.t[0].hi;
-  if (ix->fits32) {   // the 4-byte column, bounds clamped into int32 like the scans' (INT32_MIN is what a tombstone looks like there; an empty range stays empty)
-    A.lo = std::max<int64_t>(A.t[0].lo, (int64_t)INT32_MIN + 1); A.hi = std::min<int64_t>(A.t[0].hi, INT32_MAX);
-    if (A.t[0].lo > INT32_MAX || A.t[0].hi < INT32_MIN) { A.lo = 1; A.hi = 0; }
-  }
+  if (ix->fits32) { const Range32 r = clamp_i32(A.lo, A.hi); A.lo = r.lo; A.hi = r.hi; }    // the 4-byte column
   if (after) {
     const unsigned long long u = (unsigned long long)after->val ^ 0x8000000000000000ull;
     A.has_after = 1u; A.au = A.desc ? ~u : u; A.aid = after->id;

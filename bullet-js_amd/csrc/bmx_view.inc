@@ -337,9 +337,8 @@ void launch_ordered(bmx_ctx* ctx, const Index* ix, int64_t lo, int64_t hi, OutT*
   if (filter && !d_n) d_n = &ctx->ds->n_out;       // (the filter appends through a counter even when nobody asked for the count)
   const OrderedView& v = ix->view;
   if (v.ord_fits32) {     // the view was sorted from the 4-byte column: bounds clamped into int32 like the scans' (an empty range stays empty)
-    int64_t l = std::max<int64_t>(lo, (int64_t)INT32_MIN + 1), h = std::min<int64_t>(hi, INT32_MAX);
-    if (lo > INT32_MAX || hi < INT32_MIN) { l = 1; h = 0; }
-    launch_ordered_t<POS, OutT, int32_t>(ctx, v, (int32_t)l, (int32_t)h, d_out, d_cap, d_n, filter);
+    const Range32 r = clamp_i32(lo, hi);
+    launch_ordered_t<POS, OutT, int32_t>(ctx, v, (int32_t)r.lo, (int32_t)r.hi, d_out, d_cap, d_n, filter);
   } else launch_ordered_t<POS, OutT, int64_t>(ctx, v, lo, hi, d_out, d_cap, d_n, filter);
 }
 

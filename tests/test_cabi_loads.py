@@ -94,3 +94,56 @@ def test_oversize_tables_are_refused_before_any_device_work(lib):
     assert lib.bmx_create_ex(0, 1000, 95, 0, C.byref(h)) == bmx.ERR_INVALID      # load factor out of range
     assert lib.bmx_vc_create(0, 1 << 31, 3, 0, C.byref(h)) == bmx.ERR_INVALID
     assert b"2^32 slots" in lib.bmx_vc_last_error(None)
+
+
+def test_the_three_error_channels_stay_separate(lib):
+    """bmx_ctx, bmx_vc and bmx_comm share one set of error helpers but keep three thread-local last-error words: a failure of one handle type leaves its text
+    in its own word and changes neither of the other two. The argument errors of the queries keep their texts. Nothing here needs a device: every call is
+    refused in front of the first look at one."""
+    import ctypes as C
+    h = C.c_void_p()
+    words = {"ctx": lambda: lib.bmx_last_error(None), "vc": lambda: lib.bmx_vc_last_error(None), "comm": lambda: lib.bmx_comm_last_error(None)}
+    dev = (C.c_int * 1)(0)
+    fails = {
+        "vc": (lambda: lib.bmx_vc_create(0, 1 << 31, 3, 0, C.byref(h)),
+               b"bmx_vc_create: table would need more than 2^32 slots (slot indices are 32-bit): shard the graph"),
+        "comm": (lambda: lib.bmx_comm_create(0, dev, 1000, 0, C.byref(h)), b"bmx_comm_create: bad arguments (1..16 shards)"),
+        "ctx": (lambda: lib.bmx_create_ex(0, 1000, 95, 0, C.byref(h)), b"bmx_create_ex: max_load_pct must be 5..90 (0 = default)"),
+    }
+    for name in ("vc", "comm", "ctx", "comm", "vc", "ctx"):    # every channel fails once after each of the other two
+        call, text = fails[name]
+        before = {k: w() for k, w in words.items()}
+        assert call() == bmx.ERR_INVALID and not h.value
+        assert words[name]() == text
+        for other in words:
+            if other != name:
+                assert words[other]() == before[other], (name, other)
+    # by now all three words are set, and they differ
+    assert len({w() for w in words.values()}) == 3
+
+    terms = (bmx.Term * 9)(*[bmx.Term(7 + k, 0, 0, 10) for k in range(9)])
+    out = (C.c_uint64 * 64)()
+    op = C.cast(out, C.c_void_p)
+    n = C.c_uint64(0)
+    for nt in (0, 9):
+        comm_before = words["comm"]()
+        assert lib.bmx_scan_aggregate(None, nt, terms, 7, 0xFFFFFFFF, 0, 0, op, bmx.MEM_HOST) == bmx.ERR_INVALID
+        assert words["ctx"]() == b"aggregate needs 1..8 terms"
+        assert lib.bmx_scan_top(None, nt, terms, 0, None, 4, op, None, None, bmx.MEM_HOST) == bmx.ERR_INVALID
+        assert words["ctx"]() == b"bmx_scan_top needs 1..8 terms"
+        assert lib.bmx_scan_filter(None, nt, terms, op, 8, None, bmx.MEM_HOST) == bmx.ERR_INVALID      # (the handle is looked at first)
+        assert words["ctx"]() == b"null context"
+        assert words["comm"]() == comm_before and words["vc"]() == fails["vc"][1]
+        ctx_before = words["ctx"]()
+        assert lib.bmx_comm_scan_filter(None, nt, terms, op, 8, C.byref(n)) == bmx.ERR_INVALID
+        assert words["comm"]() == b"null communicator"
+        assert lib.bmx_comm_scan_aggregate(None, nt, terms, 7, 0xFFFFFFFF, 0, 0, op) == bmx.ERR_INVALID
+        assert words["comm"]() == b"aggregate needs 1..8 terms"
+        assert lib.bmx_comm_scan_top(None, nt, terms, 0, None, 4, op, None, None) == bmx.ERR_INVALID
+        assert words["comm"]() == b"bmx_scan_top needs 1..8 terms"
+        assert words["ctx"]() == ctx_before and words["vc"]() == fails["vc"][1]
+    # well-formed terms, no handle
+    assert lib.bmx_scan_aggregate(None, 1, terms, 7, 0xFFFFFFFF, 0, 0, op, bmx.MEM_HOST) == bmx.ERR_INVALID and words["ctx"]() == b"null context"
+    assert lib.bmx_scan_top(None, 8, terms, 0, None, 4, op, None, None, bmx.MEM_HOST) == bmx.ERR_INVALID and words["ctx"]() == b"null context"
+    assert lib.bmx_comm_scan_aggregate(None, 1, terms, 7, 0xFFFFFFFF, 0, 0, op) == bmx.ERR_INVALID and words["comm"]() == b"null communicator"
+    assert not any(out) and n.value == 0, "a refused call writes nothing"
