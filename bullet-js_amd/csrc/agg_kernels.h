@@ -62,11 +62,11 @@ __device__ __forceinline__ bool agg_probe(const Slot* __restrict__ slots, uint64
   for (uint64_t p = 0; p < nslots; ++p) {
     const uint4* q = reinterpret_cast<const uint4*>(slots + ps.slot());
     const uint4 lo = q[0];
-    const uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    const uint64_t sid = u64_of(lo.x, lo.y);
     if (sid == EMPTY_ID) return false;
     if (sid == id && lo.z == field) {
       const uint4 hi = q[1];
-      x = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+      x = i64_of(hi.z, hi.w);
       return true;
     }
     ps.next();

@@ -91,10 +91,10 @@ __device__ __forceinline__ void load_delta(const MergeArgs& A, uint32_t j, uint6
   if (AOS) {
     const uint4* p = reinterpret_cast<const uint4*>(A.recs + j);
     uint4 lo = p[0], hi = p[1];
-    id = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    id = u64_of(lo.x, lo.y);
     field = lo.z;
-    ts = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
-    val = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+    ts = i64_of(hi.x, hi.y);
+    val = i64_of(hi.z, hi.w);
   } else {
     id = A.id[j]; field = A.field[j]; ts = A.ts[j]; val = A.val[j];
   }
@@ -103,16 +103,15 @@ template <bool AOS>
 __device__ __forceinline__ void load_delta_tv(const MergeArgs& A, uint32_t j, int64_t& ts, int64_t& val) {
   if (AOS) {
     uint4 hi = reinterpret_cast<const uint4*>(A.recs + j)[1];
-    ts = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
-    val = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+    ts = i64_of(hi.x, hi.y);
+    val = i64_of(hi.z, hi.w);
   } else {
     ts = A.ts[j]; val = A.val[j];
   }
 }
 
 __device__ __forceinline__ void store_tv(Slot* sl, int64_t ts, int64_t val) {
-  uint4 v = make_uint4((uint32_t)(uint64_t)ts, (uint32_t)((uint64_t)ts >> 32), (uint32_t)(uint64_t)val, (uint32_t)((uint64_t)val >> 32));
-  reinterpret_cast<uint4*>(sl)[1] = v;  // one aligned global_store_dwordx4: (ts,val) never tears
+  reinterpret_cast<uint4*>(sl)[1] = uint4_of((uint64_t)ts, (uint64_t)val);  // one aligned global_store_dwordx4: (ts,val) never tears
 }
 
 // Locate (or create) the slot of key (id, field). Returns false if the table is full / protocol fault.
@@ -140,7 +139,7 @@ __device__ __forceinline__ bool probe_or_insert(const MergeArgs& A, uint32_t tag
       Slot* sl = A.slots + s;
       const uint4* q = reinterpret_cast<const uint4*>(sl);
       uint4 lo = q[0], hi = q[1];
-      uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+      uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);   // (the packings of this function are spelled out on purpose: u64_of / i64_of change k_probe_apply*'s code)
       uint32_t sf = lo.z;
       bool fresh = false;
       if (sid == EMPTY_ID) {
@@ -338,8 +337,8 @@ __device__ __forceinline__ void resolve_one(const MergeArgs& A, const uint32_t j
   int64_t t, v; load_delta_tv<AOS>(A, j, t, v);
   Slot* sl = A.slots + A.slot_of[j];
   const uint4 hi = reinterpret_cast<const uint4*>(sl)[1];
-  const int64_t tsw = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
-  const int64_t cval = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+  const int64_t tsw = i64_of(hi.x, hi.y);
+  const int64_t cval = i64_of(hi.z, hi.w);
   const bool is_new = tsw == TS_NEW || ts_mark(tsw) == A.epoch;  // row created in this batch: no pre-batch state
   const uint32_t base_owner = (wf & W_WINNER) ? j : ~0u;   // the first claimer stored iff it beat the pre-batch row
   int64_t bt, bv;
@@ -486,8 +485,8 @@ __global__ __launch_bounds__(256) void k_resolve_strict(MergeArgs A) {
   const uint32_t head = lo.w & IDX_MASK;
   if (APPLY && head != j) return;
   int64_t aj, vj; load_delta_tv<AOS>(A, j, aj, vj);
-  const int64_t tsw = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
-  const int64_t rval = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+  const int64_t tsw = i64_of(hi.x, hi.y);
+  const int64_t rval = i64_of(hi.z, hi.w);
   const bool is_new = tsw == TS_NEW;            // unwritten = absent before the batch (strict mode writes rows only in the APPLY launch)
   // one walk over the whole list, from the last claimer to the first
   uint32_t j0 = ~0u; int64_t t_j0 = 0, v_j0 = 0;   // smallest index of the list and its delta
@@ -552,12 +551,12 @@ __global__ __launch_bounds__(256) void k_selfcheck_tear(uint4* slots, uint32_t n
     if (writer) {
       const uint64_t a = x, b = ~x ^ TEAR_K;
       if (SPLIT) { reinterpret_cast<volatile uint64_t*>(p)[0] = a; reinterpret_cast<volatile uint64_t*>(p)[1] = b; }
-      else *p = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+      else *p = uint4_of(a, b);
     } else {
       u32x4 v;
       if (blockIdx.x & 2u) v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
       else { v = *reinterpret_cast<const u32x4*>(p); asm volatile("" ::: "memory"); }     // the probe's own form: one plain global_load_dwordx4
-      const uint64_t a = (uint64_t)v.x | ((uint64_t)v.y << 32), b = (uint64_t)v.z | ((uint64_t)v.w << 32);
+      const uint64_t a = u64_of(v.x, v.y), b = u64_of(v.z, v.w);
       if (!(a == 0 && b == 0) && b != (~a ^ TEAR_K)) bad++;
       n++;
     }
@@ -605,10 +604,10 @@ __global__ __launch_bounds__(256) void k_rehash(const Slot* old_slots, uint64_t 
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < old_n; i += (uint64_t)gridDim.x * 256u) {
     const uint4* q = reinterpret_cast<const uint4*>(old_slots + i);
     uint4 lo = q[0];
-    uint64_t id = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    uint64_t id = u64_of(lo.x, lo.y);
     if (id == EMPTY_ID) continue;
     uint4 hi = q[1];
-    int64_t t = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
+    int64_t t = i64_of(hi.x, hi.y);
     if (t != TS_NEW) t = ts_value(t);          // creation marks do not survive a rehash
     ProbeSeq<4> ps(id, lo.z, nslots);
     bool done = false;
@@ -617,7 +616,7 @@ __global__ __launch_bounds__(256) void k_rehash(const Slot* old_slots, uint64_t 
       unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&sl->id), (unsigned long long)EMPTY_ID, (unsigned long long)id);
       if (old == EMPTY_ID) {
         sl->field = lo.z; sl->head = 0;
-        reinterpret_cast<uint4*>(sl)[1] = make_uint4((uint32_t)(uint64_t)t, (uint32_t)((uint64_t)t >> 32), hi.z, hi.w);
+        reinterpret_cast<uint4*>(sl)[1] = make_uint4(lo32((uint64_t)t), hi32((uint64_t)t), hi.z, hi.w);
         done = true;
       } else {
         ps.next();
@@ -638,12 +637,12 @@ __global__ __launch_bounds__(256) void k_get_rows(const Slot* slots, uint64_t ns
   for (uint64_t p = 0; p < nslots; ++p) {
     const uint4* q = reinterpret_cast<const uint4*>(slots + ps.slot());
     uint4 lo = q[0];
-    uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    uint64_t sid = u64_of(lo.x, lo.y);
     if (sid == EMPTY_ID) break;
     if (sid == kid && lo.z == kf) {
       uint4 hi = q[1];
-      t = (int64_t)((uint64_t)hi.x | ((uint64_t)hi.y << 32));
-      v = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+      t = i64_of(hi.x, hi.y);
+      v = i64_of(hi.z, hi.w);
       f = t != TS_NEW;
       t = ts_value(t);
       break;
@@ -848,8 +847,8 @@ __global__ __launch_bounds__(256) void k_part_scatter(const uint64_t* id, const 
     for (int i = 0; i < 4; i++) {
       if (g[i] != 0xFFu) {
         const uint32_t p = F[g[i] * 16 + (uint32_t)i * 4u + w] + rk[i];
-        stage[2 * p] = make_uint4((uint32_t)kid[i], (uint32_t)(kid[i] >> 32), rf[i], po.aux_base + t0 + (uint32_t)i * 256u + threadIdx.x);
-        stage[2 * p + 1] = make_uint4((uint32_t)rt[i], (uint32_t)(rt[i] >> 32), (uint32_t)rv[i], (uint32_t)(rv[i] >> 32));
+        stage[2 * p] = make_uint4(lo32(kid[i]), hi32(kid[i]), rf[i], po.aux_base + t0 + (uint32_t)i * 256u + threadIdx.x);
+        stage[2 * p + 1] = uint4_of((uint64_t)rt[i], (uint64_t)rv[i]);
       }
     }
     __syncthreads();

@@ -46,7 +46,7 @@ struct PredSlotAny {  // every occupied slot that holds data (tombstones are not
       if (s < n) {
         const uint4* q = reinterpret_cast<const uint4*>(slots + s);
         uint4 lo = q[0], hi = q[1];
-        const int64_t v = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+        const int64_t v = i64_of(hi.z, hi.w);
         if (!(lo.x == 0xFFFFFFFFu && lo.y == 0xFFFFFFFFu) && v != VAL_DELETED) m |= 1u << e;
       }
     }
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void k_ix_update(const uint2* __restrict__ chg
       const uint32_t p = slot_pos[s];
       if (p != POS_NONE) {
         const uint4 hi = reinterpret_cast<const uint4*>(slots + s)[1];
-        const int64_t v = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+        const int64_t v = i64_of(hi.z, hi.w);
         if (track == 2u) {
           old = (int64_t)atomicExch(reinterpret_cast<unsigned long long*>(v64 + p), (unsigned long long)v);
           if (old != v) { hole = p; wide[1] = 1u; }
@@ -219,11 +219,11 @@ struct PredFilter {
       for (uint64_t p = 0; p < nslots; ++p) {
         const uint4* q = reinterpret_cast<const uint4*>(slots + ps.slot());
         uint4 lo = q[0];
-        uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+        uint64_t sid = u64_of(lo.x, lo.y);
         if (sid == EMPTY_ID) break;
         if (sid == id && lo.z == t[k].field) {
           uint4 hi = q[1];
-          int64_t x = (int64_t)((uint64_t)hi.z | ((uint64_t)hi.w << 32));
+          int64_t x = i64_of(hi.z, hi.w);
           ok = x >= t[k].lo && x <= t[k].hi;
           break;
         }
@@ -338,26 +338,10 @@ __global__ __launch_bounds__(256) void k_gather_ids(const uint64_t* __restrict__
     reinterpret_cast<T*>(keys)[i] = k == 0 ? TOMB : (T)((U)(k - 1) + (U)lo);
   }
 }
-// One wave per bound, 64-ary search: every round 63 lanes probe evenly spaced keys of [L, R) and the ballot says between which two the bound lies
-// (a 100M-row column: five dependent rounds instead of the 27 of a binary search). UPPER = false: first index with v >= key; true: first with v > key.
+// One wave per bound (wave_bound, slot.h) on a sorted column. UPPER = false: first index with v >= key; true: first with v > key.
 template <class T, bool UPPER>
 __device__ __forceinline__ uint64_t ordered_bound(const T* __restrict__ v, uint64_t n, T key) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint64_t L = 0, R = n;                         // invariant: every index < L is in front of the bound, every index >= R behind it
-  while (R - L > 64) {
-    const uint64_t step = (R - L + 63) / 64;
-    const uint64_t c = L + (uint64_t)lane * step;        // lane 0 probes nothing (c == L)
-    bool before = false;
-    if (lane > 0 && c < R) { const T x = v[c]; before = UPPER ? x <= key : x < key; }
-    const uint32_t t = (uint32_t)__popcll(__ballot(before));        // sorted column: lanes 1..t are in front of the bound
-    const uint64_t nl = t ? L + (uint64_t)t * step + 1 : L;
-    const uint64_t cr = L + (uint64_t)(t + 1) * step;
-    R = (t < 63 && cr < R) ? cr : R;
-    L = nl;
-  }
-  bool before = false;
-  if (L + lane < R) { const T x = v[L + lane]; before = UPPER ? x <= key : x < key; }
-  return L + (uint64_t)__popcll(__ballot(before));
+  return wave_bound(0, n, [&](uint64_t i) { const T x = v[i]; return UPPER ? x <= key : x < key; });
 }
 // ab[0] = first match, ab[1] = one past the last; *n_out = matches (optional). An empty range (lo > hi) matches nothing.
 template <class T>

@@ -17,7 +17,6 @@ __device__ __forceinline__ uint4 load_half(const uint4* p) {
   if (NT) { const sync_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const sync_u32x4*>(p)); return make_uint4(v.x, v.y, v.z, v.w); }
   return *p;
 }
-__host__ __device__ inline int64_t i64_of(uint32_t lo, uint32_t hi) { return (int64_t)((uint64_t)lo | ((uint64_t)hi << 32)); }
 
 // The project's row digest (oracle/bmx_oracle.c orc_row_digest, oracle/oracle.py rows_digest, oracle/gen_golden.js rowDigest), restated: four chained
 // splitmix64 over val, ts, field, id. A state digest is the sum mod 2^64 of it over the rows, so it does not depend on their order.
@@ -57,7 +56,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 template <bool LDS_ACC>
 __device__ __forceinline__ void digest_row(const uint4 a, const uint4 b, uint32_t L, unsigned long long* s_sum, uint32_t* s_cnt,
                                            unsigned long long* __restrict__ sums, unsigned long long* __restrict__ counts) {
-  const uint64_t id = (uint64_t)a.x | ((uint64_t)a.y << 32);
+  const uint64_t id = u64_of(a.x, a.y);
   const uint32_t field = a.z;
   const uint64_t d = row_digest(id, field, ts_value(i64_of(b.x, b.y)), i64_of(b.z, b.w));   // the epoch mark of a row created by the running epoch is no part of its clock
   const uint32_t bk = key_bucket(id, field, L);
@@ -134,7 +133,7 @@ struct PredSlotSync {  // occupied slots of one kind (data rows, or tombstones) 
         const bool occ = !(lo.x == 0xFFFFFFFFu && lo.y == 0xFFFFFFFFu);
         if (occ && (i64_of(hi.z, hi.w) == VAL_DELETED) == tombs && ts_value(i64_of(hi.x, hi.y)) >= since) {
           bool want = true;
-          if (bits) { const uint32_t bk = key_bucket((uint64_t)lo.x | ((uint64_t)lo.y << 32), lo.z, L); want = (bits[bk >> 6] >> (bk & 63u)) & 1ull; }
+          if (bits) { const uint32_t bk = key_bucket(u64_of(lo.x, lo.y), lo.z, L); want = (bits[bk >> 6] >> (bk & 63u)) & 1ull; }
           if (want) m |= 1u << e;
         }
       }

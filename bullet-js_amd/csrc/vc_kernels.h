@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_vc_rehash(const VSlot* old_slots, uint6
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < old_n; i += (uint64_t)gridDim.x * 256u) {
     const uint4* q = reinterpret_cast<const uint4*>(old_slots + i);
     const uint4 lo = q[0];
-    const uint64_t id = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    const uint64_t id = u64_of(lo.x, lo.y);
     if (id == EMPTY_ID) continue;
     ProbeSeq<2> ps(id, lo.z, nslots);
     bool placed = false;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_vc_link(VcArgs A) {
           s = ps.slot();
           VSlot* sl = A.slots + s;
           uint4 lo = reinterpret_cast<const uint4*>(sl)[0];
-          uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+          uint64_t sid = u64_of(lo.x, lo.y);
           uint32_t sf = lo.z;
           if (sid == EMPTY_ID) {
             unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&sl->id), (unsigned long long)EMPTY_ID, (unsigned long long)id);
@@ -249,7 +249,7 @@ __device__ __forceinline__ uint32_t vc_resolve_row(const VcArgs& A, VSlot* sl, u
   VcState R;
   {
     const uint4 mid = q[1], c0 = q[2], c1 = q[3];
-    R.val = (int64_t)((uint64_t)mid.x | ((uint64_t)mid.y << 32)); R.state = mid.z; R.ks = mid.w;
+    R.val = i64_of(mid.x, mid.y); R.state = mid.z; R.ks = mid.w;
     R.c[0] = c0.x; R.c[1] = c0.y; R.c[2] = c0.z; R.c[3] = c0.w; R.c[4] = c1.x; R.c[5] = c1.y; R.c[6] = c1.z; R.c[7] = c1.w;
   }
   const uint32_t dense_ks = vc_ks_dense(A.K);
@@ -298,7 +298,7 @@ __device__ __forceinline__ uint32_t vc_resolve_row(const VcArgs& A, VSlot* sl, u
   }
   // one writer per row, after all reads of this launch pair
   uint4* w = reinterpret_cast<uint4*>(sl);
-  w[1] = make_uint4((uint32_t)(uint64_t)R.val, (uint32_t)((uint64_t)R.val >> 32), R.state, R.ks);
+  w[1] = make_uint4(lo32((uint64_t)R.val), hi32((uint64_t)R.val), R.state, R.ks);
   w[2] = make_uint4(R.c[0], R.c[1], R.c[2], R.c[3]);
   w[3] = make_uint4(R.c[4], R.c[5], R.c[6], R.c[7]);
   return last_upd;
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void k_vc_resolve_long(VcArgs A) {
     if (threadIdx.x == 0) {
       const uint4* q = reinterpret_cast<const uint4*>(sl);
       const uint4 mid = q[1], c0 = q[2], c1 = q[3];
-      R.val = (int64_t)((uint64_t)mid.x | ((uint64_t)mid.y << 32)); R.state = mid.z; R.ks = mid.w;
+      R.val = i64_of(mid.x, mid.y); R.state = mid.z; R.ks = mid.w;
       R.c[0] = c0.x; R.c[1] = c0.y; R.c[2] = c0.z; R.c[3] = c0.w; R.c[4] = c1.x; R.c[5] = c1.y; R.c[6] = c1.z; R.c[7] = c1.w;
     }
     for (uint32_t c0 = 0; c0 < tot; c0 += 256) {
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void k_vc_resolve_long(VcArgs A) {
     }
     if (threadIdx.x == 0) {
       uint4* w = reinterpret_cast<uint4*>(sl);
-      w[1] = make_uint4((uint32_t)(uint64_t)R.val, (uint32_t)((uint64_t)R.val >> 32), R.state, R.ks);
+      w[1] = make_uint4(lo32((uint64_t)R.val), hi32((uint64_t)R.val), R.state, R.ks);
       w[2] = make_uint4(R.c[0], R.c[1], R.c[2], R.c[3]);
       w[3] = make_uint4(R.c[4], R.c[5], R.c[6], R.c[7]);
       if (last_upd != ~0u) { A.wflag[last_upd] = W_WINNER; atomicAdd(&A.blk_info[last_upd >> 8], 1u); }
@@ -416,11 +416,11 @@ __global__ __launch_bounds__(256) void k_vc_get(const VSlot* slots, uint64_t nsl
   for (uint64_t p = 0; p < nslots; ++p) {
     const uint4* q = reinterpret_cast<const uint4*>(slots + ps.slot());
     uint4 lo = q[0];
-    uint64_t sid = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+    uint64_t sid = u64_of(lo.x, lo.y);
     if (sid == EMPTY_ID) break;
     if (sid == kid && lo.z == kf) {
       uint4 mid = q[1], c0 = q[2], c1 = q[3];
-      v = (int64_t)((uint64_t)mid.x | ((uint64_t)mid.y << 32)); st = (uint8_t)mid.z; ks = mid.w;
+      v = i64_of(mid.x, mid.y); st = (uint8_t)mid.z; ks = mid.w;
       c[0] = c0.x; c[1] = c0.y; c[2] = c0.z; c[3] = c0.w; c[4] = c1.x; c[5] = c1.y; c[6] = c1.z; c[7] = c1.w;
       break;
     }
@@ -447,7 +447,7 @@ struct PredVSlotRange {
         const uint4 a = q[0];
         if (!(a.x == 0xFFFFFFFFu && a.y == 0xFFFFFFFFu) && a.z == field) {
           const uint4 b = q[1];
-          const int64_t v = (int64_t)((uint64_t)b.x | ((uint64_t)b.y << 32));
+          const int64_t v = i64_of(b.x, b.y);
           if (b.z != VC_ABSENT && v >= lo && v <= hi) m |= 1u << e;
         }
       }

@@ -44,42 +44,6 @@ __device__ __forceinline__ uint32_t u32_lower_bound(const uint32_t* __restrict__
   while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
   return lo;
 }
-// The same bounds found by a whole WAVE (every lane calls it with the same arguments and gets the answer): 64-ary search like ordered_bound — every round
-// 63 lanes probe evenly spaced keys of [L, R) and a ballot says between which two the bound lies. A binary search over a run of a million keys is a chain of
-// 20 dependent loads (10-15 us of latency that every workgroup of a merge pass paid before its first key moved); this is four rounds.
-template <class T, bool UPPER = false>
-__device__ __forceinline__ uint64_t vk_bound_wave(const T* __restrict__ v, const uint32_t* __restrict__ p, uint64_t L, uint64_t R, T kv, uint32_t kp) {
-  const uint32_t lane = threadIdx.x & 63u;
-  while (R - L > 64) {
-    const uint64_t step = (R - L + 63) / 64;
-    const uint64_t c = L + (uint64_t)lane * step;        // lane 0 probes nothing (c == L)
-    bool before = false;
-    if (lane > 0 && c < R) { const T x = v[c]; const uint32_t xp = p[c]; before = UPPER ? !vk_less<T>(kv, kp, x, xp) : vk_less<T>(x, xp, kv, kp); }
-    const uint32_t t = (uint32_t)__popcll(__ballot(before));        // sorted keys: lanes 1..t are in front of the bound
-    const uint64_t nl = t ? L + (uint64_t)t * step + 1 : L;
-    const uint64_t cr = L + (uint64_t)(t + 1) * step;
-    R = (t < 63 && cr < R) ? cr : R;
-    L = nl;
-  }
-  bool before = false;
-  if (L + lane < R) { const T x = v[L + lane]; const uint32_t xp = p[L + lane]; before = UPPER ? !vk_less<T>(kv, kp, x, xp) : vk_less<T>(x, xp, kv, kp); }
-  return L + (uint64_t)__popcll(__ballot(before));
-}
-__device__ __forceinline__ uint32_t u32_lower_bound_wave(const uint32_t* __restrict__ a, uint32_t L, uint32_t R, uint32_t key) {
-  const uint32_t lane = threadIdx.x & 63u;
-  while (R - L > 64) {
-    const uint32_t step = (R - L + 63) / 64;
-    const uint32_t c = L + lane * step;
-    const bool before = lane > 0 && c < R && a[c] < key;
-    const uint32_t t = (uint32_t)__popcll(__ballot(before));
-    const uint32_t nl = t ? L + t * step + 1 : L;
-    const uint32_t cr = L + (t + 1) * step;
-    R = (t < 63 && cr < R) ? cr : R;
-    L = nl;
-  }
-  const bool before = L + lane < R && a[L + lane] < key;
-  return L + (uint32_t)__popcll(__ballot(before));
-}
 
 // Up to two independent key arrays sorted by the same launches (the deleted keys and the inserted keys of one patch): segment s occupies
 // [base[s], base[s] + len[s]) of the key arrays and blocks [blk0[s], blk0[s + 1]) of the grid.
@@ -319,7 +283,7 @@ __device__ __forceinline__ void st_vec(P* dst, const V& v) { __builtin_memcpy(ds
 __device__ __forceinline__ int32_t rdlane(int32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, (int)l); }
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ int64_t rdlane(int64_t v, uint32_t l) {
-  return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), (int)l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, (int)l));
+  return i64_of(rdlane(lo32((uint64_t)v), l), rdlane(hi32((uint64_t)v), l));
 }
 
 // The streaming merge: Z = (X without the sorted keys D, which are keys of X) merged with the sorted keys Y; ids travel with the keys of X and are gathered from
