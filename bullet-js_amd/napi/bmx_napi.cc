@@ -2,19 +2,27 @@
 // arrays to pointers, calls libbmx.so and throws a JS Error carrying bmx_last_error() on failure
 // (reference error policy: the hot path reports, never aborts — src/bullet.js:230-234).
 // Built by bullet-js_amd/Makefile into bullet-js_amd/bmx.node and loaded by js/native.js.
+//
+// A new binding is put together from these, each of which exists once:
+//   HANDLE(Kind, N)            arguments + the live handle of that kind (Engine, Vc, Comm), or the kind's "invalid or closed" error
+//   get_u32 / get_count / get_i64 / get_ta / get_keys / get_cols / get_terms / is_nullish      argument parsing; all of it BEFORE the turn is taken
+//   Turn turn(h->q)            the call runs in issue order with everything else on the handle (bmx_ticket.h)
+//   fail<Kind>(env, h->p, rc)  the "bmx error <rc>: <text>" Error with .code
+//   make_ta / copy_ta / num / cols_result / merge_result / scan_result      results; a null from them means a JS error is pending: return it
+//   Job<Kind> + queue_job      work on a libuv worker behind a promise
+// A call that exists for the engine and for the communicator is ONE template over the kind; Init names both instances.
 #include <node_api.h>
 #include <cmath>
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <condition_variable>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "bmx.h"
 #include "bmx_top.h"
+#include "bmx_ticket.h"
 
 namespace {
 
@@ -26,66 +34,125 @@ namespace {
     }                                                           \
   } while (0)
 
-napi_value throw_bmx(napi_env env, bmx_ctx* ctx, int rc) {
-  std::string msg = "bmx error " + std::to_string(rc) + ": " + bmx_last_error(ctx);
+// ---- handle kinds: what differs between the engine, the vector-clock table and the communicator ------------------------------------
+// host(fn, args...) calls an entry point on host buffers: the engine's take a trailing `mem`, the communicator's are host-only.
+struct Engine {
+  using T = bmx_ctx;
+  static constexpr uint32_t tag = 0x626d7801u;
+  static constexpr const char* closed = "bmx: invalid or closed engine handle";
+  static constexpr const char* gone = "engine closed";
+  static constexpr auto destroy = bmx_destroy;
+  static constexpr auto last_error = bmx_last_error;
+  static constexpr auto load_rows = bmx_load_rows;
+  static constexpr auto put_rows = bmx_put_rows;
+  static constexpr auto get_rows = bmx_get_rows;
+  static constexpr auto row_count = bmx_row_count;
+  static constexpr auto dump_rows = bmx_dump_rows;
+  static constexpr auto index_build = bmx_index_build;
+  static constexpr auto index_set_ordered = bmx_index_set_ordered;
+  static constexpr auto scan_range = bmx_scan_range;
+  static constexpr auto scan_count = bmx_scan_count;
+  static constexpr auto digest = bmx_digest;
+  static constexpr auto export_rows = bmx_export_rows;
+  static constexpr auto scan_aggregate = bmx_scan_aggregate;
+  static constexpr auto scan_top = bmx_scan_top;
+  template <class F, class... A> static int host(F fn, A... a) { return fn(a..., BMX_MEM_HOST); }
+};
+struct Comm {
+  using T = bmx_comm;
+  static constexpr uint32_t tag = 0x626d7802u;
+  static constexpr const char* closed = "bmx: invalid or closed communicator handle";
+  static constexpr auto destroy = bmx_comm_destroy;
+  static constexpr auto last_error = bmx_comm_last_error;
+  static constexpr auto load_rows = bmx_comm_load_rows;
+  static constexpr auto put_rows = bmx_comm_put_rows;
+  static constexpr auto get_rows = bmx_comm_get_rows;
+  static constexpr auto row_count = bmx_comm_row_count;
+  static constexpr auto dump_rows = bmx_comm_dump_rows;
+  static constexpr auto index_build = bmx_comm_index_build;
+  static constexpr auto index_set_ordered = bmx_comm_index_set_ordered;
+  static constexpr auto scan_range = bmx_comm_scan_range;
+  static constexpr auto scan_count = bmx_comm_scan_count;
+  static constexpr auto digest = bmx_comm_digest;
+  static constexpr auto export_rows = bmx_comm_export_rows;
+  static constexpr auto scan_aggregate = bmx_comm_scan_aggregate;
+  static constexpr auto scan_top = bmx_comm_scan_top;
+  template <class F, class... A> static int host(F fn, A... a) { return fn(a...); }
+};
+struct Vc {
+  using T = bmx_vc;
+  static constexpr uint32_t tag = 0x626d7803u;
+  static constexpr const char* closed = "bmx: invalid or closed vector-clock table handle";
+  static constexpr const char* gone = "table closed";
+  static constexpr auto destroy = bmx_vc_destroy;
+  static constexpr auto last_error = bmx_vc_last_error;
+};
+
+// What a JS external of this addon points to. The tag comes first and is checked before anything else is read: an external of another kind is
+// refused, never cast (Node 12 has no napi_type_tag_object). p == nullptr: closed. K: the vector-clock table's writers, 0 otherwise.
+template <class Kind> struct Handle {
+  const uint32_t tag = Kind::tag;
+  typename Kind::T* p = nullptr;
+  uint32_t K = 0;
+  Tickets q;
+};
+
+template <class Kind> Handle<Kind>* peek_handle(napi_env env, napi_value v) {   // open or closed; null for anything else
+  void* p = nullptr;
+  if (napi_get_value_external(env, v, &p) != napi_ok || !p || *static_cast<const uint32_t*>(p) != Kind::tag) return nullptr;
+  return static_cast<Handle<Kind>*>(p);
+}
+template <class Kind> Handle<Kind>* get_handle(napi_env env, napi_value v) {
+  Handle<Kind>* h = peek_handle<Kind>(env, v);
+  if (h && h->p) return h;
+  napi_throw_error(env, nullptr, Kind::closed);
+  return nullptr;
+}
+template <class Kind> void finalize(napi_env, void* data, void*) {
+  Handle<Kind>* h = static_cast<Handle<Kind>*>(data);
+  if (h->p) Kind::destroy(h->p);
+  delete h;
+}
+template <class Kind> napi_value wrap(napi_env env, typename Kind::T* p, uint32_t K = 0) {
+  Handle<Kind>* h = new Handle<Kind>();
+  h->p = p; h->K = K;
+  napi_value ext;
+  if (napi_create_external(env, h, finalize<Kind>, nullptr, &ext) != napi_ok) { finalize<Kind>(env, h, nullptr); napi_throw_error(env, nullptr, "bmx: external refused"); return nullptr; }
+  return ext;
+}
+
+// ---- errors ---------------------------------------------------------------------------------------------------------------------------
+napi_value bmx_error(napi_env env, int rc, const char* text) {
+  std::string msg = "bmx error " + std::to_string(rc) + ": " + text;
   napi_value code, err, m;
   napi_create_string_utf8(env, msg.c_str(), NAPI_AUTO_LENGTH, &m);
   napi_create_error(env, nullptr, m, &err);
   napi_create_int32(env, rc, &code);
   napi_set_named_property(env, err, "code", code);
-  napi_throw(env, err);
-  return nullptr;
+  return err;
 }
+napi_value throw_bmx(napi_env env, int rc, const char* text) { napi_throw(env, bmx_error(env, rc, text)); return nullptr; }
+template <class Kind> napi_value fail(napi_env env, const typename Kind::T* p, int rc) { return throw_bmx(env, rc, Kind::last_error(p)); }
 
-// A context is not re-entrant and the ORDER of merges matters (which delta creates a row decides its stored clock), so every
-// operation on a handle takes a ticket when it is issued on the JS thread and runs when its turn comes: asynchronous merges
-// (libuv workers) and synchronous calls execute in exactly the order JS issued them.
-struct Handle {
-  bmx_ctx* ctx = nullptr;
-  std::mutex mu; std::condition_variable cv;
-  uint64_t next_ticket = 0, serving = 0;
-  uint64_t take() { std::lock_guard<std::mutex> g(mu); return next_ticket++; }
-};
-struct Turn {   // RAII: wait for the ticket's turn, release it on scope exit
-  Handle* h; std::unique_lock<std::mutex> lk;
-  Turn(Handle* hh, uint64_t ticket) : h(hh), lk(hh->mu) { h->cv.wait(lk, [&] { return h->serving == ticket; }); }
-  explicit Turn(Handle* hh) : h(hh), lk(hh->mu) { const uint64_t t = h->next_ticket++; h->cv.wait(lk, [&] { return h->serving == t; }); }
-  ~Turn() { h->serving++; lk.unlock(); h->cv.notify_all(); }
-};
+// ---- arguments ------------------------------------------------------------------------------------------------------------------------
+#define ARGS_OPT(MIN, MAX)                                   \
+  size_t argc = MAX; napi_value argv[MAX];                   \
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr)); \
+  if (argc < MIN) { napi_throw_type_error(env, nullptr, "bmx: missing arguments"); return nullptr; }
+#define ARGS(N) ARGS_OPT(N, N)
+#define HANDLE(Kind, N) ARGS(N); Handle<Kind>* h = get_handle<Kind>(env, argv[0]); if (!h) return nullptr;
 
-void finalize_handle(napi_env, void* data, void*) {
-  Handle* h = static_cast<Handle*>(data);
-  if (h->ctx) bmx_destroy(h->ctx);
-  delete h;
+bool is_nullish(napi_env env, napi_value v) { napi_valuetype t; napi_typeof(env, v, &t); return t == napi_undefined || t == napi_null; }
+bool get_u32(napi_env env, napi_value v, uint32_t* out) {
+  if (napi_get_value_uint32(env, v, out) == napi_ok) return true;
+  napi_throw_error(env, nullptr, "N-API call failed: napi_get_value_uint32");
+  return false;
 }
-
-bool get_handle(napi_env env, napi_value v, Handle** out) {
-  void* p = nullptr;
-  if (napi_get_value_external(env, v, &p) != napi_ok || !p || !static_cast<Handle*>(p)->ctx) {
-    napi_throw_error(env, nullptr, "bmx: invalid or closed engine handle");
-    return false;
-  }
-  *out = static_cast<Handle*>(p);
-  return true;
+bool get_count(napi_env env, napi_value v, double* out) {   // a row count or position: a double on the way in, checked or cast by the caller
+  if (napi_get_value_double(env, v, out) == napi_ok) return true;
+  napi_throw_error(env, nullptr, "N-API call failed: napi_get_value_double");
+  return false;
 }
-
-// typed array -> (pointer, element count); checks the element type
-bool get_ta(napi_env env, napi_value v, napi_typedarray_type want, void** data, size_t* len) {
-  napi_typedarray_type t; napi_value ab; size_t off;
-  if (napi_get_typedarray_info(env, v, &t, len, data, &ab, &off) != napi_ok || t != want) {
-    napi_throw_type_error(env, nullptr, "bmx: wrong typed-array type (id BigUint64Array, field Uint32Array, ts/val BigInt64Array)");
-    return false;
-  }
-  return true;
-}
-
-napi_value make_ta(napi_env env, napi_typedarray_type t, size_t elem, size_t n, void** data) {
-  napi_value ab, ta;
-  if (napi_create_arraybuffer(env, n * elem, data, &ab) != napi_ok) return nullptr;
-  if (napi_create_typedarray(env, t, n, ab, 0, &ta) != napi_ok) return nullptr;
-  return ta;
-}
-
 // number | bigint -> int64 (saturating; +-Infinity allowed, as range() accepts them: src/bullet-query.js:248-253)
 bool get_i64(napi_env env, napi_value v, int64_t* out) {
   napi_valuetype t;
@@ -99,170 +166,159 @@ bool get_i64(napi_env env, napi_value v, int64_t* out) {
   if (d >= 9.2e18) *out = INT64_MAX; else if (d <= -9.2e18) *out = INT64_MIN; else *out = (int64_t)d;
   return true;
 }
-
-void set_num(napi_env env, napi_value obj, const char* k, double v) { napi_value n; napi_create_double(env, v, &n); napi_set_named_property(env, obj, k, n); }
-
-#define ARGS(N)                                              \
-  size_t argc = N; napi_value argv[N];                       \
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr)); \
-  if (argc < N) { napi_throw_type_error(env, nullptr, "bmx: missing arguments"); return nullptr; }
-
-// ownersOf(id: BigUint64Array, nshards) -> Uint8Array: bmx_owner_of for every id (the host-side routing of small batches and of the K-writer table)
-napi_value OwnersOf(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  void* p; size_t n;
-  if (!get_ta(env, argv[0], napi_biguint64_array, &p, &n)) return nullptr;
-  uint32_t ns; NAPI_OK(napi_get_value_uint32(env, argv[1], &ns));
-  if (ns == 0 || ns > 255) { napi_throw_range_error(env, nullptr, "bmx: 1..255 shards"); return nullptr; }
-  void* o; napi_value out = make_ta(env, napi_uint8_array, 1, n, &o);
-  const uint64_t* id = (const uint64_t*)p; uint8_t* ow = (uint8_t*)o;
-  for (size_t i = 0; i < n; i++) ow[i] = (uint8_t)bmx_owner_of(id[i], ns);
-  return out;
-}
-
-napi_value AbiVersion(napi_env env, napi_callback_info) { napi_value v; napi_create_int32(env, bmx_abi_version(), &v); return v; }
-
-napi_value Create(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  int32_t device; double cap;
-  NAPI_OK(napi_get_value_int32(env, argv[0], &device));
-  NAPI_OK(napi_get_value_double(env, argv[1], &cap));
-  bmx_ctx* ctx = nullptr;
-  int rc = bmx_create(device, (uint64_t)cap, 0, &ctx);
-  if (rc) return throw_bmx(env, nullptr, rc);
-  Handle* h = new Handle();
-  h->ctx = ctx;
-  napi_value ext;
-  NAPI_OK(napi_create_external(env, h, finalize_handle, nullptr, &ext));
-  return ext;
-}
-
-napi_value Destroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  void* p = nullptr;
-  if (napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
-    Handle* h = static_cast<Handle*>(p);
-    Turn turn(h);                                   // after every operation issued before the close
-    if (h->ctx) { bmx_destroy(h->ctx); h->ctx = nullptr; }
+// typed array -> (pointer, element count); checks the element type
+template <class E> bool get_ta(napi_env env, napi_value v, napi_typedarray_type want, const E** data, size_t* len) {
+  napi_typedarray_type t; napi_value ab; size_t off; void* p;
+  if (napi_get_typedarray_info(env, v, &t, len, &p, &ab, &off) != napi_ok || t != want) {
+    napi_throw_type_error(env, nullptr, "bmx: wrong typed-array type (id BigUint64Array, field Uint32Array, ts/val BigInt64Array)");
+    return false;
   }
-  return nullptr;
-}
-
-bool get_cols(napi_env env, napi_value* a, const uint64_t** id, const uint32_t** field, const int64_t** ts, const int64_t** val, size_t* n) {
-  void *p0, *p1, *p2, *p3; size_t n0, n1, n2, n3;
-  if (!get_ta(env, a[0], napi_biguint64_array, &p0, &n0) || !get_ta(env, a[1], napi_uint32_array, &p1, &n1) ||
-      !get_ta(env, a[2], napi_bigint64_array, &p2, &n2) || !get_ta(env, a[3], napi_bigint64_array, &p3, &n3)) return false;
-  if (n0 != n1 || n0 != n2 || n0 != n3) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return false; }
-  *id = (const uint64_t*)p0; *field = (const uint32_t*)p1; *ts = (const int64_t*)p2; *val = (const int64_t*)p3; *n = n0;
+  *data = static_cast<const E*>(p);
   return true;
 }
+struct Cols { const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n; };
+bool get_keys(napi_env env, napi_value* a, Cols* c) {   // (id, field) of one length
+  size_t n1;
+  if (!get_ta(env, a[0], napi_biguint64_array, &c->id, &c->n) || !get_ta(env, a[1], napi_uint32_array, &c->field, &n1)) return false;
+  if (c->n != n1) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return false; }
+  return true;
+}
+bool get_cols(napi_env env, napi_value* a, Cols* c) {   // (id, field, ts, val) of one length
+  size_t n1, n2, n3;
+  if (!get_ta(env, a[0], napi_biguint64_array, &c->id, &c->n) || !get_ta(env, a[1], napi_uint32_array, &c->field, &n1) ||
+      !get_ta(env, a[2], napi_bigint64_array, &c->ts, &n2) || !get_ta(env, a[3], napi_bigint64_array, &c->val, &n3)) return false;
+  if (c->n != n1 || c->n != n2 || c->n != n3) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return false; }
+  return true;
+}
+// [[field, lo, hi], ...] -> terms[8]; returns the count, 0 with a JS error pending. `what` words the message: filter, aggregate, top
+uint32_t get_terms(napi_env env, napi_value list, const char* what, bmx_term* terms) {
+  uint32_t nt = 0;
+  if (napi_get_array_length(env, list, &nt) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return 0; }
+  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, (std::string("bmx: ") + what + " needs 1..8 terms").c_str()); return 0; }
+  for (uint32_t k = 0; k < nt; k++) {
+    napi_value t, e0, e1, e2;
+    if (napi_get_element(env, list, k, &t) != napi_ok || napi_get_element(env, t, 0, &e0) != napi_ok || napi_get_element(env, t, 1, &e1) != napi_ok ||
+        napi_get_element(env, t, 2, &e2) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return 0; }
+    terms[k].reserved = 0;
+    if (!get_u32(env, e0, &terms[k].field) || !get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return 0;
+  }
+  return nt;
+}
 
-// mergeBatch(h, id, field, ts, val, mode) -> {applied: Uint32Array, flags: Uint8Array, nApplied, nConflicts, nRows}
-napi_value MergeBatch(napi_env env, napi_callback_info info) {
-  ARGS(6);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
-  int32_t mode; NAPI_OK(napi_get_value_int32(env, argv[5], &mode));
-  std::vector<uint32_t> applied(n ? n : 1);
-  void* fl = nullptr;
-  napi_value flags = make_ta(env, napi_uint8_array, 1, n, &fl);
-  uint64_t na = 0; bmx_merge_stats st; memset(&st, 0, sizeof(st));
-  Turn turn(h);
-  int rc = bmx_merge_batch(h->ctx, n, id, field, ts, val, mode, BMX_MEM_HOST, applied.data(), &na, (uint8_t*)fl, &st);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  void* ap = nullptr;
-  napi_value ta = make_ta(env, napi_uint32_array, 4, (size_t)na, &ap);
-  if (na) memcpy(ap, applied.data(), (size_t)na * 4);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "applied", ta);
-  napi_set_named_property(env, out, "flags", flags);
-  set_num(env, out, "nApplied", (double)st.n_applied); set_num(env, out, "nConflicts", (double)st.n_conflicts); set_num(env, out, "nRows", (double)st.n_rows);
+// ---- results: a null return means a JS error is pending --------------------------------------------------------------------------------
+size_t ta_elem(napi_typedarray_type t) { return t == napi_uint8_array ? 1 : t == napi_uint32_array ? 4 : 8; }   // the three widths this addon hands out
+napi_value make_ta(napi_env env, napi_typedarray_type t, size_t n, void** data) {
+  napi_value ab, ta;
+  if (napi_create_arraybuffer(env, n * ta_elem(t), data, &ab) == napi_ok && napi_create_typedarray(env, t, n, ab, 0, &ta) == napi_ok) return ta;
+  napi_throw_error(env, nullptr, "bmx: could not allocate a result array");
+  return nullptr;
+}
+napi_value copy_ta(napi_env env, napi_typedarray_type t, size_t n, const void* src) {
+  void* p; napi_value ta = make_ta(env, t, n, &p);
+  if (ta && n) memcpy(p, src, n * ta_elem(t));
+  return ta;
+}
+napi_value num(napi_env env, double v) { napi_value n; napi_create_double(env, v, &n); return n; }
+void set_num(napi_env env, napi_value obj, const char* k, double v) { napi_set_named_property(env, obj, k, num(env, v)); }
+// {k0: v0, k1: v1, ...} in this order; null if a value is
+struct Member { const char* key; napi_value v; };
+napi_value object_of(napi_env env, std::initializer_list<Member> members) {
+  napi_value out;
+  for (const Member& m : members) if (!m.v) return nullptr;
+  NAPI_OK(napi_create_object(env, &out));
+  for (const Member& m : members) napi_set_named_property(env, out, m.key, m.v);
   return out;
 }
+napi_value cols_object(napi_env env, napi_value id, napi_value field, napi_value ts, napi_value val) { return object_of(env, {{"id", id}, {"field", field}, {"ts", ts}, {"val", val}}); }
+napi_value cols_result(napi_env env, size_t m, const uint64_t* id, const uint32_t* field, const int64_t* ts, const int64_t* val) {
+  return cols_object(env, copy_ta(env, napi_biguint64_array, m, id), copy_ta(env, napi_uint32_array, m, field), copy_ta(env, napi_bigint64_array, m, ts), copy_ta(env, napi_bigint64_array, m, val));
+}
+napi_value cols_result(napi_env env, size_t m, const bmx_delta_rec* recs) {
+  void *pi = nullptr, *pf = nullptr, *pt = nullptr, *pv = nullptr;
+  napi_value out = cols_object(env, make_ta(env, napi_biguint64_array, m, &pi), make_ta(env, napi_uint32_array, m, &pf), make_ta(env, napi_bigint64_array, m, &pt), make_ta(env, napi_bigint64_array, m, &pv));
+  if (out) for (size_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((uint32_t*)pf)[i] = recs[i].field; ((int64_t*)pt)[i] = recs[i].ts; ((int64_t*)pv)[i] = recs[i].val; }
+  return out;
+}
+// {applied, [flags,] nApplied, nConflicts, nRows}; flags == nullptr: the communicator's, which collects none
+napi_value merge_result(napi_env env, const uint32_t* applied, uint64_t na, const napi_value* flags, const bmx_merge_stats& st) {
+  napi_value ta = copy_ta(env, napi_uint32_array, (size_t)na, applied);
+  napi_value out = flags ? object_of(env, {{"applied", ta}, {"flags", *flags}}) : object_of(env, {{"applied", ta}});
+  if (out) { set_num(env, out, "nApplied", (double)st.n_applied); set_num(env, out, "nConflicts", (double)st.n_conflicts); set_num(env, out, "nRows", (double)st.n_rows); }
+  return out;
+}
+// count-then-fill: count(&m) sizes the array, fill(out, m) writes it; both return a bmx status. Takes the turn.
+template <class Kind, class Count, class Fill>
+napi_value scan_result(napi_env env, Handle<Kind>* h, napi_typedarray_type t, Count count, Fill fill) {
+  Turn turn(h->q);
+  uint64_t m = 0; int rc = count(&m);
+  if (rc) return fail<Kind>(env, h->p, rc);
+  void* out; napi_value ta = make_ta(env, t, m, &out);
+  if (ta && m && (rc = fill(out, m))) return fail<Kind>(env, h->p, rc);
+  return ta;
+}
 
-// ---- asynchronous merge: the H2D copy, kernels and D2H copy run on a libuv worker thread; resolves to the same object
-// as mergeBatch. The input typed arrays are referenced until completion (they must not be mutated meanwhile).
-struct MergeJob {
+// ---- asynchronous work: the job runs on a libuv worker thread in its turn; the promise resolves to the job's result() -------------------
+template <class Kind> struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
-  napi_ref refs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the four columns and the engine handle itself: the engine outlives the job
-  Handle* h = nullptr;
+  std::vector<napi_ref> refs;            // the handle and the input arrays: they outlive the job (and must not be mutated meanwhile)
+  Handle<Kind>* h = nullptr;
   uint64_t ticket = 0;
-  const uint64_t* id = nullptr; const uint32_t* field = nullptr; const int64_t* ts = nullptr; const int64_t* val = nullptr;
-  size_t n = 0; int mode = 0;
-  std::vector<uint32_t> applied; std::vector<uint8_t> flags;
-  uint64_t na = 0; bmx_merge_stats st; int rc = 0; std::string err;
+  int rc = 0; std::string err;
+  virtual ~Job() {}
+  virtual int run() = 0;                 // worker thread, inside the turn, handle open: the bmx status
+  virtual napi_value result(napi_env env) = 0;   // JS thread, after run() returned BMX_OK
 };
-
-void merge_execute(napi_env, void* data) {
-  MergeJob* j = static_cast<MergeJob*>(data);
-  Turn turn(j->h, j->ticket);                       // merges apply in the order JS issued them, whatever worker picks them up
-  if (!j->h->ctx) { j->rc = BMX_ERR_INVALID; j->err = "engine closed"; return; }
-  j->rc = bmx_merge_batch(j->h->ctx, j->n, j->id, j->field, j->ts, j->val, j->mode, BMX_MEM_HOST, j->applied.data(), &j->na, j->flags.data(), &j->st);
-  if (j->rc) j->err = bmx_last_error(j->h->ctx);
+template <class Kind> void job_execute(napi_env, void* data) {
+  Job<Kind>* j = static_cast<Job<Kind>*>(data);
+  Turn turn(j->h->q, j->ticket);         // in the order JS issued it, whatever worker picks it up
+  if (!j->h->p) { j->rc = BMX_ERR_INVALID; j->err = Kind::gone; return; }
+  if ((j->rc = j->run())) j->err = Kind::last_error(j->h->p);
 }
-
-void merge_complete(napi_env env, napi_status, void* data) {
-  MergeJob* j = static_cast<MergeJob*>(data);
-  for (auto& r : j->refs) if (r) napi_delete_reference(env, r);
-  if (j->rc) {
-    napi_value msg, err, code;
-    std::string m = "bmx error " + std::to_string(j->rc) + ": " + j->err;
-    napi_create_string_utf8(env, m.c_str(), NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);
-    napi_create_int32(env, j->rc, &code);
-    napi_set_named_property(env, err, "code", code);
-    napi_reject_deferred(env, j->deferred, err);
-  } else {
-    void *ap = nullptr, *fl = nullptr;
-    napi_value ta = make_ta(env, napi_uint32_array, 4, (size_t)j->na, &ap);
-    if (j->na) memcpy(ap, j->applied.data(), (size_t)j->na * 4);
-    napi_value fa = make_ta(env, napi_uint8_array, 1, j->n, &fl);
-    if (j->n) memcpy(fl, j->flags.data(), j->n);
-    napi_value out;
-    napi_create_object(env, &out);
-    napi_set_named_property(env, out, "applied", ta);
-    napi_set_named_property(env, out, "flags", fa);
-    set_num(env, out, "nApplied", (double)j->st.n_applied); set_num(env, out, "nConflicts", (double)j->st.n_conflicts); set_num(env, out, "nRows", (double)j->st.n_rows);
-    napi_resolve_deferred(env, j->deferred, out);
-  }
-  napi_delete_async_work(env, j->work);
+template <class Kind> void job_drop(napi_env env, Job<Kind>* j) {
+  for (napi_ref r : j->refs) napi_delete_reference(env, r);
+  if (j->work) napi_delete_async_work(env, j->work);
   delete j;
 }
-
-// mergeBatchAsync(h, id, field, ts, val, mode) -> Promise<{applied, flags, nApplied, nConflicts, nRows}>
-napi_value MergeBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(6);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  MergeJob* j = new MergeJob();
-  j->h = h;
-  if (!get_cols(env, argv + 1, &j->id, &j->field, &j->ts, &j->val, &j->n)) { delete j; return nullptr; }
-  int32_t mode; if (napi_get_value_int32(env, argv[5], &mode) != napi_ok) { delete j; napi_throw_type_error(env, nullptr, "bmx: bad mode"); return nullptr; }
-  j->mode = mode;
-  j->applied.resize(j->n ? j->n : 1); j->flags.resize(j->n ? j->n : 1);
-  memset(&j->st, 0, sizeof(j->st));
-  napi_value promise, name;
-  auto drop = [&](const char* what) {
-    for (auto& r : j->refs) if (r) napi_delete_reference(env, r);
-    if (j->work) napi_delete_async_work(env, j->work);
-    delete j;
-    napi_throw_error(env, nullptr, what);
-    return (napi_value) nullptr;
-  };
+template <class Kind> void job_complete(napi_env env, napi_status, void* data) {
+  Job<Kind>* j = static_cast<Job<Kind>*>(data);
+  napi_value out = j->rc ? nullptr : j->result(env);
+  if (j->rc) napi_reject_deferred(env, j->deferred, bmx_error(env, j->rc, j->err.c_str()));
+  else if (out) napi_resolve_deferred(env, j->deferred, out);
+  else { napi_value thrown; napi_get_and_clear_last_exception(env, &thrown); napi_reject_deferred(env, j->deferred, thrown); }   // a result array was refused
+  job_drop(env, j);
+}
+// Owns j from here on. keep[0..nkeep): the values to reference until completion. Call it when nothing else can fail.
+template <class Kind> napi_value queue_job(napi_env env, Job<Kind>* j, const char* name, napi_value* keep, size_t nkeep) {
+  napi_value promise, nm;
+  auto drop = [&](const char* what) { job_drop(env, j); napi_throw_error(env, nullptr, what); return (napi_value) nullptr; };
   if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) return drop("bmx: could not create a promise");
-  for (int k = 0; k < 4; k++) napi_create_reference(env, argv[1 + k], 1, &j->refs[k]);
-  napi_create_reference(env, argv[0], 1, &j->refs[4]);
-  if (napi_create_string_utf8(env, "bmx.mergeBatchAsync", NAPI_AUTO_LENGTH, &name) != napi_ok ||
-      napi_create_async_work(env, nullptr, name, merge_execute, merge_complete, j, &j->work) != napi_ok) return drop("bmx: could not create the async work item");
+  for (size_t k = 0; k < nkeep; k++) { napi_ref r; if (napi_create_reference(env, keep[k], 1, &r) == napi_ok) j->refs.push_back(r); }   // (an absent optional argument takes none)
+  if (napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &nm) != napi_ok ||
+      napi_create_async_work(env, nullptr, nm, job_execute<Kind>, job_complete<Kind>, j, &j->work) != napi_ok) return drop("bmx: could not create the async work item");
   // the ticket is taken last: a ticket that never runs would block every later operation on this handle
-  j->ticket = h->take();
+  j->ticket = j->h->q.take();
   if (napi_queue_async_work(env, j->work) != napi_ok) {
-    { Turn skip(h, j->ticket); }                    // give the turn back
+    { Turn skip(j->h->q, j->ticket); }   // give the turn back
     return drop("bmx: could not queue the async work item");
   }
   return promise;
 }
+
+// ---- no handle ------------------------------------------------------------------------------------------------------------------------
+// ownersOf(id: BigUint64Array, nshards) -> Uint8Array: bmx_owner_of for every id (the host-side routing of small batches and of the K-writer table)
+napi_value OwnersOf(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  const uint64_t* id; size_t n;
+  if (!get_ta(env, argv[0], napi_biguint64_array, &id, &n)) return nullptr;
+  uint32_t ns; if (!get_u32(env, argv[1], &ns)) return nullptr;
+  if (ns == 0 || ns > 255) { napi_throw_range_error(env, nullptr, "bmx: 1..255 shards"); return nullptr; }
+  void* o; napi_value out = make_ta(env, napi_uint8_array, n, &o);
+  if (out) for (size_t i = 0; i < n; i++) ((uint8_t*)o)[i] = (uint8_t)bmx_owner_of(id[i], ns);
+  return out;
+}
+
+napi_value AbiVersion(napi_env env, napi_callback_info) { napi_value v; napi_create_int32(env, bmx_abi_version(), &v); return v; }
 
 // hostColumns(n) -> {id: BigUint64Array, field: Uint32Array, ts: BigInt64Array, val: BigInt64Array} of n rows over ONE page-locked allocation
 // (bmx_host_alloc): batches built in it upload at the link's rate, with no pinning of fresh pages by the runtime. Freed when the buffer is collected.
@@ -274,253 +330,316 @@ napi_value HostColumns(napi_env env, napi_callback_info info) {
   const size_t n = (size_t)dn;
   void* mem = nullptr;
   int rc = bmx_host_alloc(28ull * n, &mem);
-  if (rc) return throw_bmx(env, nullptr, rc);
-  napi_value ab, out, id, field, ts, val;
+  if (rc) return fail<Engine>(env, nullptr, rc);
+  napi_value ab, id, field, ts, val;
   if (napi_create_external_arraybuffer(env, mem, 28 * n, finalize_host_buffer, nullptr, &ab) != napi_ok) { (void)bmx_host_free(mem); napi_throw_error(env, nullptr, "bmx: external ArrayBuffer refused"); return nullptr; }
   NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, n, ab, 0, &id));
   NAPI_OK(napi_create_typedarray(env, napi_bigint64_array, n, ab, 8 * n, &ts));
   NAPI_OK(napi_create_typedarray(env, napi_bigint64_array, n, ab, 16 * n, &val));
   NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, ab, 24 * n, &field));
-  NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "id", id); napi_set_named_property(env, out, "field", field);
-  napi_set_named_property(env, out, "ts", ts); napi_set_named_property(env, out, "val", val);
+  return cols_object(env, id, field, ts, val);
+}
+
+// ---- every kind -----------------------------------------------------------------------------------------------------------------------
+template <class Kind> napi_value Destroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  if (Handle<Kind>* h = peek_handle<Kind>(env, argv[0])) {
+    Turn turn(h->q);                                // after every operation issued before the close
+    if (h->p) { Kind::destroy(h->p); h->p = nullptr; }
+  }
+  return nullptr;
+}
+
+// ---- the engine and the communicator: one body per call -------------------------------------------------------------------------------
+// loadRows / putRows(h, id, field, ts, val): putRows stores rows decided on the host as given; val == -2^63 (BMX_VAL_DELETED) leaves a tombstone
+template <class Kind, bool put> napi_value StoreRows(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 5);
+  Cols c; if (!get_cols(env, argv + 1, &c)) return nullptr;
+  Turn turn(h->q);
+  int rc = put ? Kind::host(Kind::put_rows, h->p, c.n, c.id, c.field, c.ts, c.val) : Kind::host(Kind::load_rows, h->p, c.n, c.id, c.field, c.ts, c.val);
+  return rc ? fail<Kind>(env, h->p, rc) : nullptr;
+}
+// getRows(h, id, field) -> {ts, val, found}
+template <class Kind> napi_value GetRows(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 3);
+  Cols c; if (!get_keys(env, argv + 1, &c)) return nullptr;
+  void *ts = nullptr, *val = nullptr, *found = nullptr;
+  napi_value out = object_of(env, {{"ts", make_ta(env, napi_bigint64_array, c.n, &ts)}, {"val", make_ta(env, napi_bigint64_array, c.n, &val)}, {"found", make_ta(env, napi_uint8_array, c.n, &found)}});
+  if (!out) return nullptr;
+  Turn turn(h->q);
+  int rc = Kind::host(Kind::get_rows, h->p, c.n, c.id, c.field, (int64_t*)ts, (int64_t*)val, (uint8_t*)found);
+  return rc ? fail<Kind>(env, h->p, rc) : out;
+}
+template <class Kind> napi_value RowCount(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 1);
+  Turn turn(h->q);
+  uint64_t n = 0; int rc = Kind::row_count(h->p, &n);
+  return rc ? fail<Kind>(env, h->p, rc) : num(env, (double)n);
+}
+template <class Kind> napi_value DumpRows(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 1);
+  Turn turn(h->q);
+  uint64_t n = 0; int rc = Kind::row_count(h->p, &n);
+  if (rc) return fail<Kind>(env, h->p, rc);
+  std::vector<uint64_t> id(n ? n : 1); std::vector<uint32_t> f(n ? n : 1); std::vector<int64_t> ts(n ? n : 1), val(n ? n : 1);
+  uint64_t m = 0;
+  rc = Kind::host(Kind::dump_rows, h->p, n, id.data(), f.data(), ts.data(), val.data(), &m);
+  if (rc) return fail<Kind>(env, h->p, rc);
+  if (m > n) m = n;                    // rows in use >= rows dumped: tombstones keep their slot and are not data
+  return cols_result(env, m, id.data(), f.data(), ts.data(), val.data());
+}
+template <class Kind> napi_value IndexBuild(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
+  int rc = Kind::index_build(h->p, f);
+  return rc ? fail<Kind>(env, h->p, rc) : nullptr;
+}
+/* indexSetOrdered(handle, field, afterQueries): value-ordered view of the index (bmx_index_set_ordered); 0 = off */
+template <class Kind> napi_value IndexSetOrdered(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 3);
+  uint32_t f, n; if (!get_u32(env, argv[1], &f) || !get_u32(env, argv[2], &n)) return nullptr;
+  Turn turn(h->q);
+  int rc = Kind::index_set_ordered(h->p, f, n);
+  return rc ? fail<Kind>(env, h->p, rc) : nullptr;
+}
+// scanRange(h, field, lo, hi) -> BigUint64Array of node ids
+template <class Kind> napi_value ScanRange(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 4);
+  uint32_t f; int64_t lo, hi; if (!get_u32(env, argv[1], &f) || !get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
+  return scan_result(env, h, napi_biguint64_array, [&](uint64_t* m) { return Kind::host(Kind::scan_count, h->p, f, lo, hi, m); },
+                     [&](void* out, uint64_t m) { uint64_t m2 = 0; return Kind::host(Kind::scan_range, h->p, f, lo, hi, (uint64_t*)out, m, &m2); });
+}
+template <class Kind> napi_value ScanCount(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 4);
+  uint32_t f; int64_t lo, hi; if (!get_u32(env, argv[1], &f) || !get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
+  Turn turn(h->q);
+  uint64_t m = 0; int rc = Kind::host(Kind::scan_count, h->p, f, lo, hi, &m);
+  return rc ? fail<Kind>(env, h->p, rc) : num(env, (double)m);
+}
+/* Replica reconciliation (bmx.h): thin bindings, no logic.
+ * digest(handle, log2Buckets, tombstones) / commDigest(comm, ...) -> {sums: BigUint64Array, counts: BigUint64Array}
+ * exportRows(handle, since, log2Buckets, bucketBits: BigUint64Array | null, onlyTombstones) / commExportRows(comm, ...) -> {id, field, ts, val, n} */
+template <class Kind> napi_value Digest(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 3);
+  uint32_t L; if (!get_u32(env, argv[1], &L)) return nullptr;
+  bool tomb = false; NAPI_OK(napi_get_value_bool(env, argv[2], &tomb));
+  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
+  void *ps = nullptr, *pc = nullptr;
+  napi_value out = object_of(env, {{"sums", make_ta(env, napi_biguint64_array, (size_t)1 << L, &ps)}, {"counts", make_ta(env, napi_biguint64_array, (size_t)1 << L, &pc)}});
+  if (!out) return nullptr;
+  Turn turn(h->q);
+  const int rc = Kind::host(Kind::digest, h->p, L, tomb ? BMX_SYNC_TOMBSTONES : 0u, (uint64_t*)ps, (uint64_t*)pc);
+  return rc ? fail<Kind>(env, h->p, rc) : out;
+}
+template <class Kind> napi_value ExportRows(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 5);
+  int64_t since; if (!get_i64(env, argv[1], &since)) return nullptr;
+  uint32_t L; if (!get_u32(env, argv[2], &L)) return nullptr;
+  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
+  const uint64_t* bits = nullptr;
+  if (!is_nullish(env, argv[3])) {
+    size_t words;
+    if (!get_ta(env, argv[3], napi_biguint64_array, &bits, &words)) return nullptr;
+    if (words < std::max<size_t>(1, ((size_t)1 << L) / 64)) { napi_throw_range_error(env, nullptr, "bmx: bucketBits needs 2^log2Buckets bits"); return nullptr; }
+  }
+  bool only_tomb = false; NAPI_OK(napi_get_value_bool(env, argv[4], &only_tomb));
+  const uint32_t fl = only_tomb ? BMX_EXPORT_ONLY_TOMBSTONES : 0u;
+  Turn turn(h->q);
+  uint64_t n = 0, m = 0;
+  int rc = Kind::host(Kind::export_rows, h->p, since, L, bits, fl, (bmx_delta_rec*)nullptr, (uint64_t)0, &n);
+  std::vector<bmx_delta_rec> recs(n ? n : 1);
+  if (!rc && n) rc = Kind::host(Kind::export_rows, h->p, since, L, bits, fl, recs.data(), n, &m);
+  if (rc) return fail<Kind>(env, h->p, rc);
+  if (m > n) m = n;
+  napi_value out = cols_result(env, m, recs.data());
+  if (out) set_num(env, out, "n", (double)m);
   return out;
+}
+/* Aggregate queries (bmx.h bmx_scan_aggregate): thin bindings, no logic.
+ * scanAggregate(handle, [[field, lo, hi], ...], measure | null, group | null, groupLo, nGroups) / commScanAggregate(comm, ...) ->
+ * {nMatch, n: BigUint64Array, min, max: BigInt64Array, sumLo: BigUint64Array, sumHi: BigInt64Array}, one entry per record (nGroups + 1, or 1 without groups) */
+template <class Kind> napi_value ScanAggregate(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 6);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "aggregate", terms); if (!nt) return nullptr;
+  uint32_t fld[2] = {BMX_AGG_NO_FIELD, BMX_AGG_NO_FIELD};
+  for (int k = 0; k < 2; k++) if (!is_nullish(env, argv[2 + k]) && !get_u32(env, argv[2 + k], &fld[k])) return nullptr;
+  int64_t glo; if (!get_i64(env, argv[4], &glo)) return nullptr;
+  uint32_t ng; if (!get_u32(env, argv[5], &ng)) return nullptr;
+  if (ng > BMX_AGG_MAX_GROUPS || (ng && fld[1] == BMX_AGG_NO_FIELD)) { napi_throw_range_error(env, nullptr, "bmx: nGroups is 0..65536 and needs a group field"); return nullptr; }
+  const size_t nrec = ng ? (size_t)ng + 1 : 1;
+  std::vector<bmx_agg> recs(nrec);
+  int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::scan_aggregate, h->p, nt, (const bmx_term*)terms, fld[0], fld[1], glo, ng, recs.data()); }
+  if (rc) return fail<Kind>(env, h->p, rc);
+  void *pm = nullptr, *pn = nullptr, *plo = nullptr, *phi = nullptr, *psl = nullptr, *psh = nullptr;
+  napi_value out = object_of(env, {{"nMatch", make_ta(env, napi_biguint64_array, nrec, &pm)}, {"n", make_ta(env, napi_biguint64_array, nrec, &pn)}, {"min", make_ta(env, napi_bigint64_array, nrec, &plo)},
+                                   {"max", make_ta(env, napi_bigint64_array, nrec, &phi)}, {"sumLo", make_ta(env, napi_biguint64_array, nrec, &psl)}, {"sumHi", make_ta(env, napi_bigint64_array, nrec, &psh)}});
+  if (out) for (size_t i = 0; i < nrec; i++) {
+    ((uint64_t*)pm)[i] = recs[i].n_match; ((uint64_t*)pn)[i] = recs[i].n; ((int64_t*)plo)[i] = recs[i].min; ((int64_t*)phi)[i] = recs[i].max;
+    ((uint64_t*)psl)[i] = recs[i].sum_lo; ((int64_t*)psh)[i] = recs[i].sum_hi;
+  }
+  return out;
+}
+/* Ordered top-k queries (bmx_top.h bmx_scan_top): thin bindings, no logic.
+ * scanTop(handle, [[field, lo, hi], ...], desc, after | null, k) / commScanTop(comm, ...) -> {ids: BigUint64Array, vals: BigInt64Array, nEligible}: the first k
+ * eligible nodes in (value, id) order; after = [id (BigInt), value] is the cursor. Ids are BigUint64Array entries, as scanFilter delivers them. */
+template <class Kind> napi_value ScanTop(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 5);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "top", terms); if (!nt) return nullptr;
+  bool desc = false; NAPI_OK(napi_get_value_bool(env, argv[2], &desc));
+  bmx_top_rec cur{0, 0}; const bool have_cur = !is_nullish(env, argv[3]);
+  if (have_cur) {
+    napi_value e0, e1; bool lossless = false;
+    NAPI_OK(napi_get_element(env, argv[3], 0, &e0)); NAPI_OK(napi_get_element(env, argv[3], 1, &e1));
+    NAPI_OK(napi_get_value_bigint_uint64(env, e0, &cur.id, &lossless));
+    if (!get_i64(env, e1, &cur.val)) return nullptr;
+  }
+  uint32_t k; if (!get_u32(env, argv[4], &k)) return nullptr;
+  if (k == 0 || k > BMX_TOP_MAX_K) { napi_throw_range_error(env, nullptr, "bmx: k is 1..4096"); return nullptr; }
+  std::vector<bmx_top_rec> recs(k);
+  uint64_t m = 0, ne = 0; int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::scan_top, h->p, nt, (const bmx_term*)terms, desc ? BMX_TOP_DESC : 0u, have_cur ? (const bmx_top_rec*)&cur : nullptr, k, recs.data(), &m, &ne); }
+  if (rc) return fail<Kind>(env, h->p, rc);
+  void *pi = nullptr, *pv = nullptr;
+  napi_value out = object_of(env, {{"ids", make_ta(env, napi_biguint64_array, m, &pi)}, {"vals", make_ta(env, napi_bigint64_array, m, &pv)}, {"nEligible", num(env, (double)ne)}});
+  if (out) for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((int64_t*)pv)[i] = recs[i].val; }
+  return out;
+}
+
+// ---- the engine alone -----------------------------------------------------------------------------------------------------------------
+napi_value Create(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  int32_t device; double cap;
+  NAPI_OK(napi_get_value_int32(env, argv[0], &device));
+  if (!get_count(env, argv[1], &cap)) return nullptr;
+  bmx_ctx* ctx = nullptr;
+  int rc = bmx_create(device, (uint64_t)cap, 0, &ctx);
+  return rc ? fail<Engine>(env, nullptr, rc) : wrap<Engine>(env, ctx);
+}
+
+// mergeBatch(h, id, field, ts, val, mode) -> {applied: Uint32Array, flags: Uint8Array, nApplied, nConflicts, nRows}
+napi_value MergeBatch(napi_env env, napi_callback_info info) {
+  HANDLE(Engine, 6);
+  Cols c; if (!get_cols(env, argv + 1, &c)) return nullptr;
+  int32_t mode; NAPI_OK(napi_get_value_int32(env, argv[5], &mode));
+  std::vector<uint32_t> applied(c.n ? c.n : 1);
+  void* fl = nullptr;
+  napi_value flags = make_ta(env, napi_uint8_array, c.n, &fl); if (!flags) return nullptr;
+  uint64_t na = 0; bmx_merge_stats st; memset(&st, 0, sizeof(st));
+  Turn turn(h->q);
+  int rc = bmx_merge_batch(h->p, c.n, c.id, c.field, c.ts, c.val, mode, BMX_MEM_HOST, applied.data(), &na, (uint8_t*)fl, &st);
+  return rc ? fail<Engine>(env, h->p, rc) : merge_result(env, applied.data(), na, &flags, st);
+}
+
+// mergeBatchAsync(h, id, field, ts, val, mode) -> Promise<{applied, flags, nApplied, nConflicts, nRows}>: the H2D copy, kernels and D2H copy run on a
+// libuv worker thread; resolves to the same object as mergeBatch
+struct MergeJob : Job<Engine> {
+  Cols c; int mode = 0;
+  std::vector<uint32_t> applied; std::vector<uint8_t> flags;
+  uint64_t na = 0; bmx_merge_stats st;
+  int run() override { return bmx_merge_batch(h->p, c.n, c.id, c.field, c.ts, c.val, mode, BMX_MEM_HOST, applied.data(), &na, flags.data(), &st); }
+  napi_value result(napi_env env) override {
+    napi_value fl = copy_ta(env, napi_uint8_array, c.n, flags.data());
+    return fl ? merge_result(env, applied.data(), na, &fl, st) : nullptr;
+  }
+};
+napi_value MergeBatchAsync(napi_env env, napi_callback_info info) {
+  HANDLE(Engine, 6);
+  Cols c; if (!get_cols(env, argv + 1, &c)) return nullptr;
+  int32_t mode; if (napi_get_value_int32(env, argv[5], &mode) != napi_ok) { napi_throw_type_error(env, nullptr, "bmx: bad mode"); return nullptr; }
+  MergeJob* j = new MergeJob();
+  j->h = h; j->c = c; j->mode = mode;
+  j->applied.resize(c.n ? c.n : 1); j->flags.resize(c.n ? c.n : 1);
+  memset(&j->st, 0, sizeof(j->st));
+  return queue_job<Engine>(env, j, "bmx.mergeBatchAsync", argv, 5);   // the engine handle and the four columns
 }
 
 napi_value Reserve(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  double cap; NAPI_OK(napi_get_value_double(env, argv[1], &cap));
-  Turn turn(h);
-  int rc = bmx_reserve(h->ctx, (uint64_t)cap);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
+  HANDLE(Engine, 2);
+  double cap; if (!get_count(env, argv[1], &cap)) return nullptr;
+  Turn turn(h->q);
+  int rc = bmx_reserve(h->p, (uint64_t)cap);
+  return rc ? fail<Engine>(env, h->p, rc) : nullptr;
 }
-
-napi_value LoadRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
-  int rc = bmx_load_rows(h->ctx, n, id, field, ts, val, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
-}
-
-// putRows(h, id, field, ts, val): rows decided on the host, stored as given; val == -2^63 (BMX_VAL_DELETED) leaves a tombstone
-napi_value PutRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
-  int rc = bmx_put_rows(h->ctx, n, id, field, ts, val, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
-}
-
-// getRows(h, id, field) -> {ts, val, found}
-napi_value GetRows(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  void *p0, *p1; size_t n0, n1;
-  if (!get_ta(env, argv[1], napi_biguint64_array, &p0, &n0) || !get_ta(env, argv[2], napi_uint32_array, &p1, &n1)) return nullptr;
-  if (n0 != n1) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return nullptr; }
-  void *ts, *val, *found;
-  napi_value a = make_ta(env, napi_bigint64_array, 8, n0, &ts), b = make_ta(env, napi_bigint64_array, 8, n0, &val), c = make_ta(env, napi_uint8_array, 1, n0, &found);
-  int rc = bmx_get_rows(h->ctx, n0, (const uint64_t*)p0, (const uint32_t*)p1, (int64_t*)ts, (int64_t*)val, (uint8_t*)found, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "ts", a); napi_set_named_property(env, out, "val", b); napi_set_named_property(env, out, "found", c);
-  return out;
-}
-
-napi_value RowCount(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint64_t n = 0; int rc = bmx_row_count(h->ctx, &n);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  napi_value v; napi_create_double(env, (double)n, &v); return v;
-}
-
-napi_value DumpRows(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint64_t n = 0; int rc = bmx_row_count(h->ctx, &n);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  std::vector<uint64_t> id(n ? n : 1); std::vector<uint32_t> f(n ? n : 1); std::vector<int64_t> ts(n ? n : 1), val(n ? n : 1);
-  uint64_t m = 0;
-  rc = bmx_dump_rows(h->ctx, n, id.data(), f.data(), ts.data(), val.data(), &m, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  if (m > n) m = n;                    // rows in use >= rows dumped: tombstones keep their slot and are not data
-  void *pi, *pf, *pt, *pv;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_uint32_array, 4, m, &pf),
-             c = make_ta(env, napi_bigint64_array, 8, m, &pt), d = make_ta(env, napi_bigint64_array, 8, m, &pv);
-  if (m) { memcpy(pi, id.data(), m * 8); memcpy(pf, f.data(), m * 4); memcpy(pt, ts.data(), m * 8); memcpy(pv, val.data(), m * 8); }
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "id", a); napi_set_named_property(env, out, "field", b);
-  napi_set_named_property(env, out, "ts", c); napi_set_named_property(env, out, "val", d);
-  return out;
-}
-
-napi_value IndexBuild(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int rc = bmx_index_build(h->ctx, f);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
-}
-/* indexSetOrdered(handle, field, afterQueries): value-ordered view of the index (bmx_index_set_ordered); 0 = off. -> {afterQueries, valid, sorts} */
-napi_value IndexSetOrdered(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f, n; NAPI_OK(napi_get_value_uint32(env, argv[1], &f)); NAPI_OK(napi_get_value_uint32(env, argv[2], &n));
-  int rc = bmx_index_set_ordered(h->ctx, f, n);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
-}
+/* indexOrderedInfo(handle, field) -> {afterQueries, valid, sorts, ...} */
 napi_value IndexOrderedInfo(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
+  HANDLE(Engine, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
   uint32_t after = 0; int valid = 0; uint64_t sorts = 0;
-  int rc = bmx_index_ordered_info(h->ctx, f, &after, &valid, &sorts);
-  if (rc) return throw_bmx(env, h->ctx, rc);
+  int rc = bmx_index_ordered_info(h->p, f, &after, &valid, &sorts);
+  if (rc) return fail<Engine>(env, h->p, rc);
   napi_value out; NAPI_OK(napi_create_object(env, &out));
   set_num(env, out, "afterQueries", after); set_num(env, out, "valid", valid); set_num(env, out, "sorts", (double)sorts);
   // round 5 (ABI 4): what kept the view current — patches from the change log instead of sorts (bmx_index_ordered_stats)
   uint64_t s2 = 0, patches = 0, keys = 0, rewrites = 0, pending = 0; double sort_us = 0, patch_us = 0;
-  if (bmx_index_ordered_stats(h->ctx, f, &s2, &patches, &keys, &sort_us, &patch_us, &rewrites, &pending) == BMX_OK) {
+  if (bmx_index_ordered_stats(h->p, f, &s2, &patches, &keys, &sort_us, &patch_us, &rewrites, &pending) == BMX_OK) {
     set_num(env, out, "patches", (double)patches); set_num(env, out, "keysPatched", (double)keys); set_num(env, out, "lastSortUs", sort_us); set_num(env, out, "lastPatchUs", patch_us);
     set_num(env, out, "rewrites", (double)rewrites); set_num(env, out, "pendingKeys", (double)pending);
   }
   return out;
 }
 napi_value IndexDrop(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int rc = bmx_index_drop(h->ctx, f);
-  if (rc && rc != BMX_ERR_NO_INDEX) return throw_bmx(env, h->ctx, rc);
-  return nullptr;
+  HANDLE(Engine, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
+  int rc = bmx_index_drop(h->p, f);
+  return rc && rc != BMX_ERR_NO_INDEX ? fail<Engine>(env, h->p, rc) : nullptr;
 }
 napi_value IndexSize(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  uint64_t n = 0; int rc = bmx_index_size(h->ctx, f, &n);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  napi_value v; napi_create_double(env, (double)n, &v); return v;
+  HANDLE(Engine, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
+  uint64_t n = 0; int rc = bmx_index_size(h->p, f, &n);
+  return rc ? fail<Engine>(env, h->p, rc) : num(env, (double)n);
 }
 // indexRefreshCounts(h) -> {fullBuilds, incremental}: how often the indexes were rebuilt from the table / brought up to date from the change log
 napi_value IndexRefreshCounts(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);
-  uint64_t a = 0, b = 0; int rc = bmx_index_refresh_counts(h->ctx, &a, &b);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  set_num(env, out, "fullBuilds", (double)a); set_num(env, out, "incremental", (double)b);
-  return out;
-}
-
-// scanRange(h, field, lo, hi) -> BigUint64Array of node ids
-napi_value ScanRange(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  uint64_t m = 0; int rc = bmx_scan_count(h->ctx, f, lo, hi, &m, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, m, &out);
-  if (m) { uint64_t m2 = 0; rc = bmx_scan_range(h->ctx, f, lo, hi, (uint64_t*)out, m, &m2, BMX_MEM_HOST); if (rc) return throw_bmx(env, h->ctx, rc); }
-  return ta;
-}
-napi_value ScanCount(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  uint64_t m = 0; int rc = bmx_scan_count(h->ctx, f, lo, hi, &m, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  napi_value v; napi_create_double(env, (double)m, &v); return v;
+  HANDLE(Engine, 1);
+  Turn turn(h->q);
+  uint64_t a = 0, b = 0; int rc = bmx_index_refresh_counts(h->p, &a, &b);
+  return rc ? fail<Engine>(env, h->p, rc) : object_of(env, {{"fullBuilds", num(env, (double)a)}, {"incremental", num(env, (double)b)}});
 }
 // scanRangePos(h, field, lo, hi) -> Uint32Array of index positions (ascending): no id gather on the device, no id -> path lookup on the host
 napi_value ScanRangePos(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  uint64_t m = 0; int rc = bmx_scan_count(h->ctx, f, lo, hi, &m, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  void* out; napi_value ta = make_ta(env, napi_uint32_array, 4, m, &out);
-  if (m) { uint64_t m2 = 0; rc = bmx_scan_range_pos(h->ctx, f, lo, hi, (uint32_t*)out, m, &m2, BMX_MEM_HOST); if (rc) return throw_bmx(env, h->ctx, rc); }
-  return ta;
+  HANDLE(Engine, 4);
+  uint32_t f; int64_t lo, hi; if (!get_u32(env, argv[1], &f) || !get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
+  return scan_result(env, h, napi_uint32_array, [&](uint64_t* m) { return bmx_scan_count(h->p, f, lo, hi, m, BMX_MEM_HOST); },
+                     [&](void* out, uint64_t m) { uint64_t m2 = 0; return bmx_scan_range_pos(h->p, f, lo, hi, (uint32_t*)out, m, &m2, BMX_MEM_HOST); });
 }
 // indexIds(h, field, first, count) -> BigUint64Array: node ids of index positions [first, first + count)
 napi_value IndexIds(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  double first, count; NAPI_OK(napi_get_value_double(env, argv[2], &first)); NAPI_OK(napi_get_value_double(env, argv[3], &count));
+  HANDLE(Engine, 4);
+  uint32_t f; double first, count; if (!get_u32(env, argv[1], &f) || !get_count(env, argv[2], &first) || !get_count(env, argv[3], &count)) return nullptr;
+  Turn turn(h->q);
   // validated BEFORE anything is allocated: a negative, fractional or NaN count cast to size_t is undefined behaviour or a huge allocation
-  uint64_t size = 0; int src = bmx_index_size(h->ctx, f, &size);
-  if (src) return throw_bmx(env, h->ctx, src);
+  uint64_t size = 0; int rc = bmx_index_size(h->p, f, &size);
+  if (rc) return fail<Engine>(env, h->p, rc);
   if (!(first >= 0 && count >= 0) || first != std::floor(first) || count != std::floor(count) || first > (double)size || count > (double)size - first) {
     napi_throw_range_error(env, nullptr, "bmx: indexIds(first, count) reaches outside the index");
     return nullptr;
   }
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, (size_t)count, &out);
-  int rc = bmx_index_ids(h->ctx, f, (uint64_t)first, (uint64_t)count, (uint64_t*)out, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  return ta;
+  void* out; napi_value ta = make_ta(env, napi_biguint64_array, (size_t)count, &out); if (!ta) return nullptr;
+  rc = bmx_index_ids(h->p, f, (uint64_t)first, (uint64_t)count, (uint64_t*)out, BMX_MEM_HOST);
+  return rc ? fail<Engine>(env, h->p, rc) : ta;
 }
-// scanFilter(h, [[field, lo, hi], ...]) -> BigUint64Array
+// scanFilter(h, [[field, lo, hi], ...]) -> BigUint64Array; sized by the first term's index
 napi_value ScanFilter(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
-  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: filter needs 1..8 terms"); return nullptr; }
-  bmx_term terms[8];
-  for (uint32_t k = 0; k < nt; k++) {
-    napi_value t, e0, e1, e2;
-    NAPI_OK(napi_get_element(env, argv[1], k, &t));
-    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
-    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
-    terms[k].reserved = 0;
-    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
-  }
-  uint64_t cap = 0; int rc = bmx_index_size(h->ctx, terms[0].field, &cap);
-  if (rc) return throw_bmx(env, h->ctx, rc);
+  HANDLE(Engine, 2);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "filter", terms); if (!nt) return nullptr;
+  Turn turn(h->q);
+  uint64_t cap = 0; int rc = bmx_index_size(h->p, terms[0].field, &cap);
+  if (rc) return fail<Engine>(env, h->p, rc);
   std::vector<uint64_t> tmp(cap ? cap : 1);
-  uint64_t m = 0; rc = bmx_scan_filter(h->ctx, nt, terms, tmp.data(), cap, &m, BMX_MEM_HOST);
-  if (rc) return throw_bmx(env, h->ctx, rc);
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, m, &out);
-  if (m) memcpy(out, tmp.data(), m * 8);
-  return ta;
+  uint64_t m = 0; rc = bmx_scan_filter(h->p, nt, terms, tmp.data(), cap, &m, BMX_MEM_HOST);
+  return rc ? fail<Engine>(env, h->p, rc) : copy_ta(env, napi_biguint64_array, m, tmp.data());
 }
-
 napi_value Info(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  bmx_info i; int rc = bmx_get_info(h->ctx, &i);
-  if (rc) return throw_bmx(env, h->ctx, rc);
+  HANDLE(Engine, 1);
+  Turn turn(h->q);
+  bmx_info i; int rc = bmx_get_info(h->p, &i);
+  if (rc) return fail<Engine>(env, h->p, rc);
   napi_value out; NAPI_OK(napi_create_object(env, &out));
   set_num(env, out, "capacityRows", (double)i.capacity_rows); set_num(env, out, "nSlots", (double)i.n_slots);
   set_num(env, out, "tableBytes", (double)i.table_bytes); set_num(env, out, "nRows", (double)i.n_rows);
@@ -529,298 +648,127 @@ napi_value Info(napi_env env, napi_callback_info info) {
 }
 
 // ---- N4: vector-clock table (bmx_vc_*) -----------------------------------------------------------------------------
-// operations on a table run in the order JS issued them, on whatever thread (the asynchronous merge runs on a libuv worker): tickets, as for the scalar engine
-struct VcHandle {
-  bmx_vc* t; uint32_t K;
-  std::mutex mu; std::condition_variable cv;
-  uint64_t next_ticket = 0, serving = 0;
-  uint64_t take() { std::lock_guard<std::mutex> g(mu); return next_ticket++; }
-};
-struct VcTurn {
-  VcHandle* h; std::unique_lock<std::mutex> lk;
-  VcTurn(VcHandle* hh, uint64_t ticket) : h(hh), lk(hh->mu) { h->cv.wait(lk, [&] { return h->serving == ticket; }); }
-  explicit VcTurn(VcHandle* hh) : h(hh), lk(hh->mu) { const uint64_t t = h->next_ticket++; h->cv.wait(lk, [&] { return h->serving == t; }); }
-  ~VcTurn() { h->serving++; lk.unlock(); h->cv.notify_all(); }
-};
-
-void finalize_vc(napi_env, void* data, void*) {
-  VcHandle* h = static_cast<VcHandle*>(data);
-  if (h->t) bmx_vc_destroy(h->t);
-  delete h;
-}
-
-bool get_vc(napi_env env, napi_value v, VcHandle** out) {
-  void* p = nullptr;
-  if (napi_get_value_external(env, v, &p) != napi_ok || !p || !static_cast<VcHandle*>(p)->t) {
-    napi_throw_error(env, nullptr, "bmx: invalid or closed vector-clock table handle");
-    return false;
-  }
-  *out = static_cast<VcHandle*>(p);
-  return true;
-}
-
-napi_value throw_vc(napi_env env, bmx_vc* t, int rc) {
-  std::string msg = "bmx error " + std::to_string(rc) + ": " + bmx_vc_last_error(t);
-  napi_value code, err, m;
-  napi_create_string_utf8(env, msg.c_str(), NAPI_AUTO_LENGTH, &m);
-  napi_create_error(env, nullptr, m, &err);
-  napi_create_int32(env, rc, &code);
-  napi_set_named_property(env, err, "code", code);
-  napi_throw(env, err);
-  return nullptr;
-}
-
 // vcCreate(device, capacityRows, kWriters, localWriter) -> handle
 napi_value VcCreate(napi_env env, napi_callback_info info) {
   ARGS(4);
   int32_t device; double cap; uint32_t K, local;
   NAPI_OK(napi_get_value_int32(env, argv[0], &device));
-  NAPI_OK(napi_get_value_double(env, argv[1], &cap));
-  NAPI_OK(napi_get_value_uint32(env, argv[2], &K));
-  NAPI_OK(napi_get_value_uint32(env, argv[3], &local));
+  if (!get_count(env, argv[1], &cap) || !get_u32(env, argv[2], &K) || !get_u32(env, argv[3], &local)) return nullptr;
   bmx_vc* t = nullptr;
   int rc = bmx_vc_create(device, (uint64_t)cap, K, local, &t);
-  if (rc) return throw_vc(env, nullptr, rc);
-  VcHandle* h = new VcHandle();
-  h->t = t; h->K = K;
-  napi_value ext;
-  NAPI_OK(napi_create_external(env, h, finalize_vc, nullptr, &ext));
-  return ext;
+  return rc ? fail<Vc>(env, nullptr, rc) : wrap<Vc>(env, t, K);
 }
 
-napi_value VcDestroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  void* p = nullptr;
-  if (napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
-    VcHandle* h = static_cast<VcHandle*>(p);
-    VcTurn turn(h);
-    if (h->t) { bmx_vc_destroy(h->t); h->t = nullptr; }
-  }
-  return nullptr;
-}
-
-// (id BigUint64Array, field Uint32Array, clocks Uint32Array[n*K], val BigInt64Array)
-bool get_vc_cols(napi_env env, napi_value* a, uint32_t K, const uint64_t** id, const uint32_t** field, const uint32_t** clocks, const int64_t** val, size_t* n) {
-  void *p0, *p1, *p2, *p3; size_t n0, n1, n2, n3;
-  if (!get_ta(env, a[0], napi_biguint64_array, &p0, &n0) || !get_ta(env, a[1], napi_uint32_array, &p1, &n1) ||
-      !get_ta(env, a[2], napi_uint32_array, &p2, &n2) || !get_ta(env, a[3], napi_bigint64_array, &p3, &n3)) return false;
-  if (n0 != n1 || n0 != n3 || n2 != n0 * K) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ (clocks must hold n*K counters)"); return false; }
-  *id = (const uint64_t*)p0; *field = (const uint32_t*)p1; *clocks = (const uint32_t*)p2; *val = (const int64_t*)p3; *n = n0;
+// (id BigUint64Array, field Uint32Array, clocks Uint32Array[n*K], val BigInt64Array[, keysets Uint32Array[n]]): keysets say which writers each clock names,
+// in which order (include/bmx.h); absent / undefined = all K, in order
+struct VcCols { const uint64_t* id; const uint32_t *field, *clocks, *ks; const int64_t* val; size_t n; };
+bool get_vc_cols(napi_env env, size_t argc, napi_value* argv, uint32_t K, VcCols* c) {
+  size_t n1, n2, n3, nk;
+  if (!get_ta(env, argv[1], napi_biguint64_array, &c->id, &c->n) || !get_ta(env, argv[2], napi_uint32_array, &c->field, &n1) ||
+      !get_ta(env, argv[3], napi_uint32_array, &c->clocks, &n2) || !get_ta(env, argv[4], napi_bigint64_array, &c->val, &n3)) return false;
+  if (c->n != n1 || c->n != n3 || n2 != c->n * K) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ (clocks must hold n*K counters)"); return false; }
+  c->ks = nullptr;
+  if (argc <= 5 || is_nullish(env, argv[5])) return true;
+  if (!get_ta(env, argv[5], napi_uint32_array, &c->ks, &nk)) return false;
+  if (nk != c->n) { napi_throw_range_error(env, nullptr, "bmx: keysets must hold one word per row"); return false; }
   return true;
 }
-
-// optional trailing argument: keysets Uint32Array[n] (which writers each clock names, in which order: include/bmx.h); absent / undefined = all K, in order
-bool get_keysets(napi_env env, size_t argc, napi_value* argv, size_t at, size_t n, const uint32_t** ks) {
-  *ks = nullptr;
-  if (argc <= at) return true;
-  napi_valuetype t; napi_typeof(env, argv[at], &t);
-  if (t == napi_undefined || t == napi_null) return true;
-  void* p; size_t m;
-  if (!get_ta(env, argv[at], napi_uint32_array, &p, &m)) return false;
-  if (m != n) { napi_throw_range_error(env, nullptr, "bmx: keysets must hold one word per row"); return false; }
-  *ks = (const uint32_t*)p;
-  return true;
+// {updated, flags, [rows,] nRows}
+napi_value vc_merge_result(napi_env env, const uint32_t* upd, uint64_t nu, napi_value flags, const napi_value* rows, uint64_t nrows) {
+  napi_value updated = copy_ta(env, napi_uint32_array, (size_t)nu, upd);
+  napi_value out = rows ? object_of(env, {{"updated", updated}, {"flags", flags}, {"rows", *rows}}) : object_of(env, {{"updated", updated}, {"flags", flags}});
+  if (out) set_num(env, out, "nRows", (double)nrows);
+  return out;
 }
-#define ARGS_OPT(MIN, MAX)                                   \
-  size_t argc = MAX; napi_value argv[MAX];                   \
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr)); \
-  if (argc < MIN) { napi_throw_type_error(env, nullptr, "bmx: missing arguments"); return nullptr; }
 
 // vcLoadRows(h, id, field, clocks, val[, keysets])
 napi_value VcLoadRows(napi_env env, napi_callback_info info) {
   ARGS_OPT(5, 6);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t *field, *clocks, *ks; const int64_t* val; size_t n;
-  if (!get_vc_cols(env, argv + 1, h->K, &id, &field, &clocks, &val, &n) || !get_keysets(env, argc, argv, 5, n, &ks)) return nullptr;
-  VcTurn turn(h);
-  int rc = bmx_vc_load_rows_ks(h->t, n, id, field, clocks, ks, val);
-  if (rc) return throw_vc(env, h->t, rc);
-  return nullptr;
+  Handle<Vc>* h = get_handle<Vc>(env, argv[0]); if (!h) return nullptr;
+  VcCols c; if (!get_vc_cols(env, argc, argv, h->K, &c)) return nullptr;
+  Turn turn(h->q);
+  int rc = bmx_vc_load_rows_ks(h->p, c.n, c.id, c.field, c.clocks, c.ks, c.val);
+  return rc ? fail<Vc>(env, h->p, rc) : nullptr;
 }
 
 // vcMergeBatch(h, id, field, clocks, val[, keysets]) -> {updated: Uint32Array, flags: Uint8Array, nRows}
 napi_value VcMergeBatch(napi_env env, napi_callback_info info) {
   ARGS_OPT(5, 6);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t *field, *clocks, *ks; const int64_t* val; size_t n;
-  if (!get_vc_cols(env, argv + 1, h->K, &id, &field, &clocks, &val, &n) || !get_keysets(env, argc, argv, 5, n, &ks)) return nullptr;
-  std::vector<uint32_t> upd(n ? n : 1);
+  Handle<Vc>* h = get_handle<Vc>(env, argv[0]); if (!h) return nullptr;
+  VcCols c; if (!get_vc_cols(env, argc, argv, h->K, &c)) return nullptr;
+  std::vector<uint32_t> upd(c.n ? c.n : 1);
   void* fl = nullptr;
-  napi_value flags = make_ta(env, napi_uint8_array, 1, n, &fl);
+  napi_value flags = make_ta(env, napi_uint8_array, c.n, &fl); if (!flags) return nullptr;
   uint64_t nu = 0, rows = 0;
-  VcTurn turn(h);
-  int rc = bmx_vc_merge_batch_ks(h->t, n, id, field, clocks, ks, val, upd.data(), &nu, (uint8_t*)fl);
-  if (rc) return throw_vc(env, h->t, rc);
-  bmx_vc_row_count(h->t, &rows);
-  void* up = nullptr;
-  napi_value updated = make_ta(env, napi_uint32_array, 4, nu, &up);
-  if (nu) memcpy(up, upd.data(), nu * 4);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "updated", updated);
-  napi_set_named_property(env, out, "flags", flags);
-  set_num(env, out, "nRows", (double)rows);
-  return out;
+  Turn turn(h->q);
+  int rc = bmx_vc_merge_batch_ks(h->p, c.n, c.id, c.field, c.clocks, c.ks, c.val, upd.data(), &nu, (uint8_t*)fl);
+  if (rc) return fail<Vc>(env, h->p, rc);
+  bmx_vc_row_count(h->p, &rows);
+  return vc_merge_result(env, upd.data(), nu, flags, nullptr, rows);
 }
 
 // vcMergeBatchAsync(h, id, field, clocks, val[, keysets]) -> Promise<{updated, flags, nRows, rows: {clocks, keysets} of the updated rows}>: the upload,
 // the kernels and the read-back of the updated rows' clocks run on a libuv worker thread, in issue order with every other operation on the table
 // (reference seam: the sync loop src/bullet-network-sync.js:551-569 under general vector clocks, src/bullet-crt.js:68-153). The rows' clocks come back
 // with the merge because a later merge — already in flight when this one is applied — would have moved them.
-struct VcJob {
-  napi_async_work work = nullptr; napi_deferred deferred = nullptr;
-  napi_ref refs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  VcHandle* h = nullptr; uint64_t ticket = 0;
-  const uint64_t* id = nullptr; const uint32_t *field = nullptr, *clocks = nullptr, *ks = nullptr; const int64_t* val = nullptr; size_t n = 0;
+struct VcJob : Job<Vc> {
+  VcCols c;
   std::vector<uint32_t> upd, rclocks, rks; std::vector<uint8_t> flags, rstate; std::vector<int64_t> rval;
-  uint64_t nu = 0, rows = 0; int rc = 0; std::string err;
+  uint64_t nu = 0, rows = 0;
+  int run() override {
+    int rc = bmx_vc_merge_batch_ks(h->p, c.n, c.id, c.field, c.clocks, c.ks, c.val, upd.data(), &nu, flags.data());
+    if (rc) return rc;
+    bmx_vc_row_count(h->p, &rows);
+    if (!nu) return BMX_OK;
+    std::vector<uint64_t> ids(nu); std::vector<uint32_t> fields(nu);
+    for (uint64_t k = 0; k < nu; k++) { ids[k] = c.id[upd[k]]; fields[k] = c.field[upd[k]]; }
+    rclocks.resize(nu * h->K); rks.resize(nu); rval.resize(nu); rstate.resize(nu);
+    return bmx_vc_get_rows_ks(h->p, nu, ids.data(), fields.data(), rclocks.data(), rks.data(), rval.data(), rstate.data());
+  }
+  napi_value result(napi_env env) override {
+    napi_value fl = copy_ta(env, napi_uint8_array, c.n, flags.data());
+    napi_value rows_of = object_of(env, {{"clocks", copy_ta(env, napi_uint32_array, (size_t)nu * h->K, rclocks.data())}, {"keysets", copy_ta(env, napi_uint32_array, (size_t)nu, rks.data())}});
+    return fl && rows_of ? vc_merge_result(env, upd.data(), nu, fl, &rows_of, rows) : nullptr;
+  }
 };
-void vc_execute(napi_env, void* data) {
-  VcJob* j = static_cast<VcJob*>(data);
-  VcTurn turn(j->h, j->ticket);
-  if (!j->h->t) { j->rc = BMX_ERR_INVALID; j->err = "table closed"; return; }
-  j->rc = bmx_vc_merge_batch_ks(j->h->t, j->n, j->id, j->field, j->clocks, j->ks, j->val, j->upd.data(), &j->nu, j->flags.data());
-  if (j->rc) { j->err = bmx_vc_last_error(j->h->t); return; }
-  bmx_vc_row_count(j->h->t, &j->rows);
-  if (j->nu) {
-    std::vector<uint64_t> ids(j->nu); std::vector<uint32_t> fields(j->nu);
-    for (uint64_t k = 0; k < j->nu; k++) { ids[k] = j->id[j->upd[k]]; fields[k] = j->field[j->upd[k]]; }
-    j->rclocks.resize(j->nu * j->h->K); j->rks.resize(j->nu); j->rval.resize(j->nu); j->rstate.resize(j->nu);
-    j->rc = bmx_vc_get_rows_ks(j->h->t, j->nu, ids.data(), fields.data(), j->rclocks.data(), j->rks.data(), j->rval.data(), j->rstate.data());
-    if (j->rc) j->err = bmx_vc_last_error(j->h->t);
-  }
-}
-void vc_complete(napi_env env, napi_status, void* data) {
-  VcJob* j = static_cast<VcJob*>(data);
-  for (auto& r : j->refs) if (r) napi_delete_reference(env, r);
-  if (j->rc) {
-    napi_value msg, err, code;
-    std::string m = "bmx error " + std::to_string(j->rc) + ": " + j->err;
-    napi_create_string_utf8(env, m.c_str(), NAPI_AUTO_LENGTH, &msg);
-    napi_create_error(env, nullptr, msg, &err);
-    napi_create_int32(env, j->rc, &code);
-    napi_set_named_property(env, err, "code", code);
-    napi_reject_deferred(env, j->deferred, err);
-  } else {
-    void *up = nullptr, *fl = nullptr, *c = nullptr, *ks = nullptr;
-    napi_value updated = make_ta(env, napi_uint32_array, 4, (size_t)j->nu, &up);
-    if (j->nu) memcpy(up, j->upd.data(), (size_t)j->nu * 4);
-    napi_value flags = make_ta(env, napi_uint8_array, 1, j->n, &fl);
-    if (j->n) memcpy(fl, j->flags.data(), j->n);
-    napi_value clocks = make_ta(env, napi_uint32_array, 4, (size_t)j->nu * j->h->K, &c);
-    napi_value keysets = make_ta(env, napi_uint32_array, 4, (size_t)j->nu, &ks);
-    if (j->nu) { memcpy(c, j->rclocks.data(), (size_t)j->nu * j->h->K * 4); memcpy(ks, j->rks.data(), (size_t)j->nu * 4); }
-    napi_value out, rows;
-    napi_create_object(env, &out); napi_create_object(env, &rows);
-    napi_set_named_property(env, rows, "clocks", clocks); napi_set_named_property(env, rows, "keysets", keysets);
-    napi_set_named_property(env, out, "updated", updated); napi_set_named_property(env, out, "flags", flags); napi_set_named_property(env, out, "rows", rows);
-    set_num(env, out, "nRows", (double)j->rows);
-    napi_resolve_deferred(env, j->deferred, out);
-  }
-  napi_delete_async_work(env, j->work);
-  delete j;
-}
 napi_value VcMergeBatchAsync(napi_env env, napi_callback_info info) {
   ARGS_OPT(5, 6);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
+  Handle<Vc>* h = get_handle<Vc>(env, argv[0]); if (!h) return nullptr;
+  VcCols c; if (!get_vc_cols(env, argc, argv, h->K, &c)) return nullptr;
   VcJob* j = new VcJob();
-  j->h = h;
-  if (!get_vc_cols(env, argv + 1, h->K, &j->id, &j->field, &j->clocks, &j->val, &j->n) || !get_keysets(env, argc, argv, 5, j->n, &j->ks)) { delete j; return nullptr; }
-  j->upd.resize(j->n ? j->n : 1); j->flags.resize(j->n ? j->n : 1);
-  napi_value promise, name;
-  auto drop = [&](const char* what) {
-    for (auto& r : j->refs) if (r) napi_delete_reference(env, r);
-    if (j->work) napi_delete_async_work(env, j->work);
-    delete j;
-    napi_throw_error(env, nullptr, what);
-    return (napi_value) nullptr;
-  };
-  if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) return drop("bmx: could not create a promise");
-  for (size_t k = 0; k < argc && k < 6; k++) napi_create_reference(env, argv[k], 1, &j->refs[k]);     // the table handle and the columns outlive the job
-  if (napi_create_string_utf8(env, "bmx.vcMergeBatchAsync", NAPI_AUTO_LENGTH, &name) != napi_ok ||
-      napi_create_async_work(env, nullptr, name, vc_execute, vc_complete, j, &j->work) != napi_ok) return drop("bmx: could not create the async work item");
-  j->ticket = h->take();                            // taken last: a ticket that never runs would block every later operation on this table
-  if (napi_queue_async_work(env, j->work) != napi_ok) {
-    { VcTurn skip(h, j->ticket); }
-    return drop("bmx: could not queue the async work item");
-  }
-  return promise;
+  j->h = h; j->c = c;
+  j->upd.resize(c.n ? c.n : 1); j->flags.resize(c.n ? c.n : 1);
+  return queue_job<Vc>(env, j, "bmx.vcMergeBatchAsync", argv, std::min<size_t>(argc, 6));   // the table handle and the columns
 }
 
 // vcGetRows(h, id, field) -> {clocks: Uint32Array[n*K], val: BigInt64Array, state: Uint8Array, keysets: Uint32Array}
 napi_value VcGetRows(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
-  void *p0, *p1; size_t n0, n1;
-  if (!get_ta(env, argv[1], napi_biguint64_array, &p0, &n0) || !get_ta(env, argv[2], napi_uint32_array, &p1, &n1)) return nullptr;
-  if (n0 != n1) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return nullptr; }
-  void *c, *v, *st, *ks;
-  napi_value clocks = make_ta(env, napi_uint32_array, 4, n0 * h->K, &c);
-  napi_value val = make_ta(env, napi_bigint64_array, 8, n0, &v);
-  napi_value state = make_ta(env, napi_uint8_array, 1, n0, &st);
-  napi_value keysets = make_ta(env, napi_uint32_array, 4, n0, &ks);
-  VcTurn turn(h);
-  int rc = bmx_vc_get_rows_ks(h->t, n0, (const uint64_t*)p0, (const uint32_t*)p1, (uint32_t*)c, (uint32_t*)ks, (int64_t*)v, (uint8_t*)st);
-  if (rc) return throw_vc(env, h->t, rc);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "keysets", keysets);
-  napi_set_named_property(env, out, "clocks", clocks);
-  napi_set_named_property(env, out, "val", val);
-  napi_set_named_property(env, out, "state", state);
-  return out;
+  HANDLE(Vc, 3);
+  Cols k; if (!get_keys(env, argv + 1, &k)) return nullptr;
+  void *c = nullptr, *v = nullptr, *st = nullptr, *ks = nullptr;
+  napi_value clocks = make_ta(env, napi_uint32_array, k.n * h->K, &c), val = make_ta(env, napi_bigint64_array, k.n, &v), state = make_ta(env, napi_uint8_array, k.n, &st);
+  napi_value out = object_of(env, {{"keysets", make_ta(env, napi_uint32_array, k.n, &ks)}, {"clocks", clocks}, {"val", val}, {"state", state}});
+  if (!out) return nullptr;
+  Turn turn(h->q);
+  int rc = bmx_vc_get_rows_ks(h->p, k.n, k.id, k.field, (uint32_t*)c, (uint32_t*)ks, (int64_t*)v, (uint8_t*)st);
+  return rc ? fail<Vc>(env, h->p, rc) : out;
 }
 
 // vcScanRange(h, field, lo, hi) -> BigUint64Array of node ids (rows of `field` with lo <= val <= hi)
 napi_value VcScanRange(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  VcTurn turn(h);
-  uint64_t m = 0; int rc = bmx_vc_scan_range(h->t, f, lo, hi, nullptr, 0, &m);
-  if (rc) return throw_vc(env, h->t, rc);
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, m, &out);
-  if (m) { uint64_t m2 = 0; rc = bmx_vc_scan_range(h->t, f, lo, hi, (uint64_t*)out, m, &m2); if (rc) return throw_vc(env, h->t, rc); }
-  return ta;
+  HANDLE(Vc, 4);
+  uint32_t f; int64_t lo, hi; if (!get_u32(env, argv[1], &f) || !get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
+  return scan_result(env, h, napi_biguint64_array, [&](uint64_t* m) { return bmx_vc_scan_range(h->p, f, lo, hi, nullptr, 0, m); },
+                     [&](void* out, uint64_t m) { uint64_t m2 = 0; return bmx_vc_scan_range(h->p, f, lo, hi, (uint64_t*)out, m, &m2); });
 }
 napi_value VcRowCount(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  VcHandle* h; if (!get_vc(env, argv[0], &h)) return nullptr;
-  uint64_t n = 0;
-  VcTurn turn(h);
-  int rc = bmx_vc_row_count(h->t, &n);
-  if (rc) return throw_vc(env, h->t, rc);
-  napi_value v; napi_create_double(env, (double)n, &v);
-  return v;
+  HANDLE(Vc, 1);
+  Turn turn(h->q);
+  uint64_t n = 0; int rc = bmx_vc_row_count(h->p, &n);
+  return rc ? fail<Vc>(env, h->p, rc) : num(env, (double)n);
 }
 
 // ---- N shards in one process (bmx_comm_*): one JS object owns all GPUs of the node ------------------------------------
-struct CommHandle { bmx_comm* c; std::mutex mu; };
-
-void finalize_comm(napi_env, void* data, void*) {
-  CommHandle* h = static_cast<CommHandle*>(data);
-  if (h->c) bmx_comm_destroy(h->c);
-  delete h;
-}
-bool get_comm(napi_env env, napi_value v, CommHandle** out) {
-  void* p = nullptr;
-  if (napi_get_value_external(env, v, &p) != napi_ok || !p || !static_cast<CommHandle*>(p)->c) {
-    napi_throw_error(env, nullptr, "bmx: invalid or closed communicator handle");
-    return false;
-  }
-  *out = static_cast<CommHandle*>(p);
-  return true;
-}
-napi_value throw_comm(napi_env env, bmx_comm* c, int rc) {
-  std::string msg = "bmx error " + std::to_string(rc) + ": " + bmx_comm_last_error(c);
-  napi_value code, err, m;
-  napi_create_string_utf8(env, msg.c_str(), NAPI_AUTO_LENGTH, &m);
-  napi_create_error(env, nullptr, m, &err);
-  napi_create_int32(env, rc, &code);
-  napi_set_named_property(env, err, "code", code);
-  napi_throw(env, err);
-  return nullptr;
-}
-
 // commCreate([device, device, ...], capacityRowsPerShard) -> handle   (a device may be listed several times: logical shards)
 napi_value CommCreate(napi_env env, napi_callback_info info) {
   ARGS(2);
@@ -828,377 +776,63 @@ napi_value CommCreate(napi_env env, napi_callback_info info) {
   if (n == 0 || n > 16) { napi_throw_range_error(env, nullptr, "bmx: a communicator has 1..16 shards"); return nullptr; }
   std::vector<int> devs(n);
   for (uint32_t i = 0; i < n; i++) { napi_value e; NAPI_OK(napi_get_element(env, argv[0], i, &e)); int32_t d; NAPI_OK(napi_get_value_int32(env, e, &d)); devs[i] = d; }
-  double cap; NAPI_OK(napi_get_value_double(env, argv[1], &cap));
+  double cap; if (!get_count(env, argv[1], &cap)) return nullptr;
   bmx_comm* c = nullptr;
   int rc = bmx_comm_create(n, devs.data(), (uint64_t)cap, 0, &c);
-  if (rc) return throw_comm(env, nullptr, rc);
-  CommHandle* h = new CommHandle(); h->c = c;
-  napi_value ext;
-  NAPI_OK(napi_create_external(env, h, finalize_comm, nullptr, &ext));
-  return ext;
-}
-napi_value CommDestroy(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  void* p = nullptr;
-  if (napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
-    CommHandle* h = static_cast<CommHandle*>(p);
-    std::lock_guard<std::mutex> g(h->mu);
-    if (h->c) { bmx_comm_destroy(h->c); h->c = nullptr; }
-  }
-  return nullptr;
+  return rc ? fail<Comm>(env, nullptr, rc) : wrap<Comm>(env, c);
 }
 // commMergeBatch(h, id, field, ts, val, mode) -> {applied: Uint32Array (indices into this batch), nApplied, nConflicts, nRows}
 napi_value CommMergeBatch(napi_env env, napi_callback_info info) {
-  ARGS(6);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
+  HANDLE(Comm, 6);
+  Cols c; if (!get_cols(env, argv + 1, &c)) return nullptr;
   int32_t mode; NAPI_OK(napi_get_value_int32(env, argv[5], &mode));
-  std::vector<uint32_t> applied(n ? n : 1);
+  std::vector<uint32_t> applied(c.n ? c.n : 1);
   uint64_t na = 0; bmx_merge_stats st; memset(&st, 0, sizeof(st));
-  std::lock_guard<std::mutex> g(h->mu);
-  int rc = bmx_comm_merge(h->c, n, id, field, ts, val, mode, applied.data(), &na, &st);
-  if (rc) return throw_comm(env, h->c, rc);
-  void* ap = nullptr;
-  napi_value ta = make_ta(env, napi_uint32_array, 4, (size_t)na, &ap);
-  if (na) memcpy(ap, applied.data(), (size_t)na * 4);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "applied", ta);
-  set_num(env, out, "nApplied", (double)st.n_applied); set_num(env, out, "nConflicts", (double)st.n_conflicts); set_num(env, out, "nRows", (double)st.n_rows);
-  return out;
+  Turn turn(h->q);
+  int rc = bmx_comm_merge(h->p, c.n, c.id, c.field, c.ts, c.val, mode, applied.data(), &na, &st);
+  return rc ? fail<Comm>(env, h->p, rc) : merge_result(env, applied.data(), na, nullptr, st);
 }
-napi_value CommLoadRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  int rc = bmx_comm_load_rows(h->c, n, id, field, ts, val);
-  if (rc) return throw_comm(env, h->c, rc);
+napi_value CommIndexDrop(napi_env env, napi_callback_info info) {   // every shard, whatever it answers
+  HANDLE(Comm, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
+  for (uint32_t s = 0; s < bmx_comm_nshards(h->p); s++) (void)bmx_index_drop(bmx_comm_shard(h->p, s), f);
   return nullptr;
 }
-napi_value CommPutRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  const uint64_t* id; const uint32_t* field; const int64_t *ts, *val; size_t n;
-  if (!get_cols(env, argv + 1, &id, &field, &ts, &val, &n)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  int rc = bmx_comm_put_rows(h->c, n, id, field, ts, val);
-  if (rc) return throw_comm(env, h->c, rc);
-  return nullptr;
-}
-napi_value CommGetRows(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  void *p0, *p1; size_t n0, n1;
-  if (!get_ta(env, argv[1], napi_biguint64_array, &p0, &n0) || !get_ta(env, argv[2], napi_uint32_array, &p1, &n1)) return nullptr;
-  if (n0 != n1) { napi_throw_range_error(env, nullptr, "bmx: column lengths differ"); return nullptr; }
-  void *ts, *val, *found;
-  napi_value a = make_ta(env, napi_bigint64_array, 8, n0, &ts), b = make_ta(env, napi_bigint64_array, 8, n0, &val), c = make_ta(env, napi_uint8_array, 1, n0, &found);
-  std::lock_guard<std::mutex> g(h->mu);
-  int rc = bmx_comm_get_rows(h->c, n0, (const uint64_t*)p0, (const uint32_t*)p1, (int64_t*)ts, (int64_t*)val, (uint8_t*)found);
-  if (rc) return throw_comm(env, h->c, rc);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "ts", a); napi_set_named_property(env, out, "val", b); napi_set_named_property(env, out, "found", c);
-  return out;
-}
-napi_value CommRowCount(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  uint64_t n = 0; int rc = bmx_comm_row_count(h->c, &n);
-  if (rc) return throw_comm(env, h->c, rc);
-  napi_value v; napi_create_double(env, (double)n, &v); return v;
-}
-napi_value CommDumpRows(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  uint64_t n = 0; int rc = bmx_comm_row_count(h->c, &n);
-  if (rc) return throw_comm(env, h->c, rc);
-  std::vector<uint64_t> id(n ? n : 1); std::vector<uint32_t> f(n ? n : 1); std::vector<int64_t> ts(n ? n : 1), val(n ? n : 1);
-  uint64_t m = 0;
-  rc = bmx_comm_dump_rows(h->c, n, id.data(), f.data(), ts.data(), val.data(), &m);
-  if (rc) return throw_comm(env, h->c, rc);
-  if (m > n) m = n;                    // tombstones keep their slot and are not dumped
-  void *pi, *pf, *pt, *pv;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_uint32_array, 4, m, &pf),
-             c = make_ta(env, napi_bigint64_array, 8, m, &pt), d = make_ta(env, napi_bigint64_array, 8, m, &pv);
-  if (m) { memcpy(pi, id.data(), m * 8); memcpy(pf, f.data(), m * 4); memcpy(pt, ts.data(), m * 8); memcpy(pv, val.data(), m * 8); }
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "id", a); napi_set_named_property(env, out, "field", b);
-  napi_set_named_property(env, out, "ts", c); napi_set_named_property(env, out, "val", d);
-  return out;
-}
-/* Replica reconciliation (bmx.h): thin bindings, no logic.
- * digest(handle, log2Buckets, tombstones) / commDigest(comm, ...) -> {sums: BigUint64Array, counts: BigUint64Array}
- * exportRows(handle, since, log2Buckets, bucketBits: BigUint64Array | null, onlyTombstones) / commExportRows(comm, ...) -> {id, field, ts, val, n} */
-template <class H>
-napi_value digest_impl(napi_env env, napi_value* argv, H* h, bmx_ctx* ctx, bmx_comm* comm) {
-  uint32_t L; NAPI_OK(napi_get_value_uint32(env, argv[1], &L));
-  bool tomb = false; NAPI_OK(napi_get_value_bool(env, argv[2], &tomb));
-  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
-  void *ps, *pc;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, (size_t)1 << L, &ps), b = make_ta(env, napi_biguint64_array, 8, (size_t)1 << L, &pc);
-  const uint32_t fl = tomb ? BMX_SYNC_TOMBSTONES : 0u;
-  const int rc = ctx ? bmx_digest(ctx, L, fl, (uint64_t*)ps, (uint64_t*)pc, BMX_MEM_HOST) : bmx_comm_digest(comm, L, fl, (uint64_t*)ps, (uint64_t*)pc);
-  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "sums", a); napi_set_named_property(env, out, "counts", b);
-  return out;
-}
-napi_value export_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
-  int64_t since; if (!get_i64(env, argv[1], &since)) return nullptr;
-  uint32_t L; NAPI_OK(napi_get_value_uint32(env, argv[2], &L));
-  if (L > 16) { napi_throw_range_error(env, nullptr, "bmx: log2Buckets is 0..16"); return nullptr; }
-  napi_valuetype bt; napi_typeof(env, argv[3], &bt);
-  const uint64_t* bits = nullptr;
-  if (bt != napi_null && bt != napi_undefined) {
-    void* p; size_t words;
-    if (!get_ta(env, argv[3], napi_biguint64_array, &p, &words)) return nullptr;
-    if (words < std::max<size_t>(1, ((size_t)1 << L) / 64)) { napi_throw_range_error(env, nullptr, "bmx: bucketBits needs 2^log2Buckets bits"); return nullptr; }
-    bits = (const uint64_t*)p;
-  }
-  bool only_tomb = false; NAPI_OK(napi_get_value_bool(env, argv[4], &only_tomb));
-  const uint32_t fl = only_tomb ? BMX_EXPORT_ONLY_TOMBSTONES : 0u;
-  uint64_t n = 0;
-  int rc = ctx ? bmx_export_rows(ctx, since, L, bits, fl, nullptr, 0, &n, BMX_MEM_HOST) : bmx_comm_export_rows(comm, since, L, bits, fl, nullptr, 0, &n);
-  std::vector<bmx_delta_rec> recs(n ? n : 1);
-  uint64_t m = 0;
-  if (!rc && n) rc = ctx ? bmx_export_rows(ctx, since, L, bits, fl, recs.data(), n, &m, BMX_MEM_HOST) : bmx_comm_export_rows(comm, since, L, bits, fl, recs.data(), n, &m);
-  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
-  if (m > n) m = n;
-  void *pi, *pf, *pt, *pv;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_uint32_array, 4, m, &pf),
-             c = make_ta(env, napi_bigint64_array, 8, m, &pt), d = make_ta(env, napi_bigint64_array, 8, m, &pv);
-  for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((uint32_t*)pf)[i] = recs[i].field; ((int64_t*)pt)[i] = recs[i].ts; ((int64_t*)pv)[i] = recs[i].val; }
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "id", a); napi_set_named_property(env, out, "field", b);
-  napi_set_named_property(env, out, "ts", c); napi_set_named_property(env, out, "val", d);
-  set_num(env, out, "n", (double)m);
-  return out;
-}
-napi_value Digest(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  return digest_impl(env, argv, h, h->ctx, nullptr);
-}
-napi_value ExportRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);
-  return export_impl(env, argv, h->ctx, nullptr);
-}
-napi_value CommDigest(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  return digest_impl(env, argv, h, nullptr, h->c);
-}
-napi_value CommExportRows(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  return export_impl(env, argv, nullptr, h->c);
-}
-napi_value CommIndexSetOrdered(napi_env env, napi_callback_info info) {
-  ARGS(3);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  uint32_t f, n; NAPI_OK(napi_get_value_uint32(env, argv[1], &f)); NAPI_OK(napi_get_value_uint32(env, argv[2], &n));
-  int rc = bmx_comm_index_set_ordered(h->c, f, n);
-  if (rc) return throw_comm(env, h->c, rc);
-  return nullptr;
-}
-napi_value CommIndexBuild(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  std::lock_guard<std::mutex> g(h->mu);
-  int rc = bmx_comm_index_build(h->c, f);
-  if (rc) return throw_comm(env, h->c, rc);
-  return nullptr;
-}
-napi_value CommIndexDrop(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  std::lock_guard<std::mutex> g(h->mu);
-  for (uint32_t s = 0; s < bmx_comm_nshards(h->c); s++) (void)bmx_index_drop(bmx_comm_shard(h->c, s), f);
-  return nullptr;
-}
-napi_value CommIndexSize(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  std::lock_guard<std::mutex> g(h->mu);
+napi_value CommIndexSize(napi_env env, napi_callback_info info) {   // the shards' sizes added; a shard's error is that shard's
+  HANDLE(Comm, 2);
+  uint32_t f; if (!get_u32(env, argv[1], &f)) return nullptr;
+  Turn turn(h->q);
   uint64_t tot = 0;
-  for (uint32_t s = 0; s < bmx_comm_nshards(h->c); s++) {
-    uint64_t n = 0; int rc = bmx_index_size(bmx_comm_shard(h->c, s), f, &n);
-    if (rc) return throw_bmx(env, bmx_comm_shard(h->c, s), rc);
+  for (uint32_t s = 0; s < bmx_comm_nshards(h->p); s++) {
+    uint64_t n = 0; int rc = bmx_index_size(bmx_comm_shard(h->p, s), f, &n);
+    if (rc) return fail<Engine>(env, bmx_comm_shard(h->p, s), rc);
     tot += n;
   }
-  napi_value v; napi_create_double(env, (double)tot, &v); return v;
+  return num(env, (double)tot);
 }
-napi_value CommScanRange(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  uint64_t m = 0; int rc = bmx_comm_scan_count(h->c, f, lo, hi, &m);
-  if (rc) return throw_comm(env, h->c, rc);
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, m, &out);
-  if (m) { uint64_t m2 = 0; rc = bmx_comm_scan_range(h->c, f, lo, hi, (uint64_t*)out, m, &m2); if (rc) return throw_comm(env, h->c, rc); }
-  return ta;
-}
-napi_value CommScanCount(napi_env env, napi_callback_info info) {
-  ARGS(4);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t f; NAPI_OK(napi_get_value_uint32(env, argv[1], &f));
-  int64_t lo, hi; if (!get_i64(env, argv[2], &lo) || !get_i64(env, argv[3], &hi)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  uint64_t m = 0; int rc = bmx_comm_scan_count(h->c, f, lo, hi, &m);
-  if (rc) return throw_comm(env, h->c, rc);
-  napi_value v; napi_create_double(env, (double)m, &v); return v;
-}
-napi_value CommScanFilter(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
-  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: filter needs 1..8 terms"); return nullptr; }
-  bmx_term terms[8];
-  for (uint32_t k = 0; k < nt; k++) {
-    napi_value t, e0, e1, e2;
-    NAPI_OK(napi_get_element(env, argv[1], k, &t));
-    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
-    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
-    terms[k].reserved = 0;
-    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
-  }
-  std::lock_guard<std::mutex> g(h->mu);
-  uint64_t m = 0; int rc = bmx_comm_scan_filter(h->c, nt, terms, nullptr, 0, &m);
-  if (rc) return throw_comm(env, h->c, rc);
-  void* out; napi_value ta = make_ta(env, napi_biguint64_array, 8, m, &out);
-  if (m) { uint64_t m2 = 0; rc = bmx_comm_scan_filter(h->c, nt, terms, (uint64_t*)out, m, &m2); if (rc) return throw_comm(env, h->c, rc); }
-  return ta;
-}
-
-/* Aggregate queries (bmx.h bmx_scan_aggregate): thin bindings, no logic.
- * scanAggregate(handle, [[field, lo, hi], ...], measure | null, group | null, groupLo, nGroups) / commScanAggregate(comm, ...) ->
- * {nMatch, n: BigUint64Array, min, max: BigInt64Array, sumLo: BigUint64Array, sumHi: BigInt64Array}, one entry per record (nGroups + 1, or 1 without groups) */
-napi_value aggregate_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
-  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
-  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: aggregate needs 1..8 terms"); return nullptr; }
-  bmx_term terms[8];
-  for (uint32_t k = 0; k < nt; k++) {
-    napi_value t, e0, e1, e2;
-    NAPI_OK(napi_get_element(env, argv[1], k, &t));
-    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
-    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
-    terms[k].reserved = 0;
-    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
-  }
-  uint32_t fld[2] = {BMX_AGG_NO_FIELD, BMX_AGG_NO_FIELD};
-  for (int k = 0; k < 2; k++) {
-    napi_valuetype vt; napi_typeof(env, argv[2 + k], &vt);
-    if (vt != napi_null && vt != napi_undefined) NAPI_OK(napi_get_value_uint32(env, argv[2 + k], &fld[k]));
-  }
-  int64_t glo; if (!get_i64(env, argv[4], &glo)) return nullptr;
-  uint32_t ng; NAPI_OK(napi_get_value_uint32(env, argv[5], &ng));
-  if (ng > BMX_AGG_MAX_GROUPS || (ng && fld[1] == BMX_AGG_NO_FIELD)) { napi_throw_range_error(env, nullptr, "bmx: nGroups is 0..65536 and needs a group field"); return nullptr; }
-  const size_t nrec = ng ? (size_t)ng + 1 : 1;
-  std::vector<bmx_agg> recs(nrec);
-  const int rc = ctx ? bmx_scan_aggregate(ctx, nt, terms, fld[0], fld[1], glo, ng, recs.data(), BMX_MEM_HOST) : bmx_comm_scan_aggregate(comm, nt, terms, fld[0], fld[1], glo, ng, recs.data());
-  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
-  void *pm, *pn, *plo, *phi, *psl, *psh;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, nrec, &pm), b = make_ta(env, napi_biguint64_array, 8, nrec, &pn), c = make_ta(env, napi_bigint64_array, 8, nrec, &plo),
-             d = make_ta(env, napi_bigint64_array, 8, nrec, &phi), e = make_ta(env, napi_biguint64_array, 8, nrec, &psl), f = make_ta(env, napi_bigint64_array, 8, nrec, &psh);
-  for (size_t i = 0; i < nrec; i++) {
-    ((uint64_t*)pm)[i] = recs[i].n_match; ((uint64_t*)pn)[i] = recs[i].n; ((int64_t*)plo)[i] = recs[i].min; ((int64_t*)phi)[i] = recs[i].max;
-    ((uint64_t*)psl)[i] = recs[i].sum_lo; ((int64_t*)psh)[i] = recs[i].sum_hi;
-  }
-  napi_value out; NAPI_OK(napi_create_object(env, &out));
-  napi_set_named_property(env, out, "nMatch", a); napi_set_named_property(env, out, "n", b); napi_set_named_property(env, out, "min", c);
-  napi_set_named_property(env, out, "max", d); napi_set_named_property(env, out, "sumLo", e); napi_set_named_property(env, out, "sumHi", f);
-  return out;
-}
-napi_value ScanAggregate(napi_env env, napi_callback_info info) {
-  ARGS(6);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  return aggregate_impl(env, argv, h->ctx, nullptr);
-}
-napi_value CommScanAggregate(napi_env env, napi_callback_info info) {
-  ARGS(6);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  return aggregate_impl(env, argv, nullptr, h->c);
-}
-
-/* Ordered top-k queries (bmx_top.h bmx_scan_top): thin bindings, no logic.
- * scanTop(handle, [[field, lo, hi], ...], desc, after | null, k) / commScanTop(comm, ...) -> {ids: BigUint64Array, vals: BigInt64Array, nEligible}: the first k
- * eligible nodes in (value, id) order; after = [id (BigInt), value] is the cursor. Ids are BigUint64Array entries, as scanFilter delivers them. */
-napi_value top_impl(napi_env env, napi_value* argv, bmx_ctx* ctx, bmx_comm* comm) {
-  uint32_t nt = 0; NAPI_OK(napi_get_array_length(env, argv[1], &nt));
-  if (nt == 0 || nt > 8) { napi_throw_range_error(env, nullptr, "bmx: top needs 1..8 terms"); return nullptr; }
-  bmx_term terms[8];
-  for (uint32_t k = 0; k < nt; k++) {
-    napi_value t, e0, e1, e2;
-    NAPI_OK(napi_get_element(env, argv[1], k, &t));
-    NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1)); NAPI_OK(napi_get_element(env, t, 2, &e2));
-    NAPI_OK(napi_get_value_uint32(env, e0, &terms[k].field));
-    terms[k].reserved = 0;
-    if (!get_i64(env, e1, &terms[k].lo) || !get_i64(env, e2, &terms[k].hi)) return nullptr;
-  }
-  bool desc = false; NAPI_OK(napi_get_value_bool(env, argv[2], &desc));
-  bmx_top_rec cur{0, 0}; bool have_cur = false;
-  napi_valuetype vt; napi_typeof(env, argv[3], &vt);
-  if (vt != napi_null && vt != napi_undefined) {
-    napi_value e0, e1; bool lossless = false;
-    NAPI_OK(napi_get_element(env, argv[3], 0, &e0)); NAPI_OK(napi_get_element(env, argv[3], 1, &e1));
-    NAPI_OK(napi_get_value_bigint_uint64(env, e0, &cur.id, &lossless));
-    if (!get_i64(env, e1, &cur.val)) return nullptr;
-    have_cur = true;
-  }
-  uint32_t k; NAPI_OK(napi_get_value_uint32(env, argv[4], &k));
-  if (k == 0 || k > BMX_TOP_MAX_K) { napi_throw_range_error(env, nullptr, "bmx: k is 1..4096"); return nullptr; }
-  std::vector<bmx_top_rec> recs(k);
-  uint64_t m = 0, ne = 0;
-  const uint32_t flags = desc ? BMX_TOP_DESC : 0u;
-  const int rc = ctx ? bmx_scan_top(ctx, nt, terms, flags, have_cur ? &cur : nullptr, k, recs.data(), &m, &ne, BMX_MEM_HOST)
-                     : bmx_comm_scan_top(comm, nt, terms, flags, have_cur ? &cur : nullptr, k, recs.data(), &m, &ne);
-  if (rc) return ctx ? throw_bmx(env, ctx, rc) : throw_comm(env, comm, rc);
-  void *pi, *pv;
-  napi_value a = make_ta(env, napi_biguint64_array, 8, m, &pi), b = make_ta(env, napi_bigint64_array, 8, m, &pv);
-  for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((int64_t*)pv)[i] = recs[i].val; }
-  napi_value out, nev; NAPI_OK(napi_create_object(env, &out)); napi_create_double(env, (double)ne, &nev);
-  napi_set_named_property(env, out, "ids", a); napi_set_named_property(env, out, "vals", b); napi_set_named_property(env, out, "nEligible", nev);
-  return out;
-}
-napi_value ScanTop(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  Handle* h; if (!get_handle(env, argv[0], &h)) return nullptr;
-  Turn turn(h);   // runs in issue order with the asynchronous merges
-  return top_impl(env, argv, h->ctx, nullptr);
-}
-napi_value CommScanTop(napi_env env, napi_callback_info info) {
-  ARGS(5);
-  CommHandle* h; if (!get_comm(env, argv[0], &h)) return nullptr;
-  std::lock_guard<std::mutex> g(h->mu);
-  return top_impl(env, argv, nullptr, h->c);
+napi_value CommScanFilter(napi_env env, napi_callback_info info) {   // counts first: the shards' indexes have no common size
+  HANDLE(Comm, 2);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "filter", terms); if (!nt) return nullptr;
+  return scan_result(env, h, napi_biguint64_array, [&](uint64_t* m) { return bmx_comm_scan_filter(h->p, nt, terms, nullptr, 0, m); },
+                     [&](void* out, uint64_t m) { uint64_t m2 = 0; return bmx_comm_scan_filter(h->p, nt, terms, (uint64_t*)out, m, &m2); });
 }
 
 napi_value Init(napi_env env, napi_value exports) {
   struct { const char* name; napi_callback fn; } fns[] = {
-      {"abiVersion", AbiVersion}, {"create", Create}, {"destroy", Destroy}, {"mergeBatch", MergeBatch}, {"mergeBatchAsync", MergeBatchAsync}, {"reserve", Reserve}, {"loadRows", LoadRows}, {"putRows", PutRows}, {"hostColumns", HostColumns}, {"scanRangePos", ScanRangePos}, {"indexIds", IndexIds}, {"commPutRows", CommPutRows},
-      {"getRows", GetRows}, {"rowCount", RowCount}, {"dumpRows", DumpRows}, {"indexBuild", IndexBuild}, {"indexDrop", IndexDrop}, {"indexSetOrdered", IndexSetOrdered}, {"indexOrderedInfo", IndexOrderedInfo},
-      {"indexSize", IndexSize}, {"indexRefreshCounts", IndexRefreshCounts}, {"scanRange", ScanRange}, {"scanCount", ScanCount}, {"scanFilter", ScanFilter}, {"info", Info},
-      {"vcCreate", VcCreate}, {"vcDestroy", VcDestroy}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows}, {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}, {"ownersOf", OwnersOf},
-      {"commCreate", CommCreate}, {"commDestroy", CommDestroy}, {"commMergeBatch", CommMergeBatch}, {"commLoadRows", CommLoadRows}, {"commGetRows", CommGetRows},
-      {"commRowCount", CommRowCount}, {"commDumpRows", CommDumpRows}, {"digest", Digest}, {"exportRows", ExportRows}, {"commDigest", CommDigest}, {"commExportRows", CommExportRows}, {"commIndexBuild", CommIndexBuild}, {"commIndexSetOrdered", CommIndexSetOrdered}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize},
-      {"commScanRange", CommScanRange}, {"commScanCount", CommScanCount}, {"commScanFilter", CommScanFilter}, {"scanAggregate", ScanAggregate}, {"commScanAggregate", CommScanAggregate}, {"scanTop", ScanTop}, {"commScanTop", CommScanTop}};
+      {"abiVersion", AbiVersion}, {"ownersOf", OwnersOf}, {"hostColumns", HostColumns},
+      {"create", Create}, {"destroy", Destroy<Engine>}, {"mergeBatch", MergeBatch}, {"mergeBatchAsync", MergeBatchAsync}, {"reserve", Reserve}, {"indexDrop", IndexDrop},
+      {"indexOrderedInfo", IndexOrderedInfo}, {"indexSize", IndexSize}, {"indexRefreshCounts", IndexRefreshCounts}, {"scanRangePos", ScanRangePos}, {"indexIds", IndexIds},
+      {"scanFilter", ScanFilter}, {"info", Info},
+      {"loadRows", StoreRows<Engine, false>}, {"putRows", StoreRows<Engine, true>}, {"getRows", GetRows<Engine>}, {"rowCount", RowCount<Engine>}, {"dumpRows", DumpRows<Engine>},
+      {"indexBuild", IndexBuild<Engine>}, {"indexSetOrdered", IndexSetOrdered<Engine>}, {"scanRange", ScanRange<Engine>}, {"scanCount", ScanCount<Engine>}, {"digest", Digest<Engine>},
+      {"exportRows", ExportRows<Engine>}, {"scanAggregate", ScanAggregate<Engine>}, {"scanTop", ScanTop<Engine>},
+      {"commLoadRows", StoreRows<Comm, false>}, {"commPutRows", StoreRows<Comm, true>}, {"commGetRows", GetRows<Comm>}, {"commRowCount", RowCount<Comm>}, {"commDumpRows", DumpRows<Comm>},
+      {"commIndexBuild", IndexBuild<Comm>}, {"commIndexSetOrdered", IndexSetOrdered<Comm>}, {"commScanRange", ScanRange<Comm>}, {"commScanCount", ScanCount<Comm>}, {"commDigest", Digest<Comm>},
+      {"commExportRows", ExportRows<Comm>}, {"commScanAggregate", ScanAggregate<Comm>}, {"commScanTop", ScanTop<Comm>},
+      {"commCreate", CommCreate}, {"commDestroy", Destroy<Comm>}, {"commMergeBatch", CommMergeBatch}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize}, {"commScanFilter", CommScanFilter},
+      {"vcCreate", VcCreate}, {"vcDestroy", Destroy<Vc>}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows},
+      {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}};
   for (auto& f : fns) {
     napi_value v;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v) != napi_ok) return nullptr;
