@@ -45,6 +45,9 @@ EXPORTS = [
 # include/bmx_top.h: additions to the ABI that bmx.h does not declare
 EXPORTS_TOP = ["bmx_scan_top", "bmx_comm_scan_top"]
 
+# include/bmx_vc_sync.h: replica reconciliation of the vector-clock table, likewise
+EXPORTS_VC_SYNC = ["bmx_vc_rec_digest", "bmx_vc_info", "bmx_vc_digest", "bmx_vc_frontier", "bmx_vc_export_rows", "bmx_vc_merge_records"]
+
 
 class BmxError(RuntimeError):
     def __init__(self, code, msg):
@@ -130,6 +133,20 @@ class Info(C.Structure):
 
 
 DELTA_REC_DTYPE = np.dtype([("id", "<u8"), ("field", "<u4"), ("aux", "<u4"), ("ts", "<i8"), ("val", "<i8")])
+
+
+class VcRec(C.Structure):
+    """bmx_vc_rec: one row of a K-writer table as a delta (64 bytes, include/bmx_vc_sync.h)"""
+    _fields_ = [("id", C.c_uint64), ("field", C.c_uint32), ("aux", C.c_uint32), ("val", C.c_int64), ("state", C.c_uint32), ("keyset", C.c_uint32), ("clock", C.c_uint32 * 8)]
+
+
+VC_REC_DTYPE = np.dtype([("id", "<u8"), ("field", "<u4"), ("aux", "<u4"), ("val", "<i8"), ("state", "<u4"), ("keyset", "<u4"), ("clock", "<u4", (8,))])
+
+
+class VcTableInfo(C.Structure):
+    """bmx_vc_table_info (48 bytes)"""
+    _fields_ = [("n_slots", C.c_uint64), ("n_rows", C.c_uint64), ("capacity_rows", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("k_writers", C.c_uint32), ("local_writer", C.c_uint32), ("device", C.c_uint32), ("reserved", C.c_uint32)]
 
 # OR-ed into the flags of every Engine this process creates
 DEFAULT_CTX_FLAGS = int(os.environ.get("BMX_CTX_FLAGS", "0"), 0)
@@ -266,6 +283,12 @@ def load_library():
     L.bmx_vc_keyset_dense.argtypes = [C.c_uint32]; L.bmx_vc_keyset_dense.restype = C.c_uint32
     L.bmx_vc_set_stream.argtypes = [vp, vp]; L.bmx_vc_set_stream.restype = i32
     L.bmx_vc_sync.argtypes = [vp]; L.bmx_vc_sync.restype = i32
+    L.bmx_vc_rec_digest.argtypes = [vp]; L.bmx_vc_rec_digest.restype = u64
+    L.bmx_vc_info.argtypes = [vp, C.POINTER(VcTableInfo)]; L.bmx_vc_info.restype = i32
+    L.bmx_vc_digest.argtypes = [vp, u32, u32, vp, vp, i32]; L.bmx_vc_digest.restype = i32
+    L.bmx_vc_frontier.argtypes = [vp, vp, i32]; L.bmx_vc_frontier.restype = i32
+    L.bmx_vc_export_rows.argtypes = [vp, vp, u32, vp, u32, vp, u64, vp, i32]; L.bmx_vc_export_rows.restype = i32
+    L.bmx_vc_merge_records.argtypes = [vp, u64, vp, vp, vp, vp, i32]; L.bmx_vc_merge_records.restype = i32
     _lib = L
     return L
 
@@ -916,6 +939,7 @@ class EngineVC:
             raise BmxError(rc, (self.L.bmx_vc_last_error(None) or b"").decode())
         self.h = h
         self.K = int(k_writers)
+        self.device = int(device)
 
     def _chk(self, rc):
         if rc < 0:
@@ -996,6 +1020,82 @@ class EngineVC:
     def sync(self):
         self._chk(self.L.bmx_vc_sync(self.h))
 
+    # ---- replica reconciliation (include/bmx_vc_sync.h; bmx/replica.py pull_vc / reconcile_vc drive it) ----
+    def info(self):
+        out = VcTableInfo()
+        self._chk(self.L.bmx_vc_info(self.h, C.byref(out)))
+        return out
+
+    def digest(self, log2_buckets=10):
+        """-> (sums u64[2^L], counts u64[2^L]): per-bucket sum of the row digests (vc_rows_digest) and number of rows; counts.sum() == row_count()"""
+        B = 1 << int(log2_buckets)
+        sums = np.zeros(B, np.uint64); counts = np.zeros(B, np.uint64)
+        self._chk(self.L.bmx_vc_digest(self.h, int(log2_buckets), 0, _ptr(sums), _ptr(counts), MEM_HOST))
+        return sums, counts
+
+    def digest_dev(self, log2_buckets, sums, counts):
+        """same into device memory (u64[2^L] each); enqueue-only"""
+        self._chk(self.L.bmx_vc_digest(self.h, int(log2_buckets), 0, _ptr(sums), _ptr(counts), MEM_DEVICE))
+
+    def frontier(self):
+        """-> u32[8]: the table's version vector, the component-wise maximum of its rows' clocks (zeros behind K and for an empty table)"""
+        out = np.zeros(8, np.uint32)
+        self._chk(self.L.bmx_vc_frontier(self.h, _ptr(out), MEM_HOST))
+        return out
+
+    def frontier_dev(self, out8):
+        self._chk(self.L.bmx_vc_frontier(self.h, _ptr(out8), MEM_DEVICE))
+
+    @staticmethod
+    def _frontier_words(frontier):
+        if frontier is None:
+            return None
+        f = np.zeros(8, np.uint32)
+        v = _np(frontier, np.uint32)
+        if len(v) > 8:
+            raise ValueError("a frontier has at most 8 components")
+        f[:len(v)] = v
+        return f
+
+    def export_rows(self, frontier=None, log2_buckets=0, bucket_bits=None, cap=None, out=None):
+        """-> (records, n): the rows whose bucket's bit is set (bucket_bits: u64 words, None = every bucket) and, with a frontier (up to 8 u32), whose clock
+        exceeds it in some component, as VC_REC_DTYPE records in slot order; n = number of matches, len(records) = min(n, cap). cap=None: everything (one
+        counting call first). out: a VC_REC_DTYPE array to fill (e.g. in a HostBuffer) — its length is the cap and the result a view of it."""
+        bits = _bucket_words(bucket_bits, log2_buckets)
+        fr = self._frontier_words(frontier)
+        m = C.c_uint64()
+        if out is not None:
+            if out.dtype != VC_REC_DTYPE or not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a contiguous VC_REC_DTYPE array")
+            cap = len(out)
+        elif cap is None:
+            self._chk(self.L.bmx_vc_export_rows(self.h, _ptr(fr), int(log2_buckets), _ptr(bits), 0, None, 0, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+            cap = m.value
+        recs = out if out is not None else np.zeros(int(cap), VC_REC_DTYPE)
+        self._chk(self.L.bmx_vc_export_rows(self.h, _ptr(fr), int(log2_buckets), _ptr(bits), 0, _ptr(recs) if cap else None, int(cap), C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+        return recs[:min(m.value, int(cap))], m.value
+
+    def export_rows_dev(self, out, cap, n_out, frontier=None, log2_buckets=0, bucket_bits=None):
+        """same with device memory: out = room for cap 64-byte records (None: count only), n_out = one u64, bucket_bits = device u64 words or None; the frontier
+        stays a host vector; enqueue-only"""
+        self._chk(self.L.bmx_vc_export_rows(self.h, _ptr(self._frontier_words(frontier)), int(log2_buckets), _ptr(bucket_bits), 0, _ptr(out), int(cap), _ptr(n_out), MEM_DEVICE))
+
+    def dump_rows(self):
+        """every row as VC_REC_DTYPE records, in slot order"""
+        return self.export_rows()[0]
+
+    def merge_records(self, recs):
+        """merge_batch over the records' columns (id, field, clock[:K], keyset, val) -> (flags uint8[n], updated uint32[])"""
+        recs = np.ascontiguousarray(recs, VC_REC_DTYPE)
+        n = len(recs)
+        flags = np.zeros(n, np.uint8); upd = np.zeros(max(n, 1), np.uint32); nu = C.c_uint64()
+        self._chk(self.L.bmx_vc_merge_records(self.h, n, _ptr(recs) if n else None, _ptr(upd), C.cast(C.byref(nu), C.c_void_p), _ptr(flags) if n else None, MEM_HOST))
+        return flags, upd[: nu.value].copy()
+
+    def merge_records_dev(self, n, recs, updated=None, n_updated=None, flags=None):
+        """device-pointer form: recs = n 64-byte records in device memory; enqueue-only, errors are reported by sync()"""
+        self._chk(self.L.bmx_vc_merge_records(self.h, int(n), _ptr(recs), _ptr(updated), _ptr(n_updated), _ptr(flags), MEM_DEVICE))
+
 
 KEYSET_NONE = 0xFFFFFFFF
 
@@ -1017,6 +1117,30 @@ def keyset_writers(ks):
             break
         out.append(w)
     return out
+
+
+def vc_rows_digest(id, field, clocks8, keysets, state, val, summed=False):
+    """The row digest of include/bmx_vc_sync.h, restated in numpy: eight chained splitmix64 over val, keyset | state << 32, the eight clock components in
+    pairs, field, id. clocks8: (n, k) u32 with k <= 8 (padded with zeros). -> u64[n], or with summed=True their sum mod 2^64 as a Python int."""
+    u = np.uint64
+    id = np.asarray(id, u); n = len(id)
+    c = np.zeros((n, 8), u)
+    if n:
+        cl = np.asarray(clocks8, np.uint32).reshape(n, -1)
+        c[:, :cl.shape[1]] = cl
+    with np.errstate(over="ignore"):
+        def sm(x):
+            z = x + u(0x9e3779b97f4a7c15)
+            z = (z ^ (z >> u(30))) * u(0xbf58476d1ce4e5b9)
+            z = (z ^ (z >> u(27))) * u(0x94d049bb133111eb)
+            return z ^ (z >> u(31))
+        h = sm(np.asarray(val, np.int64).astype(u))
+        h = sm(h ^ (np.asarray(keysets, np.uint32).astype(u) | (np.asarray(state, np.uint32).astype(u) << u(32))))
+        for i in range(4):
+            h = sm(h ^ (c[:, 2 * i] | (c[:, 2 * i + 1] << u(32))))
+        h = sm(h ^ np.asarray(field, np.uint32).astype(u))
+        d = sm(h ^ id)
+        return int(d.sum(dtype=u)) if summed else d
 
 
 def owner_of(ids, nshards):

@@ -9,7 +9,7 @@ An endpoint is an Engine or a Comm. Nothing is computed here but the comparison 
 """
 import numpy as np
 
-from . import Engine, INSERT_DELTA, MAX_BATCH, VAL_DELETED
+from . import Engine, EngineVC, INSERT_DELTA, MAX_BATCH, VAL_DELETED, VC_REC_DTYPE
 
 
 def diff_buckets(dig_a, dig_b):
@@ -94,3 +94,60 @@ def pull(dst, src, L=10, since=0):
 def reconcile(a, b, L=10, since=0):
     """pull both ways; afterwards a and b hold the join of their states. -> (pull(a <- b), pull(b <- a))"""
     return pull(a, b, L, since), pull(b, a, L, since)
+
+
+# ---- the vector-clock table (include/bmx_vc_sync.h) ----
+
+def _ship_device_vc(dst, src, L, frontier, bits):
+    """src's rows of the chosen buckets -> dst, device to device: the 64-byte records never leave the GPU. -> (rows shipped, rows updated)"""
+    import torch
+    dev = torch.device("cuda", int(src.device))
+    d_bits = torch.from_numpy(bits.view(np.int64)).to(dev)
+    d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    src.export_rows_dev(None, 0, d_n, frontier=frontier, log2_buckets=L, bucket_bits=d_bits)
+    src.sync()
+    n = int(d_n.item())
+    if n == 0:
+        return 0, 0
+    recs = torch.empty(8 * n, dtype=torch.int64, device=dev)          # n records of 64 bytes
+    src.export_rows_dev(recs, n, d_n, frontier=frontier, log2_buckets=L, bucket_bits=d_bits)
+    src.sync()                                                          # the tables run on streams of their own
+    updated = 0
+    for o in range(0, n, MAX_BATCH):
+        dst.merge_records_dev(min(MAX_BATCH, n - o), recs.data_ptr() + 64 * o, n_updated=d_n)
+        dst.sync()
+        updated += int(d_n.item())
+    return n, updated
+
+
+def pull_vc(dst, src, L=10, frontier=None):
+    """Bring into `dst` (an EngineVC) what `src` has and `dst` holds differently, for the buckets (2^L of them) whose digests differ: src's rows of those
+    buckets — with a frontier, only those whose clock exceeds it in some component — are merged into dst through its own resolve() (merge_records).
+    Device to device when both tables are on one GPU, through host memory otherwise. -> {buckets_differing, rows_shipped, rows_updated}"""
+    bits = diff_buckets(dst.digest(L), src.digest(L))
+    out = {"buckets_differing": bucket_count(bits), "rows_shipped": 0, "rows_updated": 0}
+    if out["buckets_differing"] == 0:
+        return out
+    if isinstance(dst, EngineVC) and isinstance(src, EngineVC) and dst.device == src.device:
+        out["rows_shipped"], out["rows_updated"] = _ship_device_vc(dst, src, L, frontier, bits)
+    else:
+        recs, n = src.export_rows(frontier=frontier, log2_buckets=L, bucket_bits=bits)
+        assert recs.dtype == VC_REC_DTYPE
+        for o in range(0, len(recs), MAX_BATCH):
+            out["rows_updated"] += len(dst.merge_records(recs[o:o + MAX_BATCH])[1])
+        out["rows_shipped"] = int(n)
+    return out
+
+
+def reconcile_vc(a, b, L=10, rounds=3):
+    """pull_vc(a <- b) then pull_vc(b <- a), round after round, until a round finds no differing bucket (at most `rounds`). The join is the reference's
+    resolve(), whose first write stores {local: 2} instead of the incoming clock (src/bullet-crt.js:172-185): one round does not always equalise two tables.
+    -> the per-round records [(pull_vc(a <- b), pull_vc(b <- a)), ...]; the tables are equal iff the last round's buckets_differing are both 0."""
+    out = []
+    for _ in range(int(rounds)):
+        r = (pull_vc(a, b, L), pull_vc(b, a, L))
+        out.append(r)
+        if r[0]["buckets_differing"] == 0 and r[1]["buckets_differing"] == 0:
+            break
+    return out

@@ -894,3 +894,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_top.inc"
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"
+#include "bmx_vc_sync.inc"   // (behind everything that was here before it: its kernels follow the others in the code object)

@@ -2,6 +2,7 @@
 // Included at the end of bmx.hip (one translation unit: the kernels in the shared headers are not inline).
 // Host buffers only; every call is synchronous. No CPU path: fails without a GPU.
 #include "vc_kernels.h"
+#include "../../include/bmx_vc_sync.h"   // (bmx_vc_rec: the handle keeps the staging of bmx_vc_sync.inc)
 
 namespace {
 
@@ -26,6 +27,16 @@ struct VcScanScratch {
   uint64_t* scan_out = nullptr; uint64_t scan_cap = 0;
   void release() { dev_free(sel_counts); dev_free(scan_out); scan_cap = 0; }
 };
+// Scratch of the reconciliation sweeps (bmx_vc_sync.inc): what a BMX_MEM_HOST caller's digest vectors, version vector, bucket set and records pass through.
+// Allocated by the first call that needs it, grow-only.
+struct VcSyncScratch {
+  unsigned long long* dig = nullptr;         // 2 x 2^16 words: sums and counts
+  unsigned long long* bits = nullptr;        // 2^16 bits
+  uint32_t* frontier = nullptr;              // 8 words
+  bmx_vc_rec* recs = nullptr; uint64_t recs_cap = 0;
+  int cus = 0;                               // compute units of the device (the sweeps' grids), looked up by the first sweep
+  void release() { dev_free(dig); dev_free(bits); dev_free(frontier); dev_free(recs); recs_cap = 0; }
+};
 
 }  // namespace
 
@@ -45,8 +56,9 @@ struct bmx_vc {
   uint64_t rows_ub = 0;                      // upper bound while device-pointer batches are in flight
   VcWorkspace ws;
   VcScanScratch scan;
+  VcSyncScratch sync;
   std::string err;
-  void release() { dev_free(slots); dev_free(row_count); dev_free(n_out); dev_free(status); dev_free(shard_dummy); dev_free(lctl); ws.release(); scan.release(); }
+  void release() { dev_free(slots); dev_free(row_count); dev_free(n_out); dev_free(status); dev_free(shard_dummy); dev_free(lctl); ws.release(); scan.release(); sync.release(); }
 };
 
 namespace {

@@ -569,6 +569,8 @@ int bmx_vc_merge_batch_ks_dev(bmx_vc* t, uint64_t n, const uint64_t* id, const u
                               const int64_t* val, uint32_t* updated_idx, uint64_t* n_updated, uint8_t* flags);
 int bmx_vc_set_stream(bmx_vc* t, void* hip_stream);
 int bmx_vc_sync(bmx_vc* t);
+/* Replica reconciliation of this table — bmx_vc_info, bmx_vc_digest, bmx_vc_frontier, bmx_vc_export_rows, bmx_vc_merge_records — is declared in bmx_vc_sync.h
+ * (include it next to this header): an addition to ABI 4 with a header of its own. */
 
 /* ---- direct exchange between PROCESSES, one per GPU (what `bench.py --gpus N` runs; replaces the gossip fan-out of src/bullet-network.js:378-418
  * inside a node, like the all-to-all it supersedes): every rank owns receive slabs other ranks write into.
