@@ -26,6 +26,7 @@ FLAG_INCOMING, FLAG_CURRENT, FLAG_HISTORICAL = 1, 2, 4
 MAX_BATCH = 1 << 24
 AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
+LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
@@ -47,6 +48,9 @@ EXPORTS_TOP = ["bmx_scan_top", "bmx_comm_scan_top"]
 
 # include/bmx_vc_sync.h: replica reconciliation of the vector-clock table, likewise
 EXPORTS_VC_SYNC = ["bmx_vc_rec_digest", "bmx_vc_info", "bmx_vc_digest", "bmx_vc_frontier", "bmx_vc_export_rows", "bmx_vc_merge_records"]
+
+# include/bmx_where.h: boolean filters, likewise
+EXPORTS_WHERE = ["bmx_scan_where", "bmx_comm_scan_where"]
 
 
 class BmxError(RuntimeError):
@@ -125,6 +129,19 @@ def top_merge(lists, k, desc=False):
     a = np.concatenate(parts)
     order = np.lexsort((a["id"], -a["val"] if desc else a["val"]))     # (|val| <= 2^53 - 1: the negation is exact)
     return a[order[:int(k)]]
+
+
+class Lit(C.Structure):
+    """bmx_lit: one literal of a bmx_scan_where program (24 bytes, the layout of bmx_term); flags: LIT_NOT"""
+    _fields_ = [("field", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+def _where_args(base, clauses):
+    """clauses: a list of lists of (field, lo, hi) or (field, lo, hi, negated) -> (base_field, nclauses, clause_len, lits)"""
+    flat = [t for c in clauses for t in c]
+    lens = (C.c_uint32 * max(len(clauses), 1))(*[len(c) for c in clauses])
+    lits = (Lit * max(len(flat), 1))(*[Lit(int(t[0]), LIT_NOT if len(t) > 3 and t[3] else 0, int(t[1]), int(t[2])) for t in flat])
+    return (int(base), len(clauses), lens, lits)
 
 
 class Info(C.Structure):
@@ -226,6 +243,8 @@ def load_library():
     L.bmx_comm_scan_aggregate.argtypes = [vp, u32, C.POINTER(Term), u32, u32, i64, u32, vp]; L.bmx_comm_scan_aggregate.restype = i32
     L.bmx_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp, i32]; L.bmx_scan_top.restype = i32
     L.bmx_comm_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp]; L.bmx_comm_scan_top.restype = i32
+    L.bmx_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp, i32]; L.bmx_scan_where.restype = i32
+    L.bmx_comm_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp]; L.bmx_comm_scan_where.restype = i32
     L.bmx_partition_by_owner.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp]; L.bmx_partition_by_owner.restype = i32
     L.bmx_partition_by_owner_slabs.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp]; L.bmx_partition_by_owner_slabs.restype = i32
     L.bmx_partition_scatter.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, u32, u64]; L.bmx_partition_scatter.restype = i32
@@ -589,6 +608,20 @@ class Engine:
         self._chk(self.L.bmx_scan_top(self.h, *_top_args(terms, k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p), C.cast(C.byref(ne), C.c_void_p), MEM_HOST))
         return out[:m.value].copy(), ne.value
 
+    def scan_where(self, base, clauses, cap=None, count_only=False):
+        """Boolean filter (bmx_where.h): the nodes holding data in field `base` for which some clause of `clauses` has all of its literals true; a literal is
+        (field, lo, hi) or (field, lo, hi, negated), the negated one being true for an absent or tombstoned field too. -> ids in index order of `base`
+        (at most cap of them). count_only (as Comm.scan_where has it): -> the number of matches, no id is fetched."""
+        args = _where_args(base, clauses)
+        m = C.c_uint64()
+        if count_only:
+            self._chk(self.L.bmx_scan_where(self.h, *args, None, 0, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+            return m.value
+        cap = self.index_size(base) if cap is None else cap
+        out = np.zeros(max(cap, 1), np.uint64)
+        self._chk(self.L.bmx_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
+        return out[:min(m.value, cap)].copy()
+
     def info(self):
         i = Info()
         self._chk(self.L.bmx_get_info(self.h, C.byref(i)))
@@ -723,6 +756,10 @@ class Engine:
         """scan_top into device memory (`out`: room for k records of 16 bytes; n_out, n_eligible: one uint64 each, or None); enqueue-only. The cursor is
         host data either way."""
         self._chk(self.L.bmx_scan_top(self.h, *_top_args(terms, k, desc, after), _ptr(out), _ptr(n_out), _ptr(n_eligible), MEM_DEVICE))
+
+    def scan_where_dev(self, base, clauses, out, cap, n_out):
+        """scan_where into device memory (`out`: room for cap ids, or None to count; n_out: one uint64); enqueue-only. The program is host data."""
+        self._chk(self.L.bmx_scan_where(self.h, *_where_args(base, clauses), _ptr(out), int(cap), _ptr(n_out), MEM_DEVICE))
 
     def scan_range_pos_dev(self, field, lo, hi, out_pos, cap, n_out):
         self._chk(self.L.bmx_scan_range_pos(self.h, int(field), int(lo), int(hi), _ptr(out_pos), int(cap), _ptr(n_out), MEM_DEVICE))
@@ -920,6 +957,18 @@ class Comm:
         cap = m.value
         out = np.zeros(max(cap, 1), np.uint64)
         self._chk(self.L.bmx_comm_scan_filter(self.h, len(terms), arr, _ptr(out), cap, C.byref(m)))
+        return out[:min(m.value, cap)].copy()
+
+    def scan_where(self, base, clauses, count_only=False):
+        """Engine.scan_where over all shards, shard after shard: the set one engine holding the same rows gives. It counts first and then fetches."""
+        args = _where_args(base, clauses)
+        m = C.c_uint64()
+        self._chk(self.L.bmx_comm_scan_where(self.h, *args, None, 0, C.cast(C.byref(m), C.c_void_p)))
+        if count_only:
+            return m.value
+        cap = m.value
+        out = np.zeros(max(cap, 1), np.uint64)
+        self._chk(self.L.bmx_comm_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p)))
         return out[:min(m.value, cap)].copy()
 
 

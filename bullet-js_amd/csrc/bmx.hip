@@ -30,6 +30,7 @@
 #include "view_kernels.h"
 #include "agg_kernels.h"
 #include "top_kernels.h"
+#include "where_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -895,3 +896,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"
 #include "bmx_vc_sync.inc"   // (behind everything that was here before it: its kernels follow the others in the code object)
+#include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls)

@@ -459,15 +459,19 @@ int bmx_comm_index_set_ordered(bmx_comm* c, uint32_t field, uint32_t after_queri
 // Sharded scan (src/bullet-query.js:221-261, 186-210 on a graph split over shards): every shard scans its own rows, the results are
 // concatenated in shard order. Two phases: the scans of ALL shards are enqueued first (each into its context's own result buffer), then the
 // results are fetched shard by shard — N GPUs scan at the same time, and the host waits once per shard for work that is already running.
-static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
+}  // extern "C"
+namespace {
+// (bmx_where.inc sits behind this file in bmx.hip's include list)
+const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, WhereProg* out);
+int where_run(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred);
+template <class Enqueue>   // enqueue(shard context, want, cap): the shard's deferred host-mode scan
+int comm_scan_with(bmx_comm* c, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, Enqueue enqueue) {
   if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   DevGuard guard;
   uint64_t* want = (out_ids && cap) ? out_ids : nullptr;
   uint64_t tot = 0;
   const int rc = comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) {
-      return terms ? scan_filter_impl(x, nterms, terms, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true) : scan_range_impl(x, field, lo, hi, want, cap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
-    },
+    [&](uint32_t, bmx_ctx* x) { return enqueue(x, want, cap); },
     [&](uint32_t, bmx_ctx* x) {
       uint64_t m = 0;
       const uint64_t room = (want && cap > tot) ? cap - tot : 0;
@@ -478,6 +482,13 @@ static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32
   if (rc) return rc;
   if (n_out) *n_out = tot;
   return BMX_OK;
+}
+}  // namespace
+extern "C" {
+static int comm_scan(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint32_t nterms, const bmx_term* terms, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
+  return comm_scan_with(c, out_ids, cap, n_out, [&](bmx_ctx* x, uint64_t* want, uint64_t wcap) {
+    return terms ? scan_filter_impl(x, nterms, terms, want, wcap, nullptr, BMX_MEM_HOST, /*deferred=*/true) : scan_range_impl(x, field, lo, hi, want, wcap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
+  });
 }
 int bmx_comm_scan_range(bmx_comm* c, uint32_t field, int64_t lo, int64_t hi, uint64_t* out_ids, uint64_t cap, uint64_t* n_out) {
   return comm_scan(c, field, lo, hi, 0, nullptr, out_ids, cap, n_out);
@@ -492,6 +503,17 @@ int bmx_comm_scan_filter(bmx_comm* c, uint32_t nterms, const bmx_term* terms, ui
   if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
   if (nterms == 0 || !terms) return fail(c, BMX_ERR_INVALID, "filter needs 1..8 terms");
   return comm_scan(c, 0, 0, 0, nterms, terms, out_ids, cap, n_out);
+}
+
+// bmx_scan_where over the shards (bmx_where.h, host memory): the program is checked and prepared once, then every shard sweeps its own index of the base field. A node's rows
+// all live on the shard that owns its id, so every literal of a candidate is decided on its own shard.
+int bmx_comm_scan_where(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint64_t* out_ids, uint64_t cap,
+                        uint64_t* n_out) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
+  return comm_scan_with(c, out_ids, cap, n_out, [&](bmx_ctx* x, uint64_t* want, uint64_t wcap) {
+    return where_run(x, base_field, W, want, wcap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
+  });
 }
 
 // bmx_scan_aggregate over the shards (host memory). A node's rows all live on the shard that owns its id, so a node is selected, measured and grouped by one

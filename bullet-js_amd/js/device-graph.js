@@ -125,6 +125,13 @@ class DeviceGraph {
     const after = opts.after === undefined ? null : opts.after;
     return this.comm ? this.native.commScanTop(this.comm, terms, !!opts.desc, after, k >>> 0) : this.native.scanTop(this.handle, terms, !!opts.desc, after, k >>> 0);
   }
+  /* Boolean filter (bmx_scan_where, include/bmx_where.h): the nodes holding data in field `base` for which some clause of clauses has all of its literals
+   * true. clauses: [[[field, lo, hi, not], ...], ...] — a literal is true iff the node's row of field holds data inside lo..hi; with a truthy `not` it is
+   * the exact complement, so true for an absent or deleted field too. -> BigUint64Array of node ids, in index order of `base` (shard after shard). */
+  scanWhere(base, clauses) {
+    if (this.preOp) this.preOp();
+    return this.comm ? this.native.commScanWhere(this.comm, base, clauses) : this.native.scanWhere(this.handle, base, clauses);
+  }
   info() { return this.comm ? { nShards: this.nShards, devices: this.devices, nRows: this.rowCount() } : this.native.info(this.handle); }
   close() {
     if (this.handle) { this.native.destroy(this.handle); this.handle = null; }

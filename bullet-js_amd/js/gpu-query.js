@@ -350,6 +350,99 @@ class GpuQuery {
     return this._nodes(ixs[0], this._ordinals(ixs[0], ids).sort((a, b) => a - b));
   }
 
+  /* "device" / "host" / "absent" (no child carries the field): the kind of the index of (path, field). An index that exists answers, brought up to date as for
+   * any query (work proportional to what was written since). Only a field without an index costs one walk over the children of path; its result is recorded as
+   * an index where that needs no device (host, absent), and by the device build that follows where the query goes to the device. */
+  _fieldKind(path, field) {
+    if (this.indices[GpuQuery.keyOf(path, field)]) {
+      const ix = this._fresh(path, field);
+      return ix.kind === "device" ? "device" : (ix.values && ix.values.length ? "host" : "absent");
+    }
+    const base = this.bullet._getData(path);
+    let kind = "absent";
+    if (typeof base === "object" && base !== null) {
+      for (const v of Object.values(base)) {
+        if (typeof v !== "object" || v === null) continue;
+        const x = v[field];
+        if (x === null || x === undefined) continue;
+        if (!isDeviceInt(x)) { kind = "host"; break; }
+        kind = "device";
+      }
+    }
+    if (kind !== "device") this.index(path, field);      // a host index (empty for "absent"): built from the store, the next query asks it
+    return kind;
+  }
+
+  /**
+   * Boolean filter: OR of AND-clauses over fields of the same child node, with NOT and with defined behaviour for absent fields — the shapes of
+   * filter(path, fn) that an AND of ranges cannot say (docs/querying.md Example 8: `user.active === true && user.age < 30 && user.role !== "admin"`).
+   * clauses: [[{field, min, max, not}, ...], ...]; {field, eq: v} is min = max = v and {field, ne: v} is its negation; a bound left out (or +-Infinity) is
+   * not checked, so {field} alone tests presence and {field, not: true} absence.
+   * opts.over (required) names the field that defines the universe: only children that carry it are candidates — the children filter() would iterate,
+   * provided every child the caller cares about carries it. A literal is true iff the child's field is present (not null / undefined) and inside its bounds;
+   * a negated literal is the exact complement, so it is true for a child WITHOUT the field, as `undefined !== "admin"` is.
+   * When every index involved is an integer index the device answers (bmx_scan_where); when one lives on the host (strings, booleans, objects, fractions)
+   * the same semantics are evaluated over the host mirror, as top() does for host indexes. -> the BulletNodes in the scan order of `over`'s index.
+   * Host cost: the kind of every literal's field comes from its index (O(1) while nothing was written); the FIRST query that names a field without an index
+   * walks the children once to build it, like index(). The host evaluation is one loop over the children that carry `over`.
+   */
+  where(path, clauses, opts = {}) {
+    if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: where needs opts.over, the field that defines the universe");
+    if (!clauses || clauses.length === 0) return [];
+    const open = (x) => x === undefined || x === null || x === Infinity || x === -Infinity;
+    const norm = clauses.map((c) => c.map((t) => {
+      if ("eq" in t) return { field: t.field, min: t.eq, max: t.eq, eq: true, not: !!t.not };
+      if ("ne" in t) return { field: t.field, min: t.ne, max: t.ne, eq: true, not: !t.not };
+      return { field: t.field, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
+    }));
+    const base = this._fresh(path, opts.over);
+    // Which side answers is decided before a DEVICE index of a literal's field is built (it needs the device; the host evaluation below reads the store and
+    // needs none): "device" = every child that carries the field has a safe integer there, "absent" = no child carries it (_fieldKind).
+    const kinds = new Map();
+    for (const c of norm) for (const t of c) if (!kinds.has(t.field)) kinds.set(t.field, this._fieldKind(path, t.field));
+    const onDevice = base.kind === "device" && Array.from(kinds.values()).every((k) => k !== "host");
+    if (onDevice) {
+      this.lastPath = "device";
+      const num = (x) => typeof x === "number" && !Number.isNaN(x);
+      // A field no child carries is decided here: its positive literals are false (their clause goes), its negated ones true (the literal goes); a clause
+      // left without a literal is true for every candidate, which a presence literal on the base field says.
+      const native = [];
+      for (const c of norm) {
+        if (c.some((t) => kinds.get(t.field) === "absent" && !t.not)) continue;
+        const lits = c.filter((t) => kinds.get(t.field) !== "absent").map((t) => {
+          const f = this._fresh(path, t.field).deviceField;
+          // bounds no integer satisfies (a string against an integer field, a fraction as eq): the empty range, whose negation is always true
+          if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not];
+          return [f, Math.ceil(t.min), Math.floor(t.max), t.not];
+        });
+        native.push(lits.length ? lits : [[base.deviceField, -Infinity, Infinity, false]]);
+      }
+      if (native.length === 0) return [];
+      const ids = this.graph.scanWhere(base.deviceField, native);
+      if (base.source === "device") return this._nodesFromIds(ids);
+      return this._nodes(base, this._ordinals(base, ids).sort((a, b) => a - b));
+    }
+    if (!base.paths) {
+      const err = new Error("bmx: where over a device-sourced index needs integer-valued fields on every literal");
+      err.code = "BMX_NOT_DEVICE_INDEX";
+      throw err;
+    }
+    this.lastPath = "host";
+    const store = this.bullet._getData(path);
+    const truth = (child, t) => {
+      const x = child && typeof child === "object" ? child[t.field] : undefined;
+      let pos = x !== null && x !== undefined;
+      if (pos) pos = t.eq ? x === t.min : (t.min === -Infinity || x >= t.min) && (t.max === Infinity || x <= t.max);
+      return pos !== t.not;
+    };
+    const out = [];
+    base.paths.forEach((p, i) => {
+      const child = store[p.slice(path.length + 1)];
+      if (norm.some((c) => c.every((t) => truth(child, t)))) out.push(i);
+    });
+    return this._nodes(base, out);
+  }
+
   /* device indexes of the fields an aggregate names, or BMX_NOT_DEVICE_INDEX exactly where filterWhere throws it */
   _deviceIndexes(path, fields, what) {
     const ixs = fields.map((f) => this._fresh(path, f));

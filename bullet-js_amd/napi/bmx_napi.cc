@@ -22,6 +22,7 @@
 
 #include "bmx.h"
 #include "bmx_top.h"
+#include "bmx_where.h"
 #include "bmx_ticket.h"
 
 namespace {
@@ -506,6 +507,46 @@ template <class Kind> napi_value ScanTop(napi_env env, napi_callback_info info) 
   if (out) for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((int64_t*)pv)[i] = recs[i].val; }
   return out;
 }
+// The engine sweeps once: room for the whole index of `base`, as scanFilter sizes its answer (the sweep is bound by its probes: a count in front would double
+// it). The communicator's shards have no common size: it counts first, then fetches — two sweeps.
+napi_value where_answer(napi_env env, Handle<Engine>* h, uint32_t base, uint32_t nc, const uint32_t* lens, const std::vector<bmx_lit>& lits) {
+  Turn turn(h->q);
+  uint64_t cap = 0; int rc = bmx_index_size(h->p, base, &cap);
+  if (rc) return fail<Engine>(env, h->p, rc);
+  std::vector<uint64_t> tmp(cap ? cap : 1);
+  uint64_t m = 0; rc = bmx_scan_where(h->p, base, nc, lens, lits.data(), tmp.data(), cap, &m, BMX_MEM_HOST);
+  return rc ? fail<Engine>(env, h->p, rc) : copy_ta(env, napi_biguint64_array, (size_t)std::min(m, cap), tmp.data());
+}
+napi_value where_answer(napi_env env, Handle<Comm>* h, uint32_t base, uint32_t nc, const uint32_t* lens, const std::vector<bmx_lit>& lits) {
+  return scan_result(env, h, napi_biguint64_array, [&](uint64_t* m) { return bmx_comm_scan_where(h->p, base, nc, lens, lits.data(), nullptr, 0, m); },
+                     [&](void* out, uint64_t m) { uint64_t m2 = 0; return bmx_comm_scan_where(h->p, base, nc, lens, lits.data(), (uint64_t*)out, m, &m2); });
+}
+/* Boolean filters (bmx_where.h bmx_scan_where): thin bindings, no logic.
+ * scanWhere(handle, base, [[[field, lo, hi, not], ...], ...]) / commScanWhere(comm, ...) -> BigUint64Array: the nodes holding data in field `base` for which some
+ * clause has all of its literals true (not: a truthy fourth entry negates the literal), in index order of `base`. */
+template <class Kind> napi_value ScanWhere(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 3);
+  uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
+  uint32_t nc = 0;
+  if (napi_get_array_length(env, argv[2], &nc) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return nullptr; }
+  if (nc == 0 || nc > BMX_WHERE_MAX_CLAUSES) { napi_throw_range_error(env, nullptr, "bmx: where needs 1..8 clauses"); return nullptr; }
+  uint32_t lens[BMX_WHERE_MAX_CLAUSES]; std::vector<bmx_lit> lits;
+  for (uint32_t c = 0; c < nc; c++) {
+    napi_value cl; NAPI_OK(napi_get_element(env, argv[2], c, &cl));
+    if (napi_get_array_length(env, cl, &lens[c]) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return nullptr; }
+    if (lens[c] == 0 || lens[c] > 8 || lits.size() + lens[c] > BMX_WHERE_MAX_LITS) { napi_throw_range_error(env, nullptr, "bmx: a where clause has 1..8 literals, a program 32 at most"); return nullptr; }
+    for (uint32_t k = 0; k < lens[c]; k++) {
+      napi_value t, e0, e1, e2, e3; bmx_lit L{0, 0, 0, 0}; bool neg = false;
+      NAPI_OK(napi_get_element(env, cl, k, &t)); NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1));
+      NAPI_OK(napi_get_element(env, t, 2, &e2)); NAPI_OK(napi_get_element(env, t, 3, &e3));
+      if (!get_u32(env, e0, &L.field) || !get_i64(env, e1, &L.lo) || !get_i64(env, e2, &L.hi)) return nullptr;
+      NAPI_OK(napi_coerce_to_bool(env, e3, &e3)); NAPI_OK(napi_get_value_bool(env, e3, &neg));
+      L.flags = neg ? BMX_LIT_NOT : 0u;
+      lits.push_back(L);
+    }
+  }
+  return where_answer(env, h, base, nc, lens, lits);
+}
 
 // ---- the engine alone -----------------------------------------------------------------------------------------------------------------
 napi_value Create(napi_env env, napi_callback_info info) {
@@ -826,10 +867,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"scanFilter", ScanFilter}, {"info", Info},
       {"loadRows", StoreRows<Engine, false>}, {"putRows", StoreRows<Engine, true>}, {"getRows", GetRows<Engine>}, {"rowCount", RowCount<Engine>}, {"dumpRows", DumpRows<Engine>},
       {"indexBuild", IndexBuild<Engine>}, {"indexSetOrdered", IndexSetOrdered<Engine>}, {"scanRange", ScanRange<Engine>}, {"scanCount", ScanCount<Engine>}, {"digest", Digest<Engine>},
-      {"exportRows", ExportRows<Engine>}, {"scanAggregate", ScanAggregate<Engine>}, {"scanTop", ScanTop<Engine>},
+      {"exportRows", ExportRows<Engine>}, {"scanAggregate", ScanAggregate<Engine>}, {"scanTop", ScanTop<Engine>}, {"scanWhere", ScanWhere<Engine>},
       {"commLoadRows", StoreRows<Comm, false>}, {"commPutRows", StoreRows<Comm, true>}, {"commGetRows", GetRows<Comm>}, {"commRowCount", RowCount<Comm>}, {"commDumpRows", DumpRows<Comm>},
       {"commIndexBuild", IndexBuild<Comm>}, {"commIndexSetOrdered", IndexSetOrdered<Comm>}, {"commScanRange", ScanRange<Comm>}, {"commScanCount", ScanCount<Comm>}, {"commDigest", Digest<Comm>},
-      {"commExportRows", ExportRows<Comm>}, {"commScanAggregate", ScanAggregate<Comm>}, {"commScanTop", ScanTop<Comm>},
+      {"commExportRows", ExportRows<Comm>}, {"commScanAggregate", ScanAggregate<Comm>}, {"commScanTop", ScanTop<Comm>}, {"commScanWhere", ScanWhere<Comm>},
       {"commCreate", CommCreate}, {"commDestroy", Destroy<Comm>}, {"commMergeBatch", CommMergeBatch}, {"commIndexDrop", CommIndexDrop}, {"commIndexSize", CommIndexSize}, {"commScanFilter", CommScanFilter},
       {"vcCreate", VcCreate}, {"vcDestroy", Destroy<Vc>}, {"vcLoadRows", VcLoadRows}, {"vcMergeBatch", VcMergeBatch}, {"vcMergeBatchAsync", VcMergeBatchAsync}, {"vcGetRows", VcGetRows},
       {"vcRowCount", VcRowCount}, {"vcScanRange", VcScanRange}};
