@@ -27,6 +27,7 @@ MAX_BATCH = 1 << 24
 AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
+WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2   # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
@@ -51,6 +52,9 @@ EXPORTS_VC_SYNC = ["bmx_vc_rec_digest", "bmx_vc_info", "bmx_vc_digest", "bmx_vc_
 
 # include/bmx_where.h: boolean filters, likewise
 EXPORTS_WHERE = ["bmx_scan_where", "bmx_comm_scan_where"]
+
+# include/bmx_watch.h: standing queries, likewise
+EXPORTS_WATCH = ["bmx_watch_create", "bmx_watch_poll", "bmx_watch_destroy", "bmx_comm_watch_create", "bmx_comm_watch_poll", "bmx_comm_watch_destroy"]
 
 
 class BmxError(RuntimeError):
@@ -142,6 +146,25 @@ def _where_args(base, clauses):
     lens = (C.c_uint32 * max(len(clauses), 1))(*[len(c) for c in clauses])
     lits = (Lit * max(len(flat), 1))(*[Lit(int(t[0]), LIT_NOT if len(t) > 3 and t[3] else 0, int(t[1]), int(t[2])) for t in flat])
     return (int(base), len(clauses), lens, lits)
+
+
+class WatchRes(C.Structure):
+    """bmx_watch_res: what one bmx_watch_poll found (32 bytes); flags: WATCH_RESET, WATCH_OVERFLOW"""
+    _fields_ = [("n_entered", C.c_uint64), ("n_left", C.c_uint64), ("n_match", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WatchPoll:
+    """One poll of a watch: entered / left (uint64 ids in index order, cut at the caps), the true counts n_entered / n_left, n_match = size of the answer now,
+    reset (the lists are relative to the empty set: replace yours with `entered`), overflow (a list did not fit: nothing was committed, poll again with more room)."""
+    __slots__ = ("entered", "left", "n_entered", "n_left", "n_match", "reset", "overflow")
+
+    def __init__(self, res, entered, left):
+        self.n_entered, self.n_left, self.n_match = int(res.n_entered), int(res.n_left), int(res.n_match)
+        self.reset, self.overflow = bool(res.flags & WATCH_RESET), bool(res.flags & WATCH_OVERFLOW)
+        self.entered, self.left = entered[:min(self.n_entered, len(entered))].copy(), left[:min(self.n_left, len(left))].copy()
+
+    def __repr__(self):
+        return "WatchPoll(+%d -%d, %d match%s%s)" % (self.n_entered, self.n_left, self.n_match, ", reset" if self.reset else "", ", overflow" if self.overflow else "")
 
 
 class Info(C.Structure):
@@ -245,6 +268,12 @@ def load_library():
     L.bmx_comm_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp]; L.bmx_comm_scan_top.restype = i32
     L.bmx_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp, i32]; L.bmx_scan_where.restype = i32
     L.bmx_comm_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp]; L.bmx_comm_scan_where.restype = i32
+    L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
+    L.bmx_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp, i32]; L.bmx_watch_poll.restype = i32
+    L.bmx_watch_destroy.argtypes = [vp, u32]; L.bmx_watch_destroy.restype = i32
+    L.bmx_comm_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_comm_watch_create.restype = i32
+    L.bmx_comm_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp]; L.bmx_comm_watch_poll.restype = i32
+    L.bmx_comm_watch_destroy.argtypes = [vp, u32]; L.bmx_comm_watch_destroy.restype = i32
     L.bmx_partition_by_owner.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp]; L.bmx_partition_by_owner.restype = i32
     L.bmx_partition_by_owner_slabs.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp]; L.bmx_partition_by_owner_slabs.restype = i32
     L.bmx_partition_scatter.argtypes = [vp, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, u32, u64]; L.bmx_partition_scatter.restype = i32
@@ -387,6 +416,7 @@ class Engine:
             raise BmxError(rc, (self.L.bmx_last_error(None) or b"").decode())
         self.h = h
         self.device = device
+        self._watch_base = {}        # watch id -> base field (watch_poll sizes its default lists from that field's index)
 
     def _chk(self, rc):
         if rc < 0:
@@ -622,6 +652,28 @@ class Engine:
         self._chk(self.L.bmx_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
         return out[:min(m.value, cap)].copy()
 
+    def watch_create(self, base, clauses):
+        """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
+        w = C.c_uint32()
+        self._chk(self.L.bmx_watch_create(self.h, *_where_args(base, clauses), C.byref(w)))
+        self._watch_base[w.value] = int(base)
+        return w.value
+
+    def watch_poll(self, w, cap_entered=None, cap_left=None):
+        """What changed in the watch's answer since its last committed poll -> WatchPoll. A cap of None is room for the whole index (such a poll always commits)."""
+        if cap_entered is None or cap_left is None:
+            base = self._watch_base.get(int(w))
+            n = self.index_size(base) if base is not None else 0       # (an unknown id: the library refuses it below)
+            cap_entered = n if cap_entered is None else cap_entered
+            cap_left = n if cap_left is None else cap_left
+        ent, lft, res = np.zeros(max(int(cap_entered), 1), np.uint64), np.zeros(max(int(cap_left), 1), np.uint64), WatchRes()
+        self._chk(self.L.bmx_watch_poll(self.h, int(w), _ptr(ent), int(cap_entered), _ptr(lft), int(cap_left), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return WatchPoll(res, ent[:int(cap_entered)], lft[:int(cap_left)])
+
+    def watch_destroy(self, w):
+        self._chk(self.L.bmx_watch_destroy(self.h, int(w)))
+        self._watch_base.pop(int(w), None)
+
     def info(self):
         i = Info()
         self._chk(self.L.bmx_get_info(self.h, C.byref(i)))
@@ -760,6 +812,11 @@ class Engine:
     def scan_where_dev(self, base, clauses, out, cap, n_out):
         """scan_where into device memory (`out`: room for cap ids, or None to count; n_out: one uint64); enqueue-only. The program is host data."""
         self._chk(self.L.bmx_scan_where(self.h, *_where_args(base, clauses), _ptr(out), int(cap), _ptr(n_out), MEM_DEVICE))
+
+    def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
+        """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
+        decision whether the poll commits is taken on the device."""
+        self._chk(self.L.bmx_watch_poll(self.h, int(w), _ptr(entered), int(cap_entered), _ptr(left), int(cap_left), _ptr(res), MEM_DEVICE))
 
     def scan_range_pos_dev(self, field, lo, hi, out_pos, cap, n_out):
         self._chk(self.L.bmx_scan_range_pos(self.h, int(field), int(lo), int(hi), _ptr(out_pos), int(cap), _ptr(n_out), MEM_DEVICE))
@@ -970,6 +1027,29 @@ class Comm:
         out = np.zeros(max(cap, 1), np.uint64)
         self._chk(self.L.bmx_comm_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p)))
         return out[:min(m.value, cap)].copy()
+
+    def watch_create(self, base, clauses):
+        """Engine.watch_create on every shard: one id, valid on all of them"""
+        w = C.c_uint32()
+        self._chk(self.L.bmx_comm_watch_create(self.h, *_where_args(base, clauses), C.byref(w)))
+        return w.value
+
+    def watch_poll(self, w, cap_entered=None, cap_left=None):
+        """Engine.watch_poll over all shards: the lists are the shards' one after the other, the counts their sums, reset the OR of theirs; a poll that overflows
+        commits on no shard. A cap of None: the poll counts first (caps of 0: it commits only if nothing changed) and then fetches with room for exactly that."""
+        res = WatchRes()
+        if cap_entered is None or cap_left is None:
+            self._chk(self.L.bmx_comm_watch_poll(self.h, int(w), None, 0, None, 0, C.cast(C.byref(res), C.c_void_p)))
+            if not res.flags & WATCH_OVERFLOW:
+                return WatchPoll(res, np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+            cap_entered = int(res.n_entered) if cap_entered is None else cap_entered
+            cap_left = int(res.n_left) if cap_left is None else cap_left
+        ent, lft = np.zeros(max(int(cap_entered), 1), np.uint64), np.zeros(max(int(cap_left), 1), np.uint64)
+        self._chk(self.L.bmx_comm_watch_poll(self.h, int(w), _ptr(ent), int(cap_entered), _ptr(lft), int(cap_left), C.cast(C.byref(res), C.c_void_p)))
+        return WatchPoll(res, ent[:int(cap_entered)], lft[:int(cap_left)])
+
+    def watch_destroy(self, w):
+        self._chk(self.L.bmx_comm_watch_destroy(self.h, int(w)))
 
 
 FLAG_CONCURRENT = 8

@@ -31,6 +31,7 @@
 #include "agg_kernels.h"
 #include "top_kernels.h"
 #include "where_kernels.h"
+#include "watch_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -99,6 +100,8 @@ struct Index {
   uint64_t version = ~0ull;  // table version it was built from
   bool has_pos = false;      // its rows' positions are in ctx->chg.slot_pos (it can be maintained from the change log)
   uint64_t content = 0;      // counts the refreshes that really changed something in the columns (a value, a new row, a rebuild)
+  uint64_t layout = 0;       // stamp of the build that laid the columns out (build_index, from bmx_ctx::layout_seq: never 0, never repeated in a context); between two
+                             // builds a row keeps its position and new rows are appended. Read by the standing queries alone (bmx_watch.inc)
   OrderedView view;
 };
 // What the views of one context share (bmx_view.inc).
@@ -304,6 +307,30 @@ struct TopScratch {
   void release() { dev_free(state); dev_free(cand_u); dev_free(cand_id); dev_free(stage); clean = false; }
 };
 
+// The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
+// field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
+// last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
+// (tot[0]; tot[1] is where a host-mode poll's record waits for its download when there is no mapped word), and what the first half of a poll leaves the second.
+struct Watch {
+  bool live = false; uint32_t base_field = 0; WhereProg W{};
+  uint32_t* prev = nullptr; uint64_t prev_words = 0; uint64_t layout = 0;
+};
+struct WatchState {
+  Watch w[BMX_WATCH_MAX];
+  unsigned long long* committed = nullptr;   // [BMX_WATCH_MAX]
+  uint32_t* entered = nullptr; uint32_t* left = nullptr; uint32_t* counts = nullptr; uint64_t blocks_cap = 0;   // masks: one allocation, 256 words per 8192-row block, `left` blocks_cap blocks behind `entered`; counts: 3 x blocks_cap
+  WatchTotals* tot = nullptr;
+  bmx_watch_res* hres = nullptr;             // mapped page-locked record of the host-mode polls
+  struct Pending { bool on = false; uint32_t watch = 0; uint64_t n = 0; uint32_t nb = 0; const uint64_t* ids = nullptr; uint64_t layout = 0; } pend;
+  int ensure(bmx_ctx* ctx, uint64_t nb);     // scratch for an index of nb blocks
+  void release() {
+    for (auto& x : w) { dev_free(x.prev); x.prev_words = 0; x.live = false; }
+    dev_free(committed); dev_free(entered); left = nullptr; dev_free(counts); dev_free(tot); blocks_cap = 0; pend.on = false;
+    if (hres) (void)hipHostFree(hres);
+    hres = nullptr;
+  }
+};
+
 // bmx_timer_* events and the optional per-kernel profiling (bmx_profile_enable).
 struct Profiling {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -340,6 +367,7 @@ struct bmx_ctx {
   SyncScratch sync;
   AggScratch agg;
   TopScratch top;
+  WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
   bool fixed_capacity = false;
@@ -353,6 +381,7 @@ struct bmx_ctx {
   uint64_t batch_seq = 0;
   std::deque<std::pair<uint64_t, uint64_t>> inflight;   // (sequence number, deltas) of batches whose row count the host has not seen yet
   std::vector<Index> indexes;
+  uint64_t layout_seq = 0;            // index builds so far (Index::layout)
   SlabProtocol slab;
   uint32_t placement_tries = 0, placement_tries_asked = 0; float placement_us_best = 0, placement_us_worst = 0;   // what alloc_table_tuned saw for the current table
   uint64_t n_row_waits = 0;           // merges that waited for a batch in flight to report its row count (wait_for_row_reports)
@@ -609,6 +638,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->sync.release();
   ctx->agg.release();
   ctx->top.release();
+  ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -897,3 +927,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_comm.inc"
 #include "bmx_vc_sync.inc"   // (behind everything that was here before it: its kernels follow the others in the code object)
 #include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls)
+#include "bmx_watch.inc"     // (likewise)

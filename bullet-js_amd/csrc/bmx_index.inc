@@ -73,6 +73,7 @@ int build_index(bmx_ctx* ctx, Index* ix) {
   ix->n = n;
   ix->fits32 = wide == 0;
   ix->content++;             // every position may be another row's now
+  ix->layout = ++ctx->layout_seq;
   ix->version = ctx->version;
   ix->has_pos = ctx->chg.slot_pos != nullptr;
   ctx->chg.full_builds++;
