@@ -56,6 +56,9 @@ EXPORTS_WHERE = ["bmx_scan_where", "bmx_comm_scan_where"]
 # include/bmx_watch.h: standing queries, likewise
 EXPORTS_WATCH = ["bmx_watch_create", "bmx_watch_poll", "bmx_watch_destroy", "bmx_comm_watch_create", "bmx_comm_watch_poll", "bmx_comm_watch_destroy"]
 
+# include/bmx_where_agg.h: aggregates and top-k over boolean filters, likewise
+EXPORTS_WHERE_AGG = ["bmx_where_aggregate", "bmx_where_top", "bmx_comm_where_aggregate", "bmx_comm_where_top"]
+
 
 class BmxError(RuntimeError):
     def __init__(self, code, msg):
@@ -138,6 +141,14 @@ def top_merge(lists, k, desc=False):
 class Lit(C.Structure):
     """bmx_lit: one literal of a bmx_scan_where program (24 bytes, the layout of bmx_term); flags: LIT_NOT"""
     _fields_ = [("field", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+def _where_agg_tail(measure, group, group_lo, ngroups):
+    return (AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group), int(group_lo), int(ngroups))
+
+
+def _where_top_tail(k, desc, after):
+    return _top_args([], k, desc, after)[2:]          # (flags, cursor, k)
 
 
 def _where_args(base, clauses):
@@ -268,6 +279,10 @@ def load_library():
     L.bmx_comm_scan_top.argtypes = [vp, u32, C.POINTER(Term), u32, vp, u32, vp, vp, vp]; L.bmx_comm_scan_top.restype = i32
     L.bmx_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp, i32]; L.bmx_scan_where.restype = i32
     L.bmx_comm_scan_where.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), vp, u64, vp]; L.bmx_comm_scan_where.restype = i32
+    L.bmx_where_aggregate.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, i64, u32, vp, i32]; L.bmx_where_aggregate.restype = i32
+    L.bmx_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp, i32]; L.bmx_where_top.restype = i32
+    L.bmx_comm_where_aggregate.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, i64, u32, vp]; L.bmx_comm_where_aggregate.restype = i32
+    L.bmx_comm_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp]; L.bmx_comm_where_top.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
     L.bmx_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp, i32]; L.bmx_watch_poll.restype = i32
     L.bmx_watch_destroy.argtypes = [vp, u32]; L.bmx_watch_destroy.restype = i32
@@ -652,6 +667,22 @@ class Engine:
         self._chk(self.L.bmx_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p), MEM_HOST))
         return out[:min(m.value, cap)].copy()
 
+    def where_aggregate(self, base, clauses, measure=None, group=None, group_lo=0, ngroups=0):
+        """scan_aggregate over the selection of scan_where(base, clauses) (bmx_where_agg.h): count / sum / min / max of field `measure`, grouped by field `group`
+        in the window group_lo .. group_lo + ngroups - 1, without fetching an id. -> what scan_aggregate returns"""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        self._chk(self.L.bmx_where_aggregate(self.h, *_where_args(base, clauses), *_where_agg_tail(measure, group, group_lo, ngroups), _ptr(out), MEM_HOST))
+        return agg_results(out, int(ngroups))
+
+    def where_top(self, base, clauses, k, desc=False, after=None):
+        """scan_top over the selection of scan_where(base, clauses): the first k nodes ordered by (value of `base`, id) — value descending with desc — that come
+        strictly after the cursor `after`. -> (records: ndarray of TOP_DTYPE, n_eligible)"""
+        out = np.zeros(max(int(k), 1), TOP_DTYPE)
+        m, ne = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.bmx_where_top(self.h, *_where_args(base, clauses), *_where_top_tail(k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p),
+                                       C.cast(C.byref(ne), C.c_void_p), MEM_HOST))
+        return out[:m.value].copy(), ne.value
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -812,6 +843,14 @@ class Engine:
     def scan_where_dev(self, base, clauses, out, cap, n_out):
         """scan_where into device memory (`out`: room for cap ids, or None to count; n_out: one uint64); enqueue-only. The program is host data."""
         self._chk(self.L.bmx_scan_where(self.h, *_where_args(base, clauses), _ptr(out), int(cap), _ptr(n_out), MEM_DEVICE))
+
+    def where_aggregate_dev(self, base, clauses, out, measure=None, group=None, group_lo=0, ngroups=0):
+        """where_aggregate into device memory (`out` as for scan_aggregate_dev); enqueue-only. The program is host data."""
+        self._chk(self.L.bmx_where_aggregate(self.h, *_where_args(base, clauses), *_where_agg_tail(measure, group, group_lo, ngroups), _ptr(out), MEM_DEVICE))
+
+    def where_top_dev(self, base, clauses, k, out, n_out=None, n_eligible=None, desc=False, after=None):
+        """where_top into device memory (`out`, n_out, n_eligible as for scan_top_dev); enqueue-only. The program and the cursor are host data."""
+        self._chk(self.L.bmx_where_top(self.h, *_where_args(base, clauses), *_where_top_tail(k, desc, after), _ptr(out), _ptr(n_out), _ptr(n_eligible), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1027,6 +1066,20 @@ class Comm:
         out = np.zeros(max(cap, 1), np.uint64)
         self._chk(self.L.bmx_comm_scan_where(self.h, *args, _ptr(out), cap, C.cast(C.byref(m), C.c_void_p)))
         return out[:min(m.value, cap)].copy()
+
+    def where_aggregate(self, base, clauses, measure=None, group=None, group_lo=0, ngroups=0):
+        """Engine.where_aggregate over all shards: the records one engine holding the same rows gives"""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        self._chk(self.L.bmx_comm_where_aggregate(self.h, *_where_args(base, clauses), *_where_agg_tail(measure, group, group_lo, ngroups), _ptr(out)))
+        return agg_results(out, int(ngroups))
+
+    def where_top(self, base, clauses, k, desc=False, after=None):
+        """Engine.where_top over all shards: every shard answers with its first k, the library merges them as top_merge does and adds up the n_eligible"""
+        out = np.zeros(max(int(k), 1), TOP_DTYPE)
+        m, ne = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.bmx_comm_where_top(self.h, *_where_args(base, clauses), *_where_top_tail(k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p),
+                                            C.cast(C.byref(ne), C.c_void_p)))
+        return out[:m.value].copy(), ne.value
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

@@ -32,6 +32,8 @@
 #include "top_kernels.h"
 #include "where_kernels.h"
 #include "watch_kernels.h"
+#include "where_agg_kernels.h"
+#include "../../include/bmx_where_agg.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -928,3 +930,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_vc_sync.inc"   // (behind everything that was here before it: its kernels follow the others in the code object)
 #include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls)
 #include "bmx_watch.inc"     // (likewise)
+#include "bmx_where_agg.inc" // (likewise)

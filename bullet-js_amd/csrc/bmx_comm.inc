@@ -516,18 +516,18 @@ int bmx_comm_scan_where(bmx_comm* c, uint32_t base_field, uint32_t nclauses, con
   });
 }
 
-// bmx_scan_aggregate over the shards (host memory). A node's rows all live on the shard that owns its id, so a node is selected, measured and grouped by one
-// shard alone and the shards' records combine exactly: the counts and the 128-bit sums add, the minima and maxima fold. Every shard's query is enqueued
-// before the first shard's records are fetched.
-int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups,
-                            bmx_agg* out) {
-  if (const char* bad = agg_bad_args(nterms, terms, group_field, ngroups, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+}  // extern "C"
+namespace {
+// The shards' aggregate records combined into `out` (host memory). A node's rows all live on the shard that owns its id, so a node is selected, measured and
+// grouped by one shard alone and the shards' records combine exactly: the counts and the 128-bit sums add, the minima and maxima fold. enqueue(shard) enqueues
+// the query into the shard's staging buffer; every shard's query is enqueued before the first shard's records are fetched.
+template <class Enqueue>
+int comm_agg_with(bmx_comm* c, uint32_t ngroups, bmx_agg* out, Enqueue enqueue) {
   DevGuard guard;
   const uint32_t nrec = agg_records(ngroups);
   std::vector<bmx_agg> part(nrec);
   return comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) { const int rc = enter(x); return rc ? rc : agg_enqueue(x, nterms, terms, measure_field, group_field, group_lo, ngroups, nullptr); },
+    [&](uint32_t, bmx_ctx* x) { const int rc = enter(x); return rc ? rc : enqueue(x); },
     [&](uint32_t g, bmx_ctx* x) {
       int rc = enter(x);
       if (!rc) rc = agg_collect(x, nrec, g == 0 ? out : part.data());
@@ -543,20 +543,18 @@ int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms,
     });
 }
 
-// bmx_scan_top over the shards (bmx_top.h, host memory). A node lives on one shard and the order (value, id) is total, so the first k of the whole graph are
-// the first k of the shards' first k: every shard's query is enqueued before the first answer is fetched, the answers (each ordered, <= k records) are merged
-// on the host and the shards' n_eligible add up.
-int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t flags, const bmx_top_rec* after, uint32_t k, bmx_top_rec* out, uint64_t* n_out,
-                      uint64_t* n_eligible) {
-  if (const char* bad = top_bad_args(nterms, terms, flags, k, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+// The shards' top-k answers merged into `out` (host memory). A node lives on one shard and the order (value, id) is total, so the first k of the whole graph are
+// the first k of the shards' first k: every shard's query is enqueued (enqueue(shard), into the shard's staging buffer) before the first answer is fetched, the
+// answers (each ordered, <= k records) are merged on the host and the shards' n_eligible add up.
+template <class Enqueue>
+int comm_top_with(bmx_comm* c, uint32_t flags, uint32_t k, bmx_top_rec* out, uint64_t* n_out, uint64_t* n_eligible, Enqueue enqueue) {
   DevGuard guard;
   const bool desc = (flags & BMX_TOP_DESC) != 0;
   auto before = [desc](const bmx_top_rec& a, const bmx_top_rec& b) { return a.val != b.val ? (desc ? a.val > b.val : a.val < b.val) : a.id < b.id; };
   std::vector<bmx_top_rec> all, part, tmp;
   uint64_t tot = 0;
   const int rc = comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : top_enqueue(x, nterms, terms, flags, after, k, nullptr, nullptr, nullptr); },
+    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : enqueue(x); },
     [&](uint32_t, bmx_ctx* x) {
       uint64_t ne = 0;
       int crc = enter(x);
@@ -574,6 +572,24 @@ int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint3
   if (n_out) *n_out = all.size();
   if (n_eligible) *n_eligible = tot;
   return BMX_OK;
+}
+}  // namespace
+extern "C" {
+
+// bmx_scan_aggregate over the shards (host memory): comm_agg_with
+int bmx_comm_scan_aggregate(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups,
+                            bmx_agg* out) {
+  if (const char* bad = agg_bad_args(nterms, terms, group_field, ngroups, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  return comm_agg_with(c, ngroups, out, [&](bmx_ctx* x) { return agg_enqueue(x, nterms, terms, measure_field, group_field, group_lo, ngroups, nullptr); });
+}
+
+// bmx_scan_top over the shards (bmx_top.h, host memory): comm_top_with
+int bmx_comm_scan_top(bmx_comm* c, uint32_t nterms, const bmx_term* terms, uint32_t flags, const bmx_top_rec* after, uint32_t k, bmx_top_rec* out, uint64_t* n_out,
+                      uint64_t* n_eligible) {
+  if (const char* bad = top_bad_args(nterms, terms, flags, k, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  return comm_top_with(c, flags, k, out, n_out, n_eligible, [&](bmx_ctx* x) { return top_enqueue(x, nterms, terms, flags, after, k, nullptr, nullptr, nullptr); });
 }
 
 // Replica reconciliation over the shards (bmx.h). The shards' key sets are disjoint and the digest is a sum, so the digest of the sharded graph is the

@@ -26,15 +26,16 @@ int top_scratch(bmx_ctx* ctx) {
   return BMX_OK;
 }
 
-// the whole chain of one query on the column of width T: pass 0, the state, the worst case of digit passes (those behind "done" return at once), the compaction
-template <class T, bool PROBE>
-int top_launch(bmx_ctx* ctx, const Index* ix, const TopArgs& A, uint32_t k) {
+// the whole chain of one query on the column of width T: pass 0, the state, the worst case of digit passes (those behind "done" return at once), the compaction.
+// pass0(col, blocks, nt) launches the query's own pass 0: k_top_sweep0 for an AND of terms (top_launch), k_where_top0 for a program (bmx_where_agg.inc).
+template <class T, bool PROBE, class Pass0>
+int top_launch_with(bmx_ctx* ctx, const Index* ix, const TopArgs& A, uint32_t k, Pass0&& pass0) {
   const T* col = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
   const uint32_t nt = ix->n * sizeof(T) > SCAN_NT_BYTES ? 1u : 0u;
   // no workgroup with fewer than four rounds of loads to spread its one flush over
   const uint32_t blocks = sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T)));
-  hipLaunchKernelGGL((k_top_sweep0<T, PROBE>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, col, ix->n, nt, A);
-  LAUNCHCHK("k_top_sweep0");
+  pass0(col, blocks, nt);
+  LAUNCHCHK("k_top_sweep0 / k_where_top0");
   hipLaunchKernelGGL(k_top_init, dim3(1), dim3(64), 0, ctx->stream, A.S, k);
   // digits of the value (key - min: at most 32 bits in the 4-byte column, 64 in the 8-byte one), then of the id
   const uint32_t passes = (uint32_t)((sizeof(T) * 8 + TOP_DIGIT_BITS - 1) / TOP_DIGIT_BITS + (64 + TOP_DIGIT_BITS - 1) / TOP_DIGIT_BITS);
@@ -45,6 +46,29 @@ int top_launch(bmx_ctx* ctx, const Index* ix, const TopArgs& A, uint32_t k) {
   LAUNCHCHK("k_top_digit / k_top_find");
   hipLaunchKernelGGL((k_top_compact<T, PROBE>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, col, ix->n, nt, A, ctx->top.cand_u, ctx->top.cand_id);
   LAUNCHCHK("k_top_compact");
+  return BMX_OK;
+}
+template <class T, bool PROBE>
+int top_launch(bmx_ctx* ctx, const Index* ix, const TopArgs& A, uint32_t k) {
+  return top_launch_with<T, PROBE>(ctx, ix, A, k, [&](const T* col, uint32_t blocks, uint32_t nt) {
+    hipLaunchKernelGGL((k_top_sweep0<T, PROBE>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, col, ix->n, nt, A);
+  });
+}
+
+// the cursor as the kernels take it
+inline void top_set_cursor(TopArgs& A, const bmx_top_rec* after) {
+  if (!after) return;
+  const unsigned long long u = (unsigned long long)after->val ^ 0x8000000000000000ull;
+  A.has_after = 1u; A.au = A.desc ? ~u : u; A.aid = after->id;
+}
+// the last kernel of a query: records and counts to the caller's device memory, or, with d_out == nullptr, to the staging buffer
+int top_launch_finish(bmx_ctx* ctx, const TopArgs& A, uint32_t k, bmx_top_rec* d_out, uint64_t* d_n_out, uint64_t* d_n_eligible) {
+  unsigned long long* st = reinterpret_cast<unsigned long long*>(ctx->top.stage);
+  hipLaunchKernelGGL(k_top_finish, dim3(1), dim3(TOP_SORT_THREADS), 0, ctx->stream, ctx->top.state, (const unsigned long long*)ctx->top.cand_u, (const unsigned long long*)ctx->top.cand_id,
+                     d_out ? d_out : reinterpret_cast<bmx_top_rec*>(st + 2), d_out ? reinterpret_cast<unsigned long long*>(d_n_out) : st,
+                     d_out ? reinterpret_cast<unsigned long long*>(d_n_eligible) : st + 1, k, A.desc);
+  LAUNCHCHK("k_top_finish");
+  ctx->top.clean = true;
   return BMX_OK;
 }
 
@@ -64,22 +88,13 @@ int top_enqueue(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint32_t f
   copy_terms(A.t, terms, nterms);
   A.lo = A.t[0].lo; A.hi = A.t[0].hi;
   if (ix->fits32) { const Range32 r = clamp_i32(A.lo, A.hi); A.lo = r.lo; A.hi = r.hi; }    // the 4-byte column
-  if (after) {
-    const unsigned long long u = (unsigned long long)after->val ^ 0x8000000000000000ull;
-    A.has_after = 1u; A.au = A.desc ? ~u : u; A.aid = after->id;
-  }
+  top_set_cursor(A, after);
   ctx->top.clean = false;
   int rc;
   if (ix->fits32) rc = probe ? top_launch<int32_t, true>(ctx, ix, A, k) : top_launch<int32_t, false>(ctx, ix, A, k);
   else rc = probe ? top_launch<int64_t, true>(ctx, ix, A, k) : top_launch<int64_t, false>(ctx, ix, A, k);
   if (rc) return rc;
-  unsigned long long* st = reinterpret_cast<unsigned long long*>(ctx->top.stage);
-  hipLaunchKernelGGL(k_top_finish, dim3(1), dim3(TOP_SORT_THREADS), 0, ctx->stream, ctx->top.state, (const unsigned long long*)ctx->top.cand_u, (const unsigned long long*)ctx->top.cand_id,
-                     d_out ? d_out : reinterpret_cast<bmx_top_rec*>(st + 2), d_out ? reinterpret_cast<unsigned long long*>(d_n_out) : st,
-                     d_out ? reinterpret_cast<unsigned long long*>(d_n_eligible) : st + 1, k, A.desc);
-  LAUNCHCHK("k_top_finish");
-  ctx->top.clean = true;
-  return BMX_OK;
+  return top_launch_finish(ctx, A, k, d_out, d_n_out, d_n_eligible);
 }
 
 // second half of a host-mode query: wait for it, copy the counts and the records down; recs gets the min(k, n_eligible) records
@@ -91,6 +106,15 @@ int top_collect(bmx_ctx* ctx, uint32_t k, std::vector<bmx_top_rec>& recs, uint64
   recs.resize(m);
   if (m) std::memcpy(recs.data(), h.data() + 2, m * sizeof(bmx_top_rec));
   *n_eligible = h[1];
+  return BMX_OK;
+}
+// ... into the caller's host memory
+int top_collect_to(bmx_ctx* ctx, uint32_t k, bmx_top_rec* out, uint64_t* n_out, uint64_t* n_eligible) {
+  std::vector<bmx_top_rec> recs; uint64_t ne = 0;
+  if (int rc = top_collect(ctx, k, recs, &ne)) return rc;
+  if (!recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(bmx_top_rec));
+  if (n_out) *n_out = recs.size();
+  if (n_eligible) *n_eligible = ne;
   return BMX_OK;
 }
 
@@ -106,12 +130,7 @@ int bmx_scan_top(bmx_ctx* ctx, uint32_t nterms, const bmx_term* terms, uint32_t 
   if (int erc = enter(ctx)) return erc;
   if (mem == BMX_MEM_DEVICE) return top_enqueue(ctx, nterms, terms, flags, after, k, out, n_out, n_eligible);
   if (int rc = top_enqueue(ctx, nterms, terms, flags, after, k, nullptr, nullptr, nullptr)) return rc;
-  std::vector<bmx_top_rec> recs; uint64_t ne = 0;
-  if (int rc = top_collect(ctx, k, recs, &ne)) return rc;
-  if (!recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(bmx_top_rec));
-  if (n_out) *n_out = recs.size();
-  if (n_eligible) *n_eligible = ne;
-  return BMX_OK;
+  return top_collect_to(ctx, k, out, n_out, n_eligible);
 }
 
 }  // extern "C"

@@ -1,0 +1,129 @@
+// bmx_where_agg.inc — aggregates and top-k over boolean filters (bmx_where_agg.h): bmx_where_aggregate, bmx_where_top and their sharded forms. The program is
+// bmx_where.inc's (where_prepare, PredWhere), the two sweeps are where_agg_kernels.h, and everything behind them is bmx_agg.inc's and bmx_top.inc's: the
+// scratch with its `clean` protocol, k_agg_finish, the select's chain (top_launch_with), the collect halves, and bmx_comm.inc's combine steps. Included by
+// bmx.hip (one translation unit), behind everything that was here before it.
+namespace {
+
+// agg_bad_args / top_bad_args without their term checks: the program stands where the terms stood and where_prepare has judged it
+const bmx_term WHERE_AGG_NO_TERMS[1] = {};
+const char* where_agg_bad_args(uint32_t group_field, uint32_t ngroups, const bmx_agg* out) { return agg_bad_args(1, WHERE_AGG_NO_TERMS, group_field, ngroups, out); }
+const char* where_top_bad_args(uint32_t flags, uint32_t k, const bmx_top_rec* out) { return top_bad_args(1, WHERE_AGG_NO_TERMS, flags, k, out); }
+
+template <class T>
+PredWhere<T> where_pred(bmx_ctx* ctx, const Index* ix, const WhereProg& W) {
+  PredWhere<T> P;
+  P.v = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
+  P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = W;
+  return P;
+}
+// the grid of the other sweeps: no workgroup with fewer than four rounds of loads to spread its one flush over
+template <class T>
+uint32_t where_agg_grid(bmx_ctx* ctx, const Index* ix) { return sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T))); }
+
+template <class T>
+void where_agg_launch(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const AggArgs& A) {
+  const PredWhere<T> P = where_pred<T>(ctx, ix, W);
+  const uint32_t blocks = where_agg_grid<T>(ctx, ix);
+  if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  else hipLaunchKernelGGL((k_where_agg<T, 2>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+}
+
+// where the sweep finds a field's value: the base field's column (0), a probe of its own, or nowhere
+inline uint32_t where_agg_source(uint32_t field, uint32_t base_field) { return field == BMX_AGG_NO_FIELD ? AGG_SRC_NONE : (field == base_field ? 0u : AGG_SRC_PROBE); }
+
+// Enqueue one aggregate over a prepared program; the records go to d_out (device memory), or, with d_out == nullptr, to the context's staging buffer
+// (agg_collect fetches them). The arguments have been checked and the context entered. A value-ordered view of the base field's index is neither read nor
+// touched (where_run).
+int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* d_out) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  const uint32_t nrec = agg_records(ngroups);
+  if (int rc = agg_scratch(ctx, nrec)) return rc;
+  AggArgs A{};
+  A.slots = ctx->slots; A.nslots = ctx->nslots; A.acc = ctx->agg.raw;
+  A.group_lo = group_lo; A.ngroups = ngroups; A.measure = measure_field; A.group = group_field;
+  A.m_src = where_agg_source(measure_field, base_field); A.g_src = ngroups ? where_agg_source(group_field, base_field) : AGG_SRC_NONE;
+  A.nterms = 0;
+  ctx->agg.clean = false;
+  if (ix->fits32) where_agg_launch<int32_t>(ctx, ix, W, A); else where_agg_launch<int64_t>(ctx, ix, W, A);
+  LAUNCHCHK("k_where_agg");
+  hipLaunchKernelGGL(k_agg_finish, dim3(std::min<uint32_t>((nrec + 255) / 256, 64)), dim3(256), 0, ctx->stream, ctx->agg.raw, d_out ? d_out : ctx->agg.stage, nrec,
+                     A.m_src != AGG_SRC_PROBE ? 1u : 0u);
+  LAUNCHCHK("k_agg_finish");
+  ctx->agg.clean = true;
+  return BMX_OK;
+}
+
+template <class T>
+int where_top_launch(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const TopArgs& A, uint32_t k) {
+  const PredWhere<T> P = where_pred<T>(ctx, ix, W);
+  return top_launch_with<T, true>(ctx, ix, A, k, [&](const T*, uint32_t blocks, uint32_t) {
+    hipLaunchKernelGGL((k_where_top0<T>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
+  });
+}
+
+// Enqueue one top-k query over a prepared program; outputs as top_enqueue's
+int where_top_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t flags, const bmx_top_rec* after, uint32_t k, bmx_top_rec* d_out, uint64_t* d_n_out,
+                      uint64_t* d_n_eligible) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  if (int rc = top_scratch(ctx)) return rc;
+  if (int rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), 0)) return rc;     // the scans' mask: one bit per index position
+  TopArgs A{};     // (no terms: pass 0 decides with the program, the passes behind it read the mask)
+  A.ids = ix->ids; A.mask = ctx->scan.mask; A.slots = ctx->slots; A.nslots = ctx->nslots; A.S = ctx->top.state;
+  A.desc = flags & BMX_TOP_DESC;
+  top_set_cursor(A, after);
+  ctx->top.clean = false;
+  if (int rc = ix->fits32 ? where_top_launch<int32_t>(ctx, ix, W, A, k) : where_top_launch<int64_t>(ctx, ix, W, A, k)) return rc;
+  return top_launch_finish(ctx, A, k, d_out, d_n_out, d_n_eligible);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_where_aggregate(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field,
+                        uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* out, int mem) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (const char* bad = where_agg_bad_args(group_field, ngroups, out)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
+  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  if (int erc = enter(ctx)) return erc;
+  if (int rc = where_agg_enqueue(ctx, base_field, W, measure_field, group_field, group_lo, ngroups, mem == BMX_MEM_DEVICE ? out : nullptr)) return rc;
+  return mem == BMX_MEM_HOST ? agg_collect(ctx, agg_records(ngroups), out) : BMX_OK;
+}
+
+int bmx_where_top(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t flags, const bmx_top_rec* after,
+                  uint32_t k, bmx_top_rec* out, uint64_t* n_out, uint64_t* n_eligible, int mem) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (const char* bad = where_top_bad_args(flags, k, out)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
+  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  if (int erc = enter(ctx)) return erc;
+  if (mem == BMX_MEM_DEVICE) return where_top_enqueue(ctx, base_field, W, flags, after, k, out, n_out, n_eligible);
+  if (int rc = where_top_enqueue(ctx, base_field, W, flags, after, k, nullptr, nullptr, nullptr)) return rc;
+  return top_collect_to(ctx, k, out, n_out, n_eligible);
+}
+
+int bmx_comm_where_aggregate(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field,
+                             uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* out) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
+  if (const char* bad = where_agg_bad_args(group_field, ngroups, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  return comm_agg_with(c, ngroups, out, [&](bmx_ctx* x) { return where_agg_enqueue(x, base_field, W, measure_field, group_field, group_lo, ngroups, nullptr); });
+}
+
+int bmx_comm_where_top(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t flags, const bmx_top_rec* after,
+                       uint32_t k, bmx_top_rec* out, uint64_t* n_out, uint64_t* n_eligible) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
+  if (const char* bad = where_top_bad_args(flags, k, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  return comm_top_with(c, flags, k, out, n_out, n_eligible, [&](bmx_ctx* x) { return where_top_enqueue(x, base_field, W, flags, after, k, nullptr, nullptr, nullptr); });
+}
+
+}  // extern "C"

@@ -1,0 +1,115 @@
+// where_agg_kernels.h — aggregates and top-k over boolean filters (bmx_where_agg.h bmx_where_aggregate, bmx_where_top): the two sweeps that decide a
+// candidate with where_kernels.h's PredWhere::row() and end like agg_kernels.h and top_kernels.h end, gfx950, wave64.
+//
+// k_where_agg<T, G> : one read of the base field's value column (top_sweep's shape: 16-byte loads, TOP_U in flight per lane, 512 threads). A candidate that
+//                     the program selects goes through where_agg_row (agg_row's tail, with no terms): the measure and the group value are the column value
+//                     when the field is the base field, otherwise one agg_probe each, made after the match is known. It probes through PredWhere's table
+//                     pointer, not AggArgs' copy of it: the two are the same table, and one pair of scalar registers less is live across row()'s loops.
+//                     agg_add<G>, the accumulators, agg_end<G> and k_agg_finish are bmx_scan_aggregate's (G = 0 / 1 / 2 as there).
+// k_where_top0<T>   : pass 0 of the radix select for a program. Eligible = row() and behind the cursor. Counts the eligible rows, takes the minimum and maximum
+//                     of their keys as k_top_sweep0 does, and leaves one bit per index position in the scans' mask scratch, composed as k_top_sweep0<T, true>
+//                     composes it; k_top_digit<T, true> and k_top_compact<T, true> read that bit and know nothing of the program.
+//
+// row() walks its clauses in loops that end on wave votes, so every lane of a wave has to reach it the same number of times: top_sweep calls its functor once
+// per unit in every lane (cnt == 0 beyond the column), and the functor calls row() for all E rows of the unit, with valid = false for a row beyond the column
+// or a tombstoned position. As in PredWhere::mask, the E rows are one copy of the walk: the element is picked with selects, not with a run-time index.
+#pragma once
+#include "where_kernels.h"
+#include "top_kernels.h"
+
+namespace bmx {
+
+static_assert(AGG_THREADS == TOP_THREADS && AGG_U == TOP_U, "k_where_agg sweeps with top_sweep and reduces with agg_end: one workgroup shape");
+
+// row e of a unit, without a run-time index into the vector
+template <class T, int E, class V>
+__device__ __forceinline__ T where_pick(const V& x, int e) {
+  T xe = x[0];
+#pragma unroll
+  for (int k = 1; k < E; k++) xe = e == k ? x[k] : xe;
+  return xe;
+}
+
+// a candidate the program selected: the measure and the group value (the column value x, or one probe each), then the add. The table is P's.
+template <int G, class T>
+__device__ __forceinline__ void where_agg_row(const PredWhere<T>& P, const AggArgs& A, int64_t x, uint64_t pos, AggLane& L, AggLds<G>& S) {
+  int64_t mval = x, gval = x;
+  bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
+  // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers
+#pragma unroll 1
+  for (uint32_t k = 0; k < 2u; k++) {
+    if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
+    int64_t y;
+    if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
+      if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
+    }
+  }
+  uint32_t g = 0;
+  if (G) {   // (the difference of two int64 is exact mod 2^64 once gval >= group_lo)
+    const uint64_t d = (uint64_t)gval - (uint64_t)A.group_lo;
+    g = (have_g && gval >= A.group_lo && d < (uint64_t)A.ngroups) ? (uint32_t)d : A.ngroups;
+  }
+  agg_add<G>(A, L, S, g, have_m, mval);
+}
+
+template <class T, int G>
+__global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T> P, AggArgs A) {
+  constexpr int E = PredWhere<T>::E;
+  typedef T vec_t __attribute__((ext_vector_type(E)));
+  __shared__ AggLds<G> S;
+  AggLane L;
+  agg_begin<G>(A, S);
+  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
+#pragma unroll 1
+    for (int e = 0; e < E; e++) {
+      const T xe = where_pick<T, E>(x, e);
+      const uint64_t pos = unit * E + (uint64_t)e;
+      if (P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) where_agg_row<G>(P, A, (int64_t)xe, pos, L, S);
+    }
+  });
+  agg_end<G>(A, L, S);
+}
+
+template <class T>
+__global__ __launch_bounds__(TOP_THREADS) void k_where_top0(uint64_t n, PredWhere<T> P, TopArgs A) {
+  constexpr int E = PredWhere<T>::E;
+  typedef T vec_t __attribute__((ext_vector_type(E)));
+  __shared__ unsigned long long s_n[TOP_WAVES], s_mn[TOP_WAVES], s_mx[TOP_WAVES];
+  unsigned long long cnt_l = 0, mn = ~0ull, mx = 0ull;
+  const uint64_t nu = (n + E - 1) / E;
+  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
+    uint32_t nib = 0;
+#pragma unroll 1
+    for (int e = 0; e < E; e++) {
+      const T xe = where_pick<T, E>(x, e);
+      const uint64_t pos = unit * E + (uint64_t)e;
+      const unsigned long long u = top_key((int64_t)xe, A.desc);
+      bool ok = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
+      ok = ok && top_after(A, u, pos, false, 0);               // (the id column is read only for a row whose value equals the cursor's)
+      nib |= (uint32_t)ok << e;
+      if (ok) { cnt_l++; mn = u < mn ? u : mn; mx = u > mx ? u : mx; }
+    }
+    // 32 / E consecutive lanes hold one mask word (a unit index is a multiple of 32 / E where a lane index is)
+    constexpr uint32_t LW = 32 / E;
+    uint32_t w = nib << (E * (threadIdx.x & (LW - 1)));
+#pragma unroll
+    for (uint32_t d = 1; d < LW; d <<= 1) w |= __shfl_xor(w, d);
+    if ((threadIdx.x & (LW - 1)) == 0 && unit < nu) A.mask[unit / LW] = w;
+  });
+  for (int d = 32; d >= 1; d >>= 1) {
+    cnt_l += __shfl_xor(cnt_l, d);
+    const unsigned long long a = __shfl_xor(mn, d), b = __shfl_xor(mx, d);
+    mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+  }
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) { s_n[w] = cnt_l; s_mn[w] = mn; s_mx[w] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long c = 0, a = ~0ull, b = 0ull;
+#pragma unroll
+    for (int i = 0; i < TOP_WAVES; i++) { c += s_n[i]; a = s_mn[i] < a ? s_mn[i] : a; b = s_mx[i] > b ? s_mx[i] : b; }
+    if (c) { atomicAdd(&A.S->n_elig, c); atomicMin(&A.S->kmin, a); atomicMax(&A.S->kmax, b); }
+  }
+}
+
+}  // namespace bmx

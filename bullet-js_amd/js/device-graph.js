@@ -107,6 +107,10 @@ class DeviceGraph {
     const measure = opts.measure === undefined ? null : opts.measure, group = opts.group === undefined ? null : opts.group;
     const groupLo = opts.groupLo || 0, nGroups = (opts.nGroups || 0) >>> 0;
     const r = this.comm ? this.native.commScanAggregate(this.comm, terms, measure, group, groupLo, nGroups) : this.native.scanAggregate(this.handle, terms, measure, group, groupLo, nGroups);
+    return this._aggRecords(r, nGroups);
+  }
+  /* the typed arrays of scanAggregate / whereAggregate -> records */
+  _aggRecords(r, nGroups) {
     const recs = new Array(r.nMatch.length);
     for (let i = 0; i < recs.length; i++) {
       const n = Number(r.n[i]);
@@ -131,6 +135,23 @@ class DeviceGraph {
   scanWhere(base, clauses) {
     if (this.preOp) this.preOp();
     return this.comm ? this.native.commScanWhere(this.comm, base, clauses) : this.native.scanWhere(this.handle, base, clauses);
+  }
+  /* Aggregate over a boolean filter (bmx_where_aggregate, include/bmx_where_agg.h): scanAggregate's records (opts: measure, group, groupLo, nGroups) over the
+   * nodes scanWhere(base, clauses) selects, answered on the device without fetching an id. */
+  whereAggregate(base, clauses, opts = {}) {
+    if (this.preOp) this.preOp();
+    const measure = opts.measure === undefined ? null : opts.measure, group = opts.group === undefined ? null : opts.group;
+    const groupLo = opts.groupLo || 0, nGroups = (opts.nGroups || 0) >>> 0;
+    const r = this.comm ? this.native.commWhereAggregate(this.comm, base, clauses, measure, group, groupLo, nGroups)
+      : this.native.whereAggregate(this.handle, base, clauses, measure, group, groupLo, nGroups);
+    return this._aggRecords(r, nGroups);
+  }
+  /* Ordered top-k over a boolean filter (bmx_where_top): the first k nodes that scanWhere(base, clauses) selects, ordered by (value of `base`, id) — value
+   * descending with opts.desc — behind the cursor opts.after = [id (BigInt), value]. -> {ids, vals, nEligible} as scanTop gives them. */
+  whereTop(base, clauses, k, opts = {}) {
+    if (this.preOp) this.preOp();
+    const after = opts.after === undefined ? null : opts.after;
+    return this.comm ? this.native.commWhereTop(this.comm, base, clauses, !!opts.desc, after, k >>> 0) : this.native.whereTop(this.handle, base, clauses, !!opts.desc, after, k >>> 0);
   }
   info() { return this.comm ? { nShards: this.nShards, devices: this.devices, nRows: this.rowCount() } : this.native.info(this.handle); }
   close() {

@@ -27,6 +27,23 @@ const { Columns, fieldId, isDeviceInt, pathId } = require("./hash");
 
 function bucketKey(v) { return (typeof v === "object" && v !== null) ? JSON.stringify(v) : String(v); }
 
+/* top() / whereTop() on a host index: numbers compare as numbers and come before everything else, which compares by its bucket key */
+function cmpVal(a, b) {
+  const na = typeof a === "number", nb = typeof b === "number";
+  if (na && nb) return a < b ? -1 : a > b ? 1 : 0;
+  if (na !== nb) return na ? -1 : 1;
+  const ka = bucketKey(a), kb = bucketKey(b);
+  return ka < kb ? -1 : ka > kb ? 1 : 0;
+}
+
+/* where() / whereTop() on the host: the truth of one normalised literal for one child of the store */
+function literalTruth(child, t) {
+  const x = child && typeof child === "object" ? child[t.field] : undefined;
+  let pos = x !== null && x !== undefined;
+  if (pos) pos = t.eq ? x === t.min : (t.min === -Infinity || x >= t.min) && (t.max === Infinity || x <= t.max);
+  return pos !== t.not;
+}
+
 const ORDERED_AUTO = 0xffffffff;      // BMX_INDEX_ORDERED_AUTO: the engine weighs a sort against the scans it saves
 const orderedOpt = (v) => (v === "auto" ? ORDERED_AUTO : v >>> 0);
 
@@ -389,58 +406,67 @@ class GpuQuery {
   where(path, clauses, opts = {}) {
     if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: where needs opts.over, the field that defines the universe");
     if (!clauses || clauses.length === 0) return [];
+    const { norm, base, native } = this._whereProgram(path, clauses, opts.over);
+    if (native) {
+      this.lastPath = "device";
+      if (native.length === 0) return [];
+      const ids = this.graph.scanWhere(base.deviceField, native);
+      if (base.source === "device") return this._nodesFromIds(ids);
+      return this._nodes(base, this._ordinals(base, ids).sort((a, b) => a - b));
+    }
+    const selected = this._whereHost(path, norm, base);
+    this.lastPath = "host";
+    return this._nodes(base, selected);
+  }
+
+  /* The program of where(), whereAggregate() and whereTop(), normalised: {field, eq: v} is min = max = v, {field, ne: v} its negation, a bound left out (or
+   * +-Infinity) is open. -> {norm, base (the index of `over`), native}: native is the program as the device takes it ([[[field, lo, hi, not], ...], ...], possibly
+   * empty: no clause can be true) when every index involved is an integer index, and null when one lives on the host. */
+  _whereProgram(path, clauses, over) {
     const open = (x) => x === undefined || x === null || x === Infinity || x === -Infinity;
     const norm = clauses.map((c) => c.map((t) => {
       if ("eq" in t) return { field: t.field, min: t.eq, max: t.eq, eq: true, not: !!t.not };
       if ("ne" in t) return { field: t.field, min: t.ne, max: t.ne, eq: true, not: !t.not };
       return { field: t.field, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
     }));
-    const base = this._fresh(path, opts.over);
-    // Which side answers is decided before a DEVICE index of a literal's field is built (it needs the device; the host evaluation below reads the store and
+    const base = this._fresh(path, over);
+    // Which side answers is decided before a DEVICE index of a literal's field is built (it needs the device; the host evaluation reads the store and
     // needs none): "device" = every child that carries the field has a safe integer there, "absent" = no child carries it (_fieldKind).
     const kinds = new Map();
     for (const c of norm) for (const t of c) if (!kinds.has(t.field)) kinds.set(t.field, this._fieldKind(path, t.field));
     const onDevice = base.kind === "device" && Array.from(kinds.values()).every((k) => k !== "host");
-    if (onDevice) {
-      this.lastPath = "device";
-      const num = (x) => typeof x === "number" && !Number.isNaN(x);
-      // A field no child carries is decided here: its positive literals are false (their clause goes), its negated ones true (the literal goes); a clause
-      // left without a literal is true for every candidate, which a presence literal on the base field says.
-      const native = [];
-      for (const c of norm) {
-        if (c.some((t) => kinds.get(t.field) === "absent" && !t.not)) continue;
-        const lits = c.filter((t) => kinds.get(t.field) !== "absent").map((t) => {
-          const f = this._fresh(path, t.field).deviceField;
-          // bounds no integer satisfies (a string against an integer field, a fraction as eq): the empty range, whose negation is always true
-          if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not];
-          return [f, Math.ceil(t.min), Math.floor(t.max), t.not];
-        });
-        native.push(lits.length ? lits : [[base.deviceField, -Infinity, Infinity, false]]);
-      }
-      if (native.length === 0) return [];
-      const ids = this.graph.scanWhere(base.deviceField, native);
-      if (base.source === "device") return this._nodesFromIds(ids);
-      return this._nodes(base, this._ordinals(base, ids).sort((a, b) => a - b));
+    if (!onDevice) return { norm, base, native: null };
+    const num = (x) => typeof x === "number" && !Number.isNaN(x);
+    // A field no child carries is decided here: its positive literals are false (their clause goes), its negated ones true (the literal goes); a clause
+    // left without a literal is true for every candidate, which a presence literal on the base field says.
+    const native = [];
+    for (const c of norm) {
+      if (c.some((t) => kinds.get(t.field) === "absent" && !t.not)) continue;
+      const lits = c.filter((t) => kinds.get(t.field) !== "absent").map((t) => {
+        const f = this._fresh(path, t.field).deviceField;
+        // bounds no integer satisfies (a string against an integer field, a fraction as eq): the empty range, whose negation is always true
+        if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not];
+        return [f, Math.ceil(t.min), Math.floor(t.max), t.not];
+      });
+      native.push(lits.length ? lits : [[base.deviceField, -Infinity, Infinity, false]]);
     }
+    return { norm, base, native };
+  }
+
+  /* the program over the host mirror of `over`'s index: the ordinals of the children it selects, in scan order */
+  _whereHost(path, norm, base) {
     if (!base.paths) {
       const err = new Error("bmx: where over a device-sourced index needs integer-valued fields on every literal");
       err.code = "BMX_NOT_DEVICE_INDEX";
       throw err;
     }
-    this.lastPath = "host";
     const store = this.bullet._getData(path);
-    const truth = (child, t) => {
-      const x = child && typeof child === "object" ? child[t.field] : undefined;
-      let pos = x !== null && x !== undefined;
-      if (pos) pos = t.eq ? x === t.min : (t.min === -Infinity || x >= t.min) && (t.max === Infinity || x <= t.max);
-      return pos !== t.not;
-    };
     const out = [];
     base.paths.forEach((p, i) => {
       const child = store[p.slice(path.length + 1)];
-      if (norm.some((c) => c.every((t) => truth(child, t)))) out.push(i);
+      if (norm.some((c) => c.every((t) => literalTruth(child, t)))) out.push(i);
     });
-    return this._nodes(base, out);
+    return out;
   }
 
   /* device indexes of the fields an aggregate names, or BMX_NOT_DEVICE_INDEX exactly where filterWhere throws it */
@@ -499,30 +525,13 @@ class GpuQuery {
     this.lastPath = ix.kind;
     const where = opts.where || [];
     const desc = !!opts.desc, after = opts.after || null;
-    const done = (nodes, values, cursor, nEligible) => { nodes.values = values; nodes.cursor = cursor; nodes.nEligible = nEligible; return nodes; };
     if (ix.kind === "device") {
       const ixs = this._deviceIndexes(path, where.map((t) => t.field), "top");
       const lo = opts.min === undefined ? -Infinity : Math.ceil(opts.min), hi = opts.max === undefined ? Infinity : Math.floor(opts.max);
       const native = [[ix.deviceField, lo, hi]].concat(where.map((t, j) => [ixs[j].deviceField, Math.ceil(t.min), Math.floor(t.max)]));
-      const r = this.graph.scanTop(native, k, { desc, after });
-      const n = r.ids.length;
-      const values = Array.from(r.vals, Number);
-      let nodes;
-      if (ix.source === "device") {
-        const u32 = new Uint32Array(r.ids.buffer, r.ids.byteOffset, n * 2);
-        nodes = [];
-        for (let i = 0; i < n; i++) nodes.push(this.bullet.get(this.graph.keys.pathOf(u32[2 * i], u32[2 * i + 1])));
-      } else nodes = this._nodes(ix, this._ordinals(ix, r.ids));
-      return done(nodes, values, n ? [r.ids[n - 1], values[n - 1]] : null, r.nEligible);
+      return this._topFromDevice(ix, this.graph.scanTop(native, k, { desc, after }));
     }
-    // host index: the same total order in JS. Numbers compare as numbers and come before everything else, which compares by its bucket key
-    const cmpVal = (a, b) => {
-      const na = typeof a === "number", nb = typeof b === "number";
-      if (na && nb) return a < b ? -1 : a > b ? 1 : 0;
-      if (na !== nb) return na ? -1 : 1;
-      const ka = bucketKey(a), kb = bucketKey(b);
-      return ka < kb ? -1 : ka > kb ? 1 : 0;
-    };
+    // host index: the same total order in JS
     const base = this.bullet._getData(path);
     const rows = [];
     ix.values.forEach((v, i) => {
@@ -532,15 +541,93 @@ class GpuQuery {
         const child = base[ix.paths[i].slice(path.length + 1)];
         for (const t of where) { const x = child && child[t.field]; if (x === null || x === undefined || !(x >= t.min && x <= t.max)) return; }
       }
-      const [l, h] = pathId(ix.paths[i]);
-      rows.push({ i, v, id: (BigInt(h) << 32n) | BigInt(l) });
+      rows.push(i);
     });
+    return this._topOnHost(ix, rows, k, desc, after);
+  }
+
+  /* the answer of top() / whereTop(): the nodes, carrying .values, .cursor and .nEligible */
+  _topDone(nodes, values, cursor, nEligible) { nodes.values = values; nodes.cursor = cursor; nodes.nEligible = nEligible; return nodes; }
+
+  /* r: {ids, vals, nEligible} of scanTop / whereTop on the index ix */
+  _topFromDevice(ix, r) {
+    const n = r.ids.length;
+    const values = Array.from(r.vals, Number);
+    let nodes;
+    if (ix.source === "device") {
+      const u32 = new Uint32Array(r.ids.buffer, r.ids.byteOffset, n * 2);
+      nodes = [];
+      for (let i = 0; i < n; i++) nodes.push(this.bullet.get(this.graph.keys.pathOf(u32[2 * i], u32[2 * i + 1])));
+    } else nodes = this._nodes(ix, this._ordinals(ix, r.ids));
+    return this._topDone(nodes, values, n ? [r.ids[n - 1], values[n - 1]] : null, r.nEligible);
+  }
+
+  /* ordinals: the selected children of the host mirror of ix -> the first k behind `after` by (value, hash of the path) */
+  _topOnHost(ix, ordinals, k, desc, after) {
+    const rows = ordinals.map((i) => { const [l, h] = pathId(ix.paths[i]); return { i, v: ix.values[i], id: (BigInt(h) << 32n) | BigInt(l) }; });
     const cmp = (a, b) => (desc ? cmpVal(b.v, a.v) : cmpVal(a.v, b.v)) || (a.id < b.id ? -1 : a.id > b.id ? 1 : 0);
     const eligible = after ? rows.filter((r) => cmp(r, { v: after[1], id: BigInt(after[0]) }) > 0) : rows;
     eligible.sort(cmp);
     const page = eligible.slice(0, k);
     const last = page.length ? page[page.length - 1] : null;
-    return done(this._nodes(ix, page.map((r) => r.i)), page.map((r) => r.v), last ? [last.id, last.v] : null, eligible.length);
+    return this._topDone(this._nodes(ix, page.map((r) => r.i)), page.map((r) => r.v), last ? [last.id, last.v] : null, eligible.length);
+  }
+
+  /**
+   * aggregateWhere() for a boolean program (bmx_where_aggregate): over the children of path that where(path, clauses, {over}) selects, the number matched, and
+   * count / sum / min / max of opts.field over those that carry it. -> {matched, count, sum, min, max} as aggregateWhere gives it. With
+   * opts.groupBy = {field, min, max}: a Map from each integer value of groupBy.field in [min, max] that occurs among the selected children to that record
+   * ("count users by role among the active non-admins"), asked in windows of 65536 values as countBy does.
+   * The device answers; an index involved that lives on the host throws BMX_NOT_DEVICE_INDEX, as aggregateWhere does.
+   */
+  whereAggregate(path, clauses, opts = {}) {
+    if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: whereAggregate needs opts.over, the field that defines the universe");
+    const groupBy = opts.groupBy || null;
+    const zero = () => (groupBy ? new Map() : { matched: 0, count: 0, sum: 0, min: null, max: null });
+    if (!clauses || clauses.length === 0) return zero();
+    const { base, native } = this._whereProgram(path, clauses, opts.over);
+    const hasMeasure = opts.field !== undefined && opts.field !== null;
+    const extra = native ? this._deviceIndexes(path, (hasMeasure ? [opts.field] : []).concat(groupBy ? [groupBy.field] : []), "whereAggregate") : null;
+    if (!native) {
+      const err = new Error("bmx: whereAggregate needs integer-valued fields on every literal");
+      err.code = "BMX_NOT_DEVICE_INDEX";
+      throw err;
+    }
+    this.lastPath = "device";
+    if (native.length === 0) return zero();
+    const measure = hasMeasure ? extra[0].deviceField : null;
+    const rec = (r) => ({ matched: r.nMatch, count: r.n, sum: r.sum, min: r.min, max: r.max });
+    if (!groupBy) return rec(this.graph.whereAggregate(base.deviceField, native, { measure }));
+    const group = extra[extra.length - 1].deviceField;
+    const out = new Map();
+    const lo = Math.ceil(groupBy.min), hi = Math.floor(groupBy.max);
+    for (let g0 = lo; g0 <= hi; g0 += 65536) {                // windows of BMX_AGG_MAX_GROUPS values
+      const n = Math.min(65536, hi - g0 + 1);
+      const recs = this.graph.whereAggregate(base.deviceField, native, { measure, group, groupLo: g0, nGroups: n });
+      for (let g = 0; g < n; g++) if (recs[g].nMatch) out.set(g0 + g, rec(recs[g]));
+    }
+    return out;
+  }
+
+  /**
+   * top() for a boolean program (bmx_where_top): the first k of the children that where(path, clauses, {over}) selects, ordered by the value of `over`, then
+   * by the 64-bit hash of their path ("the 20 youngest users who are not admins": over = "age"). opts: over (required), desc, after (the .cursor of the page
+   * before). -> the BulletNodes in order, carrying .cursor, .values and .nEligible like top().
+   * When every index involved is an integer index the device answers; when one lives on the host, where()'s literal truth and top()'s comparator run in JS.
+   */
+  whereTop(path, clauses, k, opts = {}) {
+    if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: whereTop needs opts.over, the field that defines the universe and the order");
+    const desc = !!opts.desc, after = opts.after || null;
+    if (!clauses || clauses.length === 0) return this._topDone([], [], null, 0);
+    const { norm, base, native } = this._whereProgram(path, clauses, opts.over);
+    if (native) {
+      this.lastPath = "device";
+      if (native.length === 0) return this._topDone([], [], null, 0);
+      return this._topFromDevice(base, this.graph.whereTop(base.deviceField, native, k, { desc, after }));
+    }
+    const selected = this._whereHost(path, norm, base);
+    this.lastPath = "host";
+    return this._topOnHost(base, selected, k, desc, after);
   }
 
   filter(path, fn) {

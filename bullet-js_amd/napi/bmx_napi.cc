@@ -23,6 +23,7 @@
 #include "bmx.h"
 #include "bmx_top.h"
 #include "bmx_where.h"
+#include "bmx_where_agg.h"
 #include "bmx_ticket.h"
 
 namespace {
@@ -57,6 +58,8 @@ struct Engine {
   static constexpr auto export_rows = bmx_export_rows;
   static constexpr auto scan_aggregate = bmx_scan_aggregate;
   static constexpr auto scan_top = bmx_scan_top;
+  static constexpr auto where_aggregate = bmx_where_aggregate;
+  static constexpr auto where_top = bmx_where_top;
   template <class F, class... A> static int host(F fn, A... a) { return fn(a..., BMX_MEM_HOST); }
 };
 struct Comm {
@@ -78,6 +81,8 @@ struct Comm {
   static constexpr auto export_rows = bmx_comm_export_rows;
   static constexpr auto scan_aggregate = bmx_comm_scan_aggregate;
   static constexpr auto scan_top = bmx_comm_scan_top;
+  static constexpr auto where_aggregate = bmx_comm_where_aggregate;
+  static constexpr auto where_top = bmx_comm_where_top;
   template <class F, class... A> static int host(F fn, A... a) { return fn(a...); }
 };
 struct Vc {
@@ -460,19 +465,16 @@ template <class Kind> napi_value ExportRows(napi_env env, napi_callback_info inf
 /* Aggregate queries (bmx.h bmx_scan_aggregate): thin bindings, no logic.
  * scanAggregate(handle, [[field, lo, hi], ...], measure | null, group | null, groupLo, nGroups) / commScanAggregate(comm, ...) ->
  * {nMatch, n: BigUint64Array, min, max: BigInt64Array, sumLo: BigUint64Array, sumHi: BigInt64Array}, one entry per record (nGroups + 1, or 1 without groups) */
-template <class Kind> napi_value ScanAggregate(napi_env env, napi_callback_info info) {
-  HANDLE(Kind, 6);
-  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "aggregate", terms); if (!nt) return nullptr;
-  uint32_t fld[2] = {BMX_AGG_NO_FIELD, BMX_AGG_NO_FIELD};
-  for (int k = 0; k < 2; k++) if (!is_nullish(env, argv[2 + k]) && !get_u32(env, argv[2 + k], &fld[k])) return nullptr;
-  int64_t glo; if (!get_i64(env, argv[4], &glo)) return nullptr;
-  uint32_t ng; if (!get_u32(env, argv[5], &ng)) return nullptr;
-  if (ng > BMX_AGG_MAX_GROUPS || (ng && fld[1] == BMX_AGG_NO_FIELD)) { napi_throw_range_error(env, nullptr, "bmx: nGroups is 0..65536 and needs a group field"); return nullptr; }
-  const size_t nrec = ng ? (size_t)ng + 1 : 1;
-  std::vector<bmx_agg> recs(nrec);
-  int rc;
-  { Turn turn(h->q); rc = Kind::host(Kind::scan_aggregate, h->p, nt, (const bmx_term*)terms, fld[0], fld[1], glo, ng, recs.data()); }
-  if (rc) return fail<Kind>(env, h->p, rc);
+// measure | null, group | null, groupLo, nGroups at argv[0..3] -> fld[2], glo, ng; false with a JS error pending
+bool get_agg_tail(napi_env env, const napi_value* argv, uint32_t* fld, int64_t* glo, uint32_t* ng) {
+  fld[0] = fld[1] = BMX_AGG_NO_FIELD;
+  for (int k = 0; k < 2; k++) if (!is_nullish(env, argv[k]) && !get_u32(env, argv[k], &fld[k])) return false;
+  if (!get_i64(env, argv[2], glo) || !get_u32(env, argv[3], ng)) return false;
+  if (*ng > BMX_AGG_MAX_GROUPS || (*ng && fld[1] == BMX_AGG_NO_FIELD)) { napi_throw_range_error(env, nullptr, "bmx: nGroups is 0..65536 and needs a group field"); return false; }
+  return true;
+}
+napi_value agg_result(napi_env env, const std::vector<bmx_agg>& recs) {
+  const size_t nrec = recs.size();
   void *pm = nullptr, *pn = nullptr, *plo = nullptr, *phi = nullptr, *psl = nullptr, *psh = nullptr;
   napi_value out = object_of(env, {{"nMatch", make_ta(env, napi_biguint64_array, nrec, &pm)}, {"n", make_ta(env, napi_biguint64_array, nrec, &pn)}, {"min", make_ta(env, napi_bigint64_array, nrec, &plo)},
                                    {"max", make_ta(env, napi_bigint64_array, nrec, &phi)}, {"sumLo", make_ta(env, napi_biguint64_array, nrec, &psl)}, {"sumHi", make_ta(env, napi_bigint64_array, nrec, &psh)}});
@@ -482,30 +484,50 @@ template <class Kind> napi_value ScanAggregate(napi_env env, napi_callback_info 
   }
   return out;
 }
+template <class Kind> napi_value ScanAggregate(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 6);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "aggregate", terms); if (!nt) return nullptr;
+  uint32_t fld[2]; int64_t glo; uint32_t ng;
+  if (!get_agg_tail(env, argv + 2, fld, &glo, &ng)) return nullptr;
+  std::vector<bmx_agg> recs(ng ? (size_t)ng + 1 : 1);
+  int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::scan_aggregate, h->p, nt, (const bmx_term*)terms, fld[0], fld[1], glo, ng, recs.data()); }
+  return rc ? fail<Kind>(env, h->p, rc) : agg_result(env, recs);
+}
 /* Ordered top-k queries (bmx_top.h bmx_scan_top): thin bindings, no logic.
  * scanTop(handle, [[field, lo, hi], ...], desc, after | null, k) / commScanTop(comm, ...) -> {ids: BigUint64Array, vals: BigInt64Array, nEligible}: the first k
  * eligible nodes in (value, id) order; after = [id (BigInt), value] is the cursor. Ids are BigUint64Array entries, as scanFilter delivers them. */
-template <class Kind> napi_value ScanTop(napi_env env, napi_callback_info info) {
-  HANDLE(Kind, 5);
-  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "top", terms); if (!nt) return nullptr;
-  bool desc = false; NAPI_OK(napi_get_value_bool(env, argv[2], &desc));
-  bmx_top_rec cur{0, 0}; const bool have_cur = !is_nullish(env, argv[3]);
-  if (have_cur) {
+// desc, after | null, k at argv[0..2] -> flags, the cursor, k; false with a JS error pending
+struct TopTail { uint32_t flags = 0, k = 0; bmx_top_rec cur{0, 0}; bool have_cur = false; const bmx_top_rec* after() const { return have_cur ? &cur : nullptr; } };
+bool get_top_tail(napi_env env, const napi_value* argv, TopTail* t) {
+  bool desc = false; if (napi_get_value_bool(env, argv[0], &desc) != napi_ok) { napi_throw_type_error(env, nullptr, "bmx: desc is a boolean"); return false; }
+  t->flags = desc ? BMX_TOP_DESC : 0u;
+  t->have_cur = !is_nullish(env, argv[1]);
+  if (t->have_cur) {
     napi_value e0, e1; bool lossless = false;
-    NAPI_OK(napi_get_element(env, argv[3], 0, &e0)); NAPI_OK(napi_get_element(env, argv[3], 1, &e1));
-    NAPI_OK(napi_get_value_bigint_uint64(env, e0, &cur.id, &lossless));
-    if (!get_i64(env, e1, &cur.val)) return nullptr;
+    if (napi_get_element(env, argv[1], 0, &e0) != napi_ok || napi_get_element(env, argv[1], 1, &e1) != napi_ok || napi_get_value_bigint_uint64(env, e0, &t->cur.id, &lossless) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "bmx: after is [id (BigInt), value]"); return false;
+    }
+    if (!get_i64(env, e1, &t->cur.val)) return false;
   }
-  uint32_t k; if (!get_u32(env, argv[4], &k)) return nullptr;
-  if (k == 0 || k > BMX_TOP_MAX_K) { napi_throw_range_error(env, nullptr, "bmx: k is 1..4096"); return nullptr; }
-  std::vector<bmx_top_rec> recs(k);
-  uint64_t m = 0, ne = 0; int rc;
-  { Turn turn(h->q); rc = Kind::host(Kind::scan_top, h->p, nt, (const bmx_term*)terms, desc ? BMX_TOP_DESC : 0u, have_cur ? (const bmx_top_rec*)&cur : nullptr, k, recs.data(), &m, &ne); }
-  if (rc) return fail<Kind>(env, h->p, rc);
+  if (!get_u32(env, argv[2], &t->k)) return false;
+  if (t->k == 0 || t->k > BMX_TOP_MAX_K) { napi_throw_range_error(env, nullptr, "bmx: k is 1..4096"); return false; }
+  return true;
+}
+napi_value top_result(napi_env env, const std::vector<bmx_top_rec>& recs, uint64_t m, uint64_t ne) {
   void *pi = nullptr, *pv = nullptr;
   napi_value out = object_of(env, {{"ids", make_ta(env, napi_biguint64_array, m, &pi)}, {"vals", make_ta(env, napi_bigint64_array, m, &pv)}, {"nEligible", num(env, (double)ne)}});
   if (out) for (uint64_t i = 0; i < m; i++) { ((uint64_t*)pi)[i] = recs[i].id; ((int64_t*)pv)[i] = recs[i].val; }
   return out;
+}
+template <class Kind> napi_value ScanTop(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 5);
+  bmx_term terms[8]; const uint32_t nt = get_terms(env, argv[1], "top", terms); if (!nt) return nullptr;
+  TopTail t; if (!get_top_tail(env, argv + 2, &t)) return nullptr;
+  std::vector<bmx_top_rec> recs(t.k);
+  uint64_t m = 0, ne = 0; int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::scan_top, h->p, nt, (const bmx_term*)terms, t.flags, t.after(), t.k, recs.data(), &m, &ne); }
+  return rc ? fail<Kind>(env, h->p, rc) : top_result(env, recs, m, ne);
 }
 // The engine sweeps once: room for the whole index of `base`, as scanFilter sizes its answer (the sweep is bound by its probes: a count in front would double
 // it). The communicator's shards have no common size: it counts first, then fetches — two sweeps.
@@ -524,28 +546,58 @@ napi_value where_answer(napi_env env, Handle<Comm>* h, uint32_t base, uint32_t n
 /* Boolean filters (bmx_where.h bmx_scan_where): thin bindings, no logic.
  * scanWhere(handle, base, [[[field, lo, hi, not], ...], ...]) / commScanWhere(comm, ...) -> BigUint64Array: the nodes holding data in field `base` for which some
  * clause has all of its literals true (not: a truthy fourth entry negates the literal), in index order of `base`. */
+// [[[field, lo, hi, not], ...], ...] -> the program as bmx_scan_where takes it; false with a JS error pending
+struct Program { uint32_t nc = 0; uint32_t lens[BMX_WHERE_MAX_CLAUSES]; std::vector<bmx_lit> lits; };
+bool get_program(napi_env env, napi_value clauses, Program* P) {
+  if (napi_get_array_length(env, clauses, &P->nc) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
+  if (P->nc == 0 || P->nc > BMX_WHERE_MAX_CLAUSES) { napi_throw_range_error(env, nullptr, "bmx: where needs 1..8 clauses"); return false; }
+  for (uint32_t c = 0; c < P->nc; c++) {
+    napi_value cl;
+    if (napi_get_element(env, clauses, c, &cl) != napi_ok || napi_get_array_length(env, cl, &P->lens[c]) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
+    if (P->lens[c] == 0 || P->lens[c] > 8 || P->lits.size() + P->lens[c] > BMX_WHERE_MAX_LITS) { napi_throw_range_error(env, nullptr, "bmx: a where clause has 1..8 literals, a program 32 at most"); return false; }
+    for (uint32_t k = 0; k < P->lens[c]; k++) {
+      napi_value t, e[4]; bmx_lit L{0, 0, 0, 0}; bool neg = false;
+      bool ok = napi_get_element(env, cl, k, &t) == napi_ok;
+      for (uint32_t j = 0; ok && j < 4; j++) ok = napi_get_element(env, t, j, &e[j]) == napi_ok;
+      if (!ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
+      if (!get_u32(env, e[0], &L.field) || !get_i64(env, e[1], &L.lo) || !get_i64(env, e[2], &L.hi)) return false;
+      if (napi_coerce_to_bool(env, e[3], &e[3]) != napi_ok || napi_get_value_bool(env, e[3], &neg) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_coerce_to_bool"); return false; }
+      L.flags = neg ? BMX_LIT_NOT : 0u;
+      P->lits.push_back(L);
+    }
+  }
+  return true;
+}
 template <class Kind> napi_value ScanWhere(napi_env env, napi_callback_info info) {
   HANDLE(Kind, 3);
   uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
-  uint32_t nc = 0;
-  if (napi_get_array_length(env, argv[2], &nc) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return nullptr; }
-  if (nc == 0 || nc > BMX_WHERE_MAX_CLAUSES) { napi_throw_range_error(env, nullptr, "bmx: where needs 1..8 clauses"); return nullptr; }
-  uint32_t lens[BMX_WHERE_MAX_CLAUSES]; std::vector<bmx_lit> lits;
-  for (uint32_t c = 0; c < nc; c++) {
-    napi_value cl; NAPI_OK(napi_get_element(env, argv[2], c, &cl));
-    if (napi_get_array_length(env, cl, &lens[c]) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return nullptr; }
-    if (lens[c] == 0 || lens[c] > 8 || lits.size() + lens[c] > BMX_WHERE_MAX_LITS) { napi_throw_range_error(env, nullptr, "bmx: a where clause has 1..8 literals, a program 32 at most"); return nullptr; }
-    for (uint32_t k = 0; k < lens[c]; k++) {
-      napi_value t, e0, e1, e2, e3; bmx_lit L{0, 0, 0, 0}; bool neg = false;
-      NAPI_OK(napi_get_element(env, cl, k, &t)); NAPI_OK(napi_get_element(env, t, 0, &e0)); NAPI_OK(napi_get_element(env, t, 1, &e1));
-      NAPI_OK(napi_get_element(env, t, 2, &e2)); NAPI_OK(napi_get_element(env, t, 3, &e3));
-      if (!get_u32(env, e0, &L.field) || !get_i64(env, e1, &L.lo) || !get_i64(env, e2, &L.hi)) return nullptr;
-      NAPI_OK(napi_coerce_to_bool(env, e3, &e3)); NAPI_OK(napi_get_value_bool(env, e3, &neg));
-      L.flags = neg ? BMX_LIT_NOT : 0u;
-      lits.push_back(L);
-    }
-  }
-  return where_answer(env, h, base, nc, lens, lits);
+  Program P; if (!get_program(env, argv[2], &P)) return nullptr;
+  return where_answer(env, h, base, P.nc, P.lens, P.lits);
+}
+/* Aggregates and top-k over boolean filters (bmx_where_agg.h): thin bindings, no logic. The program is scanWhere's, the other arguments and the answers are
+ * scanAggregate's and scanTop's.
+ * whereAggregate(handle, base, clauses, measure | null, group | null, groupLo, nGroups) / commWhereAggregate(comm, ...)
+ * whereTop(handle, base, clauses, desc, after | null, k) / commWhereTop(comm, ...): ordered by the value of `base`, then id */
+template <class Kind> napi_value WhereAggregate(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 7);
+  uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
+  Program P; if (!get_program(env, argv[2], &P)) return nullptr;
+  uint32_t fld[2]; int64_t glo; uint32_t ng;
+  if (!get_agg_tail(env, argv + 3, fld, &glo, &ng)) return nullptr;
+  std::vector<bmx_agg> recs(ng ? (size_t)ng + 1 : 1);
+  int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::where_aggregate, h->p, base, P.nc, (const uint32_t*)P.lens, (const bmx_lit*)P.lits.data(), fld[0], fld[1], glo, ng, recs.data()); }
+  return rc ? fail<Kind>(env, h->p, rc) : agg_result(env, recs);
+}
+template <class Kind> napi_value WhereTop(napi_env env, napi_callback_info info) {
+  HANDLE(Kind, 6);
+  uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
+  Program P; if (!get_program(env, argv[2], &P)) return nullptr;
+  TopTail t; if (!get_top_tail(env, argv + 3, &t)) return nullptr;
+  std::vector<bmx_top_rec> recs(t.k);
+  uint64_t m = 0, ne = 0; int rc;
+  { Turn turn(h->q); rc = Kind::host(Kind::where_top, h->p, base, P.nc, (const uint32_t*)P.lens, (const bmx_lit*)P.lits.data(), t.flags, t.after(), t.k, recs.data(), &m, &ne); }
+  return rc ? fail<Kind>(env, h->p, rc) : top_result(env, recs, m, ne);
 }
 
 // ---- the engine alone -----------------------------------------------------------------------------------------------------------------
@@ -868,6 +920,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"loadRows", StoreRows<Engine, false>}, {"putRows", StoreRows<Engine, true>}, {"getRows", GetRows<Engine>}, {"rowCount", RowCount<Engine>}, {"dumpRows", DumpRows<Engine>},
       {"indexBuild", IndexBuild<Engine>}, {"indexSetOrdered", IndexSetOrdered<Engine>}, {"scanRange", ScanRange<Engine>}, {"scanCount", ScanCount<Engine>}, {"digest", Digest<Engine>},
       {"exportRows", ExportRows<Engine>}, {"scanAggregate", ScanAggregate<Engine>}, {"scanTop", ScanTop<Engine>}, {"scanWhere", ScanWhere<Engine>},
+      {"whereAggregate", WhereAggregate<Engine>}, {"whereTop", WhereTop<Engine>}, {"commWhereAggregate", WhereAggregate<Comm>}, {"commWhereTop", WhereTop<Comm>},
       {"commLoadRows", StoreRows<Comm, false>}, {"commPutRows", StoreRows<Comm, true>}, {"commGetRows", GetRows<Comm>}, {"commRowCount", RowCount<Comm>}, {"commDumpRows", DumpRows<Comm>},
       {"commIndexBuild", IndexBuild<Comm>}, {"commIndexSetOrdered", IndexSetOrdered<Comm>}, {"commScanRange", ScanRange<Comm>}, {"commScanCount", ScanCount<Comm>}, {"commDigest", Digest<Comm>},
       {"commExportRows", ExportRows<Comm>}, {"commScanAggregate", ScanAggregate<Comm>}, {"commScanTop", ScanTop<Comm>}, {"commScanWhere", ScanWhere<Comm>},
