@@ -1,6 +1,7 @@
 """GPU parity, randomized: many small shapes against the oracle (merge, scans) and against a numpy stable sort (owner partition).
 Sizes sit on the kernels' internal boundaries (64-lane waves, 256-delta blocks, 1024-delta partition tiles, 4096-delta compaction
-blocks); timestamps and values come from tiny ranges so ties and duplicate keys are the norm, plus the domain's extreme values."""
+blocks); timestamps and values come from tiny ranges so ties and duplicate keys are the norm, plus the domain's extreme values.
+The deterministic counterpart, with every delta placed on one of those boundaries by construction: tests/test_gpu_merge_kernel_edges.py."""
 import os
 
 import numpy as np
