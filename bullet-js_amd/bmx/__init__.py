@@ -27,6 +27,7 @@ MAX_BATCH = 1 << 24
 AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
+GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2   # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
@@ -58,6 +59,9 @@ EXPORTS_WATCH = ["bmx_watch_create", "bmx_watch_poll", "bmx_watch_destroy", "bmx
 
 # include/bmx_where_agg.h: aggregates and top-k over boolean filters, likewise
 EXPORTS_WHERE_AGG = ["bmx_where_aggregate", "bmx_where_top", "bmx_comm_where_aggregate", "bmx_comm_where_top"]
+
+# include/bmx_group.h: group-by over discovered values, likewise
+EXPORTS_GROUP = ["bmx_where_group", "bmx_comm_where_group"]
 
 
 class BmxError(RuntimeError):
@@ -157,6 +161,64 @@ def _where_args(base, clauses):
     lens = (C.c_uint32 * max(len(clauses), 1))(*[len(c) for c in clauses])
     lits = (Lit * max(len(flat), 1))(*[Lit(int(t[0]), LIT_NOT if len(t) > 3 and t[3] else 0, int(t[1]), int(t[2])) for t in flat])
     return (int(base), len(clauses), lens, lits)
+
+
+GROUP_DTYPE = np.dtype([("key", "<i8"), ("agg", AGG_DTYPE)])      # bmx_group_rec: one record of bmx_where_group (56 bytes)
+
+
+class GroupRes(C.Structure):
+    """bmx_group_res: what one bmx_where_group found besides its records (112 bytes); flags: GROUP_OVERFLOW"""
+    _fields_ = [("n_groups", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("absent", Agg), ("total", Agg)]
+
+
+GROUP_RES_DTYPE = np.dtype([("n_groups", "<u8"), ("flags", "<u4"), ("reserved", "<u4"), ("absent", AGG_DTYPE), ("total", AGG_DTYPE)])
+
+
+class GroupResult:
+    """One where_group answer: groups = {key: AggResult} in ascending key order (empty on overflow), records (GROUP_DTYPE, sorted by key), n_groups (the
+    number of distinct keys, or on overflow a lower bound of it above cap), overflow, absent (selected nodes without a group value) and total (every
+    selected node) as AggResult."""
+    __slots__ = ("records", "groups", "n_groups", "overflow", "absent", "total")
+
+    def __init__(self, res, recs):
+        r = np.frombuffer(bytes(res), GROUP_RES_DTYPE)[0] if isinstance(res, GroupRes) else res
+        self.n_groups = int(r["n_groups"]); self.overflow = bool(int(r["flags"]) & GROUP_OVERFLOW)
+        self.absent, self.total = AggResult(r["absent"]), AggResult(r["total"])
+        self.records = recs[:0 if self.overflow else self.n_groups].copy()
+        self.groups = {int(x["key"]): AggResult(x["agg"]) for x in self.records}
+
+    def __repr__(self):
+        return "GroupResult(%d groups%s, absent=%r, total=%r)" % (self.n_groups, ", overflow" if self.overflow else "", self.absent, self.total)
+
+
+def _group_fold(o, p):
+    """o += p for one record of AGG_DTYPE (0-d views): counts and 128-bit sums add, minima and maxima fold"""
+    o["n_match"] += p["n_match"]; o["n"] += p["n"]
+    o["min"] = min(int(o["min"]), int(p["min"])); o["max"] = max(int(o["max"]), int(p["max"]))
+    s = ((int(o["sum_hi"]) << 64) + int(o["sum_lo"]) + (int(p["sum_hi"]) << 64) + int(p["sum_lo"])) & ((1 << 128) - 1)
+    o["sum_lo"] = s & ((1 << 64) - 1)
+    hi = s >> 64
+    o["sum_hi"] = hi - (1 << 64) if hi >= (1 << 63) else hi
+
+
+def group_merge(lists):
+    """The merge bmx_comm_where_group does with its shards' answers: `lists` are record arrays (GROUP_DTYPE), each with distinct keys; -> one array sorted
+    ascending by key, the records of equal keys folded (counts and 128-bit sums add, minima and maxima fold). Pure numpy: no library, no GPU."""
+    parts = [np.asarray(x, GROUP_DTYPE) for x in lists if len(x)]
+    if not parts:
+        return np.zeros(0, GROUP_DTYPE)
+    a = np.concatenate(parts)
+    a = a[np.argsort(a["key"], kind="stable")]
+    first = np.ones(len(a), bool); first[1:] = a["key"][1:] != a["key"][:-1]
+    out = a[first].copy()
+    at = np.cumsum(first) - 1
+    for i in np.nonzero(~first)[0]:
+        _group_fold(out[at[i]]["agg"], a[i]["agg"])
+    return out
+
+
+def _group_tail(measure, group):
+    return (AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group))
 
 
 class WatchRes(C.Structure):
@@ -283,6 +345,8 @@ def load_library():
     L.bmx_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp, i32]; L.bmx_where_top.restype = i32
     L.bmx_comm_where_aggregate.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, i64, u32, vp]; L.bmx_comm_where_aggregate.restype = i32
     L.bmx_comm_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp]; L.bmx_comm_where_top.restype = i32
+    L.bmx_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp, i32]; L.bmx_where_group.restype = i32
+    L.bmx_comm_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp]; L.bmx_comm_where_group.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
     L.bmx_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp, i32]; L.bmx_watch_poll.restype = i32
     L.bmx_watch_destroy.argtypes = [vp, u32]; L.bmx_watch_destroy.restype = i32
@@ -683,6 +747,15 @@ class Engine:
                                        C.cast(C.byref(ne), C.c_void_p), MEM_HOST))
         return out[:m.value].copy(), ne.value
 
+    def where_group(self, base, clauses, group, measure=None, cap=65536):
+        """Group-by over discovered values (bmx_group.h): count / sum / min / max of field `measure` over the selection of scan_where(base, clauses), one
+        record per distinct value of field `group` that occurs among the selected nodes; nobody has to know the values in advance. -> GroupResult (with
+        overflow set and no records when there are more than cap distinct values: ask again with more room or a narrower program)"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = GroupRes()
+        self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return GroupResult(res, out)
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -851,6 +924,12 @@ class Engine:
     def where_top_dev(self, base, clauses, k, out, n_out=None, n_eligible=None, desc=False, after=None):
         """where_top into device memory (`out`, n_out, n_eligible as for scan_top_dev); enqueue-only. The program and the cursor are host data."""
         self._chk(self.L.bmx_where_top(self.h, *_where_args(base, clauses), *_where_top_tail(k, desc, after), _ptr(out), _ptr(n_out), _ptr(n_eligible), MEM_DEVICE))
+
+    def where_group_dev(self, base, clauses, group, out, res, measure=None, cap=65536):
+        """where_group into device memory (`out`: room for cap records of 56 bytes; res: 112 bytes, a bmx_group_res); enqueue-only. The records come in no
+        particular order; after sync(), GroupResult(res.cpu().numpy().view(GROUP_RES_DTYPE)[0], np.sort(out.cpu().numpy().view(GROUP_DTYPE)[:n], order="key"))
+        reads them. The program is host data."""
+        self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1080,6 +1159,13 @@ class Comm:
         self._chk(self.L.bmx_comm_where_top(self.h, *_where_args(base, clauses), *_where_top_tail(k, desc, after), _ptr(out), C.cast(C.byref(m), C.c_void_p),
                                             C.cast(C.byref(ne), C.c_void_p)))
         return out[:m.value].copy(), ne.value
+
+    def where_group(self, base, clauses, group, measure=None, cap=65536):
+        """Engine.where_group over all shards: every shard answers with its own groups, the library merges them by key as group_merge does"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = GroupRes()
+        self._chk(self.L.bmx_comm_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p)))
+        return GroupResult(res, out)
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

@@ -34,6 +34,7 @@
 #include "watch_kernels.h"
 #include "where_agg_kernels.h"
 #include "../../include/bmx_where_agg.h"
+#include "group_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -309,6 +310,16 @@ struct TopScratch {
   void release() { dev_free(state); dev_free(cand_u); dev_free(cand_id); dev_free(stage); clean = false; }
 };
 
+// Scratch of the group-by over discovered values (bmx_group.inc): the open-addressed table (a key word and an accumulator per slot) and the state record, which
+// every query's last kernel leaves empty again (clean), and the records + result record of a BMX_MEM_HOST answer on their way down. Grows to the largest cap
+// asked so far, all or nothing; a query with a smaller cap uses the head of the table.
+struct GroupScratch {
+  long long* keys = nullptr; AggRaw* acc = nullptr; GroupState* state = nullptr; bmx_group_rec* stage = nullptr; bmx_group_res* stage_res = nullptr;
+  uint64_t cap = 0, slots = 0;
+  bool clean = false;
+  void release() { dev_free(keys); dev_free(acc); dev_free(state); dev_free(stage); dev_free(stage_res); cap = 0; slots = 0; clean = false; }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -369,6 +380,7 @@ struct bmx_ctx {
   SyncScratch sync;
   AggScratch agg;
   TopScratch top;
+  GroupScratch group;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -640,6 +652,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->sync.release();
   ctx->agg.release();
   ctx->top.release();
+  ctx->group.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -931,3 +944,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls)
 #include "bmx_watch.inc"     // (likewise)
 #include "bmx_where_agg.inc" // (likewise)
+#include "bmx_group.inc"     // (likewise)

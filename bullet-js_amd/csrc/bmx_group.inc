@@ -1,0 +1,154 @@
+// bmx_group.inc — group-by over discovered values (bmx_group.h): bmx_where_group and its sharded form. The program is bmx_where.inc's (where_prepare), the
+// predicate and the sweep grid are bmx_where_agg.inc's (where_pred, where_agg_grid), the kernels are group_kernels.h. The context keeps their scratch
+// (GroupScratch): the table, the state record, which every query's last kernel leaves empty again (clean), and the answer of a host-mode call on its way down.
+// Included by bmx.hip (one translation unit), behind everything that was here before it.
+namespace {
+
+const char* group_bad_args(uint32_t group_field, const bmx_group_rec* out, uint64_t cap, const bmx_group_res* res) {
+  if (!res) return "bmx_where_group: null result record";
+  if (cap == 0 || cap > BMX_GROUP_MAX_CAP) return "bmx_where_group: cap outside 1..BMX_GROUP_MAX_CAP";
+  if (!out) return "bmx_where_group: null output";
+  if (group_field == BMX_AGG_NO_FIELD) return "bmx_where_group: no group field";
+  return nullptr;
+}
+
+inline uint64_t group_slots(uint64_t cap) {
+  uint64_t s = 64;
+  while (s < 2 * cap) s <<= 1;
+  return s;
+}
+// (every workgroup of k_group_finish ends with one returning atomic on one word: few workgroups, each with several rounds of slots)
+inline uint32_t group_finish_grid(uint64_t slots) { return (uint32_t)std::min<uint64_t>((slots + 255) / 256, 256); }
+
+// the scratch for a query of `cap` records: grows to the largest cap asked so far, all or nothing
+int group_scratch(bmx_ctx* ctx, uint64_t cap) {
+  GroupScratch& s = ctx->group;
+  if (cap > s.cap) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    s.cap = 0; s.slots = 0;
+    const uint64_t slots = group_slots(cap);
+    if (int rc = dev_alloc_all(ctx, {{s.keys, slots * sizeof(long long)}, {s.acc, slots * sizeof(AggRaw)}, {s.state, sizeof(GroupState)},
+                                     {s.stage, cap * sizeof(bmx_group_rec)}, {s.stage_res, sizeof(bmx_group_res)}})) return rc;
+    s.cap = cap; s.slots = slots; s.clean = false;
+  }
+  if (!s.clean) {     // a new table, or a query that did not get as far as its last kernel
+    hipLaunchKernelGGL(k_group_clear, dim3(group_finish_grid(s.slots)), dim3(256), 0, ctx->stream, s.keys, s.acc, s.slots, s.state);
+    LAUNCHCHK("k_group_clear");
+  }
+  return BMX_OK;
+}
+
+// Enqueue one group-by over a prepared program; the records and the result record go to d_out / d_res (device memory), or, with d_out == nullptr, to the
+// context's staging buffers (group_collect fetches them). The arguments have been checked and the context entered. A value-ordered view of the base field's
+// index is neither read nor touched (where_run).
+int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t group_field, uint64_t cap, bmx_group_rec* d_out,
+                  bmx_group_res* d_res) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  if (int rc = group_scratch(ctx, cap)) return rc;
+  GroupScratch& s = ctx->group;
+  GroupArgs A{};
+  A.keys = s.keys; A.acc = s.acc; A.S = s.state;
+  A.slots = group_slots(cap); A.cap = cap;                         // (a query uses the head of a table that an earlier, larger one left empty)
+  A.measure = measure_field; A.group = group_field;
+  A.m_src = where_agg_source(measure_field, base_field); A.g_src = where_agg_source(group_field, base_field);
+  s.clean = false;
+  if (ix->fits32) hipLaunchKernelGGL((k_group_sweep<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, W), A);
+  else hipLaunchKernelGGL((k_group_sweep<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, W), A);
+  LAUNCHCHK("k_group_sweep");
+  hipLaunchKernelGGL(k_group_finish, dim3(group_finish_grid(A.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,
+                     A.m_src != AGG_SRC_PROBE ? 1u : 0u);
+  LAUNCHCHK("k_group_finish");
+  s.clean = true;
+  return BMX_OK;
+}
+
+inline bool group_key_less(const bmx_group_rec& a, const bmx_group_rec& b) { return a.key < b.key; }
+
+// second half of a host-mode query: the result record, then (if they fit) the records, sorted by key. `recs` gets them; nothing of the caller's is written.
+int group_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_group_rec>& recs, bmx_group_res* res) {
+  HIPCHK(hipMemcpyAsync(res, ctx->group.stage_res, sizeof(bmx_group_res), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  recs.clear();
+  if (res->flags & BMX_GROUP_OVERFLOW) return BMX_OK;
+  if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, "bmx_where_group: more records than cap without the overflow flag");
+  recs.resize(res->n_groups);
+  if (res->n_groups) {
+    HIPCHK(hipMemcpyAsync(recs.data(), ctx->group.stage, res->n_groups * sizeof(bmx_group_rec), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    std::sort(recs.begin(), recs.end(), group_key_less);
+  }
+  return BMX_OK;
+}
+
+// a += b: counts and 128-bit sums add, minima and maxima fold (comm_agg_with's combine)
+inline void group_fold(bmx_agg& o, const bmx_agg& p) {
+  o.n_match += p.n_match; o.n += p.n;
+  o.min = std::min(o.min, p.min); o.max = std::max(o.max, p.max);
+  const unsigned __int128 s = (((unsigned __int128)(uint64_t)o.sum_hi << 64) | o.sum_lo) + (((unsigned __int128)(uint64_t)p.sum_hi << 64) | p.sum_lo);
+  o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_where_group(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field,
+                    uint32_t group_field, bmx_group_rec* out, uint64_t cap, bmx_group_res* res, int mem) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (const char* bad = group_bad_args(group_field, out, cap, res)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
+  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  if (int erc = enter(ctx)) return erc;
+  if (mem == BMX_MEM_DEVICE) return group_enqueue(ctx, base_field, W, measure_field, group_field, cap, out, res);
+  if (int rc = group_enqueue(ctx, base_field, W, measure_field, group_field, cap, nullptr, nullptr)) return rc;
+  std::vector<bmx_group_rec> recs;
+  bmx_group_res r;
+  if (int rc = group_collect(ctx, cap, recs, &r)) return rc;
+  if (!recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(bmx_group_rec));
+  *res = r;
+  return BMX_OK;
+}
+
+int bmx_comm_where_group(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field,
+                         uint32_t group_field, bmx_group_rec* out, uint64_t cap, bmx_group_res* res) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
+  if (const char* bad = group_bad_args(group_field, out, cap, res)) return fail(c, BMX_ERR_INVALID, bad);
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  DevGuard guard;
+  std::vector<bmx_group_rec> all, part, tmp;
+  bmx_group_res tot{};
+  uint64_t lower = 0;                                               // the largest lower bound of D any overflowing shard reported
+  bool overflow = false;
+  const int rc = comm_two_phase(c,
+    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : group_enqueue(x, base_field, W, measure_field, group_field, cap, nullptr, nullptr); },
+    [&](uint32_t g, bmx_ctx* x) {
+      bmx_group_res r;
+      int crc = enter(x);
+      if (!crc) crc = group_collect(x, cap, part, &r);
+      if (crc) return crc;
+      if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
+      if (r.flags & BMX_GROUP_OVERFLOW) { overflow = true; lower = std::max(lower, r.n_groups); return (int)BMX_OK; }
+      // the shards' lists are sorted by key: one merge, equal keys folded
+      tmp.clear(); tmp.reserve(all.size() + part.size());
+      size_t i = 0, j = 0;
+      while (i < all.size() || j < part.size()) {
+        if (j == part.size() || (i < all.size() && all[i].key < part[j].key)) tmp.push_back(all[i++]);
+        else if (i == all.size() || part[j].key < all[i].key) tmp.push_back(part[j++]);
+        else { bmx_group_rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
+      }
+      all.swap(tmp);
+      return (int)BMX_OK;
+    });
+  if (rc) return rc;
+  lower = std::max<uint64_t>(lower, all.size());
+  if (overflow || all.size() > cap) { tot.flags = BMX_GROUP_OVERFLOW; tot.n_groups = lower; }
+  else { tot.flags = 0; tot.n_groups = all.size(); if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(bmx_group_rec)); }
+  tot.reserved = 0;
+  *res = tot;
+  return BMX_OK;
+}
+
+}  // extern "C"
