@@ -28,7 +28,8 @@ AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measu
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
-WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2   # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
+ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
+WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2  # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
 EXPORTS = [
@@ -62,6 +63,9 @@ EXPORTS_WHERE_AGG = ["bmx_where_aggregate", "bmx_where_top", "bmx_comm_where_agg
 
 # include/bmx_group.h: group-by over discovered values, likewise
 EXPORTS_GROUP = ["bmx_where_group", "bmx_comm_where_group"]
+
+# include/bmx_rows.h: row projection, likewise
+EXPORTS_ROWS = ["bmx_where_rows", "bmx_comm_where_rows"]
 
 
 class BmxError(RuntimeError):
@@ -221,6 +225,41 @@ def _group_tail(measure, group):
     return (AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group))
 
 
+class RowsRes(C.Structure):
+    """bmx_rows_res: what one bmx_where_rows found besides its rows (40 bytes)"""
+    _fields_ = [("n_match", C.c_uint64), ("n_out", C.c_uint64), ("next_pos", C.c_uint64), ("layout", C.c_uint64), ("next_shard", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ROWS_RES_DTYPE = np.dtype([("n_match", "<u8"), ("n_out", "<u8"), ("next_pos", "<u8"), ("layout", "<u8"), ("next_shard", "<u4"), ("reserved", "<u4")])
+
+
+class RowsResult:
+    """One where_rows answer: ids (uint64, n_out of them, in index order of the base field), vals (int64, shape (nfields, n_out); VAL_DELETED in a cell
+    without data), ts (the clocks, same shape; ROWS_NO_CLOCK in an absent cell; None without with_ts), n_match (the selected nodes at or behind the cursor),
+    next_pos (and next_shard: the cursor of the next page) and layout (the cursor is good while this stays the same)."""
+    __slots__ = ("ids", "vals", "ts", "n_match", "n_out", "next_pos", "next_shard", "layout")
+
+    def __init__(self, res, ids, vals, ts):
+        r = np.frombuffer(bytes(res), ROWS_RES_DTYPE)[0] if isinstance(res, RowsRes) else res
+        self.n_match, self.n_out, self.next_pos, self.layout, self.next_shard = int(r["n_match"]), int(r["n_out"]), int(r["next_pos"]), int(r["layout"]), int(r["next_shard"])
+        self.ids = ids[:self.n_out].copy()
+        self.vals = vals[:, :self.n_out].copy()
+        self.ts = None if ts is None else ts[:, :self.n_out].copy()
+
+    def __repr__(self):
+        return "RowsResult(%d of %d rows, %d fields, next_pos=%d)" % (self.n_out, self.n_match, self.vals.shape[0], self.next_pos)
+
+
+def _rows_fields(fields, with_ts):
+    """-> (nfields, fields, flags) of bmx_where_rows"""
+    fields = [int(f) for f in fields]
+    return (len(fields), (C.c_uint32 * max(len(fields), 1))(*fields), ROWS_TS if with_ts else 0)
+
+
+def _rows_buffers(nfields, cap, with_ts):
+    return np.zeros(max(cap, 1), np.uint64), np.zeros((nfields, max(cap, 1)), np.int64), np.zeros((nfields, max(cap, 1)), np.int64) if with_ts else None
+
+
 class WatchRes(C.Structure):
     """bmx_watch_res: what one bmx_watch_poll found (32 bytes); flags: WATCH_RESET, WATCH_OVERFLOW"""
     _fields_ = [("n_entered", C.c_uint64), ("n_left", C.c_uint64), ("n_match", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -347,6 +386,8 @@ def load_library():
     L.bmx_comm_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp]; L.bmx_comm_where_top.restype = i32
     L.bmx_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp, i32]; L.bmx_where_group.restype = i32
     L.bmx_comm_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp]; L.bmx_comm_where_group.restype = i32
+    L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
+    L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
     L.bmx_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp, i32]; L.bmx_watch_poll.restype = i32
     L.bmx_watch_destroy.argtypes = [vp, u32]; L.bmx_watch_destroy.restype = i32
@@ -756,6 +797,18 @@ class Engine:
         self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return GroupResult(res, out)
 
+    def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=0):
+        """Row projection (bmx_rows.h): the selection of scan_where(base, clauses) from index position `start` on, and for each of the first cap selected nodes
+        its id and the values (with_ts: and clocks) of `fields`, in one call. cap None: room for the whole index. -> RowsResult; its next_pos is the `start` of
+        the next page."""
+        cap = self.index_size(base) if cap is None else int(cap)
+        nf, farr, flags = _rows_fields(fields, with_ts)
+        ids, vals, ts = _rows_buffers(nf, cap, with_ts)
+        res = RowsRes()
+        self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), cap, _ptr(ids), _ptr(vals), _ptr(ts),
+                                        C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return RowsResult(res, ids, vals, ts)
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -930,6 +983,13 @@ class Engine:
         particular order; after sync(), GroupResult(res.cpu().numpy().view(GROUP_RES_DTYPE)[0], np.sort(out.cpu().numpy().view(GROUP_DTYPE)[:n], order="key"))
         reads them. The program is host data."""
         self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_rows_dev(self, base, clauses, fields, cap, out_ids, out_val, out_ts, res, start=0):
+        """where_rows into device memory (out_ids: room for cap ids; out_val: len(fields) columns of cap int64 each, field after field; out_ts: the same for
+        the clocks, or None for none; res: 40 bytes, a bmx_rows_res); enqueue-only. After sync(), res.cpu().numpy().view(ROWS_RES_DTYPE)[0] reads the record.
+        The program, the fields and the cursor are host data."""
+        nf, farr, flags = _rows_fields(fields, out_ts is not None)
+        self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1166,6 +1226,19 @@ class Comm:
         res = GroupRes()
         self._chk(self.L.bmx_comm_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p)))
         return GroupResult(res, out)
+
+    def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=(0, 0)):
+        """Engine.where_rows over the shards, shard after shard from the cursor start = (shard, position) on: the rows one engine holding the same rows gives,
+        in shard order. cap None: it counts first (cap 0) and then fetches with room for exactly that. -> RowsResult; (next_shard, next_pos) is the next start."""
+        nf, farr, flags = _rows_fields(fields, with_ts)
+        args = (*_where_args(base, clauses), nf, farr, flags, int(start[0]), int(start[1]))
+        res = RowsRes()
+        if cap is None:
+            self._chk(self.L.bmx_comm_where_rows(self.h, *args, 0, None, None, None, C.cast(C.byref(res), C.c_void_p)))
+            cap = int(res.n_match)
+        ids, vals, ts = _rows_buffers(nf, int(cap), with_ts)
+        self._chk(self.L.bmx_comm_where_rows(self.h, *args, int(cap), _ptr(ids), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
+        return RowsResult(res, ids, vals, ts)
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

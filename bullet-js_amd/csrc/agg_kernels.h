@@ -56,8 +56,9 @@ struct AggLds {                                 // G = 1: the workgroup's record
   unsigned long long slo[N]; long long shi[N];
 };
 
-// the row (id, field) of the table: false = absent; x = its value (VAL_DELETED for a tombstone)
-__device__ __forceinline__ bool agg_probe(const Slot* __restrict__ slots, uint64_t nslots, uint64_t id, uint32_t field, int64_t& x) {
+// the row (id, field) of the table: false = absent; x = its value (VAL_DELETED for a tombstone), ts = its clock (a tombstone's is the clock of the delete):
+// the slot's second 16 bytes hold both, so the clock costs no further load
+__device__ __forceinline__ bool agg_probe_ts(const Slot* __restrict__ slots, uint64_t nslots, uint64_t id, uint32_t field, int64_t& x, int64_t& ts) {
   ProbeSeq<4> ps(id, field, nslots);
   for (uint64_t p = 0; p < nslots; ++p) {
     const uint4* q = reinterpret_cast<const uint4*>(slots + ps.slot());
@@ -66,12 +67,18 @@ __device__ __forceinline__ bool agg_probe(const Slot* __restrict__ slots, uint64
     if (sid == EMPTY_ID) return false;
     if (sid == id && lo.z == field) {
       const uint4 hi = q[1];
+      ts = ts_value(i64_of(hi.x, hi.y));
       x = i64_of(hi.z, hi.w);
       return true;
     }
     ps.next();
   }
   return false;
+}
+// ... for the callers that want the value alone
+__device__ __forceinline__ bool agg_probe(const Slot* __restrict__ slots, uint64_t nslots, uint64_t id, uint32_t field, int64_t& x) {
+  int64_t ts;
+  return agg_probe_ts(slots, nslots, id, field, x, ts);
 }
 
 // one matching row into the record of group g

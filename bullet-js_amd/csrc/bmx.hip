@@ -35,6 +35,7 @@
 #include "where_agg_kernels.h"
 #include "../../include/bmx_where_agg.h"
 #include "group_kernels.h"
+#include "rows_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -104,7 +105,7 @@ struct Index {
   bool has_pos = false;      // its rows' positions are in ctx->chg.slot_pos (it can be maintained from the change log)
   uint64_t content = 0;      // counts the refreshes that really changed something in the columns (a value, a new row, a rebuild)
   uint64_t layout = 0;       // stamp of the build that laid the columns out (build_index, from bmx_ctx::layout_seq: never 0, never repeated in a context); between two
-                             // builds a row keeps its position and new rows are appended. Read by the standing queries alone (bmx_watch.inc)
+                             // builds a row keeps its position and new rows are appended. Read by the standing queries (bmx_watch.inc) and handed to the callers of the row projection, whose cursors are positions (bmx_rows.inc)
   OrderedView view;
 };
 // What the views of one context share (bmx_view.inc).
@@ -320,6 +321,14 @@ struct GroupScratch {
   void release() { dev_free(keys); dev_free(acc); dev_free(state); dev_free(stage); dev_free(stage_res); cap = 0; slots = 0; clean = false; }
 };
 
+// Scratch of the row projection (bmx_rows.inc): the columns and the result record of a BMX_MEM_HOST answer on their way down (`stage`: 8-byte words, grown on
+// demand), and what a call's mask pass leaves its emit pass (the base index as the mask pass saw it; the sharded form enqueues every shard's mask pass first).
+struct RowsScratch {
+  unsigned long long* stage = nullptr; uint64_t stage_words = 0; bmx_rows_res* stage_res = nullptr;
+  struct Masked { const uint64_t* ids = nullptr; const void* v = nullptr; uint64_t n = 0, layout = 0; bool fits32 = false; uint32_t nb = 0; } masked;
+  void release() { dev_free(stage); dev_free(stage_res); stage_words = 0; }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -381,6 +390,7 @@ struct bmx_ctx {
   AggScratch agg;
   TopScratch top;
   GroupScratch group;
+  RowsScratch rows;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -653,6 +663,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->agg.release();
   ctx->top.release();
   ctx->group.release();
+  ctx->rows.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -945,3 +956,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_watch.inc"     // (likewise)
 #include "bmx_where_agg.inc" // (likewise)
 #include "bmx_group.inc"     // (likewise)
+#include "bmx_rows.inc"      // (likewise)

@@ -76,7 +76,10 @@ struct PredWhere {   // T = int32_t / int64_t: the width of the base field's val
     return match;
   }
 
-  __device__ uint32_t mask(uint64_t first, uint64_t n) const {
+  __device__ uint32_t mask(uint64_t first, uint64_t n) const { return mask_from(first, n, 0); }
+
+  // ... of the positions from `from` on (rows_kernels.h: a page's cursor); a position in front of it is no candidate and its lane never probes
+  __device__ __forceinline__ uint32_t mask_from(uint64_t first, uint64_t n, uint64_t from) const {
     typedef T vec_t __attribute__((ext_vector_type(E)));
     T x[E];
     if (first + E <= n) {
@@ -93,7 +96,7 @@ struct PredWhere {   // T = int32_t / int64_t: the width of the base field's val
       T xe = x[0];
 #pragma unroll
       for (int k = 1; k < E; k++) xe = e == k ? x[k] : xe;
-      if (row(xe != TOMB, (int64_t)xe, first + (uint64_t)e)) m |= 1u << e;
+      if (row(xe != TOMB && first + (uint64_t)e >= from, (int64_t)xe, first + (uint64_t)e)) m |= 1u << e;
     }
     return m;
   }

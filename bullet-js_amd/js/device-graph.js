@@ -153,6 +153,20 @@ class DeviceGraph {
     const after = opts.after === undefined ? null : opts.after;
     return this.comm ? this.native.commWhereTop(this.comm, base, clauses, !!opts.desc, after, k >>> 0) : this.native.whereTop(this.handle, base, clauses, !!opts.desc, after, k >>> 0);
   }
+  /* Row projection (bmx_where_rows, include/bmx_rows.h): the nodes scanWhere(base, clauses) selects from the cursor on, and the values of `fields` (device
+   * field ids, 0..8 of them, repeats allowed) on each, in one call. opts: cap (rows at most; left out: the call counts first — cap 0 — and fetches with room for
+   * exactly that), ts (also the clocks), start (the cursor: nextPos of the page before; with shards [nextShard, nextPos]).
+   * -> {ids: BigUint64Array, vals: BigInt64Array[] (one per field; VAL_DELETED in a cell without data), ts?: BigInt64Array[] (NO_CLOCK in an absent cell),
+   *     nMatch (selected nodes at or behind the cursor), nextPos, nextShard, layout (a cursor is good while this stays the same)}. */
+  whereRows(base, clauses, fields, opts = {}) {
+    if (this.preOp) this.preOp();
+    const start = opts.start === undefined || opts.start === null ? 0 : opts.start;
+    const shard = Array.isArray(start) ? start[0] >>> 0 : 0, pos = Array.isArray(start) ? start[1] : start;
+    const call = (cap) => (this.comm ? this.native.commWhereRows(this.comm, base, clauses, fields, !!opts.ts, shard, pos, cap)
+      : this.native.whereRows(this.handle, base, clauses, fields, !!opts.ts, pos, cap));
+    const cap = opts.cap === undefined || opts.cap === null ? call(0).nMatch : opts.cap;
+    return call(cap);
+  }
   info() { return this.comm ? { nShards: this.nShards, devices: this.devices, nRows: this.rowCount() } : this.native.info(this.handle); }
   close() {
     if (this.handle) { this.native.destroy(this.handle); this.handle = null; }

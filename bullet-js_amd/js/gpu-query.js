@@ -630,6 +630,66 @@ class GpuQuery {
     return this._topOnHost(base, selected, k, desc, after);
   }
 
+  /**
+   * where() that also reads (bmx_where_rows): the children that where(path, clauses, {over}) selects, each with the values of fieldNames — what
+   * filter(path, fn) followed by .value() on every node, or map(path, fn) (src/bullet-query.js:322-333), does on the host.
+   * opts: over (required), cap (children per page; left out: all of them), start (the .next of the page before).
+   * -> {paths, rows, nMatch, next}: paths[i] is the path of the i-th delivered child, rows[i] = {name: value} with undefined for a cell without data (the
+   * field is absent, null or deleted); nMatch counts the selected children from the cursor on; next is the cursor of the following page, null behind the last.
+   * When every index involved — the program's and the projected fields' — is an integer index the device answers, in index order of `over`; a cursor is bound
+   * to the layout of that index and a page asked with a cursor of an older layout throws BMX_STALE_CURSOR (start over). When an index lives on the host
+   * (strings, booleans) the same answer comes from where()'s host evaluation and a projection from the store, in the scan order of `over`'s index.
+   */
+  whereRows(path, clauses, fieldNames, opts = {}) {
+    if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: whereRows needs opts.over, the field that defines the universe");
+    const names = Array.from(new Set(fieldNames));
+    const done = (paths, rows, nMatch, next) => ({ paths, rows, nMatch, next });
+    if (!clauses || clauses.length === 0) return done([], [], 0, null);
+    const { norm, base, native } = this._whereProgram(path, clauses, opts.over);
+    const kinds = names.map((f) => this._fieldKind(path, f));
+    const cap = opts.cap === undefined || opts.cap === null ? null : opts.cap;
+    const start = opts.start || null;
+    if (native && kinds.every((k) => k !== "host")) {
+      this.lastPath = "device";
+      if (native.length === 0) return done([], [], 0, null);
+      const present = names.filter((f, j) => kinds[j] === "device");       // (a field no child carries is undefined everywhere: nothing to ask)
+      if (present.length > 8) throw new RangeError("bmx: whereRows projects 8 distinct fields at most");
+      const r = this.graph.whereRows(base.deviceField, native, present.map((f) => this._fresh(path, f).deviceField), { cap, start: start ? start.at : null });
+      if (start && start.layout !== r.layout) {
+        const err = new Error("bmx: the cursor belongs to an older layout of the index; start over");
+        err.code = "BMX_STALE_CURSOR";
+        throw err;
+      }
+      const n = r.ids.length;
+      const u32 = new Uint32Array(r.ids.buffer, r.ids.byteOffset, n * 2);
+      const paths = new Array(n), rows = new Array(n);
+      const NONE = -(2n ** 63n);
+      for (let i = 0; i < n; i++) {
+        paths[i] = this.graph.keys.pathOf(u32[2 * i], u32[2 * i + 1]);
+        const row = {};
+        for (const f of names) row[f] = undefined;
+        present.forEach((f, j) => { const v = r.vals[j][i]; if (v !== NONE) row[f] = Number(v); });
+        rows[i] = row;
+      }
+      const more = r.nMatch > n;
+      return done(paths, rows, r.nMatch, more ? { at: this.graph.comm ? [r.nextShard, r.nextPos] : r.nextPos, layout: r.layout } : null);
+    }
+    const selected = this._whereHost(path, norm, base);
+    this.lastPath = "host";
+    const from = start ? start.at : 0;
+    const page = selected.slice(from, cap === null ? undefined : from + cap);
+    const store = this.bullet._getData(path);
+    const paths = page.map((i) => base.paths[i]);
+    const rows = paths.map((p) => {
+      const child = store[p.slice(path.length + 1)];
+      const row = {};
+      for (const f of names) { const v = child ? child[f] : undefined; row[f] = v === null ? undefined : v; }
+      return row;
+    });
+    const end = from + page.length;
+    return done(paths, rows, selected.length - from, end < selected.length ? { at: end, layout: 0 } : null);
+  }
+
   filter(path, fn) {
     const base = this.bullet._getData(path);
     const out = [];

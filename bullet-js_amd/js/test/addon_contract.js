@@ -26,7 +26,7 @@ const FUNCTIONS = ["abiVersion", "create", "destroy", "mergeBatch", "mergeBatchA
   "scanCount", "scanFilter", "info", "vcCreate", "vcDestroy", "vcLoadRows", "vcMergeBatch", "vcMergeBatchAsync", "vcGetRows", "vcRowCount", "vcScanRange", "ownersOf",
   "commCreate", "commDestroy", "commMergeBatch", "commLoadRows", "commGetRows", "commRowCount", "commDumpRows", "digest", "exportRows", "commDigest", "commExportRows",
   "commIndexBuild", "commIndexSetOrdered", "commIndexDrop", "commIndexSize", "commScanRange", "commScanCount", "commScanFilter", "scanAggregate", "commScanAggregate",
-  "scanTop", "commScanTop", "scanWhere", "commScanWhere", "whereAggregate", "commWhereAggregate", "whereTop", "commWhereTop"];
+  "scanTop", "commScanTop", "scanWhere", "commScanWhere", "whereAggregate", "commWhereAggregate", "whereTop", "commWhereTop", "whereRows", "commWhereRows"];
 const CONSTANTS = { INSERT_REFERENCE: 0, INSERT_DELTA: 1, MERGE_UNIQUE_KEYS: 0x100, MERGE_STRICT_FLAGS: 0x200, MERGE_MARK_CREATED: 0x1000, FLAG_INCOMING: 1, FLAG_CURRENT: 2,
   FLAG_HISTORICAL: 4, FLAG_CONCURRENT: 8, VC_MAX_WRITERS: 8, VC_ABSENT: 0, VC_DENSE: 1, VC_SPARSE: 2 };   // include/bmx.h
 
@@ -61,6 +61,7 @@ const CALLS = {
     scanAggregate: (h) => b.scanAggregate(h, TERM, null, null, 0, 0), scanTop: (h) => b.scanTop(h, TERM, false, null, 1),
     scanWhere: (h) => b.scanWhere(h, 7, [TERM]),
     whereAggregate: (h) => b.whereAggregate(h, 7, [TERM], null, null, 0, 0), whereTop: (h) => b.whereTop(h, 7, [TERM], false, null, 1),
+    whereRows: (h) => b.whereRows(h, 7, [TERM], [7], false, 0, 1),
   },
   vc: {
     vcLoadRows: (h) => b.vcLoadRows(h, I1, F1, C2, V1), vcMergeBatch: (h) => b.vcMergeBatch(h, I1, F1, C2, V1), vcMergeBatchAsync: (h) => b.vcMergeBatchAsync(h, I1, F1, C2, V1),
@@ -75,6 +76,7 @@ const CALLS = {
     commScanTop: (h) => b.commScanTop(h, TERM, false, null, 1),
     commScanWhere: (h) => b.commScanWhere(h, 7, [TERM]),
     commWhereAggregate: (h) => b.commWhereAggregate(h, 7, [TERM], null, null, 0, 0), commWhereTop: (h) => b.commWhereTop(h, 7, [TERM], false, null, 1),
+    commWhereRows: (h) => b.commWhereRows(h, 7, [TERM], [7], false, 0, 0, 1),
   },
 };
 
@@ -86,7 +88,7 @@ function refusedByAll(kind, h, what) {
 function host() {
   assert.strictEqual(b.abiVersion(), 4);
   assert.deepStrictEqual(Object.keys(b).sort(), FUNCTIONS.concat(Object.keys(CONSTANTS)).sort());
-  assert.strictEqual(Object.keys(b).length, 75);
+  assert.strictEqual(Object.keys(b).length, 77);
   for (const k of FUNCTIONS) assert.strictEqual(typeof b[k], "function", k);
   for (const [k, v] of Object.entries(CONSTANTS)) assert.strictEqual(b[k], v, k);
   // the tables above name every function that takes a handle

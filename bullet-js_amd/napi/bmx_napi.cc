@@ -24,6 +24,7 @@
 #include "bmx_top.h"
 #include "bmx_where.h"
 #include "bmx_where_agg.h"
+#include "bmx_rows.h"
 #include "bmx_ticket.h"
 
 namespace {
@@ -599,6 +600,80 @@ template <class Kind> napi_value WhereTop(napi_env env, napi_callback_info info)
   { Turn turn(h->q); rc = Kind::host(Kind::where_top, h->p, base, P.nc, (const uint32_t*)P.lens, (const bmx_lit*)P.lits.data(), t.flags, t.after(), t.k, recs.data(), &m, &ne); }
   return rc ? fail<Kind>(env, h->p, rc) : top_result(env, recs, m, ne);
 }
+/* Row projection (bmx_rows.h bmx_where_rows): thin bindings, no logic. The program is scanWhere's.
+ * whereRows(handle, base, clauses, [field, ...], ts, start, cap) / commWhereRows(comm, base, clauses, [field, ...], ts, startShard, startPos, cap) ->
+ * {ids: BigUint64Array, vals: [BigInt64Array per field], ts: [BigInt64Array per field] (with a truthy ts), nMatch, nextPos, nextShard, layout}: the first cap
+ * selected nodes from the cursor on, in index order of `base`; a cell without data holds BMX_VAL_DELETED, the clock of an absent cell BMX_ROWS_NO_CLOCK. */
+struct RowsTail { uint32_t nf = 0, fields[BMX_ROWS_MAX_FIELDS] = {}, flags = 0; };
+bool get_rows_tail(napi_env env, const napi_value* argv, RowsTail* t) {        // [field, ...], ts at argv[0..1]; false with a JS error pending
+  if (napi_get_array_length(env, argv[0], &t->nf) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
+  if (t->nf > BMX_ROWS_MAX_FIELDS) { napi_throw_range_error(env, nullptr, "bmx: whereRows takes 0..8 fields"); return false; }
+  for (uint32_t k = 0; k < t->nf; k++) {
+    napi_value e;
+    if (napi_get_element(env, argv[0], k, &e) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
+    if (!get_u32(env, e, &t->fields[k])) return false;
+  }
+  napi_value b; bool ts = false;
+  if (napi_coerce_to_bool(env, argv[1], &b) != napi_ok || napi_get_value_bool(env, b, &ts) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_coerce_to_bool"); return false; }
+  t->flags = ts ? BMX_ROWS_TS : 0u;
+  return true;
+}
+bool get_rows_count(napi_env env, napi_value v, const char* what, uint64_t* out) {      // a cursor position or a cap: a whole number below 2^53
+  double d;
+  if (!get_count(env, v, &d)) return false;
+  if (!(d >= 0) || d > 9007199254740991.0 || d != floor(d)) { napi_throw_range_error(env, nullptr, (std::string("bmx: ") + what + " is a whole number >= 0").c_str()); return false; }
+  *out = (uint64_t)d;
+  return true;
+}
+napi_value rows_columns(napi_env env, uint32_t nf, uint64_t m, uint64_t cap, const int64_t* cells) {
+  napi_value arr;
+  NAPI_OK(napi_create_array_with_length(env, nf, &arr));
+  for (uint32_t f = 0; f < nf; f++) {
+    napi_value col = copy_ta(env, napi_bigint64_array, (size_t)m, cells + (size_t)f * cap);
+    if (!col) return nullptr;
+    NAPI_OK(napi_set_element(env, arr, f, col));
+  }
+  return arr;
+}
+// call(out_ids, out_val, out_ts, &res) -> rc, inside the handle's turn
+template <class Kind, class Call> napi_value rows_answer(napi_env env, Handle<Kind>* h, const RowsTail& t, uint64_t cap, Call call) {
+  const bool ts = (t.flags & BMX_ROWS_TS) != 0;
+  if (cap > (1ull << 31)) { napi_throw_range_error(env, nullptr, "bmx: cap is 2^31 rows at most (page with start)"); return nullptr; }
+  std::vector<uint64_t> ids(cap ? cap : 1);
+  std::vector<int64_t> vals((size_t)t.nf * cap + 1), clk(ts ? (size_t)t.nf * cap + 1 : 1);
+  bmx_rows_res r; int rc;
+  { Turn turn(h->q); rc = call(ids.data(), vals.data(), clk.data(), &r); }
+  if (rc) return fail<Kind>(env, h->p, rc);
+  napi_value out = object_of(env, {{"ids", copy_ta(env, napi_biguint64_array, (size_t)r.n_out, ids.data())}, {"vals", rows_columns(env, t.nf, r.n_out, cap, vals.data())},
+                                   {"nMatch", num(env, (double)r.n_match)}, {"nextPos", num(env, (double)r.next_pos)}, {"nextShard", num(env, r.next_shard)}, {"layout", num(env, (double)r.layout)}});
+  if (out && ts) {
+    napi_value c = rows_columns(env, t.nf, r.n_out, cap, clk.data());
+    if (!c) return nullptr;
+    napi_set_named_property(env, out, "ts", c);
+  }
+  return out;
+}
+napi_value WhereRows(napi_env env, napi_callback_info info) {
+  HANDLE(Engine, 7);
+  uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
+  Program P; if (!get_program(env, argv[2], &P)) return nullptr;
+  RowsTail t; if (!get_rows_tail(env, argv + 3, &t)) return nullptr;
+  uint64_t start, cap; if (!get_rows_count(env, argv[5], "start", &start) || !get_rows_count(env, argv[6], "cap", &cap)) return nullptr;
+  return rows_answer(env, h, t, cap, [&](uint64_t* ids, int64_t* vals, int64_t* clk, bmx_rows_res* r) {
+    return bmx_where_rows(h->p, base, P.nc, P.lens, P.lits.data(), t.nf, t.fields, t.flags, start, cap, ids, vals, clk, r, BMX_MEM_HOST);
+  });
+}
+napi_value CommWhereRows(napi_env env, napi_callback_info info) {
+  HANDLE(Comm, 8);
+  uint32_t base; if (!get_u32(env, argv[1], &base)) return nullptr;
+  Program P; if (!get_program(env, argv[2], &P)) return nullptr;
+  RowsTail t; if (!get_rows_tail(env, argv + 3, &t)) return nullptr;
+  uint32_t shard; if (!get_u32(env, argv[5], &shard)) return nullptr;
+  uint64_t start, cap; if (!get_rows_count(env, argv[6], "start", &start) || !get_rows_count(env, argv[7], "cap", &cap)) return nullptr;
+  return rows_answer(env, h, t, cap, [&](uint64_t* ids, int64_t* vals, int64_t* clk, bmx_rows_res* r) {
+    return bmx_comm_where_rows(h->p, base, P.nc, P.lens, P.lits.data(), t.nf, t.fields, t.flags, shard, start, cap, ids, vals, clk, r);
+  });
+}
 
 // ---- the engine alone -----------------------------------------------------------------------------------------------------------------
 napi_value Create(napi_env env, napi_callback_info info) {
@@ -921,6 +996,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"indexBuild", IndexBuild<Engine>}, {"indexSetOrdered", IndexSetOrdered<Engine>}, {"scanRange", ScanRange<Engine>}, {"scanCount", ScanCount<Engine>}, {"digest", Digest<Engine>},
       {"exportRows", ExportRows<Engine>}, {"scanAggregate", ScanAggregate<Engine>}, {"scanTop", ScanTop<Engine>}, {"scanWhere", ScanWhere<Engine>},
       {"whereAggregate", WhereAggregate<Engine>}, {"whereTop", WhereTop<Engine>}, {"commWhereAggregate", WhereAggregate<Comm>}, {"commWhereTop", WhereTop<Comm>},
+      {"whereRows", WhereRows}, {"commWhereRows", CommWhereRows},
       {"commLoadRows", StoreRows<Comm, false>}, {"commPutRows", StoreRows<Comm, true>}, {"commGetRows", GetRows<Comm>}, {"commRowCount", RowCount<Comm>}, {"commDumpRows", DumpRows<Comm>},
       {"commIndexBuild", IndexBuild<Comm>}, {"commIndexSetOrdered", IndexSetOrdered<Comm>}, {"commScanRange", ScanRange<Comm>}, {"commScanCount", ScanCount<Comm>}, {"commDigest", Digest<Comm>},
       {"commExportRows", ExportRows<Comm>}, {"commScanAggregate", ScanAggregate<Comm>}, {"commScanTop", ScanTop<Comm>}, {"commScanWhere", ScanWhere<Comm>},
