@@ -29,6 +29,7 @@ TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_sca
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
+SEMI_ANTI, SEMI_OVERFLOW, SEMI_MAX_SET = 1, 1, 1 << 20   # BMX_SEMI_ANTI (flags of the call), BMX_SEMI_OVERFLOW (flags of bmx_semi_res), BMX_SEMI_MAX_SET (bmx_semi.h bmx_where_semijoin)
 WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2  # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
@@ -66,6 +67,9 @@ EXPORTS_GROUP = ["bmx_where_group", "bmx_comm_where_group"]
 
 # include/bmx_rows.h: row projection, likewise
 EXPORTS_ROWS = ["bmx_where_rows", "bmx_comm_where_rows"]
+
+# include/bmx_semi.h: semi-joins, likewise
+EXPORTS_SEMI = ["bmx_where_semijoin", "bmx_where_in", "bmx_comm_where_semijoin", "bmx_comm_where_in"]
 
 
 class BmxError(RuntimeError):
@@ -260,6 +264,35 @@ def _rows_buffers(nfields, cap, with_ts):
     return np.zeros(max(cap, 1), np.uint64), np.zeros((nfields, max(cap, 1)), np.int64), np.zeros((nfields, max(cap, 1)), np.int64) if with_ts else None
 
 
+class SemiRes(C.Structure):
+    """bmx_semi_res: what one bmx_where_semijoin / bmx_where_in found besides its ids (32 bytes); flags: SEMI_OVERFLOW"""
+    _fields_ = [("n_match", C.c_uint64), ("set_size", C.c_uint64), ("n_inner", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SEMI_RES_DTYPE = np.dtype([("n_match", "<u8"), ("set_size", "<u8"), ("n_inner", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+
+
+class SemiResult:
+    """One where_semijoin / where_in answer: ids (uint64, min(n_match, cap) of them, in index order of the base field; none on overflow or with count_only),
+    n_match (the selected nodes, however small cap was; 0 on overflow), set_size (distinct values in the set, or on overflow a lower bound of it above
+    set_cap), n_inner (inner nodes selected / listed values inside the domain) and overflow."""
+    __slots__ = ("ids", "n_match", "set_size", "n_inner", "overflow")
+
+    def __init__(self, res, ids, cap):
+        r = np.frombuffer(bytes(res), SEMI_RES_DTYPE)[0] if isinstance(res, SemiRes) else res
+        self.n_match, self.set_size, self.n_inner = int(r["n_match"]), int(r["set_size"]), int(r["n_inner"])
+        self.overflow = bool(int(r["flags"]) & SEMI_OVERFLOW)
+        self.ids = np.zeros(0, np.uint64) if ids is None else ids[:min(self.n_match, int(cap))].copy()
+
+    def __repr__(self):
+        return "SemiResult(%d of %d ids, set of %d from %d%s)" % (len(self.ids), self.n_match, self.set_size, self.n_inner, ", overflow" if self.overflow else "")
+
+
+def _semi_values(values):
+    v = _np(values, np.int64).ravel()
+    return v, len(v)
+
+
 class WatchRes(C.Structure):
     """bmx_watch_res: what one bmx_watch_poll found (32 bytes); flags: WATCH_RESET, WATCH_OVERFLOW"""
     _fields_ = [("n_entered", C.c_uint64), ("n_left", C.c_uint64), ("n_match", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -386,6 +419,11 @@ def load_library():
     L.bmx_comm_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp]; L.bmx_comm_where_top.restype = i32
     L.bmx_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp, i32]; L.bmx_where_group.restype = i32
     L.bmx_comm_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp]; L.bmx_comm_where_group.restype = i32
+    prog = [u32, u32, C.POINTER(u32), C.POINTER(Lit)]
+    L.bmx_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp, i32]; L.bmx_where_semijoin.restype = i32
+    L.bmx_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp, i32]; L.bmx_where_in.restype = i32
+    L.bmx_comm_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp]; L.bmx_comm_where_semijoin.restype = i32
+    L.bmx_comm_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp]; L.bmx_comm_where_in.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
@@ -809,6 +847,28 @@ class Engine:
                                         C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return RowsResult(res, ids, vals, ts)
 
+    def where_semijoin(self, base, clauses, link, inner_base, inner_clauses, key, anti=False, cap=None, set_cap=65536, count_only=False):
+        """Semi-join (bmx_semi.h): the selection of scan_where(base, clauses) whose field `link` holds a value that field `key` holds on some node of
+        scan_where(inner_base, inner_clauses); anti: whose `link` holds no such value (or nothing). The set is built and tested on the device. cap None: room
+        for the whole index of `base`; count_only: no id is fetched. -> SemiResult (with overflow set, n_match 0 and no ids when the inner side has more than
+        set_cap distinct keys)"""
+        cap = 0 if count_only else (self.index_size(base) if cap is None else int(cap))
+        ids = None if count_only else np.zeros(max(cap, 1), np.uint64)
+        res = SemiRes()
+        self._chk(self.L.bmx_where_semijoin(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, *_where_args(inner_base, inner_clauses), int(key),
+                                            int(set_cap), _ptr(ids), cap, C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return SemiResult(res, ids, cap)
+
+    def where_in(self, base, clauses, link, values, anti=False, cap=None, count_only=False):
+        """where_semijoin with the set given as a list of 1..SEMI_MAX_SET int64 values (duplicates allowed; a value outside +-(2^53 - 1) is skipped)"""
+        cap = 0 if count_only else (self.index_size(base) if cap is None else int(cap))
+        ids = None if count_only else np.zeros(max(cap, 1), np.uint64)
+        v, n = _semi_values(values)
+        res = SemiRes()
+        self._chk(self.L.bmx_where_in(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, _ptr(v), n, _ptr(ids), cap,
+                                      C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return SemiResult(res, ids, cap)
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -990,6 +1050,17 @@ class Engine:
         The program, the fields and the cursor are host data."""
         nf, farr, flags = _rows_fields(fields, out_ts is not None)
         self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
+
+    def where_semijoin_dev(self, base, clauses, link, inner_base, inner_clauses, key, out_ids, cap, res, anti=False, set_cap=65536):
+        """where_semijoin into device memory (out_ids: room for cap ids, or None with cap 0; res: 32 bytes, a bmx_semi_res); enqueue-only. After sync(),
+        SemiResult(res.cpu().numpy().view(SEMI_RES_DTYPE)[0], out_ids.cpu().numpy(), cap) is what where_semijoin returns."""
+        self._chk(self.L.bmx_where_semijoin(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, *_where_args(inner_base, inner_clauses), int(key),
+                                            int(set_cap), _ptr(out_ids), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_in_dev(self, base, clauses, link, values, nvalues, out_ids, cap, res, anti=False):
+        """where_in into device memory; `values` is a device array of nvalues int64. Enqueue-only."""
+        self._chk(self.L.bmx_where_in(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, _ptr(values), int(nvalues), _ptr(out_ids), int(cap),
+                                      _ptr(res), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1239,6 +1310,28 @@ class Comm:
         ids, vals, ts = _rows_buffers(nf, int(cap), with_ts)
         self._chk(self.L.bmx_comm_where_rows(self.h, *args, int(cap), _ptr(ids), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
         return RowsResult(res, ids, vals, ts)
+
+    def where_semijoin(self, base, clauses, link, inner_base, inner_clauses, key, anti=False, cap=None, set_cap=65536, count_only=False):
+        """Engine.where_semijoin over all shards: every shard builds its own set, the library unites them and sends the union to every shard, so the answer
+        is the set of ids one engine holding the same rows gives, in shard order. cap None: it counts first (cap 0) and then fetches with room for exactly that."""
+        args = (*_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, *_where_args(inner_base, inner_clauses), int(key), int(set_cap))
+        return self._semi(self.L.bmx_comm_where_semijoin, args, cap, count_only)
+
+    def where_in(self, base, clauses, link, values, anti=False, cap=None, count_only=False):
+        """Engine.where_in over all shards"""
+        v, n = _semi_values(values)
+        return self._semi(self.L.bmx_comm_where_in, (*_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, _ptr(v), n), cap, count_only)
+
+    def _semi(self, fn, args, cap, count_only):
+        res = SemiRes()
+        if cap is None or count_only:
+            self._chk(fn(self.h, *args, None, 0, C.cast(C.byref(res), C.c_void_p)))
+            if count_only or res.flags & SEMI_OVERFLOW:
+                return SemiResult(res, None, 0)
+            cap = int(res.n_match)
+        ids = np.zeros(max(int(cap), 1), np.uint64)
+        self._chk(fn(self.h, *args, _ptr(ids), int(cap), C.cast(C.byref(res), C.c_void_p)))
+        return SemiResult(res, ids, cap)
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

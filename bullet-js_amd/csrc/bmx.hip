@@ -36,6 +36,7 @@
 #include "../../include/bmx_where_agg.h"
 #include "group_kernels.h"
 #include "rows_kernels.h"
+#include "semi_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -329,6 +330,18 @@ struct RowsScratch {
   void release() { dev_free(stage); dev_free(stage_res); stage_words = 0; }
 };
 
+// Scratch of the semi-joins (bmx_semi.inc): the open-addressed table of key words and the state record, which every query's last kernel leaves empty again
+// (clean), and the staging of the host-mode and sharded forms: a list of values on its way up or of exported keys on its way down (stage_keys, `cap` words), the
+// result record, and the ids of an answer on their way down (stage_ids, grown on demand; `staged`: how many the last staged query had room for). The table
+// grows to the largest set_cap asked so far, all or nothing; a query with a smaller set_cap uses the head of the table.
+struct SemiScratch {
+  long long* keys = nullptr; SemiState* state = nullptr; long long* stage_keys = nullptr; bmx_semi_res* stage_res = nullptr;
+  uint64_t* stage_ids = nullptr; uint64_t ids_cap = 0, staged = 0;
+  uint64_t cap = 0, slots = 0;
+  bool clean = false;
+  void release() { dev_free(keys); dev_free(state); dev_free(stage_keys); dev_free(stage_res); dev_free(stage_ids); ids_cap = 0; staged = 0; cap = 0; slots = 0; clean = false; }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -391,6 +404,7 @@ struct bmx_ctx {
   TopScratch top;
   GroupScratch group;
   RowsScratch rows;
+  SemiScratch semi;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -664,6 +678,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->top.release();
   ctx->group.release();
   ctx->rows.release();
+  ctx->semi.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -957,3 +972,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_where_agg.inc" // (likewise)
 #include "bmx_group.inc"     // (likewise)
 #include "bmx_rows.inc"      // (likewise)
+#include "bmx_semi.inc"      // (likewise)
