@@ -70,6 +70,8 @@ EXPORTS_ROWS = ["bmx_where_rows", "bmx_comm_where_rows"]
 
 # include/bmx_semi.h: semi-joins, likewise
 EXPORTS_SEMI = ["bmx_where_semijoin", "bmx_where_in", "bmx_comm_where_semijoin", "bmx_comm_where_in"]
+# the probe kernel's claim mode (include/bmx_claim.h), likewise
+EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
 
 
 class BmxError(RuntimeError):
@@ -364,6 +366,8 @@ def load_library():
     L.bmx_last_error.argtypes = [vp]; L.bmx_last_error.restype = C.c_char_p
     L.bmx_abi_version.argtypes = []; L.bmx_abi_version.restype = i32
     L.bmx_selfcheck.argtypes = [i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]; L.bmx_selfcheck.restype = i32
+    L.bmx_selfcheck_claim.argtypes = [i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]; L.bmx_selfcheck_claim.restype = i32
+    L.bmx_get_claim_mode.argtypes = [vp]; L.bmx_get_claim_mode.restype = i32
     L.bmx_set_deferred_compaction.argtypes = [vp, i32]; L.bmx_set_deferred_compaction.restype = i32
     L.bmx_set_side_stream.argtypes = [vp, vp]; L.bmx_set_side_stream.restype = i32
     L.bmx_set_wait_limit.argtypes = [vp, C.c_double]; L.bmx_set_wait_limit.restype = i32
@@ -504,6 +508,17 @@ def selfcheck(device=0):
     L = load_library()
     r, t, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     rc = L.bmx_selfcheck(int(device), C.byref(r), C.byref(t), C.byref(c))
+    if rc:
+        raise BmxError(rc, (L.bmx_last_error(None) or b"").decode())
+    return r.value, t.value, c.value
+
+
+def selfcheck_claim(device=0):
+    """bmx_selfcheck_claim: (checked 16-byte loads, torn pairs seen beside team swaps, torn pairs of the three-instruction control). A torn pair is
+    reported, not raised: contexts on such a device keep claim mode `store`."""
+    L = load_library()
+    r, t, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = L.bmx_selfcheck_claim(int(device), C.byref(r), C.byref(t), C.byref(c))
     if rc:
         raise BmxError(rc, (L.bmx_last_error(None) or b"").decode())
     return r.value, t.value, c.value
@@ -922,6 +937,13 @@ class Engine:
     def set_probe_waves(self, waves_per_simd):
         """resident waves per SIMD the probe kernel may take (8, 6, 5, 4, 3): fewer leave room for kernels that run beside it (bmx_set_probe_waves)"""
         self._chk(self.L.bmx_set_probe_waves(self.h, int(waves_per_simd)))
+
+    def claim_mode(self):
+        """how the probe kernel claims a row: "team" (head, ts and val in one memory-side request) or "store" (exchange + store); BMX_CLAIM_MODE at create"""
+        m = self.L.bmx_get_claim_mode(self.h)
+        if m < 0:
+            self._chk(m)
+        return "team" if m == 1 else "store"
 
     def placement(self):
         """table placement tuning at create / growth: {candidates, probe_us_chosen, probe_us_slowest} (candidates 0: not tuned)"""

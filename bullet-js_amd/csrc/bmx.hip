@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/bmx.h"
+#include "../../include/bmx_claim.h"
 #include "merge_kernels.h"
 #include "scan_kernels.h"
 #include "select.h"
@@ -423,6 +424,7 @@ struct bmx_ctx {
   SlabProtocol slab;
   uint32_t placement_tries = 0, placement_tries_asked = 0; float placement_us_best = 0, placement_us_worst = 0;   // what alloc_table_tuned saw for the current table
   uint64_t n_row_waits = 0;           // merges that waited for a batch in flight to report its row count (wait_for_row_reports)
+  bool claim_team = false;            // claim mode (BMX_CLAIM_MODE): a claimer swaps head, ts and val in one team request (team_claim) instead of exchange + store
   int k1_waves = 8;                   // BMX_K1_WAVES (8, 6 or 5): resident waves per SIMD of the probe kernel
   std::string err;
 };
@@ -536,8 +538,12 @@ const char* bmx_last_error(const bmx_ctx* ctx) { return ctx ? ctx->err.c_str() :
 
 uint32_t bmx_owner_of(uint64_t id, uint32_t nshards) { return (uint32_t)(((unsigned __int128)owner_hash(id) * nshards) >> 64); }
 
-// bmx.h "bmx_selfcheck". Synchronous for the caller, on a stream of its own (nothing else on the device is waited for); allocates and frees 128 KB + 4 words.
-int bmx_selfcheck(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t* control_torn_out) {
+}  // extern "C"
+
+namespace {
+// Both tear checks (k_selfcheck_tear: the 16-byte store, or with `team` the team swap, each followed by its control). Synchronous for the caller, on a stream of its
+// own (nothing else on the device is waited for); allocates and frees 128 KB + 4 words. -> h = {torn, reads, control torn, control reads}
+int run_tear_check(int device, bool team, unsigned long long (&h)[4]) {
   bmx_ctx* ctx = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(nullptr, BMX_ERR_NO_DEVICE, "no HIP device: this library has no CPU path");
@@ -549,20 +555,38 @@ int bmx_selfcheck(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t*
     (void)hipGetLastError(); if (slots) (void)hipFree(slots);
     return fail(nullptr, BMX_ERR_NOMEM, "bmx_selfcheck: out of device memory");
   }
-  unsigned long long h[4] = {0, 0, 0, 0};
+  h[0] = h[1] = h[2] = h[3] = 0;
   hipStream_t cs = nullptr;       // a stream of its own: no device-wide synchronisation, nothing of another context or library is waited for
   const char* nul = std::getenv("BMX_SELFCHECK_NULL_STREAM");     // measurement switch (round 5): the device's null stream, as rounds 1-4 used
   hipError_t e = (nul && nul[0] == '1') ? hipSuccess : hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMemsetAsync(slots, 0, (size_t)NS * 32, cs);
   if (e == hipSuccess) e = hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), cs);
-  if (e == hipSuccess) { hipLaunchKernelGGL(k_selfcheck_tear<false>, dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS, d, d + 1); e = hipGetLastError(); }
+  if (e == hipSuccess) {
+    if (team) hipLaunchKernelGGL((k_selfcheck_tear<false, true>), dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS, d, d + 1);
+    else hipLaunchKernelGGL((k_selfcheck_tear<false>), dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS, d, d + 1);
+    e = hipGetLastError();
+  }
   if (e == hipSuccess) e = hipMemsetAsync(slots, 0, (size_t)NS * 32, cs);
-  if (e == hipSuccess) { hipLaunchKernelGGL(k_selfcheck_tear<true>, dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS / 4, d + 2, d + 3); e = hipGetLastError(); }
+  if (e == hipSuccess) {
+    if (team) hipLaunchKernelGGL((k_selfcheck_tear<true, true>), dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS / 4, d + 2, d + 3);
+    else hipLaunchKernelGGL((k_selfcheck_tear<true>), dim3(BLOCKS), dim3(256), 0, cs, slots, NS, ITERS / 4, d + 2, d + 3);
+    e = hipGetLastError();
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, cs);
   if (e == hipSuccess) e = hipStreamSynchronize(cs);
   if (cs) (void)hipStreamDestroy(cs);
   (void)hipFree(slots); (void)hipFree(d);
   if (e != hipSuccess) return fail_hip(ctx, e, "bmx_selfcheck");
+  return BMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// bmx.h "bmx_selfcheck"
+int bmx_selfcheck(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t* control_torn_out) {
+  unsigned long long h[4];
+  if (int rc = run_tear_check(device, false, h)) return rc;
   if (reads_out) *reads_out = h[1];
   if (torn_out) *torn_out = h[0];
   if (control_torn_out) *control_torn_out = h[2];
@@ -573,6 +597,21 @@ int bmx_selfcheck(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t*
     return fail(nullptr, BMX_ERR_INTERNAL, buf);
   }
   return BMX_OK;
+}
+
+// bmx_claim.h "bmx_selfcheck_claim". A torn pair is a result, not an error: the caller (bmx_create) keeps claim mode `store` then.
+int bmx_selfcheck_claim(int device, uint64_t* reads_out, uint64_t* torn_out, uint64_t* control_torn_out) {
+  unsigned long long h[4];
+  if (int rc = run_tear_check(device, true, h)) return rc;
+  if (reads_out) *reads_out = h[1];
+  if (torn_out) *torn_out = h[0];
+  if (control_torn_out) *control_torn_out = h[2];
+  return BMX_OK;
+}
+
+int bmx_get_claim_mode(bmx_ctx* ctx) {
+  if (!ctx) return fail(ctx, BMX_ERR_INVALID, "bmx_get_claim_mode: no context");
+  return ctx->claim_team ? BMX_CLAIM_TEAM : BMX_CLAIM_STORE;
 }
 
 int bmx_create(int device, uint64_t capacity_rows, uint32_t flags, bmx_ctx** out) {
@@ -607,14 +646,20 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
       touched[device].store(1u);
     }
   }
+  bool team_checked = false;
   {  // once per device and process: the 16-byte load/store indivisibility the probe kernel relies on is checked on THIS box (BMX_SKIP_SELFCHECK=1 skips it)
     static std::atomic<unsigned> checked[64];
     const char* skip = std::getenv("BMX_SKIP_SELFCHECK");
     if (device < 64 && !(skip && skip[0] == '1') && !checked[device].load()) {
       int src = bmx_selfcheck(device, nullptr, nullptr, nullptr);
       if (src) return src;
-      checked[device].store(1u);
+      // the team swap's indivisibility, beside it: no torn pair AND a control that tore = claim mode `team` is sound on this box (2); anything else,
+      // a failed run included, silently keeps `store` (1)
+      uint64_t torn = 0, control = 0;
+      const bool team_ok = bmx_selfcheck_claim(device, nullptr, &torn, &control) == BMX_OK && torn == 0 && control != 0;
+      checked[device].store(team_ok ? 2u : 1u);
     }
+    team_checked = device < 64 && checked[device].load() == 2u;
   }
   bmx_ctx* ctx = new (std::nothrow) bmx_ctx();
   if (!ctx) return fail(nullptr, BMX_ERR_NOMEM, "out of host memory");
@@ -634,6 +679,10 @@ int bmx_create_ex(int device, uint64_t capacity_rows, uint32_t max_load_pct, uin
   ctx->nslots = nslots;
   ctx->placement_tries_asked = (flags >> 8) & 0xFu;         // BMX_CTX_PLACEMENT_TRIES(n): 0 = the default
   if (ctx->placement_tries_asked > 8) ctx->placement_tries_asked = 8;
+  // claim mode: `team` where this process has seen the team swap checked on the device; BMX_CLAIM_MODE=store|team overrides it (set before the table is placed:
+  // the placement probe issues the mode's request mix)
+  ctx->claim_team = team_checked;
+  { const char* cm = std::getenv("BMX_CLAIM_MODE"); if (cm && !std::strcmp(cm, "store")) ctx->claim_team = false; else if (cm && !std::strcmp(cm, "team")) ctx->claim_team = true; }
   int rc;
   if ((rc = alloc_table_tuned(ctx, nslots, &ctx->slots))) return bail(rc);
   if ((rc = dev_alloc(ctx, &ctx->ds, 1))) return bail(rc);

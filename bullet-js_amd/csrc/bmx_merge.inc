@@ -122,7 +122,7 @@ int alloc_table_tuned(bmx_ctx* ctx, uint64_t nslots, Slot** out, bool growing = 
     float best = 1e30f;
     for (int rep = 0; rep < 4; rep++) {                    // (the first launch on a fresh allocation also pays its page-table walk misses: not counted)
       (void)hipEventRecord(e0, ctx->stream);
-      hipLaunchKernelGGL(k_placement_probe, dim3(PN / 64), dim3(64), 0, ctx->stream, p, nslots, PN, (uint32_t)(k * 16 + rep));
+      hipLaunchKernelGGL(k_placement_probe, dim3(PN / 64), dim3(64), 0, ctx->stream, p, nslots, PN, (uint32_t)(k * 16 + rep), ctx->claim_team ? 1u : 0u);
       (void)hipEventRecord(e1, ctx->stream);
       float ms = 0;
       if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); ms = 1e9f; }
@@ -314,11 +314,14 @@ int launch_probe(bmx_ctx* ctx, const MergeArgs& A, const MergeMode& mode) {
     constexpr int NT = 64;    // every wave its own workgroup (profiles/r03_ab_inserts.log)
     const dim3 grid((A.n + NT - 1u) / NT);
     const int kw = ctx->k1_waves;   // resident waves per SIMD the probe kernel may take (8 = all; 6 / 5 leave room for the kernels that run beside it)
+    const bool team = ctx->claim_team;   // claim mode: a unique-key batch claims nothing, so only the general kernel has the team form
 #define BMX_LAUNCH_K1(KERN) do { if (mode.rule == BMX_INSERT_REFERENCE) { \
         if (mode.unique) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_REFERENCE, true, NT>), grid, dim3(NT), 0, ctx->stream, A); \
+        else if (team) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_REFERENCE, false, NT, true>), grid, dim3(NT), 0, ctx->stream, A); \
         else hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_REFERENCE, false, NT>), grid, dim3(NT), 0, ctx->stream, A); \
       } else { \
         if (mode.unique) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_DELTA, true, NT>), grid, dim3(NT), 0, ctx->stream, A); \
+        else if (team) hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_DELTA, false, NT, true>), grid, dim3(NT), 0, ctx->stream, A); \
         else hipLaunchKernelGGL((KERN<AOS, BMX_INSERT_DELTA, false, NT>), grid, dim3(NT), 0, ctx->stream, A); \
       } } while (0)
     if (kw == 6) BMX_LAUNCH_K1(k_probe_apply_w6); else if (kw == 5) BMX_LAUNCH_K1(k_probe_apply_w5); else if (kw == 4) BMX_LAUNCH_K1(k_probe_apply_w4);

@@ -12,16 +12,24 @@
 //                    field and claims the head together.
 //                    Later claimers of the same row (duplicate keys) link themselves BEHIND the previous claimer
 //                    (next[previous] = me: a forward list that starts at the first claimer) instead of writing.
+//                    Claim mode `team` (the default where bmx_selfcheck_claim passed; BMX_CLAIM_MODE): the claim and the
+//                    value go to memory as ONE request — head word, ts and val are three aligned 8-byte words of one
+//                    64-byte granule, swapped by three lanes of one 64-bit swap instruction (team_claim). No store, no
+//                    dirty line. Every claimer that beat the value it saw writes then, not the first one only: during the
+//                    launch a row with several claimers holds the value of whichever swapped last — never below the
+//                    pre-batch value, never above the list's lexmax — and k_resolve_lists rewrites every such row.
 //   k_resolve_lists  first claimers that got followers only (none in a unique-key batch): each walks its row's list
 //                    forward and applies the reference's sequential outcome (lexmax of (ts,val), ties to the
-//                    smaller index, first write of an absent key stored with ts := 2). Followers do nothing there:
+//                    smaller index, first write of an absent key stored with ts := 2), starting from its own delta, not
+//                    from what the row holds. Followers do nothing there:
 //                    who has to walk is known from next[own index], a coalesced load — no row is read to find out.
 //   select (select.h) ordered compaction of the per-delta winner bytes -> applied_idx.
 //
 // Why this shape (measured, profiles/r01_micro_probe_v2.log): a random probe costs one 128-B line
 // (~50 G lines/s), a dirty line costs its write-back, and global atomics run at ~25 G/s whatever the
-// table size — so each delta gets exactly one line read, at most one atomic, at most one 16-B store,
-// and nothing ever revisits the table unless two deltas of one batch share a key.
+// table size — so each delta gets exactly one line read, at most one atomic, at most one 16-B store
+// (claim mode `team`: the atomic carries the value, profiles/r06_team_claim_micro.log), and nothing ever
+// revisits the table unless two deltas of one batch share a key.
 #pragma once
 #include "slot.h"
 #include "../../include/bmx.h"
@@ -198,7 +206,8 @@ __device__ __forceinline__ bool probe_or_insert(const MergeArgs& A, uint32_t tag
 // What a delta does once its row is located (resolve(): src/bullet-crt.js:164-279, scalar clocks): decide against the snapshot the lane
 // saw, claim the row, store if it is the first claimer of the batch, link behind the previous claimer otherwise.
 // `created`: this lane created the row (it claimed the head with the publishing store: prev is the old head word).
-template <int MODE, bool UNIQUE>
+// TEAM: the claim has been made already by team_claim (below) — prev is the old head it returned, and a winner's (ts,val) went into the row with it.
+template <int MODE, bool UNIQUE, bool TEAM = false>
 __device__ __forceinline__ void decide_and_claim(const MergeArgs& A, const uint32_t j, const uint64_t s, const bool is_new, const bool created, uint32_t prev,
                                                  const int64_t cts, const int64_t cval, const int64_t a, const int64_t v,
                                                  uint32_t& fl, uint32_t& wf, bool& conflict) {
@@ -211,7 +220,7 @@ __device__ __forceinline__ void decide_and_claim(const MergeArgs& A, const uint3
     return;
   }
   Slot* sl = A.slots + s;
-  if (!created && !UNIQUE) prev = atomicExch(&sl->head, tag);   // UNIQUE: caller-guaranteed single claimer (prev stays 0)
+  if (!TEAM && !created && !UNIQUE) prev = atomicExch(&sl->head, tag);   // UNIQUE: caller-guaranteed single claimer (prev stays 0)
   if ((prev >> IDX_BITS) != A.epoch) {
     // first claimer of this row in this batch: its snapshot is the pre-batch row
     // it walks the row's list in k_resolve_lists if anybody follows; its slot is recorded by that follower (a unique-key batch then writes no
@@ -225,7 +234,8 @@ __device__ __forceinline__ void decide_and_claim(const MergeArgs& A, const uint3
       store_tv(sl, t0 | ((int64_t)A.epoch << TS_MARK_SHIFT), v);
       wf |= W_WINNER | W_CREATED | W_FIRSTWRITE; fl = BMX_FLAG_INCOMING;    // (a first claimer with followers is corrected by k_resolve_lists: the creating delta is the smallest index)
     } else if (c > 0) {
-      store_tv(sl, a, v); wf |= W_WINNER; fl = BMX_FLAG_INCOMING;
+      if (!TEAM) store_tv(sl, a, v);     // TEAM: the row already holds it (a row this lane created is new: the branch above)
+      wf |= W_WINNER; fl = BMX_FLAG_INCOMING;
     }  // c == 0: identical clock and value: no-op, all flags false
   } else {
     // duplicate key inside the batch: link behind the previous claimer; the row's first claimer resolves the list in k_resolve_lists
@@ -237,14 +247,43 @@ __device__ __forceinline__ void decide_and_claim(const MergeArgs& A, const uint3
   }
 }
 
+// The team claim (claim mode `team`): the head word, ts and val of a slot are three consecutive aligned 8-byte words of ONE 64-byte granule, and the lanes of one
+// atomic instruction that fall into one granule leave L2 as ONE memory-side request (profiles/r06_team_claim_micro.log: 1.0 write-side request per written slot,
+// against 2.0 for exchange + store). So the whole wave, reconverged behind the probe loop, serves its claims in four rounds of ONE returning 64-bit swap each: round p
+// takes the deltas of lanes 16p..16p+15; lanes 4i, 4i+1, 4i+2 are the team of delta 16p + i and swap field|tag, ts and val (the last two only where `wr`: a delta that
+// beat the resident value it saw), lane 4i+3 is off. Nothing is stored and no line is dirtied; the old head comes back by shuffle. A fixed trip count, no wait.
+// want: this lane claims its row's head (it located the row, was not below its snapshot and did not create the row); wr implies want. -> the old head word
+__device__ __forceinline__ uint32_t team_claim(const MergeArgs& A, const uint32_t j, const uint32_t s, const uint32_t field, const int64_t a, const int64_t v,
+                                               const bool want, const bool wr) {
+  const uint32_t lane = lane_id(), role = lane & 3u;
+  const unsigned long long mw = __ballot(want), mv = __ballot(wr);
+  uint32_t prev = 0;
+#pragma unroll
+  for (uint32_t p = 0; p < 4; p++) {
+    if (!((mw >> (16u * p)) & 0xFFFFull)) continue;          // (wave-uniform) nobody of this round claims
+    const uint32_t src = 16u * p + (lane >> 2);
+    const uint32_t ss = (uint32_t)__shfl((int)s, (int)src), sf = (uint32_t)__shfl((int)field, (int)src);
+    const uint64_t sa = u64_of((uint32_t)__shfl((int)lo32((uint64_t)a), (int)src), (uint32_t)__shfl((int)hi32((uint64_t)a), (int)src));
+    const uint64_t sv = u64_of((uint32_t)__shfl((int)lo32((uint64_t)v), (int)src), (uint32_t)__shfl((int)hi32((uint64_t)v), (int)src));
+    const bool on = role == 0 ? ((mw >> src) & 1ull) != 0 : (role != 3u && ((mv >> src) & 1ull) != 0);
+    const uint64_t opnd = role == 0 ? u64_of(sf, (A.epoch << IDX_BITS) | (j - lane + src)) : (role == 1 ? sa : sv);
+    unsigned long long old = 0;
+    if (on) old = __hip_atomic_exchange(reinterpret_cast<unsigned long long*>(A.slots + ss) + 1 + role, (unsigned long long)opnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t got = (uint32_t)__shfl((int)hi32(old), (int)(4u * (lane & 15u)));
+    if ((lane >> 4) == p) prev = got;
+  }
+  return prev;
+}
+
 // K1. One lane per delta, NO workgroup barrier and no LDS: a wave adds its winner count to its 256-delta block's summary with one global atomic
 // that returns nothing; the summaries are double-buffered and this launch zeroes the half the NEXT batch will add into (its last readers, the
 // compaction of the batch before, are long done). Waves retire on their own — NT = 64 makes every wave its own workgroup — and the CU takes new
 // ones earlier. Measured against the rounds 1-2 kernel (block summary behind a __syncthreads) and against three ways of moving the row creations
 // out of the probing waves (LDS-compacted behind a barrier, by the last wave, by a second launch = SURVEY §2.1 K4): profiles/r03_ab_inserts.log —
 // the barrier cost 2-7 us per 1M-delta launch, every split of the creations cost more than it saved.
-template <bool AOS, int MODE, bool UNIQUE, int NT>
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
 __device__ __forceinline__ void probe_apply_body(const MergeArgs& A) {
+  static_assert(!(TEAM && UNIQUE), "a unique-key batch claims nothing");
   const uint32_t j = blockIdx.x * (uint32_t)NT + threadIdx.x;
   if (A.started && j == 0) __hip_atomic_store(A.started, A.started_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (A.n_notify && j < A.n_notify && A.notify.p[j]) __hip_atomic_store(A.notify.p[j], A.notify_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -258,7 +297,16 @@ __device__ __forceinline__ void probe_apply_body(const MergeArgs& A) {
   if (active && !valid && !pad) atomicOr(A.status, ST_RANGE);
   uint32_t fl = 0, wf = W_NONE;
   bool conflict = false, created = false;
-  if (valid) {
+  if (TEAM) {
+    // three steps: every lane locates its row and decides; the reconverged wave claims in four team rounds; every lane settles with the old head it got back
+    bool is_new = false, located = false; int64_t cts = 0, cval = 0; uint64_t s = 0; uint32_t prev = 0;
+    if (valid) located = probe_or_insert<UNIQUE>(A, (A.epoch << IDX_BITS) | j, id, field, s, is_new, created, prev, cts, cval);
+    const int c = !located ? -1 : ((is_new || A.force) ? 1 : lexcmp(a, v, cts, cval));
+    const bool want = c >= 0 && !created;                  // a creating lane claimed with its publishing store and writes (ts,val) itself, as in store mode
+    const uint32_t got = team_claim(A, j, (uint32_t)s, field, a, v, want, want && c > 0 && !is_new);
+    if (want) prev = got;
+    if (located) decide_and_claim<MODE, UNIQUE, true>(A, j, s, is_new, created, prev, cts, cval, a, v, fl, wf, conflict);
+  } else if (valid) {
     bool is_new; int64_t cts, cval; uint64_t s; uint32_t prev = 0;
     if (probe_or_insert<UNIQUE>(A, (A.epoch << IDX_BITS) | j, id, field, s, is_new, created, prev, cts, cval))
       decide_and_claim<MODE, UNIQUE>(A, j, s, is_new, created, prev, cts, cval, a, v, fl, wf, conflict);
@@ -279,21 +327,21 @@ __device__ __forceinline__ void probe_apply_body(const MergeArgs& A) {
   }
 }
 
-template <bool AOS, int MODE, bool UNIQUE, int NT>
-__global__ __launch_bounds__(NT) void k_probe_apply(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT>(A); }
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
+__global__ __launch_bounds__(NT) void k_probe_apply(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT, TEAM>(A); }
 // The same kernel held to at most SIX (FIVE) resident waves per SIMD instead of eight. The probe kernel is bound by memory-side requests in flight (a CU's 64-entry
 // miss queue is full with far fewer waves), so it loses nothing — and the kernels that are meant to run BESIDE it (the deferred compaction, the owner partition of
 // the next batch on the exchange stream: 256-thread workgroups) find wave slots on every CU at once instead of waiting for four of this kernel's one-wave
 // workgroups to retire on the same CU (kernel trace of the sharded rehearsal: k_part_count 58-72 us and the deferred k_compact_winners 75 us beside the full-occupancy
 // kernel, i.e. they finished when it did).
-template <bool AOS, int MODE, bool UNIQUE, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 6))) void k_probe_apply_w6(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT>(A); }
-template <bool AOS, int MODE, bool UNIQUE, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 5))) void k_probe_apply_w5(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT>(A); }
-template <bool AOS, int MODE, bool UNIQUE, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_probe_apply_w4(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT>(A); }
-template <bool AOS, int MODE, bool UNIQUE, int NT>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 3))) void k_probe_apply_w3(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT>(A); }
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 6))) void k_probe_apply_w6(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT, TEAM>(A); }
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 5))) void k_probe_apply_w5(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT, TEAM>(A); }
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_probe_apply_w4(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT, TEAM>(A); }
+template <bool AOS, int MODE, bool UNIQUE, int NT, bool TEAM = false>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 3))) void k_probe_apply_w3(MergeArgs A) { probe_apply_body<AOS, MODE, UNIQUE, NT, TEAM>(A); }
 
 // Pending pass (duplicate keys only): one lane per delta, so every walker starts at once (the pass is latency bound:
 // few walkers, each a chain of dependent reads). Only the FIRST claimer of a row that got followers does anything:
@@ -338,17 +386,18 @@ __device__ __forceinline__ void resolve_one(const MergeArgs& A, const uint32_t j
   Slot* sl = A.slots + A.slot_of[j];
   const uint4 hi = reinterpret_cast<const uint4*>(sl)[1];
   const int64_t tsw = i64_of(hi.x, hi.y);
-  const int64_t cval = i64_of(hi.z, hi.w);
-  const bool is_new = tsw == TS_NEW || ts_mark(tsw) == A.epoch;  // row created in this batch: no pre-batch state
+  // row created in this batch: no pre-batch state. Read from the row's creation mark, which stands in either claim mode: followers never write (ts,val) of a row
+  // created in this batch. Nothing else is taken from the row — in team mode it holds the value of whichever claimer swapped last.
+  const bool is_new = tsw == TS_NEW || ts_mark(tsw) == A.epoch;
   const uint32_t base_owner = (wf & W_WINNER) ? j : ~0u;   // the first claimer stored iff it beat the pre-batch row
   int64_t bt, bv;
   uint32_t owner, created_by = ~0u;     // created_by: the delta whose write creates the row (the smallest index of the list)
   if (!is_new) {
-    // Resident row (every hot key of a streaming replay): lexmax over the list with ties to the smaller index, starting from what the row
-    // holds now — the pre-batch value, or the first claimer's if it won. A dozen instructions per hop: with one active lane per wave the walk
+    // Resident row (every hot key of a streaming replay): lexmax over the list with ties to the smaller index, starting from the first claimer's
+    // own (t, v): if it won, that is what it put into the row; if it tied, it equals the pre-batch row. A dozen instructions per hop: with one active lane per wave the walk
     // is paced by instruction issue as much as by the dependent load, so the general tracker below (second-best, smallest index) is kept
     // for rows created in this batch only.
-    bt = ts_value(tsw); bv = cval; owner = base_owner;
+    bt = t; bv = v; owner = base_owner;
     uint32_t idx = j, steps = 0;
     for (;;) {
       if (idx != j) {       // the first claimer's own value is what the row already holds (or it lost against the pre-batch row)
@@ -398,7 +447,8 @@ __device__ __forceinline__ void resolve_one(const MergeArgs& A, const uint32_t j
 
 // One workgroup per 256-delta block: every walker of the batch starts at once. (Handling several blocks per workgroup to dispatch
 // fewer workgroups when nothing is flagged was measured: no gain — the 4-5 us this launch costs on a unique-key batch are the kernel
-// boundary behind k_probe_apply, which leaves ~27 MB of dirty lines to write back, not the dispatch.)
+// boundary behind k_probe_apply, not the dispatch. They are not the write-back of that kernel's dirty lines either: claim mode `team` leaves a
+// quarter of them and the launch costs the same, profiles/r06_team_claim_ab.log.)
 template <bool AOS, int MODE>
 __global__ __launch_bounds__(256) void k_resolve_lists(MergeArgs A) {
   // 256-delta blocks none of whose deltas got a follower return after one load
@@ -536,21 +586,39 @@ __global__ __launch_bounds__(256) void k_resolve_strict(MergeArgs A) {
 // odd ones load them — alternately with the plain loads the probe uses and with loads that go to L2 every time — and count pairs that do not
 // belong together. SPLIT writes the halves with two 8-byte stores instead: the control, which must show torn pairs for the check to mean anything.
 // Run once per device and process by bmx_create (bmx_selfcheck); a few milliseconds.
+// TEAM: the second assumption, the one claim mode `team` rests on (bmx_selfcheck_claim): an aligned 16-byte load of (ts,val) never observes one word of a team swap
+// (team_claim: lanes 4i, 4i+1, 4i+2 of ONE returning 64-bit swap instruction write the head word, ts and val of a slot) without the other. Writers swap
+// (tag, x, ~x ^ K), the four lanes of a team drawing the same slots and values; the readers are the same. Its control (SPLIT) has the same lanes issue the three swaps
+// as three instructions. Swaps execute at the memory side and drop the line from the issuing L2 only, so here writers and readers alternate in groups of eight
+// workgroups: every L2 that serves readers also has writers dropping the hot lines from it, and the readers keep fetching them from memory.
 constexpr uint64_t TEAR_K = 0x5DEECE66DA5A5A5Aull;
-template <bool SPLIT>
+template <bool SPLIT, bool TEAM = false>
 __global__ __launch_bounds__(256) void k_selfcheck_tear(uint4* slots, uint32_t nslots, uint32_t iters, unsigned long long* torn, unsigned long long* reads) {
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
-  const bool writer = (blockIdx.x & 1u) == 0;
-  uint64_t x = (uint64_t)gid * 0x9E3779B97F4A7C15ull + 1;
-  unsigned long long bad = 0, n = 0;
+  const bool writer = ((TEAM ? blockIdx.x >> 3 : blockIdx.x) & 1u) == 0;
+  const uint32_t role = threadIdx.x & 3u;
+  uint64_t x = (uint64_t)((TEAM && writer) ? gid >> 2 : gid) * 0x9E3779B97F4A7C15ull + 1;
+  unsigned long long bad = 0, n = 0, sink = 0;
   for (uint32_t i = 0; i < iters; i++) {
     x = x * 6364136223846793005ull + 1442695040888963407ull;
     const uint32_t s = (uint32_t)(x >> 40) % nslots;
     uint4* p = slots + 2 * (size_t)s + 1;                       // second half of a 32-byte slot: where (ts,val) lives
     if (writer) {
       const uint64_t a = x, b = ~x ^ TEAR_K;
-      if (SPLIT) { reinterpret_cast<volatile uint64_t*>(p)[0] = a; reinterpret_cast<volatile uint64_t*>(p)[1] = b; }
+      if (TEAM) {
+        unsigned long long* w = reinterpret_cast<unsigned long long*>(p) - 1 + role;      // role 0: the field|head word in front of (ts,val)
+        const unsigned long long opnd = role == 0 ? u64_of(77u, gid) : (role == 1 ? a : b);
+        if (SPLIT) {
+          if (role == 0) sink ^= __hip_atomic_exchange(w, opnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          asm volatile("" ::: "memory");
+          if (role == 1) sink ^= __hip_atomic_exchange(w, opnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          asm volatile("" ::: "memory");
+          if (role == 2) sink ^= __hip_atomic_exchange(w, opnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if (role != 3u) {
+          sink ^= __hip_atomic_exchange(w, opnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else if (SPLIT) { reinterpret_cast<volatile uint64_t*>(p)[0] = a; reinterpret_cast<volatile uint64_t*>(p)[1] = b; }
       else *p = uint4_of(a, b);
     } else {
       u32x4 v;
@@ -562,19 +630,28 @@ __global__ __launch_bounds__(256) void k_selfcheck_tear(uint4* slots, uint32_t n
     }
   }
   if (bad) atomicAdd(torn, bad);
-  if (n) atomicAdd(reads, n);
+  if (n | (sink == 0x0123456789ABCDEFull)) atomicAdd(reads, n);     // (the swaps return, as team_claim's do: their results are kept alive)
 }
 
 // Placement probe (bmx_create): the probe kernel's request mix — one random 32-byte slot read, one atomic exchange on its head word, one 16-byte store of its
 // (ts,val) half — over an UNINITIALISED table allocation, n threads. Used to rank candidate allocations of the same size (see tune_table_placement in bmx.hip);
-// k_init_slots runs afterwards, so what it scribbles does not matter.
-__global__ __launch_bounds__(64) void k_placement_probe(Slot* slots, uint64_t nslots, uint32_t n, uint32_t salt) {
+// k_init_slots runs afterwards, so what it scribbles does not matter. `team`: the request mix of claim mode `team` instead — the read, then head, ts and val in one
+// team swap (n is a multiple of 64 then, and slot indices fit 32 bits as everywhere).
+__global__ __launch_bounds__(64) void k_placement_probe(Slot* slots, uint64_t nslots, uint32_t n, uint32_t salt, uint32_t team) {
   const uint32_t j = blockIdx.x * 64u + threadIdx.x;
   if (j >= n) return;
   const uint64_t h = mix64(((uint64_t)salt << 32) | j);
-  Slot* sl = slots + __umul64hi(h, nslots);
+  const uint64_t s = __umul64hi(h, nslots);
+  Slot* sl = slots + s;
   const uint4* q = reinterpret_cast<const uint4*>(sl);
   const uint4 lo = q[0], hi = q[1];
+  if (team) {
+    MergeArgs A{}; A.slots = slots; A.epoch = 1;
+    const bool wr = ((lo.x ^ hi.x) & 7u) != 5u;
+    const uint32_t prev = team_claim(A, j, (uint32_t)s, lo.z, (int64_t)u64_of(j, lo.y), (int64_t)u64_of(hi.z, hi.w), true, wr);
+    if (prev == 0x9E3779B9u) sl->head = j;      // (data dependent: the returned head is used)
+    return;
+  }
   const uint32_t prev = atomicExch(&sl->head, j);
   if (((lo.x ^ hi.x ^ prev) & 7u) != 5u)     // (data dependent: the loads and the exchange cannot be dropped; true for seven slots in eight)
     reinterpret_cast<uint4*>(sl)[1] = make_uint4(j, lo.y, hi.z, prev);
