@@ -30,6 +30,7 @@ LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # B
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
 SEMI_ANTI, SEMI_OVERFLOW, SEMI_MAX_SET = 1, 1, 1 << 20   # BMX_SEMI_ANTI (flags of the call), BMX_SEMI_OVERFLOW (flags of bmx_semi_res), BMX_SEMI_MAX_SET (bmx_semi.h bmx_where_semijoin)
+QUANT_MAX, QUANT_MAX_DEN = 8, 1 << 20   # BMX_QUANT_MAX (quantiles per call), BMX_QUANT_MAX_DEN (the largest denominator) (bmx_quant.h bmx_where_quantiles)
 WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2  # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
@@ -70,6 +71,8 @@ EXPORTS_ROWS = ["bmx_where_rows", "bmx_comm_where_rows"]
 
 # include/bmx_semi.h: semi-joins, likewise
 EXPORTS_SEMI = ["bmx_where_semijoin", "bmx_where_in", "bmx_comm_where_semijoin", "bmx_comm_where_in"]
+# include/bmx_quant.h: exact quantiles over boolean filters, likewise
+EXPORTS_QUANT = ["bmx_where_quantiles", "bmx_comm_where_quantiles"]
 # the probe kernel's claim mode (include/bmx_claim.h), likewise
 EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
 
@@ -295,6 +298,40 @@ def _semi_values(values):
     return v, len(v)
 
 
+class QuantQ(C.Structure):
+    """bmx_quant_q: the quantile num / den (8 bytes)"""
+    _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
+
+
+class QuantRec(C.Structure):
+    """bmx_quant_rec: one record of bmx_where_quantiles (32 bytes): the sample's element of 0-based rank `rank`, how many elements are smaller, how many equal"""
+    _fields_ = [("value", C.c_int64), ("rank", C.c_uint64), ("n_below", C.c_uint64), ("n_equal", C.c_uint64)]
+
+
+class QuantRes(C.Structure):
+    """bmx_quant_res: what one bmx_where_quantiles found besides its records (32 bytes): selected nodes, the sample's size, its minimum and maximum"""
+    _fields_ = [("n_match", C.c_uint64), ("n", C.c_uint64), ("min", C.c_int64), ("max", C.c_int64)]
+
+
+QUANT_REC_DTYPE = np.dtype([("value", "<i8"), ("rank", "<u8"), ("n_below", "<u8"), ("n_equal", "<u8")])
+QUANT_RES_DTYPE = np.dtype([("n_match", "<u8"), ("n", "<u8"), ("min", "<i8"), ("max", "<i8")])
+
+
+def quant_rank(num, den, n):
+    """The rank rule of bmx_where_quantiles, in one place: the 0-based rank, in ascending order, of the quantile num / den of a sample of n >= 1 elements
+    ("lower" nearest rank: numpy.sort(v)[quant_rank(num, den, len(v))]). 0/1 is the minimum, 1/1 the maximum, 1/2 the lower median."""
+    num, den, n = int(num), int(den), int(n)
+    if not (1 <= den <= QUANT_MAX_DEN and 0 <= num <= den and n >= 1):
+        raise ValueError("quant_rank: 0 <= num <= den, 1 <= den <= %d and n >= 1" % QUANT_MAX_DEN)
+    return (num * (n - 1)) // den
+
+
+def _quant_tail(measure, qs):
+    """-> (measure_field, nq, qs) of bmx_where_quantiles; qs: a list of (num, den)"""
+    arr = (QuantQ * max(len(qs), 1))(*[QuantQ(int(a), int(b)) for a, b in qs])
+    return (int(measure), len(qs), arr)
+
+
 class WatchRes(C.Structure):
     """bmx_watch_res: what one bmx_watch_poll found (32 bytes); flags: WATCH_RESET, WATCH_OVERFLOW"""
     _fields_ = [("n_entered", C.c_uint64), ("n_left", C.c_uint64), ("n_match", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -423,6 +460,8 @@ def load_library():
     L.bmx_comm_where_top.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, vp, u32, vp, vp, vp]; L.bmx_comm_where_top.restype = i32
     L.bmx_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp, i32]; L.bmx_where_group.restype = i32
     L.bmx_comm_where_group.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, u64, vp]; L.bmx_comm_where_group.restype = i32
+    L.bmx_where_quantiles.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, vp, vp, i32]; L.bmx_where_quantiles.restype = i32
+    L.bmx_comm_where_quantiles.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, vp, vp]; L.bmx_comm_where_quantiles.restype = i32
     prog = [u32, u32, C.POINTER(u32), C.POINTER(Lit)]
     L.bmx_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp, i32]; L.bmx_where_semijoin.restype = i32
     L.bmx_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp, i32]; L.bmx_where_in.restype = i32
@@ -850,6 +889,15 @@ class Engine:
         self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return GroupResult(res, out)
 
+    def where_quantiles(self, base, clauses, measure, qs):
+        """Exact quantiles (bmx_quant.h): the order statistics of field `measure` over the selection of scan_where(base, clauses), selected on the device.
+        qs: up to QUANT_MAX pairs (num, den), in any order, repeats allowed. -> (records: ndarray of QUANT_REC_DTYPE in the order of qs — value, rank
+        (quant_rank(num, den, n)), n_below, n_equal — and a QuantRes: n_match, n, min, max)"""
+        out = np.zeros(max(len(qs), 1), QUANT_REC_DTYPE)
+        res = QuantRes()
+        self._chk(self.L.bmx_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return out[:len(qs)].copy(), res
+
     def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=0):
         """Row projection (bmx_rows.h): the selection of scan_where(base, clauses) from index position `start` on, and for each of the first cap selected nodes
         its id and the values (with_ts: and clocks) of `fields`, in one call. cap None: room for the whole index. -> RowsResult; its next_pos is the `start` of
@@ -1065,6 +1113,11 @@ class Engine:
         particular order; after sync(), GroupResult(res.cpu().numpy().view(GROUP_RES_DTYPE)[0], np.sort(out.cpu().numpy().view(GROUP_DTYPE)[:n], order="key"))
         reads them. The program is host data."""
         self._chk(self.L.bmx_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_quantiles_dev(self, base, clauses, measure, qs, out, res=None):
+        """where_quantiles into device memory (`out`: room for len(qs) records of 32 bytes; res: 32 bytes, a bmx_quant_res, or None); enqueue-only. After
+        sync(), out.cpu().numpy().view(QUANT_REC_DTYPE) and res.cpu().numpy().view(QUANT_RES_DTYPE)[0] read them. The program and qs are host data."""
+        self._chk(self.L.bmx_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), _ptr(res), MEM_DEVICE))
 
     def where_rows_dev(self, base, clauses, fields, cap, out_ids, out_val, out_ts, res, start=0):
         """where_rows into device memory (out_ids: room for cap ids; out_val: len(fields) columns of cap int64 each, field after field; out_ts: the same for
@@ -1319,6 +1372,14 @@ class Comm:
         res = GroupRes()
         self._chk(self.L.bmx_comm_where_group(self.h, *_where_args(base, clauses), *_group_tail(measure, group), _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p)))
         return GroupResult(res, out)
+
+    def where_quantiles(self, base, clauses, measure, qs):
+        """Engine.where_quantiles over all shards: the quantiles of the shards do not combine, so the library steps one select over all of them (every shard
+        sweeps, the histograms add on the host); the bytes one engine holding the same rows gives"""
+        out = np.zeros(max(len(qs), 1), QUANT_REC_DTYPE)
+        res = QuantRes()
+        self._chk(self.L.bmx_comm_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), C.cast(C.byref(res), C.c_void_p)))
+        return out[:len(qs)].copy(), res
 
     def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=(0, 0)):
         """Engine.where_rows over the shards, shard after shard from the cursor start = (shard, position) on: the rows one engine holding the same rows gives,

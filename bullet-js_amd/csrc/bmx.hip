@@ -38,6 +38,7 @@
 #include "group_kernels.h"
 #include "rows_kernels.h"
 #include "semi_kernels.h"
+#include "quant_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -343,6 +344,15 @@ struct SemiScratch {
   void release() { dev_free(keys); dev_free(state); dev_free(stage_keys); dev_free(stage_res); dev_free(stage_ids); ids_cap = 0; staged = 0; cap = 0; slots = 0; clean = false; }
 };
 
+// Scratch of the quantiles (bmx_quant.inc): the select's state record, which every query's last kernel leaves empty again (clean), the position-indexed value
+// scratch of a probed measure (8 bytes per index position, allocated by the first such query and grown with the index) and the records + result record of a
+// BMX_MEM_HOST answer on their way down.
+struct QuantScratch {
+  QuantState* state = nullptr; int64_t* vals = nullptr; uint64_t vals_cap = 0; uint8_t* stage = nullptr;
+  bool clean = false;
+  void release() { dev_free(state); dev_free(vals); dev_free(stage); vals_cap = 0; clean = false; }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -406,6 +416,7 @@ struct bmx_ctx {
   GroupScratch group;
   RowsScratch rows;
   SemiScratch semi;
+  QuantScratch quant;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -728,6 +739,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->group.release();
   ctx->rows.release();
   ctx->semi.release();
+  ctx->quant.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1022,3 +1034,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_group.inc"     // (likewise)
 #include "bmx_rows.inc"      // (likewise)
 #include "bmx_semi.inc"      // (likewise)
+#include "bmx_quant.inc"     // (likewise)
