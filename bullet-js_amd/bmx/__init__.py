@@ -29,6 +29,7 @@ TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_sca
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
+JOIN_MAP_OVERFLOW, JOIN_GROUP_OVERFLOW, JOIN_MAX_MAP = 1, 2, 1 << 20   # BMX_JOIN_MAP_OVERFLOW, BMX_JOIN_GROUP_OVERFLOW (flags of bmx_join_res), BMX_JOIN_MAX_MAP (bmx_join.h bmx_where_join_group)
 SEMI_ANTI, SEMI_OVERFLOW, SEMI_MAX_SET = 1, 1, 1 << 20   # BMX_SEMI_ANTI (flags of the call), BMX_SEMI_OVERFLOW (flags of bmx_semi_res), BMX_SEMI_MAX_SET (bmx_semi.h bmx_where_semijoin)
 QUANT_MAX, QUANT_MAX_DEN = 8, 1 << 20   # BMX_QUANT_MAX (quantiles per call), BMX_QUANT_MAX_DEN (the largest denominator) (bmx_quant.h bmx_where_quantiles)
 WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2  # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
@@ -71,6 +72,8 @@ EXPORTS_ROWS = ["bmx_where_rows", "bmx_comm_where_rows"]
 
 # include/bmx_semi.h: semi-joins, likewise
 EXPORTS_SEMI = ["bmx_where_semijoin", "bmx_where_in", "bmx_comm_where_semijoin", "bmx_comm_where_in"]
+# include/bmx_join.h: lookup joins, likewise
+EXPORTS_JOIN = ["bmx_where_join_group", "bmx_where_map_group", "bmx_comm_where_join_group", "bmx_comm_where_map_group"]
 # include/bmx_quant.h: exact quantiles over boolean filters, likewise
 EXPORTS_QUANT = ["bmx_where_quantiles", "bmx_comm_where_quantiles"]
 # the probe kernel's claim mode (include/bmx_claim.h), likewise
@@ -298,6 +301,44 @@ def _semi_values(values):
     return v, len(v)
 
 
+class JoinRes(C.Structure):
+    """bmx_join_res: what one bmx_where_join_group / bmx_where_map_group found besides its records (184 bytes); flags: JOIN_MAP_OVERFLOW | JOIN_GROUP_OVERFLOW"""
+    _fields_ = [("n_groups", C.c_uint64), ("map_size", C.c_uint64), ("n_inner", C.c_uint64), ("n_keyed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("absent", Agg), ("unmatched", Agg), ("total", Agg)]
+
+
+JOIN_RES_DTYPE = np.dtype([("n_groups", "<u8"), ("map_size", "<u8"), ("n_inner", "<u8"), ("n_keyed", "<u8"), ("flags", "<u4"), ("reserved", "<u4"),
+                           ("absent", AGG_DTYPE), ("unmatched", AGG_DTYPE), ("total", AGG_DTYPE)])
+
+
+class JoinResult:
+    """One where_join_group / where_map_group answer: groups = {attribute: AggResult} in ascending key order (empty on either overflow), records (GROUP_DTYPE,
+    sorted by key), n_groups, map_size, n_inner, n_keyed, map_overflow, group_overflow, and absent (selected nodes whose key has no attribute), unmatched
+    (selected nodes whose link is no key of the map) and total (every selected node) as AggResult."""
+    __slots__ = ("records", "groups", "n_groups", "map_size", "n_inner", "n_keyed", "flags", "map_overflow", "group_overflow", "absent", "unmatched", "total")
+
+    def __init__(self, res, recs):
+        r = np.frombuffer(bytes(res), JOIN_RES_DTYPE)[0] if isinstance(res, JoinRes) else res
+        self.n_groups, self.map_size, self.n_inner, self.n_keyed = int(r["n_groups"]), int(r["map_size"]), int(r["n_inner"]), int(r["n_keyed"])
+        self.flags = int(r["flags"])
+        self.map_overflow = bool(self.flags & JOIN_MAP_OVERFLOW); self.group_overflow = bool(self.flags & JOIN_GROUP_OVERFLOW)
+        self.absent, self.unmatched, self.total = AggResult(r["absent"]), AggResult(r["unmatched"]), AggResult(r["total"])
+        self.records = recs[:0 if self.flags else self.n_groups].copy()
+        self.groups = {int(x["key"]): AggResult(x["agg"]) for x in self.records}
+
+    def __repr__(self):
+        return "JoinResult(%d groups, map of %d from %d/%d%s%s, absent=%r, unmatched=%r, total=%r)" % (
+            self.n_groups, self.map_size, self.n_keyed, self.n_inner, ", map overflow" if self.map_overflow else "", ", group overflow" if self.group_overflow else "",
+            self.absent, self.unmatched, self.total)
+
+
+def _join_pairs(keys, vals):
+    k, v = _np(keys, np.int64).ravel(), _np(vals, np.int64).ravel()
+    if len(k) != len(v):
+        raise ValueError("keys and vals differ in length")
+    return k, v, len(k)
+
+
 class QuantQ(C.Structure):
     """bmx_quant_q: the quantile num / den (8 bytes)"""
     _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
@@ -467,6 +508,10 @@ def load_library():
     L.bmx_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp, i32]; L.bmx_where_in.restype = i32
     L.bmx_comm_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp]; L.bmx_comm_where_semijoin.restype = i32
     L.bmx_comm_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp]; L.bmx_comm_where_in.restype = i32
+    L.bmx_where_join_group.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u32, u64, vp, u64, vp, i32]; L.bmx_where_join_group.restype = i32
+    L.bmx_where_map_group.argtypes = [vp] + prog + [u32, u32, vp, vp, u64, vp, u64, vp, i32]; L.bmx_where_map_group.restype = i32
+    L.bmx_comm_where_join_group.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u32, u64, vp, u64, vp]; L.bmx_comm_where_join_group.restype = i32
+    L.bmx_comm_where_map_group.argtypes = [vp] + prog + [u32, u32, vp, vp, u64, vp, u64, vp]; L.bmx_comm_where_map_group.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
@@ -932,6 +977,27 @@ class Engine:
                                       C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return SemiResult(res, ids, cap)
 
+    def where_join_group(self, base, clauses, link, inner_base, inner_clauses, key, attr, measure=None, cap=65536, map_cap=65536):
+        """Lookup join (bmx_join.h): the selection of scan_where(base, clauses) grouped by the value field `attr` holds on the node of
+        scan_where(inner_base, inner_clauses) whose field `key` equals the selected node's field `link` (the minimum of `attr` where several inner nodes share a
+        key). The map is built and looked up on the device. -> JoinResult"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = JoinRes()
+        self._chk(self.L.bmx_where_join_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure),
+                                              *_where_args(inner_base, inner_clauses), int(key), int(attr), int(map_cap), _ptr(out), int(cap),
+                                              C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return JoinResult(res, out)
+
+    def where_map_group(self, base, clauses, link, keys, vals, measure=None, cap=65536):
+        """where_join_group with the map given as 1..JOIN_MAX_MAP (key, val) pairs (a key outside +-(2^53 - 1) is skipped, a val outside it means "no
+        attribute", duplicate keys take the minimum of their vals)"""
+        k, v, n = _join_pairs(keys, vals)
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = JoinRes()
+        self._chk(self.L.bmx_where_map_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure), _ptr(k), _ptr(v), n,
+                                             _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return JoinResult(res, out)
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -1136,6 +1202,18 @@ class Engine:
         """where_in into device memory; `values` is a device array of nvalues int64. Enqueue-only."""
         self._chk(self.L.bmx_where_in(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, _ptr(values), int(nvalues), _ptr(out_ids), int(cap),
                                       _ptr(res), MEM_DEVICE))
+
+    def where_join_group_dev(self, base, clauses, link, inner_base, inner_clauses, key, attr, out, res, measure=None, cap=65536, map_cap=65536):
+        """where_join_group into device memory (`out`: room for cap records of 56 bytes; res: 184 bytes, a bmx_join_res); enqueue-only. The records come in no
+        particular order; after sync(), JoinResult(res.cpu().numpy().view(JOIN_RES_DTYPE)[0], np.sort(out.cpu().numpy().view(GROUP_DTYPE)[:n], order="key"))
+        is what where_join_group returns."""
+        self._chk(self.L.bmx_where_join_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure),
+                                              *_where_args(inner_base, inner_clauses), int(key), int(attr), int(map_cap), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_map_group_dev(self, base, clauses, link, keys, vals, npairs, out, res, measure=None, cap=65536):
+        """where_map_group into device memory; `keys` and `vals` are device arrays of npairs int64. Enqueue-only."""
+        self._chk(self.L.bmx_where_map_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure), _ptr(keys), _ptr(vals),
+                                             int(npairs), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1415,6 +1493,28 @@ class Comm:
         ids = np.zeros(max(int(cap), 1), np.uint64)
         self._chk(fn(self.h, *args, _ptr(ids), int(cap), C.cast(C.byref(res), C.c_void_p)))
         return SemiResult(res, ids, cap)
+
+    def where_join_group(self, base, clauses, link, inner_base, inner_clauses, key, attr, measure=None, cap=65536, map_cap=65536):
+        """Engine.where_join_group over all shards (every shard builds its own map, the library unites them by key with the minimum of the attributes and sends
+        the union to every shard; the shards' records merge by key): the selection of scan_where(base, clauses) grouped by the value field `attr` holds on the node of
+        scan_where(inner_base, inner_clauses) whose field `key` equals the selected node's field `link` (the minimum of `attr` where several inner nodes share a
+        key). The map is built and looked up on the device. -> JoinResult"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = JoinRes()
+        self._chk(self.L.bmx_comm_where_join_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure),
+                                              *_where_args(inner_base, inner_clauses), int(key), int(attr), int(map_cap), _ptr(out), int(cap),
+                                              C.cast(C.byref(res), C.c_void_p)))
+        return JoinResult(res, out)
+
+    def where_map_group(self, base, clauses, link, keys, vals, measure=None, cap=65536):
+        """Engine.where_map_group over all shards: where_join_group with the map given as 1..JOIN_MAX_MAP (key, val) pairs (a key outside +-(2^53 - 1) is skipped, a val outside it means "no
+        attribute", duplicate keys take the minimum of their vals)"""
+        k, v, n = _join_pairs(keys, vals)
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res = JoinRes()
+        self._chk(self.L.bmx_comm_where_map_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure), _ptr(k), _ptr(v), n,
+                                             _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p)))
+        return JoinResult(res, out)
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

@@ -39,6 +39,7 @@
 #include "rows_kernels.h"
 #include "semi_kernels.h"
 #include "quant_kernels.h"
+#include "join_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -344,6 +345,17 @@ struct SemiScratch {
   void release() { dev_free(keys); dev_free(state); dev_free(stage_keys); dev_free(stage_res); dev_free(stage_ids); ids_cap = 0; staged = 0; cap = 0; slots = 0; clean = false; }
 };
 
+// Scratch of the lookup joins (bmx_join.inc): the open-addressed map of {key, attribute} pairs and its state record, which every query's last kernel leaves empty
+// again (clean), and the staging of the host-mode and sharded forms: the pairs of a list on their way up or of an exported map on their way down (stage_keys,
+// stage_vals, `cap` words each) and the result record. The map grows to the largest map_cap asked so far, all or nothing; a query with a smaller map_cap uses
+// the head of the table. The records are aggregated in GroupScratch's table and come down through its staging.
+struct JoinScratch {
+  JoinPair* map = nullptr; JoinState* state = nullptr; long long* stage_keys = nullptr; long long* stage_vals = nullptr; bmx_join_res* stage_res = nullptr;
+  uint64_t cap = 0, slots = 0;
+  bool clean = false;
+  void release() { dev_free(map); dev_free(state); dev_free(stage_keys); dev_free(stage_vals); dev_free(stage_res); cap = 0; slots = 0; clean = false; }
+};
+
 // Scratch of the quantiles (bmx_quant.inc): the select's state record, which every query's last kernel leaves empty again (clean), the position-indexed value
 // scratch of a probed measure (8 bytes per index position, allocated by the first such query and grown with the index) and the records + result record of a
 // BMX_MEM_HOST answer on their way down.
@@ -417,6 +429,7 @@ struct bmx_ctx {
   RowsScratch rows;
   SemiScratch semi;
   QuantScratch quant;
+  JoinScratch join;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -740,6 +753,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->rows.release();
   ctx->semi.release();
   ctx->quant.release();
+  ctx->join.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1035,3 +1049,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_rows.inc"      // (likewise)
 #include "bmx_semi.inc"      // (likewise)
 #include "bmx_quant.inc"     // (likewise)
+#include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and bmx_semi.inc's slot count)

@@ -89,6 +89,18 @@ inline void group_fold(bmx_agg& o, const bmx_agg& p) {
   o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
 }
 
+// all = all UNION part: two lists sorted by key into one, the records of equal keys folded (tmp: scratch of the caller's)
+inline void group_merge_sorted(std::vector<bmx_group_rec>& all, const std::vector<bmx_group_rec>& part, std::vector<bmx_group_rec>& tmp) {
+  tmp.clear(); tmp.reserve(all.size() + part.size());
+  size_t i = 0, j = 0;
+  while (i < all.size() || j < part.size()) {
+    if (j == part.size() || (i < all.size() && all[i].key < part[j].key)) tmp.push_back(all[i++]);
+    else if (i == all.size() || part[j].key < all[i].key) tmp.push_back(part[j++]);
+    else { bmx_group_rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
+  }
+  all.swap(tmp);
+}
+
 }  // namespace
 
 extern "C" {
@@ -131,15 +143,7 @@ int bmx_comm_where_group(bmx_comm* c, uint32_t base_field, uint32_t nclauses, co
       if (crc) return crc;
       if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
       if (r.flags & BMX_GROUP_OVERFLOW) { overflow = true; lower = std::max(lower, r.n_groups); return (int)BMX_OK; }
-      // the shards' lists are sorted by key: one merge, equal keys folded
-      tmp.clear(); tmp.reserve(all.size() + part.size());
-      size_t i = 0, j = 0;
-      while (i < all.size() || j < part.size()) {
-        if (j == part.size() || (i < all.size() && all[i].key < part[j].key)) tmp.push_back(all[i++]);
-        else if (i == all.size() || part[j].key < all[i].key) tmp.push_back(part[j++]);
-        else { bmx_group_rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
-      }
-      all.swap(tmp);
+      group_merge_sorted(all, part, tmp);                              // the shards' lists are sorted by key: one merge, equal keys folded
       return (int)BMX_OK;
     });
   if (rc) return rc;
