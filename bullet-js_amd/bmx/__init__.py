@@ -35,6 +35,7 @@ QUANT_MAX, QUANT_MAX_DEN = 8, 1 << 20   # BMX_QUANT_MAX (quantiles per call), BM
 WATCH_MAX, WATCH_RESET, WATCH_OVERFLOW = 16, 1, 2  # BMX_WATCH_MAX (live watches per context) and the flags of bmx_watch_res (bmx_watch.h bmx_watch_poll)
 SYNC_TOMBSTONES, EXPORT_ONLY_TOMBSTONES = 1, 2   # BMX_SYNC_TOMBSTONES (bmx_digest), BMX_EXPORT_ONLY_TOMBSTONES (bmx_export_rows)
 
+JROWS_INNER, JROWS_NO_NODE = 2, (1 << 64) - 1   # BMX_JROWS_INNER (flags, next to ROWS_TS), BMX_JROWS_NO_NODE (out_in_ids of a row without inner node) (bmx_join_rows.h bmx_where_join_rows)
 EXPORTS = [
     "bmx_create", "bmx_create_ex", "bmx_destroy", "bmx_last_error", "bmx_abi_version", "bmx_selfcheck", "bmx_set_deferred_compaction", "bmx_set_side_stream", "bmx_set_wait_limit", "bmx_merge_fence", "bmx_get_deferred_counts", "bmx_get_info", "bmx_get_placement", "bmx_set_probe_waves", "bmx_sync", "bmx_set_stream", "bmx_get_stream", "bmx_seq_signal", "bmx_seq_wait",
     "bmx_load_rows", "bmx_put_rows", "bmx_merge_batch", "bmx_merge_submit", "bmx_merge_collect", "bmx_host_alloc", "bmx_host_free", "bmx_merge_records", "bmx_get_rows", "bmx_get_row", "bmx_dump_rows", "bmx_row_count", "bmx_reserve",
@@ -75,6 +76,8 @@ EXPORTS_SEMI = ["bmx_where_semijoin", "bmx_where_in", "bmx_comm_where_semijoin",
 # include/bmx_join.h: lookup joins, likewise
 EXPORTS_JOIN = ["bmx_where_join_group", "bmx_where_map_group", "bmx_comm_where_join_group", "bmx_comm_where_map_group"]
 # include/bmx_quant.h: exact quantiles over boolean filters, likewise
+# join projection (include/bmx_join_rows.h); a list of its own for the same reason
+EXPORTS_JOIN_ROWS = ["bmx_where_join_rows", "bmx_where_map_rows", "bmx_comm_where_join_rows", "bmx_comm_where_map_rows"]
 EXPORTS_QUANT = ["bmx_where_quantiles", "bmx_comm_where_quantiles"]
 # the probe kernel's claim mode (include/bmx_claim.h), likewise
 EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
@@ -339,6 +342,58 @@ def _join_pairs(keys, vals):
     return k, v, len(k)
 
 
+class JoinRowsRes(C.Structure):
+    """bmx_jrows_res: what one bmx_where_join_rows / bmx_where_map_rows found besides its rows (72 bytes); flags: JOIN_MAP_OVERFLOW"""
+    _fields_ = [("n_match", C.c_uint64), ("n_out", C.c_uint64), ("next_pos", C.c_uint64), ("layout", C.c_uint64), ("n_joined", C.c_uint64), ("map_size", C.c_uint64),
+                ("n_inner", C.c_uint64), ("n_keyed", C.c_uint64), ("flags", C.c_uint32), ("next_shard", C.c_uint32)]
+
+
+JROWS_RES_DTYPE = np.dtype([("n_match", "<u8"), ("n_out", "<u8"), ("next_pos", "<u8"), ("layout", "<u8"), ("n_joined", "<u8"), ("map_size", "<u8"), ("n_inner", "<u8"),
+                            ("n_keyed", "<u8"), ("flags", "<u4"), ("next_shard", "<u4")])
+
+
+class JoinRowsResult:
+    """One where_join_rows / where_map_rows answer: ids, vals, ts of the outer nodes as RowsResult has them; in_ids (uint64, JROWS_NO_NODE in a row without
+    inner node), in_vals, in_ts the same for the inner nodes (shape (n_in_fields, n_out)); n_match, n_out, next_pos, next_shard, layout as RowsResult; n_joined
+    (delivered rows with an inner node), map_size, n_inner, n_keyed and map_overflow as JoinResult."""
+    __slots__ = ("ids", "vals", "ts", "in_ids", "in_vals", "in_ts", "n_match", "n_out", "next_pos", "next_shard", "layout", "n_joined", "map_size", "n_inner", "n_keyed",
+                 "flags", "map_overflow")
+
+    def __init__(self, res, ids, vals, ts, in_ids, in_vals, in_ts):
+        r = np.frombuffer(bytes(res), JROWS_RES_DTYPE)[0] if isinstance(res, JoinRowsRes) else res
+        self.n_match, self.n_out, self.next_pos, self.layout, self.next_shard = int(r["n_match"]), int(r["n_out"]), int(r["next_pos"]), int(r["layout"]), int(r["next_shard"])
+        self.n_joined, self.map_size, self.n_inner, self.n_keyed, self.flags = int(r["n_joined"]), int(r["map_size"]), int(r["n_inner"]), int(r["n_keyed"]), int(r["flags"])
+        self.map_overflow = bool(self.flags & JOIN_MAP_OVERFLOW)
+        n = self.n_out
+        self.ids, self.vals, self.ts = ids[:n].copy(), vals[:, :n].copy(), None if ts is None else ts[:, :n].copy()
+        self.in_ids, self.in_vals, self.in_ts = in_ids[:n].copy(), in_vals[:, :n].copy(), None if in_ts is None else in_ts[:, :n].copy()
+
+    def __repr__(self):
+        return "JoinRowsResult(%d of %d rows, %d joined, %d + %d fields, map of %d from %d/%d%s, next_pos=%d)" % (
+            self.n_out, self.n_match, self.n_joined, self.vals.shape[0], self.in_vals.shape[0], self.map_size, self.n_keyed, self.n_inner,
+            ", map overflow" if self.map_overflow else "", self.next_pos)
+
+
+def _jrows_pairs(keys, node_ids):
+    k, v = _np(keys, np.int64).ravel(), _np(node_ids, np.uint64).ravel()
+    if len(k) != len(v):
+        raise ValueError("keys and node_ids differ in length")
+    return k, v, len(k)
+
+
+def _jrows_flags(with_ts, inner):
+    return (ROWS_TS if with_ts else 0) | (JROWS_INNER if inner else 0)
+
+
+def _jrows_host(fn, h, chk, head, mid, nf, nif, with_ts, cap):
+    """one host-memory call: fn(h, *head, *mid, cap, the six outputs, res) -> JoinRowsResult"""
+    ids, vals, ts = _rows_buffers(nf, cap, with_ts)
+    in_ids, in_vals, in_ts = _rows_buffers(nif, cap, with_ts)
+    res = JoinRowsRes()
+    chk(fn(h, *head, *mid, cap, _ptr(ids), _ptr(vals), _ptr(ts), _ptr(in_ids), _ptr(in_vals), _ptr(in_ts), C.cast(C.byref(res), C.c_void_p)))
+    return JoinRowsResult(res, ids, vals, ts, in_ids, in_vals, in_ts)
+
+
 class QuantQ(C.Structure):
     """bmx_quant_q: the quantile num / den (8 bytes)"""
     _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
@@ -512,6 +567,11 @@ def load_library():
     L.bmx_where_map_group.argtypes = [vp] + prog + [u32, u32, vp, vp, u64, vp, u64, vp, i32]; L.bmx_where_map_group.restype = i32
     L.bmx_comm_where_join_group.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u32, u64, vp, u64, vp]; L.bmx_comm_where_join_group.restype = i32
     L.bmx_comm_where_map_group.argtypes = [vp] + prog + [u32, u32, vp, vp, u64, vp, u64, vp]; L.bmx_comm_where_map_group.restype = i32
+    jr_out = [vp, vp, vp, vp, vp, vp, vp]
+    L.bmx_where_join_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32)] + prog + [u32, u32, C.POINTER(u32), u64, u32, u64, u64] + jr_out + [i32]; L.bmx_where_join_rows.restype = i32
+    L.bmx_where_map_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32), vp, vp, u64, u32, C.POINTER(u32), u32, u64, u64] + jr_out + [i32]; L.bmx_where_map_rows.restype = i32
+    L.bmx_comm_where_join_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32)] + prog + [u32, u32, C.POINTER(u32), u64, u32, u32, u64, u64] + jr_out; L.bmx_comm_where_join_rows.restype = i32
+    L.bmx_comm_where_map_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32), vp, vp, u64, u32, C.POINTER(u32), u32, u32, u64, u64] + jr_out; L.bmx_comm_where_map_rows.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
@@ -998,6 +1058,27 @@ class Engine:
                                              _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return JoinResult(res, out)
 
+    def where_join_rows(self, base, clauses, link, fields, inner_base, inner_clauses, key, in_fields, cap=None, with_ts=False, inner=False, start=0, map_cap=65536):
+        """Join projection (bmx_join_rows.h): the selection of scan_where(base, clauses) from index position `start` on, each row with the values (with_ts:
+        and clocks) of `fields` and with the id and the `in_fields` of the node of scan_where(inner_base, inner_clauses) whose field `key` equals the row's
+        field `link` (the smallest unsigned id where several share a key). A left join; inner=True drops the rows without inner node from the selection. cap
+        None: room for the whole index of `base`. -> JoinRowsResult"""
+        cap = self.index_size(base) if cap is None else int(cap)
+        nf, farr, _ = _rows_fields(fields, with_ts)
+        nif, ifarr, _ = _rows_fields(in_fields, with_ts)
+        return _jrows_host(lambda *a: self.L.bmx_where_join_rows(*a, MEM_HOST), self.h, self._chk, (*_where_args(base, clauses), int(link), nf, farr),
+                           (*_where_args(inner_base, inner_clauses), int(key), nif, ifarr, int(map_cap), _jrows_flags(with_ts, inner), int(start)), nf, nif, with_ts, cap)
+
+    def where_map_rows(self, base, clauses, link, fields, keys, node_ids, in_fields, cap=None, with_ts=False, inner=False, start=0):
+        """where_join_rows with the map given as 1..JOIN_MAX_MAP (key, node id) pairs (a key outside +-(2^53 - 1) or the id JROWS_NO_NODE is skipped,
+        duplicate keys take the smallest id)"""
+        cap = self.index_size(base) if cap is None else int(cap)
+        nf, farr, _ = _rows_fields(fields, with_ts)
+        nif, ifarr, _ = _rows_fields(in_fields, with_ts)
+        k, v, n = _jrows_pairs(keys, node_ids)
+        return _jrows_host(lambda *a: self.L.bmx_where_map_rows(*a, MEM_HOST), self.h, self._chk, (*_where_args(base, clauses), int(link), nf, farr),
+                           (_ptr(k), _ptr(v), n, nif, ifarr, _jrows_flags(with_ts, inner), int(start)), nf, nif, with_ts, cap)
+
     def watch_create(self, base, clauses):
         """A standing query (bmx_watch.h): the program of scan_where(base, clauses), kept on the device together with its last committed answer. -> the watch id"""
         w = C.c_uint32()
@@ -1214,6 +1295,28 @@ class Engine:
         """where_map_group into device memory; `keys` and `vals` are device arrays of npairs int64. Enqueue-only."""
         self._chk(self.L.bmx_where_map_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure), _ptr(keys), _ptr(vals),
                                              int(npairs), _ptr(out), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_join_rows_dev(self, base, clauses, link, fields, inner_base, inner_clauses, key, in_fields, cap, out_ids, out_val, out_ts, out_in_ids, out_in_val,
+                            out_in_ts, res, inner=False, start=0, map_cap=65536):
+        """where_join_rows into device memory (out_ids / out_in_ids: room for cap ids; out_val / out_in_val: one column of cap int64 per field of that side;
+        out_ts / out_in_ts: the same for the clocks, or both None for none; res: 72 bytes, a bmx_jrows_res); enqueue-only. After sync(),
+        res.cpu().numpy().view(JROWS_RES_DTYPE)[0] reads the record."""
+        nf, farr, _ = _rows_fields(fields, False)
+        nif, ifarr, _ = _rows_fields(in_fields, False)
+        flags = _jrows_flags(out_ts is not None or out_in_ts is not None, inner)
+        self._chk(self.L.bmx_where_join_rows(self.h, *_where_args(base, clauses), int(link), nf, farr, *_where_args(inner_base, inner_clauses), int(key), nif, ifarr,
+                                             int(map_cap), flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(out_in_ids), _ptr(out_in_val),
+                                             _ptr(out_in_ts), _ptr(res), MEM_DEVICE))
+
+    def where_map_rows_dev(self, base, clauses, link, fields, keys, node_ids, npairs, in_fields, cap, out_ids, out_val, out_ts, out_in_ids, out_in_val, out_in_ts, res,
+                           inner=False, start=0):
+        """where_map_rows into device memory; `keys` (int64) and `node_ids` (uint64 bit patterns) are device arrays of npairs words. Enqueue-only."""
+        nf, farr, _ = _rows_fields(fields, False)
+        nif, ifarr, _ = _rows_fields(in_fields, False)
+        flags = _jrows_flags(out_ts is not None or out_in_ts is not None, inner)
+        self._chk(self.L.bmx_where_map_rows(self.h, *_where_args(base, clauses), int(link), nf, farr, _ptr(keys), _ptr(node_ids), int(npairs), nif, ifarr, flags,
+                                            int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(out_in_ids), _ptr(out_in_val), _ptr(out_in_ts),
+                                            _ptr(res), MEM_DEVICE))
 
     def watch_poll_dev(self, w, entered, cap_entered, left, cap_left, res):
         """watch_poll into device memory (entered / left: room for cap ids each, or None with a cap of 0; res: 32 bytes, a bmx_watch_res); enqueue-only: the
@@ -1515,6 +1618,32 @@ class Comm:
         self._chk(self.L.bmx_comm_where_map_group(self.h, *_where_args(base, clauses), int(link), AGG_NO_FIELD if measure is None else int(measure), _ptr(k), _ptr(v), n,
                                              _ptr(out), int(cap), C.cast(C.byref(res), C.c_void_p)))
         return JoinResult(res, out)
+
+    def where_join_rows(self, base, clauses, link, fields, inner_base, inner_clauses, key, in_fields, cap=None, with_ts=False, inner=False, start=(0, 0), map_cap=65536):
+        """Engine.where_join_rows over the shards (every shard builds its own map, the library unites them by key with the smallest id and sends the union to
+        every shard; the inner cells come from the shards that own the inner nodes): the rows one engine holding the same rows gives, shard after shard from
+        the cursor start = (shard, position) on. cap None: it counts first (cap 0) and then fetches with room for exactly that. -> JoinRowsResult"""
+        nf, farr, _ = _rows_fields(fields, with_ts)
+        nif, ifarr, _ = _rows_fields(in_fields, with_ts)
+        head = (*_where_args(base, clauses), int(link), nf, farr)
+        mid = (*_where_args(inner_base, inner_clauses), int(key), nif, ifarr, int(map_cap), _jrows_flags(with_ts, inner), int(start[0]), int(start[1]))
+        return self._jrows(self.L.bmx_comm_where_join_rows, head, mid, nf, nif, with_ts, cap)
+
+    def where_map_rows(self, base, clauses, link, fields, keys, node_ids, in_fields, cap=None, with_ts=False, inner=False, start=(0, 0)):
+        """Engine.where_map_rows over the shards: where_join_rows with the map given as 1..JOIN_MAX_MAP (key, node id) pairs"""
+        nf, farr, _ = _rows_fields(fields, with_ts)
+        nif, ifarr, _ = _rows_fields(in_fields, with_ts)
+        k, v, n = _jrows_pairs(keys, node_ids)
+        head = (*_where_args(base, clauses), int(link), nf, farr)
+        mid = (_ptr(k), _ptr(v), n, nif, ifarr, _jrows_flags(with_ts, inner), int(start[0]), int(start[1]))
+        return self._jrows(self.L.bmx_comm_where_map_rows, head, mid, nf, nif, with_ts, cap)
+
+    def _jrows(self, fn, head, mid, nf, nif, with_ts, cap):
+        if cap is None:
+            res = JoinRowsRes()
+            self._chk(fn(self.h, *head, *mid, 0, None, None, None, None, None, None, C.cast(C.byref(res), C.c_void_p)))
+            cap = int(res.n_match)
+        return _jrows_host(fn, self.h, self._chk, head, mid, nf, nif, with_ts, int(cap))
 
     def watch_create(self, base, clauses):
         """Engine.watch_create on every shard: one id, valid on all of them"""

@@ -40,6 +40,7 @@
 #include "semi_kernels.h"
 #include "quant_kernels.h"
 #include "join_kernels.h"
+#include "join_rows_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -1050,3 +1051,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_semi.inc"      // (likewise)
 #include "bmx_quant.inc"     // (likewise)
 #include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and bmx_semi.inc's slot count)
+#include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch and bmx_rows.inc's mask pass and staging)
