@@ -81,6 +81,9 @@ EXPORTS_JOIN_ROWS = ["bmx_where_join_rows", "bmx_where_map_rows", "bmx_comm_wher
 EXPORTS_QUANT = ["bmx_where_quantiles", "bmx_comm_where_quantiles"]
 # the probe kernel's claim mode (include/bmx_claim.h), likewise
 EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
+# update and delete by query (include/bmx_update.h), likewise
+EXPORTS_UPDATE = ["bmx_where_update", "bmx_comm_where_update"]
+UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
 
 class BmxError(RuntimeError):
@@ -273,6 +276,41 @@ def _rows_fields(fields, with_ts):
 
 def _rows_buffers(nfields, cap, with_ts):
     return np.zeros(max(cap, 1), np.uint64), np.zeros((nfields, max(cap, 1)), np.int64), np.zeros((nfields, max(cap, 1)), np.int64) if with_ts else None
+
+
+class UpdRes(C.Structure):
+    """bmx_upd_res: what one bmx_where_update found and wrote (72 bytes)"""
+    _fields_ = [("n_match", C.c_uint64), ("n_nosrc", C.c_uint64), ("n_range", C.c_uint64), ("n_sent", C.c_uint64), ("n_applied", C.c_uint64), ("n_rows", C.c_uint64),
+                ("next_pos", C.c_uint64), ("layout", C.c_uint64), ("next_shard", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+UPD_RES_DTYPE = np.dtype([("n_match", "<u8"), ("n_nosrc", "<u8"), ("n_range", "<u8"), ("n_sent", "<u8"), ("n_applied", "<u8"), ("n_rows", "<u8"), ("next_pos", "<u8"),
+                          ("layout", "<u8"), ("next_shard", "<u4"), ("reserved", "<u4")])
+
+
+class UpdateResult:
+    """One where_update answer: n_match (the selected nodes at or behind the cursor), n_nosrc / n_range (of those: never written, for want of a source value or
+    because the sum left the value range), n_sent (records handed to the merge), n_applied (rows that changed), n_rows (resident rows afterwards), next_pos (and
+    next_shard: the cursor of the next page), layout (the cursor is good while the NEXT page reports the same) and ids (uint64, the n_applied nodes whose row
+    changed, in index order; None unless asked for)."""
+    __slots__ = ("n_match", "n_nosrc", "n_range", "n_sent", "n_applied", "n_rows", "next_pos", "next_shard", "layout", "ids")
+
+    def __init__(self, res, ids=None):
+        r = np.frombuffer(bytes(res), UPD_RES_DTYPE)[0] if isinstance(res, UpdRes) else res
+        for k in ("n_match", "n_nosrc", "n_range", "n_sent", "n_applied", "n_rows", "next_pos", "next_shard", "layout"):
+            setattr(self, k, int(r[k]))
+        self.ids = None if ids is None else ids[:self.n_applied].copy()
+
+    def __repr__(self):
+        return "UpdateResult(%d matched, %d sent, %d applied, next_pos=%d)" % (self.n_match, self.n_sent, self.n_applied, self.next_pos)
+
+
+def _upd_args(target, op, operand, src, ts, force):
+    """-> (target_field, op, src_field, operand, ts, flags) of bmx_where_update"""
+    if ts is None:
+        import time
+        ts = int(time.time() * 1000)          # the reference's clock: milliseconds since the epoch
+    return (int(target), int(op), 0 if src is None else int(src), int(operand), int(ts), UPD_FORCE if force else 0)
 
 
 class SemiRes(C.Structure):
@@ -574,6 +612,9 @@ def load_library():
     L.bmx_comm_where_map_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32), vp, vp, u64, u32, C.POINTER(u32), u32, u32, u64, u64] + jr_out; L.bmx_comm_where_map_rows.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
+    upd = [u32, u32, u32, i64, i64, u32]
+    L.bmx_where_update.argtypes = [vp] + prog + upd + [u64, u64, vp, vp, i32]; L.bmx_where_update.restype = i32
+    L.bmx_comm_where_update.argtypes = [vp] + prog + upd + [u32, u64, u64, vp, vp]; L.bmx_comm_where_update.restype = i32
     L.bmx_watch_create.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), C.POINTER(u32)]; L.bmx_watch_create.restype = i32
     L.bmx_watch_poll.argtypes = [vp, u32, vp, u64, vp, u64, vp, i32]; L.bmx_watch_poll.restype = i32
     L.bmx_watch_destroy.argtypes = [vp, u32]; L.bmx_watch_destroy.restype = i32
@@ -1015,6 +1056,41 @@ class Engine:
                                         C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return RowsResult(res, ids, vals, ts)
 
+    def where_update(self, base, clauses, target, op, operand=0, src=None, ts=None, force=False, cap=None, start=0, want_ids=False):
+        """Update by query (bmx_update.h): on every node scan_where(base, clauses) selects from index position `start` on, field `target` gets the record
+        (ts, val), val being `operand` (UPD_SET), a tombstone (UPD_DELETE; needs force), the node's value of `src` (UPD_COPY) or that value + operand (UPD_ADD).
+        Default: through conflict resolution like merge_batch(INSERT_DELTA); force: stored as given like put_rows. cap None: min(index size, UPD_MAX_CAP);
+        cap 0 counts only. ts None: the wall clock in milliseconds. want_ids: the ids of the nodes whose row changed. -> UpdateResult; its next_pos is the `start` of the next page."""
+        cap = min(self.index_size(base), UPD_MAX_CAP) if cap is None else int(cap)
+        ids = np.zeros(max(cap, 1), np.uint64) if want_ids else None
+        res = UpdRes()
+        self._chk(self.L.bmx_where_update(self.h, *_where_args(base, clauses), *_upd_args(target, op, operand, src, ts, force), int(start), cap, _ptr(ids),
+                                          C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return UpdateResult(res, ids)
+
+    def where_update_all(self, base, clauses, target, op, operand=0, src=None, ts=None, force=False, page=1 << 22):
+        """where_update over the whole selection in pages of `page` records: counts first (cap 0), reserves room for row_count + n_match rows so that no page
+        grows the table and lays the index out anew (which would make UPD_ADD onto its own source add twice when started over), then pages along the cursor
+        and sums the results. -> UpdateResult (n_match, n_nosrc, n_range of the whole selection; ids None). Raises BmxError(ERR_INTERNAL) if the layout
+        changes between two pages all the same, and says how many nodes were done."""
+        first = self.where_update(base, clauses, target, op, operand, src, ts, force, cap=0)
+        self.reserve(self.row_count() + first.n_match)
+        tot = np.zeros(1, UPD_RES_DTYPE)[0]
+        start, layout = 0, None
+        while True:
+            r = self.where_update(base, clauses, target, op, operand, src, ts, force, cap=int(page), start=start)
+            if layout is not None and r.layout != layout:
+                raise BmxError(ERR_INTERNAL, "where_update_all: the index was laid out anew between two pages; %d nodes were sent and %d rows changed before that"
+                               % (int(tot["n_sent"]), int(tot["n_applied"])))
+            if layout is None:
+                tot["n_match"], tot["n_nosrc"], tot["n_range"] = r.n_match, r.n_nosrc, r.n_range
+            layout = r.layout
+            tot["n_sent"] += r.n_sent; tot["n_applied"] += r.n_applied
+            tot["n_rows"], tot["next_pos"], tot["layout"] = r.n_rows, r.next_pos, r.layout
+            if r.n_match - r.n_nosrc - r.n_range <= r.n_sent:
+                return UpdateResult(tot)
+            start = r.next_pos
+
     def where_semijoin(self, base, clauses, link, inner_base, inner_clauses, key, anti=False, cap=None, set_cap=65536, count_only=False):
         """Semi-join (bmx_semi.h): the selection of scan_where(base, clauses) whose field `link` holds a value that field `key` holds on some node of
         scan_where(inner_base, inner_clauses); anti: whose `link` holds no such value (or nothing). The set is built and tested on the device. cap None: room
@@ -1272,6 +1348,13 @@ class Engine:
         The program, the fields and the cursor are host data."""
         nf, farr, flags = _rows_fields(fields, out_ts is not None)
         self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
+
+    def where_update_dev(self, base, clauses, target, op, cap, out_ids, res, operand=0, src=None, ts=None, force=False, start=0):
+        """where_update with out_ids (room for cap ids, or None) and res (72 bytes, a bmx_upd_res) in device memory. NOT enqueue-only: the call waits once for
+        the counts between its emit pass and the merge; out_ids and res are written by its last kernel and valid after sync() or in stream order, when
+        res.cpu().numpy().view(UPD_RES_DTYPE)[0] reads the record. The program and the operands are host data."""
+        self._chk(self.L.bmx_where_update(self.h, *_where_args(base, clauses), *_upd_args(target, op, operand, src, ts, force), int(start), int(cap), _ptr(out_ids),
+                                          _ptr(res), MEM_DEVICE))
 
     def where_semijoin_dev(self, base, clauses, link, inner_base, inner_clauses, key, out_ids, cap, res, anti=False, set_cap=65536):
         """where_semijoin into device memory (out_ids: room for cap ids, or None with cap 0; res: 32 bytes, a bmx_semi_res); enqueue-only. After sync(),
@@ -1574,6 +1657,18 @@ class Comm:
         ids, vals, ts = _rows_buffers(nf, int(cap), with_ts)
         self._chk(self.L.bmx_comm_where_rows(self.h, *args, int(cap), _ptr(ids), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
         return RowsResult(res, ids, vals, ts)
+
+    def where_update(self, base, clauses, target, op, operand=0, src=None, ts=None, force=False, cap=None, start=(0, 0), want_ids=False):
+        """Engine.where_update over the shards, shard after shard from the cursor start = (shard, position) on; every shard updates the nodes it owns. cap None:
+        it counts first (cap 0) and then sends exactly the writable nodes (at most UPD_MAX_CAP). -> UpdateResult; (next_shard, next_pos) is the next start."""
+        args = (*_where_args(base, clauses), *_upd_args(target, op, operand, src, ts, force), int(start[0]), int(start[1]))
+        res = UpdRes()
+        if cap is None:
+            self._chk(self.L.bmx_comm_where_update(self.h, *args, 0, None, C.cast(C.byref(res), C.c_void_p)))
+            cap = min(int(res.n_match - res.n_nosrc - res.n_range), UPD_MAX_CAP)
+        ids = np.zeros(max(int(cap), 1), np.uint64) if want_ids else None
+        self._chk(self.L.bmx_comm_where_update(self.h, *args, int(cap), _ptr(ids), C.cast(C.byref(res), C.c_void_p)))
+        return UpdateResult(res, ids)
 
     def where_semijoin(self, base, clauses, link, inner_base, inner_clauses, key, anti=False, cap=None, set_cap=65536, count_only=False):
         """Engine.where_semijoin over all shards: every shard builds its own set, the library unites them and sends the union to every shard, so the answer

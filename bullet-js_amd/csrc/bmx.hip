@@ -41,6 +41,7 @@
 #include "quant_kernels.h"
 #include "join_kernels.h"
 #include "join_rows_kernels.h"
+#include "update_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -366,6 +367,16 @@ struct QuantScratch {
   void release() { dev_free(state); dev_free(vals); dev_free(stage); vals_cap = 0; clean = false; }
 };
 
+// Scratch of the update by query (bmx_update.inc): the staging slab of records the emit pass fills and the merge reads, the winners' indices and ids (`cap` of
+// each, grown on demand), the words between the passes (counts: what the host waits for; ctr: the sharded counters of the mask pass, zero between two calls), the
+// merge's count and stats, the record of a BMX_MEM_HOST answer on its way down, and what a call's mask pass leaves its emit pass (as RowsScratch::masked).
+struct UpdScratch {
+  bmx_delta_rec* recs = nullptr; uint32_t* applied = nullptr; uint64_t* ids = nullptr; uint64_t cap = 0;
+  UpdCounts* counts = nullptr; unsigned long long* ctr = nullptr; unsigned long long* n_applied = nullptr; bmx_merge_stats* stats = nullptr; bmx_upd_res* stage_res = nullptr;
+  RowsScratch::Masked masked;
+  void release() { dev_free(recs); dev_free(applied); dev_free(ids); dev_free(counts); dev_free(ctr); dev_free(n_applied); dev_free(stats); dev_free(stage_res); cap = 0; }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -431,6 +442,7 @@ struct bmx_ctx {
   SemiScratch semi;
   QuantScratch quant;
   JoinScratch join;
+  UpdScratch upd;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -755,6 +767,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->semi.release();
   ctx->quant.release();
   ctx->join.release();
+  ctx->upd.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1052,3 +1065,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_quant.inc"     // (likewise)
 #include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and bmx_semi.inc's slot count)
 #include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch and bmx_rows.inc's mask pass and staging)
+#include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself)
