@@ -83,6 +83,9 @@ EXPORTS_QUANT = ["bmx_where_quantiles", "bmx_comm_where_quantiles"]
 EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
 # update and delete by query (include/bmx_update.h), likewise
 EXPORTS_UPDATE = ["bmx_where_update", "bmx_comm_where_update"]
+# group-by over several fields (include/bmx_group_multi.h), likewise
+EXPORTS_GROUP_MULTI = ["bmx_where_group_multi", "bmx_comm_where_group_multi"]
+MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14   # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
 UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
 
@@ -241,6 +244,59 @@ def group_merge(lists):
 
 def _group_tail(measure, group):
     return (AGG_NO_FIELD if measure is None else int(measure), AGG_NO_FIELD if group is None else int(group))
+
+
+MGROUP_DTYPE = np.dtype([("key", "<i8", (4,)), ("agg", AGG_DTYPE)])      # bmx_mgroup_rec: one record of bmx_where_group_multi (80 bytes)
+
+
+class GroupKey(C.Structure):
+    """bmx_group_key: one key of bmx_where_group_multi (24 bytes): floor((value(field) - origin) / width)"""
+    _fields_ = [("field", C.c_uint32), ("flags", C.c_uint32), ("origin", C.c_int64), ("width", C.c_int64)]
+
+
+def _mgroup_keys(keys):
+    """keys: a list of field or (field, origin, width) -> (nkeys, bmx_group_key array)"""
+    ks = [(k, 0, 1) if isinstance(k, (int, np.integer)) else k for k in keys]
+    return (len(ks), (GroupKey * max(len(ks), 1))(*[GroupKey(int(f), 0, int(o), int(w)) for f, o, w in ks]))
+
+
+def mgroup_sort(recs):
+    """records (MGROUP_DTYPE) in the order of a host-mode answer: lexicographic by (key[0], key[1], key[2], key[3]), each signed ascending"""
+    recs = np.asarray(recs, MGROUP_DTYPE)
+    k = recs["key"]
+    return recs[np.lexsort((k[:, 3], k[:, 2], k[:, 1], k[:, 0]))]
+
+
+class MultiGroupResult:
+    """One where_group_multi answer: groups = {key tuple (nkeys ints): AggResult} in the records' sorted order (empty on overflow), records (MGROUP_DTYPE,
+    sorted lexicographically by key), n_groups (the number of distinct tuples, or on overflow a lower bound of it above cap), overflow, absent (selected nodes
+    that lack any of the keys) and total (every selected node) as AggResult."""
+    __slots__ = ("records", "groups", "n_groups", "overflow", "absent", "total")
+
+    def __init__(self, res, recs, nkeys):
+        r = np.frombuffer(bytes(res), GROUP_RES_DTYPE)[0] if isinstance(res, GroupRes) else res
+        self.n_groups = int(r["n_groups"]); self.overflow = bool(int(r["flags"]) & GROUP_OVERFLOW)
+        self.absent, self.total = AggResult(r["absent"]), AggResult(r["total"])
+        self.records = recs[:0 if self.overflow else self.n_groups].copy()
+        self.groups = {tuple(int(v) for v in x["key"][:nkeys]): AggResult(x["agg"]) for x in self.records}
+
+    def __repr__(self):
+        return "MultiGroupResult(%d groups%s, absent=%r, total=%r)" % (self.n_groups, ", overflow" if self.overflow else "", self.absent, self.total)
+
+
+def mgroup_merge(lists):
+    """The merge bmx_comm_where_group_multi does with its shards' answers: `lists` are record arrays (MGROUP_DTYPE), each with distinct tuples; -> one array
+    sorted lexicographically by key, the records of equal tuples folded (counts and 128-bit sums add, minima and maxima fold). Pure numpy: no library, no GPU."""
+    parts = [np.asarray(x, MGROUP_DTYPE) for x in lists if len(x)]
+    if not parts:
+        return np.zeros(0, MGROUP_DTYPE)
+    a = mgroup_sort(np.concatenate(parts))
+    first = np.ones(len(a), bool); first[1:] = (a["key"][1:] != a["key"][:-1]).any(axis=1)
+    out = a[first].copy()
+    at = np.cumsum(first) - 1
+    for i in np.nonzero(~first)[0]:
+        _group_fold(out[at[i]]["agg"], a[i]["agg"])
+    return out
 
 
 class RowsRes(C.Structure):
@@ -612,6 +668,8 @@ def load_library():
     L.bmx_comm_where_map_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32), vp, vp, u64, u32, C.POINTER(u32), u32, u32, u64, u64] + jr_out; L.bmx_comm_where_map_rows.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
+    L.bmx_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp, i32]; L.bmx_where_group_multi.restype = i32
+    L.bmx_comm_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp]; L.bmx_comm_where_group_multi.restype = i32
     upd = [u32, u32, u32, i64, i64, u32]
     L.bmx_where_update.argtypes = [vp] + prog + upd + [u64, u64, vp, vp, i32]; L.bmx_where_update.restype = i32
     L.bmx_comm_where_update.argtypes = [vp] + prog + upd + [u32, u64, u64, vp, vp]; L.bmx_comm_where_update.restype = i32
@@ -1056,6 +1114,18 @@ class Engine:
                                         C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return RowsResult(res, ids, vals, ts)
 
+    def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
+        """Group-by over several fields (bmx_group_multi.h): count / sum / min / max of field `measure` over the selection of scan_where(base, clauses), one
+        record per distinct key tuple that occurs among the selected nodes. keys: 1..4 of `field` (the value itself) or (field, origin, width) (the bucket
+        (value - origin) // width). A node that lacks any key is counted in absent. -> MultiGroupResult (with overflow set and no groups if there are more
+        than cap tuples; cap <= GROUP_MAX_CAP, <= MGROUP_MAX_CAP4 with four keys)."""
+        out = np.zeros(max(int(cap), 1), MGROUP_DTYPE)
+        res = GroupRes()
+        nk, karr = _mgroup_keys(keys)
+        self._chk(self.L.bmx_where_group_multi(self.h, *_where_args(base, clauses), AGG_NO_FIELD if measure is None else int(measure), nk, karr, _ptr(out), int(cap),
+                                               C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return MultiGroupResult(res, out, nk)
+
     def where_update(self, base, clauses, target, op, operand=0, src=None, ts=None, force=False, cap=None, start=0, want_ids=False):
         """Update by query (bmx_update.h): on every node scan_where(base, clauses) selects from index position `start` on, field `target` gets the record
         (ts, val), val being `operand` (UPD_SET), a tombstone (UPD_DELETE; needs force), the node's value of `src` (UPD_COPY) or that value + operand (UPD_ADD).
@@ -1348,6 +1418,14 @@ class Engine:
         The program, the fields and the cursor are host data."""
         nf, farr, flags = _rows_fields(fields, out_ts is not None)
         self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
+
+    def where_group_multi_dev(self, base, clauses, keys, out, res, measure=None, cap=65536):
+        """where_group_multi into device memory (`out`: room for cap records of 80 bytes; res: 112 bytes, a bmx_group_res); enqueue-only. The keys are host
+        data. The records come in no particular order; after sync(), MultiGroupResult(res.cpu().numpy().view(GROUP_RES_DTYPE)[0],
+        mgroup_sort(out.cpu().numpy().view(MGROUP_DTYPE)[:n]), len(keys)) is what where_group_multi returns."""
+        nk, karr = _mgroup_keys(keys)
+        self._chk(self.L.bmx_where_group_multi(self.h, *_where_args(base, clauses), AGG_NO_FIELD if measure is None else int(measure), nk, karr, _ptr(out), int(cap),
+                                               _ptr(res), MEM_DEVICE))
 
     def where_update_dev(self, base, clauses, target, op, cap, out_ids, res, operand=0, src=None, ts=None, force=False, start=0):
         """where_update with out_ids (room for cap ids, or None) and res (72 bytes, a bmx_upd_res) in device memory. NOT enqueue-only: the call waits once for
@@ -1657,6 +1735,15 @@ class Comm:
         ids, vals, ts = _rows_buffers(nf, int(cap), with_ts)
         self._chk(self.L.bmx_comm_where_rows(self.h, *args, int(cap), _ptr(ids), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
         return RowsResult(res, ids, vals, ts)
+
+    def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
+        """Engine.where_group_multi over all shards: every shard answers with its own tuples, the library merges them as mgroup_merge does"""
+        out = np.zeros(max(int(cap), 1), MGROUP_DTYPE)
+        res = GroupRes()
+        nk, karr = _mgroup_keys(keys)
+        self._chk(self.L.bmx_comm_where_group_multi(self.h, *_where_args(base, clauses), AGG_NO_FIELD if measure is None else int(measure), nk, karr, _ptr(out),
+                                                    int(cap), C.cast(C.byref(res), C.c_void_p)))
+        return MultiGroupResult(res, out, nk)
 
     def where_update(self, base, clauses, target, op, operand=0, src=None, ts=None, force=False, cap=None, start=(0, 0), want_ids=False):
         """Engine.where_update over the shards, shard after shard from the cursor start = (shard, position) on; every shard updates the nodes it owns. cap None:

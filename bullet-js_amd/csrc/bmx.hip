@@ -42,6 +42,7 @@
 #include "join_kernels.h"
 #include "join_rows_kernels.h"
 #include "update_kernels.h"
+#include "mgroup_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -327,6 +328,17 @@ struct GroupScratch {
   void release() { dev_free(keys); dev_free(acc); dev_free(state); dev_free(stage); dev_free(stage_res); cap = 0; slots = 0; clean = false; }
 };
 
+// Scratch of the group-by over several fields (bmx_group_multi.inc): the tuple table (GroupScratch's shape, keyed by the packed word), the dictionaries
+// (dict_words key words: nkeys tables of a query's slot count at the head), the state records (the tuple table's, then one per dictionary), which every query's
+// last kernels leave empty again (clean), and the records + result record of a BMX_MEM_HOST answer on their way down. Grows to the largest cap and the most
+// dictionary words asked so far, all or nothing.
+struct MGroupScratch {
+  long long* keys = nullptr; AggRaw* acc = nullptr; long long* dict = nullptr; GroupState* state = nullptr; bmx_mgroup_rec* stage = nullptr; bmx_group_res* stage_res = nullptr;
+  uint64_t cap = 0, slots = 0, dict_words = 0;
+  bool clean = false;
+  void release() { dev_free(keys); dev_free(acc); dev_free(dict); dev_free(state); dev_free(stage); dev_free(stage_res); cap = 0; slots = 0; dict_words = 0; clean = false; }
+};
+
 // Scratch of the row projection (bmx_rows.inc): the columns and the result record of a BMX_MEM_HOST answer on their way down (`stage`: 8-byte words, grown on
 // demand), and what a call's mask pass leaves its emit pass (the base index as the mask pass saw it; the sharded form enqueues every shard's mask pass first).
 struct RowsScratch {
@@ -443,6 +455,7 @@ struct bmx_ctx {
   QuantScratch quant;
   JoinScratch join;
   UpdScratch upd;
+  MGroupScratch mgroup;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -768,6 +781,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->quant.release();
   ctx->join.release();
   ctx->upd.release();
+  ctx->mgroup.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1066,3 +1080,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and bmx_semi.inc's slot count)
 #include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch and bmx_rows.inc's mask pass and staging)
 #include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself)
+#include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid and fold, and a scratch of its own)
