@@ -1070,14 +1070,16 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_vc.inc"
 #include "bmx_comm.inc"
 #include "bmx_vc_sync.inc"   // (behind everything that was here before it: its kernels follow the others in the code object)
-#include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls)
+#include "bmx_where.inc"     // (likewise; bmx_comm.inc declares the two functions of it that it calls. It also holds what every form below shares: the predicate, the
+                             //  width dispatch of a sweep, the entry guards, the mask pass and the cursor steps of the paged sharded forms; the emit pass's
+                             //  geometry, emit_dispatch, is bmx_scan.inc's)
 #include "bmx_watch.inc"     // (likewise)
 #include "bmx_where_agg.inc" // (likewise)
-#include "bmx_group.inc"     // (likewise)
-#include "bmx_rows.inc"      // (likewise)
+#include "bmx_group.inc"     // (likewise; it holds the collect, merge and sharded combine of every grouped answer)
+#include "bmx_rows.inc"      // (likewise; it holds the staging growth and the column copy of every projected answer)
 #include "bmx_semi.inc"      // (likewise)
 #include "bmx_quant.inc"     // (likewise)
-#include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and bmx_semi.inc's slot count)
-#include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch and bmx_rows.inc's mask pass and staging)
-#include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself)
-#include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid and fold, and a scratch of its own)
+#include "bmx_join.inc"      // (likewise; it uses bmx_group.inc's scratch and grouped-answer steps and bmx_semi.inc's slot count)
+#include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch, bmx_rows.inc's mask pass, staging and column copy and bmx_where.inc's mask pass)
+#include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself; its mask pass is bmx_where.inc's)
+#include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid, fold and grouped-answer steps, and a scratch of its own)

@@ -512,7 +512,8 @@ int bmx_comm_scan_where(bmx_comm* c, uint32_t base_field, uint32_t nclauses, con
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   return comm_scan_with(c, out_ids, cap, n_out, [&](bmx_ctx* x, uint64_t* want, uint64_t wcap) {
-    return where_run(x, base_field, W, want, wcap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
+    const int erc = enter(x);
+    return erc ? erc : where_run(x, base_field, W, want, wcap, nullptr, BMX_MEM_HOST, /*deferred=*/true);
   });
 }
 

@@ -1,7 +1,9 @@
-// bmx_group.inc — group-by over discovered values (bmx_group.h): bmx_where_group and its sharded form. The program is bmx_where.inc's (where_prepare), the
-// predicate and the sweep grid are bmx_where_agg.inc's (where_pred, where_agg_grid), the kernels are group_kernels.h. The context keeps their scratch
-// (GroupScratch): the table, the state record, which every query's last kernel leaves empty again (clean), and the answer of a host-mode call on its way down.
-// Included by bmx.hip (one translation unit), behind everything that was here before it.
+// bmx_group.inc — group-by over discovered values (bmx_group.h): bmx_where_group and its sharded form, and what every grouped answer shares (this one's, the
+// group-by over several fields' and the lookup joins'): the staged answer's second half (grouped_collect), the merge of two sorted lists (merge_sorted) and
+// the sharded combine (comm_grouped). The program, the width dispatch of the sweep and the entry guards are bmx_where.inc's (where_prepare, where_sweep,
+// where_enter, where_comm_guard), the kernels are group_kernels.h. The context keeps their scratch (GroupScratch): the table, the state record, which every
+// query's last kernel leaves empty again (clean), and the answer of a host-mode call on its way down. Included by bmx.hip (one translation unit), behind
+// everything that was here before it.
 namespace {
 
 const char* group_bad_args(uint32_t group_field, const bmx_group_rec* out, uint64_t cap, const bmx_group_res* res) {
@@ -53,8 +55,9 @@ int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_
   A.measure = measure_field; A.group = group_field;
   A.m_src = where_agg_source(measure_field, base_field); A.g_src = where_agg_source(group_field, base_field);
   s.clean = false;
-  if (ix->fits32) hipLaunchKernelGGL((k_group_sweep<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, W), A);
-  else hipLaunchKernelGGL((k_group_sweep<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, W), A);
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_group_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  });
   LAUNCHCHK("k_group_sweep");
   hipLaunchKernelGGL(k_group_finish, dim3(group_finish_grid(A.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,
                      A.m_src != AGG_SRC_PROBE ? 1u : 0u);
@@ -65,20 +68,25 @@ int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_
 
 inline bool group_key_less(const bmx_group_rec& a, const bmx_group_rec& b) { return a.key < b.key; }
 
-// second half of a host-mode query: the result record, then (if they fit) the records, sorted by key. `recs` gets them; nothing of the caller's is written.
-int group_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_group_rec>& recs, bmx_group_res* res) {
-  HIPCHK(hipMemcpyAsync(res, ctx->group.stage_res, sizeof(bmx_group_res), hipMemcpyDeviceToHost, ctx->stream));
+// Second half of a staged grouped answer: the result record, then (if they fit) the records, sorted by `less`. `recs` gets them; nothing of the caller's is
+// written. no_recs: the flag bits of the record that say no records were written. fn: the entry point, for the internal error's text.
+template <class Rec, class Res, class Less>
+int grouped_collect(bmx_ctx* ctx, const Rec* stage, const Res* stage_res, uint32_t no_recs, uint64_t cap, Less less, const char* fn, std::vector<Rec>& recs, Res* res) {
+  HIPCHK(hipMemcpyAsync(res, stage_res, sizeof(Res), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   recs.clear();
-  if (res->flags & BMX_GROUP_OVERFLOW) return BMX_OK;
-  if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, "bmx_where_group: more records than cap without the overflow flag");
+  if (res->flags & no_recs) return BMX_OK;
+  if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, std::string(fn) + ": more records than cap without the overflow flag");
   recs.resize(res->n_groups);
   if (res->n_groups) {
-    HIPCHK(hipMemcpyAsync(recs.data(), ctx->group.stage, res->n_groups * sizeof(bmx_group_rec), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(recs.data(), stage, res->n_groups * sizeof(Rec), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::sort(recs.begin(), recs.end(), group_key_less);
+    std::sort(recs.begin(), recs.end(), less);
   }
   return BMX_OK;
+}
+int group_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_group_rec>& recs, bmx_group_res* res) {
+  return grouped_collect(ctx, ctx->group.stage, ctx->group.stage_res, BMX_GROUP_OVERFLOW, cap, group_key_less, "bmx_where_group", recs, res);
 }
 
 // a += b: counts and 128-bit sums add, minima and maxima fold (comm_agg_with's combine)
@@ -88,17 +96,51 @@ inline void group_fold(bmx_agg& o, const bmx_agg& p) {
   const unsigned __int128 s = (((unsigned __int128)(uint64_t)o.sum_hi << 64) | o.sum_lo) + (((unsigned __int128)(uint64_t)p.sum_hi << 64) | p.sum_lo);
   o.sum_lo = (uint64_t)s; o.sum_hi = (int64_t)(uint64_t)(s >> 64);
 }
+// the aggregates of shard g's result record into the communicator's: shard 0's start it
+inline void group_fold_res(uint32_t g, bmx_group_res& tot, const bmx_group_res& r) {
+  if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
+}
 
-// all = all UNION part: two lists sorted by key into one, the records of equal keys folded (tmp: scratch of the caller's)
-inline void group_merge_sorted(std::vector<bmx_group_rec>& all, const std::vector<bmx_group_rec>& part, std::vector<bmx_group_rec>& tmp) {
+// all = all UNION part: two lists sorted by `less` into one, the records of equal keys folded (tmp: scratch of the caller's)
+template <class Rec, class Less>
+void merge_sorted(std::vector<Rec>& all, const std::vector<Rec>& part, std::vector<Rec>& tmp, Less less) {
   tmp.clear(); tmp.reserve(all.size() + part.size());
   size_t i = 0, j = 0;
   while (i < all.size() || j < part.size()) {
-    if (j == part.size() || (i < all.size() && all[i].key < part[j].key)) tmp.push_back(all[i++]);
-    else if (i == all.size() || part[j].key < all[i].key) tmp.push_back(part[j++]);
-    else { bmx_group_rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
+    if (j == part.size() || (i < all.size() && less(all[i], part[j]))) tmp.push_back(all[i++]);
+    else if (i == all.size() || less(part[j], all[i])) tmp.push_back(part[j++]);
+    else { Rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
   }
   all.swap(tmp);
+}
+
+// A grouped answer over the shards: enqueue(x) on every shard (entered here), then shard after shard collect(x, part, &r) — its sorted list and its record — and
+// fold(g, *tot, r), the form's own aggregates; the lists merged, equal keys folded. A shard that overflowed reports a lower bound of the number of groups: the
+// answer overflows (`overflow`: the form's flag bit) with the largest bound any shard or the union gives. Otherwise the records go to `out`.
+template <class Rec, class Res, class Less, class Enqueue, class Collect, class Fold>
+int comm_grouped(bmx_comm* c, uint64_t cap, uint32_t overflow, Less less, Rec* out, Res* tot, Enqueue enqueue, Collect collect, Fold fold) {
+  std::vector<Rec> all, part, tmp;
+  uint64_t lower = 0;
+  bool over = false;
+  *tot = Res{};
+  const int rc = comm_two_phase(c,
+    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : enqueue(x); },
+    [&](uint32_t g, bmx_ctx* x) {
+      Res r;
+      int crc = enter(x);
+      if (!crc) crc = collect(x, part, &r);
+      if (crc) return crc;
+      fold(g, *tot, r);
+      if (r.flags & overflow) { over = true; lower = std::max<uint64_t>(lower, r.n_groups); return (int)BMX_OK; }
+      merge_sorted(all, part, tmp, less);
+      return (int)BMX_OK;
+    });
+  if (rc) return rc;
+  lower = std::max<uint64_t>(lower, all.size());
+  if (over || all.size() > cap) { tot->flags = overflow; tot->n_groups = lower; }
+  else { tot->flags = 0; tot->n_groups = all.size(); if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(Rec)); }
+  tot->reserved = 0;
+  return BMX_OK;
 }
 
 }  // namespace
@@ -110,9 +152,7 @@ int bmx_where_group(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const 
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (const char* bad = group_bad_args(group_field, out, cap, res)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) return group_enqueue(ctx, base_field, W, measure_field, group_field, cap, out, res);
   if (int rc = group_enqueue(ctx, base_field, W, measure_field, group_field, cap, nullptr, nullptr)) return rc;
   std::vector<bmx_group_rec> recs;
@@ -128,29 +168,12 @@ int bmx_comm_where_group(bmx_comm* c, uint32_t base_field, uint32_t nclauses, co
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (const char* bad = group_bad_args(group_field, out, cap, res)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
-  std::vector<bmx_group_rec> all, part, tmp;
-  bmx_group_res tot{};
-  uint64_t lower = 0;                                               // the largest lower bound of D any overflowing shard reported
-  bool overflow = false;
-  const int rc = comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : group_enqueue(x, base_field, W, measure_field, group_field, cap, nullptr, nullptr); },
-    [&](uint32_t g, bmx_ctx* x) {
-      bmx_group_res r;
-      int crc = enter(x);
-      if (!crc) crc = group_collect(x, cap, part, &r);
-      if (crc) return crc;
-      if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
-      if (r.flags & BMX_GROUP_OVERFLOW) { overflow = true; lower = std::max(lower, r.n_groups); return (int)BMX_OK; }
-      group_merge_sorted(all, part, tmp);                              // the shards' lists are sorted by key: one merge, equal keys folded
-      return (int)BMX_OK;
-    });
-  if (rc) return rc;
-  lower = std::max<uint64_t>(lower, all.size());
-  if (overflow || all.size() > cap) { tot.flags = BMX_GROUP_OVERFLOW; tot.n_groups = lower; }
-  else { tot.flags = 0; tot.n_groups = all.size(); if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(bmx_group_rec)); }
-  tot.reserved = 0;
+  bmx_group_res tot;
+  if (int rc = comm_grouped(c, cap, BMX_GROUP_OVERFLOW, group_key_less, out, &tot,
+        [&](bmx_ctx* x) { return group_enqueue(x, base_field, W, measure_field, group_field, cap, nullptr, nullptr); },
+        [&](bmx_ctx* x, std::vector<bmx_group_rec>& part, bmx_group_res* r) { return group_collect(x, cap, part, r); }, group_fold_res)) return rc;
   *res = tot;
   return BMX_OK;
 }

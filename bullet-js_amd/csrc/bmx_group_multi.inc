@@ -1,6 +1,7 @@
 // bmx_group_multi.inc — group-by over several fields (bmx_group_multi.h): bmx_where_group_multi and its sharded form. The program is bmx_where.inc's
-// (where_prepare), the predicate and the sweep grid are bmx_where_agg.inc's (where_pred, where_agg_grid), the slot count, the finish grid and the fold of two
-// records are bmx_group.inc's (group_slots, group_finish_grid, group_fold), the kernels are mgroup_kernels.h. The context keeps their scratch (MGroupScratch):
+// (where_prepare), and so are the width dispatch of the sweep and the entry guards (where_sweep, where_enter, where_comm_guard); the slot count, the finish
+// grid, the fold of two records and the collect, merge and sharded combine of a grouped answer are bmx_group.inc's (group_slots, group_finish_grid, group_fold,
+// grouped_collect, merge_sorted, comm_grouped), the kernels are mgroup_kernels.h. The context keeps their scratch (MGroupScratch):
 // the tuple table, the dictionaries, the state records, which every query's last kernels leave empty again (clean), and the answer of a host-mode call on its
 // way down. bmx_where_group's scratch (ctx->group) is neither read nor written. Included by bmx.hip (one translation unit), behind everything that was here
 // before it.
@@ -62,8 +63,9 @@ int mgroup_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32
   while ((1ull << A.shift) < A.T.slots) A.shift++;
   for (uint32_t j = 0; j < nkeys; j++) A.k[j] = MGroupKey{keys[j].origin, keys[j].width, keys[j].field, where_agg_source(keys[j].field, base_field)};
   s.clean = false;
-  if (ix->fits32) hipLaunchKernelGGL((k_mgroup_sweep<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, W), A);
-  else hipLaunchKernelGGL((k_mgroup_sweep<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, W), A);
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_mgroup_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  });
   LAUNCHCHK("k_mgroup_sweep");
   hipLaunchKernelGGL(k_mgroup_finish, dim3(group_finish_grid(A.T.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,
                      A.T.m_src != AGG_SRC_PROBE ? 1u : 0u);
@@ -78,32 +80,9 @@ int mgroup_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32
 
 inline bool mgroup_key_less(const bmx_mgroup_rec& a, const bmx_mgroup_rec& b) { return std::lexicographical_compare(a.key, a.key + 4, b.key, b.key + 4); }
 
-// second half of a host-mode query: the result record, then (if they fit) the records, sorted by tuple. `recs` gets them; nothing of the caller's is written.
+// second half of a host-mode query: the records sorted by tuple (grouped_collect)
 int mgroup_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_mgroup_rec>& recs, bmx_group_res* res) {
-  HIPCHK(hipMemcpyAsync(res, ctx->mgroup.stage_res, sizeof(bmx_group_res), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  recs.clear();
-  if (res->flags & BMX_GROUP_OVERFLOW) return BMX_OK;
-  if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, "bmx_where_group_multi: more records than cap without the overflow flag");
-  recs.resize(res->n_groups);
-  if (res->n_groups) {
-    HIPCHK(hipMemcpyAsync(recs.data(), ctx->mgroup.stage, res->n_groups * sizeof(bmx_mgroup_rec), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::sort(recs.begin(), recs.end(), mgroup_key_less);
-  }
-  return BMX_OK;
-}
-
-// all = all UNION part: two lists sorted by tuple into one, the records of equal tuples folded with group_fold (tmp: scratch of the caller's)
-inline void mgroup_merge_sorted(std::vector<bmx_mgroup_rec>& all, const std::vector<bmx_mgroup_rec>& part, std::vector<bmx_mgroup_rec>& tmp) {
-  tmp.clear(); tmp.reserve(all.size() + part.size());
-  size_t i = 0, j = 0;
-  while (i < all.size() || j < part.size()) {
-    if (j == part.size() || (i < all.size() && mgroup_key_less(all[i], part[j]))) tmp.push_back(all[i++]);
-    else if (i == all.size() || mgroup_key_less(part[j], all[i])) tmp.push_back(part[j++]);
-    else { bmx_mgroup_rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
-  }
-  all.swap(tmp);
+  return grouped_collect(ctx, ctx->mgroup.stage, ctx->mgroup.stage_res, BMX_GROUP_OVERFLOW, cap, mgroup_key_less, "bmx_where_group_multi", recs, res);
 }
 
 }  // namespace
@@ -115,9 +94,7 @@ int bmx_where_group_multi(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, 
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (const char* bad = mgroup_bad_args(nkeys, keys, out, cap, res)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) return mgroup_enqueue(ctx, base_field, W, measure_field, nkeys, keys, cap, out, res);
   if (int rc = mgroup_enqueue(ctx, base_field, W, measure_field, nkeys, keys, cap, nullptr, nullptr)) return rc;
   std::vector<bmx_mgroup_rec> recs;
@@ -133,29 +110,12 @@ int bmx_comm_where_group_multi(bmx_comm* c, uint32_t base_field, uint32_t nclaus
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (const char* bad = mgroup_bad_args(nkeys, keys, out, cap, res)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
-  std::vector<bmx_mgroup_rec> all, part, tmp;
-  bmx_group_res tot{};
-  uint64_t lower = 0;                                               // the largest lower bound of D any overflowing shard reported
-  bool overflow = false;
-  const int rc = comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : mgroup_enqueue(x, base_field, W, measure_field, nkeys, keys, cap, nullptr, nullptr); },
-    [&](uint32_t g, bmx_ctx* x) {
-      bmx_group_res r;
-      int crc = enter(x);
-      if (!crc) crc = mgroup_collect(x, cap, part, &r);
-      if (crc) return crc;
-      if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
-      if (r.flags & BMX_GROUP_OVERFLOW) { overflow = true; lower = std::max(lower, r.n_groups); return (int)BMX_OK; }
-      mgroup_merge_sorted(all, part, tmp);                             // the shards' lists are sorted by tuple: one merge, equal tuples folded
-      return (int)BMX_OK;
-    });
-  if (rc) return rc;
-  lower = std::max<uint64_t>(lower, all.size());
-  if (overflow || all.size() > cap) { tot.flags = BMX_GROUP_OVERFLOW; tot.n_groups = lower; }
-  else { tot.flags = 0; tot.n_groups = all.size(); if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(bmx_mgroup_rec)); }
-  tot.reserved = 0;
+  bmx_group_res tot;
+  if (int rc = comm_grouped(c, cap, BMX_GROUP_OVERFLOW, mgroup_key_less, out, &tot,
+        [&](bmx_ctx* x) { return mgroup_enqueue(x, base_field, W, measure_field, nkeys, keys, cap, nullptr, nullptr); },
+        [&](bmx_ctx* x, std::vector<bmx_mgroup_rec>& part, bmx_group_res* r) { return mgroup_collect(x, cap, part, r); }, group_fold_res)) return rc;
   *res = tot;
   return BMX_OK;
 }

@@ -1,8 +1,9 @@
 // bmx_join.inc — lookup joins (bmx_join.h): bmx_where_join_group, bmx_where_map_group and their sharded forms. The programs are bmx_where.inc's (where_prepare),
-// the predicate and the sweep grid bmx_where_agg.inc's (where_pred, where_agg_grid), the kernels join_kernels.h. The context keeps the map's scratch (JoinScratch):
-// the table of pairs and its state record, which every query's last kernel leaves empty again (clean), and the staging of the host-mode and sharded forms. The
-// records are aggregated in bmx_where_group's table (ctx->group, through group_scratch and its clean protocol), and a host-mode answer's records come down
-// through its staging. Included by bmx.hip (one translation unit), behind everything that was here before it.
+// and so are the width dispatch of the sweeps and the entry guards (where_sweep, where_enter, where_comm_guard), the kernels join_kernels.h. The context keeps
+// the map's scratch (JoinScratch): the table of pairs and its state record, which every query's last kernel leaves empty again (clean), and the staging of the
+// host-mode and sharded forms. The records are aggregated in bmx_where_group's table (ctx->group, through group_scratch and its clean protocol), and a
+// host-mode answer's records come down through its staging, collected, merged and combined over the shards by bmx_group.inc's grouped_collect, merge_sorted
+// and comm_grouped. Included by bmx.hip (one translation unit), behind everything that was here before it.
 namespace {
 
 struct JoinWant { uint32_t link_field, measure_field; bmx_group_rec* out; uint64_t cap; bmx_join_res* res; };
@@ -59,8 +60,9 @@ int join_build(bmx_ctx* ctx, const JoinArgs& J, uint32_t in_base_field, const Wh
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t ksrc = where_agg_source(key_field, in_base_field);
   const uint32_t asrc = attr_field == key_field ? JOIN_SRC_KEY : where_agg_source(attr_field, in_base_field);
-  if (ix->fits32) hipLaunchKernelGGL((k_join_build<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, WI), J, key_field, ksrc, attr_field, asrc);
-  else hipLaunchKernelGGL((k_join_build<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, WI), J, key_field, ksrc, attr_field, asrc);
+  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_join_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc, attr_field, asrc);
+  });
   LAUNCHCHK("k_join_build");
   return BMX_OK;
 }
@@ -80,8 +82,9 @@ int join_sweep(bmx_ctx* ctx, const JoinArgs& J, uint32_t base_field, const Where
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
   GroupArgs A;
   if (int rc = join_group_args(ctx, base_field, w, &A)) return rc;
-  if (ix->fits32) hipLaunchKernelGGL((k_join_group_sweep<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, W), A, J);
-  else hipLaunchKernelGGL((k_join_group_sweep<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, W), A, J);
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_join_group_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, J);
+  });
   LAUNCHCHK("k_join_group_sweep");
   hipLaunchKernelGGL(k_join_finish, dim3(semi_finish_grid(std::max(A.slots, J.slots))), dim3(JOIN_THREADS), 0, ctx->stream, A, J, d_out ? d_out : ctx->group.stage,
                      d_out ? d_res : ctx->join.stage_res, A.m_src != AGG_SRC_PROBE ? 1u : 0u);
@@ -90,20 +93,9 @@ int join_sweep(bmx_ctx* ctx, const JoinArgs& J, uint32_t base_field, const Where
   return BMX_OK;
 }
 
-// second half of a staged answer: the result record, then (if they fit) the records, sorted by key. `recs` gets them; nothing of the caller's is written.
+// second half of a staged answer (grouped_collect): ANY flag of the record says that no records were written, the map's overflow as the groups'
 int join_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_group_rec>& recs, bmx_join_res* res) {
-  HIPCHK(hipMemcpyAsync(res, ctx->join.stage_res, sizeof(bmx_join_res), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  recs.clear();
-  if (res->flags) return BMX_OK;
-  if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, "bmx_where_join_group: more records than cap without the overflow flag");
-  recs.resize(res->n_groups);
-  if (res->n_groups) {
-    HIPCHK(hipMemcpyAsync(recs.data(), ctx->group.stage, res->n_groups * sizeof(bmx_group_rec), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::sort(recs.begin(), recs.end(), group_key_less);
-  }
-  return BMX_OK;
+  return grouped_collect(ctx, ctx->group.stage, ctx->join.stage_res, ~0u, cap, group_key_less, "bmx_where_join_group", recs, res);
 }
 
 // one shard's (or the one context's) bmx_where_map_group with the pairs in HOST memory, enqueued into the staging
@@ -130,29 +122,13 @@ int join_deliver(bmx_ctx* ctx, const JoinWant& w) {
 // phase 2 of both sharded forms: the `m` pairs (host memory) to every shard, every sweep enqueued, then the answers merged shard after shard. n_inner and
 // n_keyed of *tot are shard 0's (every shard was given the same list).
 int comm_join_map(bmx_comm* c, uint32_t base_field, const WhereProg& W, const JoinWant& w, const int64_t* keys, const int64_t* vals, uint64_t m, bmx_join_res* tot) {
-  std::vector<bmx_group_rec> all, part, tmp;
-  uint64_t lower = 0;                                               // the largest lower bound of D any overflowing shard reported
-  bool overflow = false;
-  *tot = bmx_join_res{};
-  const int rc = comm_two_phase(c,
-    [&](uint32_t, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : join_map_staged(x, base_field, W, w, keys, vals, m); },
-    [&](uint32_t g, bmx_ctx* x) {
-      bmx_join_res r;
-      int crc = enter(x);
-      if (!crc) crc = join_collect(x, w.cap, part, &r);
-      if (crc) return crc;
-      if (g == 0) { *tot = r; tot->flags = 0; tot->n_groups = 0; }
-      else { group_fold(tot->absent, r.absent); group_fold(tot->unmatched, r.unmatched); group_fold(tot->total, r.total); }
-      if (r.flags & BMX_JOIN_GROUP_OVERFLOW) { overflow = true; lower = std::max(lower, r.n_groups); return (int)BMX_OK; }
-      group_merge_sorted(all, part, tmp);                              // as bmx_comm_where_group merges its shards' lists
-      return (int)BMX_OK;
+  return comm_grouped(c, w.cap, BMX_JOIN_GROUP_OVERFLOW, group_key_less, w.out, tot,
+    [&](bmx_ctx* x) { return join_map_staged(x, base_field, W, w, keys, vals, m); },
+    [&](bmx_ctx* x, std::vector<bmx_group_rec>& part, bmx_join_res* r) { return join_collect(x, w.cap, part, r); },
+    [](uint32_t g, bmx_join_res& t, const bmx_join_res& r) {
+      if (g == 0) { t = r; t.flags = 0; t.n_groups = 0; }
+      else { group_fold(t.absent, r.absent); group_fold(t.unmatched, r.unmatched); group_fold(t.total, r.total); }
     });
-  if (rc) return rc;
-  lower = std::max<uint64_t>(lower, all.size());
-  if (overflow || all.size() > w.cap) { tot->flags = BMX_JOIN_GROUP_OVERFLOW; tot->n_groups = lower; }
-  else { tot->flags = 0; tot->n_groups = all.size(); if (!all.empty()) std::memcpy(w.out, all.data(), all.size() * sizeof(bmx_group_rec)); }
-  tot->reserved = 0;
-  return BMX_OK;
 }
 
 std::string join_text(const char* fn, const char* which, const char* bad) { return std::string(fn) + ": " + which + bad; }
@@ -174,9 +150,7 @@ int bmx_where_join_group(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, c
   if (const char* bad = join_bad_args(w, map_cap, JOIN_BAD_MAP_CAP)) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "no key field"));
   if (attr_field == BMX_AGG_NO_FIELD) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "no attribute field"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   JoinArgs J;
   if (int rc = join_scratch(ctx, map_cap, &J)) return rc;
   if (int rc = join_build(ctx, J, in_base_field, WI, key_field, attr_field)) return rc;
@@ -194,9 +168,7 @@ int bmx_where_map_group(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, co
   if (const char* bad = join_bad_args(w, npairs, JOIN_BAD_NPAIRS)) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (!keys) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "null keys"));
   if (!vals) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "null vals"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) {
     JoinArgs J;
     if (int rc = join_scratch(ctx, npairs, &J)) return rc;
@@ -218,7 +190,7 @@ int bmx_comm_where_join_group(bmx_comm* c, uint32_t base_field, uint32_t nclause
   if (const char* bad = join_bad_args(w, map_cap, JOIN_BAD_MAP_CAP)) return fail(c, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "no key field"));
   if (attr_field == BMX_AGG_NO_FIELD) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "no attribute field"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   // phase 1: every shard's own map, exported; the union on the host
   std::vector<std::pair<int64_t, int64_t>> all;
@@ -287,7 +259,7 @@ int bmx_comm_where_map_group(bmx_comm* c, uint32_t base_field, uint32_t nclauses
   if (const char* bad = join_bad_args(w, npairs, JOIN_BAD_NPAIRS)) return fail(c, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (!keys) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "null keys"));
   if (!vals) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "null vals"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   bmx_join_res tot;
   if (int rc = comm_join_map(c, base_field, W, w, keys, vals, npairs, &tot)) return rc;

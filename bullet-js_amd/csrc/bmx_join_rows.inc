@@ -1,8 +1,10 @@
 // bmx_join_rows.inc — join projection (bmx_join_rows.h): bmx_where_join_rows, bmx_where_map_rows and their sharded forms. The programs are bmx_where.inc's
-// (where_prepare), the left join's mask pass bmx_rows.inc's (rows_mask), the map's scratch and its clean protocol bmx_join.inc's (join_scratch: the same table
-// bmx_where_join_group uses), the kernels join_rows_kernels.h. A host-mode answer comes down through the row projection's staging columns (RowsScratch::stage)
-// and the lookup joins' result record (JoinScratch::stage_res); a host-mode list goes up through JoinScratch::stage_keys / stage_vals. Included by bmx.hip (one
-// translation unit), behind everything that was here before it.
+// (where_prepare), and so are the width dispatch of the build sweep, the inner join's mask pass, the entry guards and the cursor steps of the sharded forms
+// (where_sweep, where_mask_pass, where_enter, where_comm_guard, where_stamp_only, page_note); the left join's mask pass is bmx_rows.inc's (rows_mask), the emit
+// pass's geometry bmx_scan.inc's (emit_dispatch), the map's scratch and its clean protocol bmx_join.inc's (join_scratch: the same table bmx_where_join_group
+// uses), the kernels join_rows_kernels.h. A host-mode answer comes down through the row projection's staging columns (RowsScratch::stage, grown by rows_stage,
+// copied out by rows_copy_cols) and the lookup joins' result record (JoinScratch::stage_res); a host-mode list goes up through JoinScratch::stage_keys /
+// stage_vals. Included by bmx.hip (one translation unit), behind everything that was here before it.
 namespace {
 
 struct JRowsWant {
@@ -44,8 +46,9 @@ int jrows_build(bmx_ctx* ctx, const JoinArgs& J, uint32_t in_base_field, const W
   Index* ix;
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t ksrc = where_agg_source(key_field, in_base_field);
-  if (ix->fits32) hipLaunchKernelGGL((k_jrows_build<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, WI), J, key_field, ksrc);
-  else hipLaunchKernelGGL((k_jrows_build<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, WI), J, key_field, ksrc);
+  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_jrows_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc);
+  });
   LAUNCHCHK("k_jrows_build");
   return BMX_OK;
 }
@@ -73,24 +76,11 @@ inline JRowsLink jrows_link(const JoinArgs& J, uint32_t link_field, uint32_t bas
 // rows_mask leaves it (ctx->rows.masked).
 int jrows_mask(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const JRowsWant& w, const JoinArgs& J, uint64_t start) {
   if (!jrows_inner(w)) return rows_mask(ctx, base_field, W, start);
-  Index* ix;
-  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  if (int rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), 0)) return rc;
-  const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
   const JRowsLink L = jrows_link(J, w.link_field, base_field);
-  if (ix->fits32) hipLaunchKernelGGL((k_scan_mask<PredJRowsFrom<int32_t>, true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, PredJRowsFrom<int32_t>{PredRowsFrom<int32_t>{where_pred<int32_t>(ctx, ix, W), start}, L}, ix->n, ctx->scan.mask, ctx->scan.counts);
-  else hipLaunchKernelGGL((k_scan_mask<PredJRowsFrom<int64_t>, true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, PredJRowsFrom<int64_t>{PredRowsFrom<int64_t>{where_pred<int64_t>(ctx, ix, W), start}, L}, ix->n, ctx->scan.mask, ctx->scan.counts);
-  LAUNCHCHK("k_scan_mask(join rows)");
-  ctx->rows.masked = RowsScratch::Masked{ix->ids, ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64), ix->n, ix->layout, ix->fits32, nb};
-  return BMX_OK;
-}
-
-template <class T>
-void jrows_launch_emit(bmx_ctx* ctx, const JRowsArgs& A, uint32_t nb) {
-  const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");       // the scans' measurement / test switch, as rows_launch_emit reads it
-  const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
-  if (nb > sub8_blocks) hipLaunchKernelGGL((k_jrows_emit<T, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, nb, A);
-  else hipLaunchKernelGGL((k_jrows_emit<T, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, nb, A);
+  return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(join rows)", &ctx->rows.masked, [&](const auto& P) {
+    using T = decltype(where_value(P));
+    return PredJRowsFrom<T>{PredRowsFrom<T>{P, start}, L};
+  });
 }
 
 // the call's last kernel: the map back to empty, the record completed
@@ -118,7 +108,11 @@ int jrows_emit(bmx_ctx* ctx, uint32_t base_field, const JRowsWant& w, const Join
   A.n_joined = &J.S->nout;
   A.n_in_fields = w.in.nfields;
   for (uint32_t g = 0; g < w.in.nfields; g++) A.in_field[g] = w.in.fields[g];
-  if (M.fits32) jrows_launch_emit<int32_t>(ctx, A, M.nb); else jrows_launch_emit<int64_t>(ctx, A, M.nb);
+  by_width(M.fits32, [&](auto t) {
+    emit_dispatch(M.nb, [&](auto B, uint32_t wgs) {
+      hipLaunchKernelGGL((k_jrows_emit<decltype(t), decltype(B)::value>), dim3(wgs), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, M.nb, A);
+    });
+  });
   LAUNCHCHK("k_jrows_emit");
   return jrows_finish(ctx, J, d_res, 1u);
 }
@@ -128,14 +122,8 @@ static_assert(offsetof(bmx_jrows_res, next_pos) == offsetof(bmx_rows_res, next_p
 
 // ... for a host-mode answer: into the staging, columns of stride `scap`: ids, the outer cells (values, then clocks), inner ids, the inner cells
 int jrows_emit_staged(bmx_ctx* ctx, uint32_t base_field, const JRowsWant& w, const JoinArgs& J, uint64_t scap) {
-  RowsScratch& s = ctx->rows;
-  const uint64_t words = std::max<uint64_t>(scap * jrows_cols(w), 1);
-  if (words > s.stage_words || !s.stage_res) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    s.stage_words = 0;
-    if (int rc = dev_alloc_all(ctx, {{s.stage, words * 8}, {s.stage_res, sizeof(bmx_rows_res)}})) return rc;
-    s.stage_words = words;
-  }
+  if (int rc = rows_stage(ctx, scap * jrows_cols(w))) return rc;
+  const RowsScratch& s = ctx->rows;
   uint64_t* d_ids = reinterpret_cast<uint64_t*>(s.stage);
   int64_t* d_val = reinterpret_cast<int64_t*>(s.stage) + scap;
   int64_t* d_ts = d_val + (uint64_t)w.o.nfields * scap;
@@ -153,19 +141,10 @@ int jrows_collect(bmx_ctx* ctx, const JRowsWant& w, uint64_t scap, uint64_t at, 
   const uint64_t m = res->n_out, cap = w.cap;
   if (!m) return BMX_OK;
   if (m > scap || at + m > cap) return fail(ctx, BMX_ERR_INTERNAL, "bmx_where_join_rows: more rows than room");
-  const bool ts = (w.flags & BMX_ROWS_TS) != 0u;
   const unsigned long long* st = ctx->rows.stage;
-  const unsigned long long* sti = st + (1 + (uint64_t)rows_cols(w.o)) * scap;
-  HIPCHK(hipMemcpyAsync(w.out_ids + at, st, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-  for (uint32_t f = 0; f < w.o.nfields; f++) {
-    HIPCHK(hipMemcpyAsync(w.out_val + (uint64_t)f * cap + at, st + (1 + (uint64_t)f) * scap, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (ts) HIPCHK(hipMemcpyAsync(w.out_ts + (uint64_t)f * cap + at, st + (1 + (uint64_t)w.o.nfields + f) * scap, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIPCHK(hipMemcpyAsync(w.out_in_ids + at, sti, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-  for (uint32_t g = 0; with_inner && g < w.in.nfields; g++) {
-    HIPCHK(hipMemcpyAsync(w.out_in_val + (uint64_t)g * cap + at, sti + (1 + (uint64_t)g) * scap, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (ts) HIPCHK(hipMemcpyAsync(w.out_in_ts + (uint64_t)g * cap + at, sti + (1 + (uint64_t)w.in.nfields + g) * scap, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  if (int rc = rows_copy_cols(ctx, w.o, st, scap, m, cap, at, w.out_ids, w.out_val, w.out_ts)) return rc;
+  // the inner block: its id column always, its cells with_inner
+  if (int rc = rows_copy_cols(ctx, with_inner ? w.in : RowsWant{0, nullptr, 0}, st + (1 + (uint64_t)rows_cols(w.o)) * scap, scap, m, cap, at, w.out_in_ids, w.out_in_val, w.out_in_ts)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return BMX_OK;
 }
@@ -193,12 +172,7 @@ int comm_jrows_map(bmx_comm* c, uint32_t base_field, const WhereProg& W, const J
   const int rc = comm_two_phase(c,
     [&](uint32_t g, bmx_ctx* x) {
       if (int erc = enter(x)) return erc;
-      if (g < start_shard) {                // (its stamp counts even in front of the cursor)
-        Index* ix;
-        if (int frc = fresh_index(x, base_field, &ix)) return frc;
-        x->rows.masked.layout = ix->layout;
-        return (int)BMX_OK;
-      }
+      if (g < start_shard) return where_stamp_only(x, base_field, &x->rows.masked);
       if (int src = join_scratch(x, m, &J[g])) return src;
       if (int src = jrows_insert_staged(x, J[g], keys, ids, m)) return src;
       return jrows_mask(x, base_field, W, w, J[g], g == start_shard ? start_pos : 0);
@@ -214,10 +188,7 @@ int comm_jrows_map(bmx_comm* c, uint32_t base_field, const WhereProg& W, const J
       if (crc) return crc;
       if (g == start_shard) { tot->map_size = r.map_size; tot->n_inner = r.n_inner; tot->n_keyed = r.n_keyed; }
       tot->n_match += r.n_match; tot->n_joined += r.n_joined; delivered += r.n_out;
-      if (!cut) {
-        tot->next_shard = g; tot->next_pos = r.next_pos;
-        cut = r.n_match > r.n_out;
-      }
+      page_note(cut, *tot, g, r.next_pos, r.n_match > r.n_out);
       return (int)BMX_OK;
     });
   if (rc) return rc;
@@ -257,9 +228,7 @@ int bmx_where_join_rows(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, co
   if (const char* bad = where_prepare(in_base_field, in_nclauses, in_clause_len, in_lits, &WI)) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "inner program: ", bad));
   if (const char* bad = jrows_bad_args(w, map_cap, JOIN_BAD_MAP_CAP)) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "no key field"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   JoinArgs J;
   if (int rc = join_scratch(ctx, map_cap, &J)) return rc;
   if (int rc = jrows_build(ctx, J, in_base_field, WI, key_field)) return rc;
@@ -279,9 +248,7 @@ int bmx_where_map_rows(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, con
   if (const char* bad = jrows_bad_args(w, npairs, JOIN_BAD_NPAIRS)) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (!keys) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "null keys"));
   if (!node_ids) return fail(ctx, BMX_ERR_INVALID, join_text(FN, "", "null node_ids"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   JoinArgs J;
   if (int rc = join_scratch(ctx, npairs, &J)) return rc;
   if (mem == BMX_MEM_HOST) {
@@ -305,8 +272,7 @@ int bmx_comm_where_join_rows(bmx_comm* c, uint32_t base_field, uint32_t nclauses
   if (const char* bad = where_prepare(in_base_field, in_nclauses, in_clause_len, in_lits, &WI)) return fail(c, BMX_ERR_INVALID, join_text(FN, "inner program: ", bad));
   if (const char* bad = jrows_bad_args(w, map_cap, JOIN_BAD_MAP_CAP)) return fail(c, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "no key field"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
-  if (start_shard >= c->N) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "start_shard is no shard"));
+  if (int rc = where_comm_guard(c, FN, start_shard)) return rc;
   DevGuard guard;
   // phase 1: every shard's own map, exported; the union on the host. The outer index is brought up to date as well: an overflow still reports its size and stamp.
   std::vector<std::pair<int64_t, int64_t>> all;     // (key, jrows_word(id)): the signed order of the words is the unsigned order of the ids
@@ -375,8 +341,7 @@ int bmx_comm_where_map_rows(bmx_comm* c, uint32_t base_field, uint32_t nclauses,
   if (const char* bad = jrows_bad_args(w, npairs, JOIN_BAD_NPAIRS)) return fail(c, BMX_ERR_INVALID, join_text(FN, "", bad));
   if (!keys) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "null keys"));
   if (!node_ids) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "null node_ids"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
-  if (start_shard >= c->N) return fail(c, BMX_ERR_INVALID, join_text(FN, "", "start_shard is no shard"));
+  if (int rc = where_comm_guard(c, FN, start_shard)) return rc;
   DevGuard guard;
   bmx_jrows_res tot;
   if (int rc = comm_jrows_map(c, base_field, W, w, keys, node_ids, npairs, start_shard, start_pos, &tot)) return rc;

@@ -1,5 +1,5 @@
 // bmx_quant.inc — exact quantiles over boolean filters (bmx_quant.h): bmx_where_quantiles and its sharded form. The program is bmx_where.inc's (where_prepare),
-// the predicate and the sweep grid bmx_where_agg.inc's (where_pred, where_agg_grid), the kernels quant_kernels.h. The context keeps the scratch (QuantScratch):
+// and so are the width dispatch of pass 0 and the entry guards (where_sweep, where_enter, where_comm_guard), the kernels quant_kernels.h. The context keeps the scratch (QuantScratch):
 // the state record, which every query's last kernel leaves empty again (clean), the value scratch of a probed measure, and the staging of a host-mode answer.
 // One context enqueues the worst-case chain blind; the communicator steps the same sweeps and finds the bins on the host with the kernels' own helpers.
 // Included by bmx.hip (one translation unit), behind everything that was here before it.
@@ -43,9 +43,7 @@ int quant_scratch(bmx_ctx* ctx, uint64_t rows) {
 struct QuantSrc { bool fits32 = false /* the 4-byte base column; otherwise 8-byte values: the int64 column or the value scratch */; const void* col = nullptr; uint64_t n = 0; uint32_t nt = 0, blocks = 1; };
 
 template <class T>
-void quant_launch0(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const QuantArgs& A, bool probe) {
-  const PredWhere<T> P = where_pred<T>(ctx, ix, W);
-  const uint32_t blocks = where_agg_grid<T>(ctx, ix);
+void quant_launch0(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, uint32_t blocks, const QuantArgs& A, bool probe) {
   if (probe) hipLaunchKernelGGL((k_quant0<T, true>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
   else hipLaunchKernelGGL((k_quant0<T, false>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
 }
@@ -61,7 +59,7 @@ int quant_enqueue0(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32
   QuantArgs A{};
   A.mask = ctx->scan.mask; A.vals = ctx->quant.vals; A.S = ctx->quant.state; A.measure = measure_field;
   ctx->quant.clean = false;
-  if (ix->fits32) quant_launch0<int32_t>(ctx, ix, W, A, probe); else quant_launch0<int64_t>(ctx, ix, W, A, probe);
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { quant_launch0(ctx, ix, P, blocks, A, probe); });
   LAUNCHCHK("k_quant0");
   src->fits32 = !probe && ix->fits32; src->n = ix->n;
   src->col = probe ? static_cast<const void*>(ctx->quant.vals) : (ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64));
@@ -121,9 +119,7 @@ int bmx_where_quantiles(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, co
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (const char* bad = quant_bad_args(nq, qs, out)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   const QuantQs q = quant_copy_qs(nq, qs);      // read now: the caller may reuse qs as soon as the call returns
   if (mem == BMX_MEM_DEVICE) return quant_enqueue(ctx, base_field, W, measure_field, nq, q, out, res);
   if (int rc = quant_enqueue(ctx, base_field, W, measure_field, nq, q, nullptr, nullptr)) return rc;
@@ -143,7 +139,7 @@ int bmx_comm_where_quantiles(bmx_comm* c, uint32_t base_field, uint32_t nclauses
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (const char* bad = quant_bad_args(nq, qs, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   std::vector<QuantSrc> src(c->N);
   unsigned long long n_match = 0, n = 0, kmin = ~0ull, kmax = 0;

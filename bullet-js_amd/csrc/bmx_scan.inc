@@ -1,5 +1,6 @@
 // bmx_scan.inc — the scans over one index (bmx.h bmx_scan_*): how an answer leaves the device (ScanDelivery: plan_delivery, deliver, scan_collect), run_scan_t as
-// plan / scratch / launch / deliver, and the range scans with their clamping rules. The position scan and the declarative filter are bmx_scan_filter.inc, behind
+// plan / scratch / launch / deliver, the width and emit-geometry dispatch every two-pass form shares (by_width, emit_dispatch: the one reader of
+// BMX_SCAN_SUB8_BLOCKS), and the range scans with their clamping rules. The position scan and the declarative filter are bmx_scan_filter.inc, behind
 // bmx.hip's own entry points (bmx.hip, the include list). Kernels: scan_kernels.h; the ordered queries' launches are bmx_view.inc. Included by bmx.hip (one
 // translation unit), which keeps the scratch (ScanScratch) and the delivery plan's type.
 namespace {
@@ -114,6 +115,24 @@ int scan_collect(bmx_ctx* ctx, uint64_t* out_ids, uint64_t cap, uint64_t* n_out)
   return BMX_OK;
 }
 
+// f(T{}) with T the width of an index's value column
+template <class F>
+auto by_width(bool fits32, F&& f) {
+  if (fits32) return f(int32_t{});
+  return f(int64_t{});
+}
+
+// The geometry of an emit pass over `nb` blocks: f(std::integral_constant<int, B>, workgroups) with B = 8 blocks per workgroup on an eighth of the workgroups beyond
+// SCAN_SUB8_BLOCKS blocks (a large column: each sums the counts in front of it once, no offsets launch), B = 1 otherwise. BMX_SCAN_SUB8_BLOCKS is a measurement
+// and test switch and is read on every call: the tests set and clear it inside one process.
+template <class F>
+void emit_dispatch(uint32_t nb, F&& f) {
+  const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");
+  const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
+  if (nb > sub8_blocks) f(std::integral_constant<int, 8>{}, (nb + 7) / 8);
+  else f(std::integral_constant<int, 1>{}, nb);
+}
+
 // Run one predicate over an index and deliver ids (POS = false: u64 node ids gathered from the id column) or index positions (POS = true: u32,
 // no gather) / the count according to `mem`. `out` is uint64_t* or uint32_t* accordingly. Plan, scratch, launch, deliver.
 template <bool POS, class Pred>
@@ -140,8 +159,6 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     LAUNCHCHK("k_scan_mask");
     if (se) HIPCHK(hipEventRecord(se[1], ctx->stream));
     typename std::conditional<POS, EmitPos, EmitIds>::type Em;
-    const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");       // measurement / test switch: blocks beyond which the emit pass takes eight per workgroup
-    const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
     if constexpr (POS) Em = EmitPos{d_out, d_cap};
     else {
       const char* sm = std::getenv("BMX_SCAN_STREAM_MIN");      // measurement switch: matches per block from which the id column is streamed (0xFFFFFFFF: never)
@@ -150,10 +167,9 @@ int run_scan_t(bmx_ctx* ctx, const Pred& P, const Index* ix, void* out_v, uint64
     }
     using EmT = decltype(Em);
     FinishCount Fin{d_n};
-    if (nb > sub8_blocks)   // large column: an eighth of the workgroups, each sums the counts in front of it once (no offsets launch)
-      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
-    else
-      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
+    emit_dispatch(nb, [&](auto B, uint32_t wgs) {
+      hipLaunchKernelGGL((k_scan_emit<EmT, FinishCount, decltype(B)::value>), dim3(wgs), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, ix->n, nb, Em, Fin);
+    });
     LAUNCHCHK("k_scan_emit");
   } else if (d_n) {
     hipLaunchKernelGGL((k_scan_mask<Pred, false>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);

@@ -1,8 +1,9 @@
 // bmx_semi.inc — semi-joins (bmx_semi.h): bmx_where_semijoin, bmx_where_in and their sharded forms. The programs are bmx_where.inc's (where_prepare), the
-// predicate and the sweep grid bmx_where_agg.inc's (where_pred, where_agg_grid), the kernels semi_kernels.h, and the probe sweep's answer is delivered by
-// run_scan_t (bmx_scan.inc) like any scan's — always on its device route: into the caller's device buffer, or into the context's staging, from where the host
-// form and the sharded forms fetch it behind the call's last kernel. The context keeps the scratch (SemiScratch): the table and the state record, which every
-// query's last kernel leaves empty again (clean), and the staging. Included by bmx.hip (one translation unit), behind everything that was here before it.
+// width dispatch of both sweeps and the entry guards as well (where_sweep, where_enter, where_comm_guard), the kernels semi_kernels.h, and the probe sweep's
+// answer is delivered by run_scan_t (bmx_scan.inc) like any scan's — always on its device route: into the caller's device buffer, or into the context's
+// staging, from where the host form and the sharded forms fetch it behind the call's last kernel. The context keeps the scratch (SemiScratch): the table and
+// the state record, which every query's last kernel leaves empty again (clean), and the staging. Included by bmx.hip (one translation unit), behind everything
+// that was here before it.
 namespace {
 
 struct SemiWant { uint32_t link_field, flags; uint64_t* out_ids; uint64_t cap; bmx_semi_res* res; };
@@ -64,8 +65,9 @@ int semi_build(bmx_ctx* ctx, const SemiArgs& A, uint32_t in_base_field, const Wh
   Index* ix;
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t src = where_agg_source(key_field, in_base_field);
-  if (ix->fits32) hipLaunchKernelGGL((k_semi_build<int32_t>), dim3(where_agg_grid<int32_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int32_t>(ctx, ix, WI), A, key_field, src);
-  else hipLaunchKernelGGL((k_semi_build<int64_t>), dim3(where_agg_grid<int64_t>(ctx, ix)), dim3(AGG_THREADS), 0, ctx->stream, ix->n, where_pred<int64_t>(ctx, ix, WI), A, key_field, src);
+  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_semi_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, key_field, src);
+  });
   LAUNCHCHK("k_semi_build");
   return BMX_OK;
 }
@@ -78,9 +80,9 @@ int semi_insert_list(bmx_ctx* ctx, const SemiArgs& A, const long long* d_values,
 }
 
 template <class T>
-int semi_scan(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const SemiArgs& A, uint32_t base_field, const SemiWant& w, uint64_t* d_ids, uint64_t d_cap) {
+int semi_scan(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, const SemiArgs& A, uint32_t base_field, const SemiWant& w, uint64_t* d_ids, uint64_t d_cap) {
   PredSemi<T> Q;
-  Q.P = where_pred<T>(ctx, ix, W);
+  Q.P = P;
   Q.keys = A.keys; Q.slots = A.slots; Q.S = A.S; Q.cap = A.cap;
   Q.link = w.link_field; Q.link_src = where_agg_source(w.link_field, base_field); Q.anti = w.flags & BMX_SEMI_ANTI;
   return run_scan_t<false>(ctx, Q, ix, d_cap ? d_ids : nullptr, d_cap, reinterpret_cast<uint64_t*>(&A.S->n_match), BMX_MEM_DEVICE, /*deferred=*/false);
@@ -98,7 +100,7 @@ int semi_probe(bmx_ctx* ctx, const SemiArgs& A, uint32_t base_field, const Where
     if (d_cap) { if (int rc = semi_stage_ids(ctx, d_cap)) return rc; d_ids = s.stage_ids; }
     s.staged = d_cap;
   }
-  if (int rc = ix->fits32 ? semi_scan<int32_t>(ctx, ix, W, A, base_field, w, d_ids, d_cap) : semi_scan<int64_t>(ctx, ix, W, A, base_field, w, d_ids, d_cap)) return rc;
+  if (int rc = where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return semi_scan(ctx, ix, P, A, base_field, w, d_ids, d_cap); })) return rc;     // (the grid is run_scan_t's own)
   hipLaunchKernelGGL(k_semi_finish, dim3(semi_finish_grid(A.slots)), dim3(SEMI_THREADS), 0, ctx->stream, A, d_res ? d_res : s.stage_res);
   LAUNCHCHK("k_semi_finish");
   s.clean = true;
@@ -159,9 +161,7 @@ int bmx_where_semijoin(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, con
   if (const char* bad = where_prepare(in_base_field, in_nclauses, in_clause_len, in_lits, &WI)) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "inner program: ", bad));
   if (const char* bad = semi_bad_args(w, set_cap, SEMI_BAD_SET_CAP)) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "", "no key field"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   SemiArgs A;
   if (int rc = semi_scratch(ctx, set_cap, &A)) return rc;
   if (int rc = semi_build(ctx, A, in_base_field, WI, key_field)) return rc;
@@ -181,9 +181,7 @@ int bmx_where_in(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uin
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "outer program: ", bad));
   if (const char* bad = semi_bad_args(w, nvalues, SEMI_BAD_NVALUES)) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "", bad));
   if (!values) return fail(ctx, BMX_ERR_INVALID, semi_text(FN, "", "null values"));
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) {
     SemiArgs A;
     if (int rc = semi_scratch(ctx, nvalues, &A)) return rc;
@@ -207,7 +205,7 @@ int bmx_comm_where_semijoin(bmx_comm* c, uint32_t base_field, uint32_t nclauses,
   if (const char* bad = where_prepare(in_base_field, in_nclauses, in_clause_len, in_lits, &WI)) return fail(c, BMX_ERR_INVALID, semi_text(FN, "inner program: ", bad));
   if (const char* bad = semi_bad_args(w, set_cap, SEMI_BAD_SET_CAP)) return fail(c, BMX_ERR_INVALID, semi_text(FN, "", bad));
   if (key_field == BMX_AGG_NO_FIELD) return fail(c, BMX_ERR_INVALID, semi_text(FN, "", "no key field"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   // phase 1: every shard's own set, exported; the union on the host
   std::vector<int64_t> all;
@@ -266,7 +264,7 @@ int bmx_comm_where_in(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, semi_text(FN, "outer program: ", bad));
   if (const char* bad = semi_bad_args(w, nvalues, SEMI_BAD_NVALUES)) return fail(c, BMX_ERR_INVALID, semi_text(FN, "", bad));
   if (!values) return fail(c, BMX_ERR_INVALID, semi_text(FN, "", "null values"));
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   bmx_semi_res tot;
   if (int rc = comm_semi_in(c, base_field, W, w, values, nvalues, &tot)) return rc;

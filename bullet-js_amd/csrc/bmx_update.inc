@@ -1,6 +1,7 @@
-// bmx_update.inc — update and delete by query (bmx_update.h): bmx_where_update and its sharded form. The program is bmx_where.inc's (where_prepare), the predicate
-// bmx_where_agg.inc's (where_pred) behind a cursor and a look at the source (update_kernels.h PredUpd), the mask pass select.h's k_scan_mask into the scans' own
-// mask and counts (ScanScratch), the emit pass update_kernels.h's k_upd_emit into the context's staging slab of records (UpdScratch). The write itself is
+// bmx_update.inc — update and delete by query (bmx_update.h): bmx_where_update and its sharded form. The program, the mask pass (select.h's k_scan_mask over the
+// predicate behind a cursor and a look at the source, update_kernels.h PredUpd, into the scans' own mask and counts), the entry guards and the cursor steps of the
+// sharded form are bmx_where.inc's (where_prepare, where_mask_pass, where_enter, where_comm_guard, where_stamp_only, page_note); the emit pass is
+// update_kernels.h's k_upd_emit, in bmx_scan.inc's geometry (emit_dispatch), into the context's staging slab of records (UpdScratch). The write itself is
 // merge_core's, called as merge_records_internal calls it for the communicator: this file is one more caller of the merge and changes nothing in it. Included by
 // bmx.hip (one translation unit), behind everything that was here before it.
 namespace {
@@ -46,32 +47,12 @@ int upd_ensure(bmx_ctx* ctx, uint64_t scap) {
   return BMX_OK;
 }
 
-template <class T>
-void upd_launch_mask(bmx_ctx* ctx, Index* ix, const WhereProg& W, const UpdWant& w, uint64_t start, uint32_t nb) {
-  PredUpd<T> P{PredRowsFrom<T>{where_pred<T>(ctx, ix, W), start}, w.S, ctx->upd.ctr};
-  hipLaunchKernelGGL((k_scan_mask<PredUpd<T>, true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
-}
-
 // Pass 1 of one call on one context: the base index brought up to date, the mask of the WRITABLE positions from `start` on and the counts per block into the
 // scans' scratch, the nodes without source and outside the range into the counter shards. The context has been entered.
 int upd_mask(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const UpdWant& w, uint64_t start) {
-  Index* ix;
-  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  if (int rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), 0)) return rc;
-  if (int rc = upd_ensure(ctx, 0)) return rc;
-  const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
-  if (ix->fits32) upd_launch_mask<int32_t>(ctx, ix, W, w, start, nb); else upd_launch_mask<int64_t>(ctx, ix, W, w, start, nb);
-  LAUNCHCHK("k_scan_mask(update)");
-  ctx->upd.masked = RowsScratch::Masked{ix->ids, ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64), ix->n, ix->layout, ix->fits32, nb};
-  return BMX_OK;
-}
-
-template <class T>
-void upd_launch_emit(bmx_ctx* ctx, const UpdArgs& A, uint32_t nb) {
-  const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");       // the scans' measurement / test switch: blocks beyond which the emit pass takes eight per workgroup
-  const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
-  if (nb > sub8_blocks) hipLaunchKernelGGL((k_upd_emit<T, 8>), dim3((nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, nb, A);
-  else hipLaunchKernelGGL((k_upd_emit<T, 1>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, nb, A);
+  return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(update)", &ctx->upd.masked,
+    [&](const auto& P) { using T = decltype(where_value(P)); return PredUpd<T>{PredRowsFrom<T>{P, start}, w.S, ctx->upd.ctr}; },
+    [](bmx_ctx* x) { return upd_ensure(x, 0); });      // (the counter shards, in front of the launch that reads their address)
 }
 
 // Behind upd_mask: the emit pass into min(cap, index size) records, the one wait, the merge, the finish kernel. d_out_ids (may be null) and d_res are device
@@ -85,7 +66,11 @@ int upd_write(bmx_ctx* ctx, const UpdWant& w, uint64_t cap, uint64_t* d_out_ids,
   A.ids = M.ids; A.v = M.v; A.slots = ctx->slots; A.nslots = ctx->nslots;
   A.recs = s.recs; A.counts = s.counts; A.ctr = s.ctr;
   A.cap = scap; A.n = M.n; A.layout = M.layout; A.ts = w.ts; A.S = w.S; A.target = w.target;
-  if (M.fits32) upd_launch_emit<int32_t>(ctx, A, M.nb); else upd_launch_emit<int64_t>(ctx, A, M.nb);
+  by_width(M.fits32, [&](auto t) {
+    emit_dispatch(M.nb, [&](auto B, uint32_t wgs) {
+      hipLaunchKernelGGL((k_upd_emit<decltype(t), decltype(B)::value>), dim3(wgs), dim3(SEL_THREADS), 0, ctx->stream, ctx->scan.mask, ctx->scan.counts, M.nb, A);
+    });
+  });
   LAUNCHCHK("k_upd_emit");
   // the one wait: the merge's grid, its workspace and a growth of the table are sized on the host by the batch size
   HIPCHK(hipMemcpyAsync(hc, s.counts, sizeof(UpdCounts), hipMemcpyDeviceToHost, ctx->stream));
@@ -133,9 +118,7 @@ int bmx_where_update(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const
   std::string why;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (int rc = upd_prepare(base_field, target_field, op, src_field, operand, ts, flags, cap, res, &w, &why)) return fail(ctx, rc, why);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (int rc = upd_mask(ctx, base_field, W, w, start_pos)) return rc;
   if (mem == BMX_MEM_HOST) return upd_write_host(ctx, w, cap, 0, out_ids, res);
   UpdCounts hc;
@@ -150,8 +133,7 @@ int bmx_comm_where_update(bmx_comm* c, uint32_t base_field, uint32_t nclauses, c
   std::string why;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (int rc = upd_prepare(base_field, target_field, op, src_field, operand, ts, flags, cap, res, &w, &why)) return fail(c, rc, why);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
-  if (start_shard >= c->N) return fail(c, BMX_ERR_INVALID, "bmx_comm_where_update: start_shard is no shard");
+  if (int rc = where_comm_guard(c, "bmx_comm_where_update", start_shard)) return rc;
   DevGuard guard;
   bmx_upd_res tot{};
   bool cut = false;                      // some shard had a writable node that was not sent: tot.next_shard / next_pos name the first such node
@@ -160,11 +142,7 @@ int bmx_comm_where_update(bmx_comm* c, uint32_t base_field, uint32_t nclauses, c
   const int rc = comm_two_phase(c,
     [&](uint32_t g, bmx_ctx* x) {         // every shard's index up to date (its stamp counts even in front of the cursor); the mask pass from the cursor on
       if (int erc = enter(x)) return erc;
-      if (g >= start_shard) return upd_mask(x, base_field, W, w, g == start_shard ? start_pos : 0);
-      Index* ix;
-      if (int frc = fresh_index(x, base_field, &ix)) return frc;
-      x->upd.masked.layout = ix->layout;
-      return (int)BMX_OK;
+      return g < start_shard ? where_stamp_only(x, base_field, &x->upd.masked) : upd_mask(x, base_field, W, w, g == start_shard ? start_pos : 0);
     },
     [&](uint32_t g, bmx_ctx* x) {         // shard after shard: its own nodes with the room that is left (none: the shard is counted only)
       tot.layout += x->upd.masked.layout;
@@ -182,10 +160,7 @@ int bmx_comm_where_update(bmx_comm* c, uint32_t base_field, uint32_t nclauses, c
       if (crc) { failed = true; return crc; }
       tot.n_match += r.n_match; tot.n_nosrc += r.n_nosrc; tot.n_range += r.n_range; tot.n_rows += r.n_rows;
       sent += r.n_sent; applied += r.n_applied;
-      if (!cut) {
-        tot.next_shard = g; tot.next_pos = r.next_pos;
-        cut = r.n_match - r.n_nosrc - r.n_range > r.n_sent;
-      }
+      page_note(cut, tot, g, r.next_pos, r.n_match - r.n_nosrc - r.n_range > r.n_sent);
       return (int)BMX_OK;
     });
   if (rc) return rc;

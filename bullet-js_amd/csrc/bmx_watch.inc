@@ -1,5 +1,6 @@
 // bmx_watch.inc — standing queries (bmx_watch.h): bmx_watch_* over one context and bmx_comm_watch_* over the shards. Kernels: watch_kernels.h, and select.h's
-// k_scan_emit as the scans use it. The program is bmx_where.inc's (where_prepare, PredWhere). Included by bmx.hip (one translation unit), which keeps the state
+// k_scan_emit as the scans use it, in bmx_scan.inc's geometry (emit_dispatch). The program, the predicate in the width of the index's column and the mem-kind and
+// communicator checks are bmx_where.inc's (where_prepare, where_sweep, where_bad_mem, where_comm_guard). Included by bmx.hip (one translation unit), which keeps the state
 // (Watch, WatchState). A poll is two halves, watch_diff (enqueue the comparison) and watch_finish (emit the lists, commit, deliver): bmx_watch_poll runs them back
 // to back, bmx_comm_watch_poll reads every shard's counts (watch_counts) in between.
 namespace {
@@ -51,15 +52,6 @@ int watch_destroy(bmx_ctx* ctx, uint32_t id) {
   return BMX_OK;
 }
 
-template <class T>
-void watch_launch_mask(bmx_ctx* ctx, const Index* ix, const Watch& w, uint32_t nb) {
-  WatchState& S = ctx->watch;
-  PredWhere<T> P;
-  P.v = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
-  P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = w.W;
-  hipLaunchKernelGGL((k_watch_mask<PredWhere<T>>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, (const uint32_t*)w.prev, S.entered, S.counts, (uint32_t)S.blocks_cap);
-}
-
 // First half of a poll: the index is brought up to date as bmx_scan_where does it (a value-ordered view is neither read nor touched), the watch's bitmap is made
 // to fit the index's layout, and the comparison and its totals are enqueued. Leaves ctx->watch.pend for watch_counts / watch_finish; nothing else may run on the
 // context in between (the two scratch masks are the context's).
@@ -90,7 +82,10 @@ int watch_diff(bmx_ctx* ctx, uint32_t id) {
   const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
   if ((uint64_t)nb * (SCAN_BLOCK_ELEMS / 32) > w.prev_words) return fail(ctx, BMX_ERR_INTERNAL, "bmx_watch_poll: the index outgrew its columns without a new layout");
   if (int rc = S.ensure(ctx, nb)) return rc;
-  if (ix->fits32) watch_launch_mask<int32_t>(ctx, ix, w, nb); else watch_launch_mask<int64_t>(ctx, ix, w, nb);
+  where_sweep(ctx, ix, w.W, [&](const auto& P, uint32_t) {      // (one workgroup per block, as the scans' mask pass: the sweep grid is not used)
+    using T = decltype(where_value(P));
+    hipLaunchKernelGGL((k_watch_mask<PredWhere<T>>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, (const uint32_t*)w.prev, S.entered, S.counts, (uint32_t)S.blocks_cap);
+  });
   LAUNCHCHK("k_watch_mask");
   hipLaunchKernelGGL(k_watch_totals, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, (const uint32_t*)S.counts, (const uint32_t*)(S.counts + S.blocks_cap),
                      (const uint32_t*)(S.counts + 2 * S.blocks_cap), nb, (const unsigned long long*)(S.committed + id), (unsigned long long)ix->layout, S.tot);
@@ -110,14 +105,11 @@ int watch_counts(bmx_ctx* ctx, WatchTotals* out) {
 
 // one list out of its mask, in position order: select.h k_scan_emit exactly as run_scan_t launches it (BMX_SCAN_SUB8_BLOCKS included); the total is k_watch_totals'
 int watch_emit(bmx_ctx* ctx, const WatchState::Pending& P, const uint32_t* mask, const uint32_t* counts, uint64_t* d_out, uint64_t d_cap) {
-  const char* s8 = std::getenv("BMX_SCAN_SUB8_BLOCKS");
-  const uint32_t sub8_blocks = s8 ? (uint32_t)std::strtoul(s8, nullptr, 0) : SCAN_SUB8_BLOCKS;
   EmitIds Em{P.ids, d_out, d_cap, P.n * sizeof(uint64_t) > SCAN_NT_BYTES, SCAN_STREAM_MIN, SCAN_NTX_DEFAULT};
   FinishCount Fin{nullptr};
-  if (P.nb > sub8_blocks)
-    hipLaunchKernelGGL((k_scan_emit<EmitIds, FinishCount, 8>), dim3((P.nb + 7) / 8), dim3(SEL_THREADS), 0, ctx->stream, mask, counts, P.n, P.nb, Em, Fin);
-  else
-    hipLaunchKernelGGL((k_scan_emit<EmitIds, FinishCount, 1>), dim3(P.nb), dim3(SEL_THREADS), 0, ctx->stream, mask, counts, P.n, P.nb, Em, Fin);
+  emit_dispatch(P.nb, [&](auto B, uint32_t wgs) {
+    hipLaunchKernelGGL((k_scan_emit<EmitIds, FinishCount, decltype(B)::value>), dim3(wgs), dim3(SEL_THREADS), 0, ctx->stream, mask, counts, P.n, P.nb, Em, Fin);
+  });
   LAUNCHCHK("k_scan_emit(watch)");
   return BMX_OK;
 }
@@ -191,7 +183,7 @@ int bmx_watch_create(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const
 }
 
 int bmx_watch_poll(bmx_ctx* ctx, uint32_t watch, uint64_t* entered, uint64_t cap_entered, uint64_t* left, uint64_t cap_left, bmx_watch_res* res, int mem) {
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
+  if (int rc = where_bad_mem(ctx, mem)) return rc;
   if (const char* bad = watch_bad_poll_args(entered, cap_entered, left, cap_left, res)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
   if (int rc = watch_diff(ctx, watch)) return rc;
@@ -208,7 +200,7 @@ int bmx_comm_watch_create(bmx_comm* c, uint32_t base_field, uint32_t nclauses, c
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (!watch_out) return fail(c, BMX_ERR_INVALID, "bmx_watch_create: null watch_out");
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   uint32_t id0 = 0;
   for (uint32_t g = 0; g < c->N; g++) {
@@ -228,7 +220,7 @@ int bmx_comm_watch_create(bmx_comm* c, uint32_t base_field, uint32_t nclauses, c
 
 int bmx_comm_watch_poll(bmx_comm* c, uint32_t watch, uint64_t* entered, uint64_t cap_entered, uint64_t* left, uint64_t cap_left, bmx_watch_res* res) {
   if (const char* bad = watch_bad_poll_args(entered, cap_entered, left, cap_left, res)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   std::vector<WatchTotals> t(c->N);
   if (int rc = comm_two_phase(c, [&](uint32_t, bmx_ctx* x) { return watch_diff(x, watch); }, [&](uint32_t g, bmx_ctx* x) { return watch_counts(x, &t[g]); })) {
@@ -254,7 +246,7 @@ int bmx_comm_watch_poll(bmx_comm* c, uint32_t watch, uint64_t* entered, uint64_t
 }
 
 int bmx_comm_watch_destroy(bmx_comm* c, uint32_t watch) {
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   DevGuard guard;
   int first = BMX_OK; std::string msg;
   for (uint32_t g = 0; g < c->N; g++) {

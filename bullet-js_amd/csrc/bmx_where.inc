@@ -1,6 +1,9 @@
-// bmx_where.inc — boolean filters (bmx_where.h): bmx_scan_where over one context. The predicate is where_kernels.h PredWhere; run_scan_t (bmx_scan.inc) delivers
-// the answer as it delivers every scan's. Included by bmx.hip (one translation unit). bmx_comm_scan_where (bmx_comm.inc) prepares the program once and enqueues it on every shard through where_run's
-// deferred form and fetches with scan_collect, like bmx_comm_scan_filter.
+// bmx_where.inc — boolean filters (bmx_where.h): bmx_scan_where over one context, and the host steps every query form over a boolean filter shares: the program
+// (where_prepare), the predicate and the sweep grid in the width of the index's column (where_pred, where_agg_grid, where_sweep), the entry guards (where_enter,
+// where_comm_guard), the mask pass in front of an emit pass (where_mask_pass) and the cursor steps of the paged sharded forms (where_stamp_only, page_note). The
+// predicate is where_kernels.h PredWhere; run_scan_t (bmx_scan.inc) delivers bmx_scan_where's answer as it delivers every scan's. Included by bmx.hip (one
+// translation unit) in front of every other query form over a filter. bmx_comm_scan_where (bmx_comm.inc) prepares the program once and enqueues it on every
+// shard through where_run's deferred form and fetches with scan_collect, like bmx_comm_scan_filter.
 namespace {
 
 // The caller's program as the kernel takes it: the field table (fields other than the base field, in order of first use), per literal its slot, per clause its
@@ -49,20 +52,80 @@ const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t
 }
 
 template <class T>
-int where_scan(bmx_ctx* ctx, const Index* ix, const WhereProg& W, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred) {
+PredWhere<T> where_pred(bmx_ctx* ctx, const Index* ix, const WhereProg& W) {
   PredWhere<T> P;
   P.v = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
   P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = W;
-  return run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem, deferred);
+  return P;
+}
+template <class T>
+T where_value(const PredWhere<T>&);      // (never defined) decltype(where_value(P)): the width of a predicate
+// the grid of the sweeps: no workgroup with fewer than four rounds of loads to spread its one flush over
+template <class T>
+uint32_t where_agg_grid(bmx_ctx* ctx, const Index* ix) { return sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T))); }
+// where a sweep finds a field's value: the base field's column (0), a probe of its own, or nowhere
+inline uint32_t where_agg_source(uint32_t field, uint32_t base_field) { return field == BMX_AGG_NO_FIELD ? AGG_SRC_NONE : (field == base_field ? 0u : AGG_SRC_PROBE); }
+
+// One sweep of a prepared program over an index: f(predicate, grid) in the width of the index's column; f's result is handed on.
+template <class F>
+auto where_sweep(bmx_ctx* ctx, const Index* ix, const WhereProg& W, F&& f) {
+  return by_width(ix->fits32, [&](auto t) { using T = decltype(t); return f(where_pred<T>(ctx, ix, W), where_agg_grid<T>(ctx, ix)); });
 }
 
-// One prepared program over one context: bmx_scan_where, and the first half of bmx_comm_scan_where on every shard (deferred). A value-ordered view of the base
-// field's index is neither read nor touched: fresh_index keeps the dense columns current whether or not a view exists.
-int where_run(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred) {
-  if (int erc = enter(ctx)) return erc;
+// What every entry point over one context ends its own checks with, in this order: the mem kind, the context, the context entered.
+inline int where_bad_mem(bmx_ctx* ctx, int mem) { return mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE ? fail(ctx, BMX_ERR_INVALID, "bad mem kind") : (int)BMX_OK; }
+inline int where_enter(bmx_ctx* ctx, int mem) {
+  if (int rc = where_bad_mem(ctx, mem)) return rc;
+  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  return enter(ctx);
+}
+// ... and every sharded one: the communicator and, for a form with a cursor (fn: its name), the cursor's shard.
+inline int where_comm_guard(bmx_comm* c, const char* fn = nullptr, uint32_t start_shard = 0) {
+  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (fn && start_shard >= c->N) return fail(c, BMX_ERR_INVALID, std::string(fn) + ": start_shard is no shard");
+  return BMX_OK;
+}
+
+// Pass 1 of the forms that emit rows, on a context that has been entered: the base index brought up to date, the scans' scratch sized, then k_scan_mask over
+// make(where_pred<T>) — the program behind whatever the form adds to it — into the scans' own mask and counts. *out: what the emit pass needs of the index as
+// this pass saw it. what: "launch k_scan_mask(<form>)", for a launch error's text. `ready` (optional) runs between the scratch and the launch.
+template <class Make>
+int where_mask_pass(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const char* what, RowsScratch::Masked* out, Make&& make, int (*ready)(bmx_ctx*) = nullptr) {
   Index* ix;
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  return ix->fits32 ? where_scan<int32_t>(ctx, ix, W, out_ids, cap, n_out, mem, deferred) : where_scan<int64_t>(ctx, ix, W, out_ids, cap, n_out, mem, deferred);
+  if (int rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), 0)) return rc;
+  if (ready) if (int rc = ready(ctx)) return rc;
+  const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
+  by_width(ix->fits32, [&](auto t) {
+    auto P = make(where_pred<decltype(t)>(ctx, ix, W));
+    hipLaunchKernelGGL((k_scan_mask<decltype(P), true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
+  });
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail_hip(ctx, e, what);      // (LAUNCHCHK with a text that is no literal)
+  *out = RowsScratch::Masked{ix->ids, ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64), ix->n, ix->layout, ix->fits32, nb};
+  return BMX_OK;
+}
+
+// The paged sharded forms. A shard in front of the cursor only refreshes its index: its layout stamp counts in the answer's.
+int where_stamp_only(bmx_ctx* ctx, uint32_t base_field, RowsScratch::Masked* masked) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  masked->layout = ix->layout;
+  return BMX_OK;
+}
+// ... and behind every shard that delivered: the answer's cursor names the first node that was selected and not delivered (more: shard g has one, at next_pos)
+template <class Res>
+void page_note(bool& cut, Res& tot, uint32_t g, uint64_t next_pos, bool more) {
+  if (cut) return;
+  tot.next_shard = g; tot.next_pos = next_pos;
+  cut = more;
+}
+
+// One prepared program over one context that has been entered: bmx_scan_where, and the first half of bmx_comm_scan_where on every shard (deferred). A
+// value-ordered view of the base field's index is neither read nor touched: fresh_index keeps the dense columns current whether or not a view exists.
+int where_run(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  return where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem, deferred); });
 }
 
 }  // namespace
@@ -73,8 +136,7 @@ int bmx_scan_where(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const u
                    uint64_t* n_out, int mem) {
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
+  if (int erc = where_enter(ctx, mem)) return erc;
   return where_run(ctx, base_field, W, out_ids, cap, n_out, mem, /*deferred=*/false);
 }
 

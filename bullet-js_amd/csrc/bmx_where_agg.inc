@@ -1,7 +1,8 @@
 // bmx_where_agg.inc — aggregates and top-k over boolean filters (bmx_where_agg.h): bmx_where_aggregate, bmx_where_top and their sharded forms. The program is
-// bmx_where.inc's (where_prepare, PredWhere), the two sweeps are where_agg_kernels.h, and everything behind them is bmx_agg.inc's and bmx_top.inc's: the
-// scratch with its `clean` protocol, k_agg_finish, the select's chain (top_launch_with), the collect halves, and bmx_comm.inc's combine steps. Included by
-// bmx.hip (one translation unit), behind everything that was here before it.
+// bmx_where.inc's, and so are the predicate, the sweep grid, the width dispatch and the entry guards (where_prepare, where_sweep, where_enter, where_comm_guard);
+// the two sweeps are where_agg_kernels.h, and everything behind them is bmx_agg.inc's and bmx_top.inc's: the scratch with its `clean` protocol, k_agg_finish, the
+// select's chain (top_launch_with), the collect halves, and bmx_comm.inc's combine steps. Included by bmx.hip (one translation unit), behind everything that was
+// here before it.
 namespace {
 
 // agg_bad_args / top_bad_args without their term checks: the program stands where the terms stood and where_prepare has judged it
@@ -9,28 +10,13 @@ const bmx_term WHERE_AGG_NO_TERMS[1] = {};
 const char* where_agg_bad_args(uint32_t group_field, uint32_t ngroups, const bmx_agg* out) { return agg_bad_args(1, WHERE_AGG_NO_TERMS, group_field, ngroups, out); }
 const char* where_top_bad_args(uint32_t flags, uint32_t k, const bmx_top_rec* out) { return top_bad_args(1, WHERE_AGG_NO_TERMS, flags, k, out); }
 
+// the sweep of one aggregate: flat, grouped in LDS, or grouped in device memory
 template <class T>
-PredWhere<T> where_pred(bmx_ctx* ctx, const Index* ix, const WhereProg& W) {
-  PredWhere<T> P;
-  P.v = sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64);
-  P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = W;
-  return P;
-}
-// the grid of the other sweeps: no workgroup with fewer than four rounds of loads to spread its one flush over
-template <class T>
-uint32_t where_agg_grid(bmx_ctx* ctx, const Index* ix) { return sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T))); }
-
-template <class T>
-void where_agg_launch(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const AggArgs& A) {
-  const PredWhere<T> P = where_pred<T>(ctx, ix, W);
-  const uint32_t blocks = where_agg_grid<T>(ctx, ix);
+void where_agg_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, uint32_t blocks, const AggArgs& A) {
   if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
   else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
   else hipLaunchKernelGGL((k_where_agg<T, 2>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
 }
-
-// where the sweep finds a field's value: the base field's column (0), a probe of its own, or nowhere
-inline uint32_t where_agg_source(uint32_t field, uint32_t base_field) { return field == BMX_AGG_NO_FIELD ? AGG_SRC_NONE : (field == base_field ? 0u : AGG_SRC_PROBE); }
 
 // Enqueue one aggregate over a prepared program; the records go to d_out (device memory), or, with d_out == nullptr, to the context's staging buffer
 // (agg_collect fetches them). The arguments have been checked and the context entered. A value-ordered view of the base field's index is neither read nor
@@ -46,7 +32,7 @@ int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   A.m_src = where_agg_source(measure_field, base_field); A.g_src = ngroups ? where_agg_source(group_field, base_field) : AGG_SRC_NONE;
   A.nterms = 0;
   ctx->agg.clean = false;
-  if (ix->fits32) where_agg_launch<int32_t>(ctx, ix, W, A); else where_agg_launch<int64_t>(ctx, ix, W, A);
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_agg_launch(ctx, ix, P, blocks, A); });
   LAUNCHCHK("k_where_agg");
   hipLaunchKernelGGL(k_agg_finish, dim3(std::min<uint32_t>((nrec + 255) / 256, 64)), dim3(256), 0, ctx->stream, ctx->agg.raw, d_out ? d_out : ctx->agg.stage, nrec,
                      A.m_src != AGG_SRC_PROBE ? 1u : 0u);
@@ -56,8 +42,7 @@ int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
 }
 
 template <class T>
-int where_top_launch(bmx_ctx* ctx, const Index* ix, const WhereProg& W, const TopArgs& A, uint32_t k) {
-  const PredWhere<T> P = where_pred<T>(ctx, ix, W);
+int where_top_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, const TopArgs& A, uint32_t k) {
   return top_launch_with<T, true>(ctx, ix, A, k, [&](const T*, uint32_t blocks, uint32_t) {
     hipLaunchKernelGGL((k_where_top0<T>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
   });
@@ -75,7 +60,7 @@ int where_top_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   A.desc = flags & BMX_TOP_DESC;
   top_set_cursor(A, after);
   ctx->top.clean = false;
-  if (int rc = ix->fits32 ? where_top_launch<int32_t>(ctx, ix, W, A, k) : where_top_launch<int64_t>(ctx, ix, W, A, k)) return rc;
+  if (int rc = where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return where_top_launch(ctx, ix, P, A, k); })) return rc;     // (the grid is top_launch_with's own)
   return top_launch_finish(ctx, A, k, d_out, d_n_out, d_n_eligible);
 }
 
@@ -88,9 +73,7 @@ int bmx_where_aggregate(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, co
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (const char* bad = where_agg_bad_args(group_field, ngroups, out)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (int rc = where_agg_enqueue(ctx, base_field, W, measure_field, group_field, group_lo, ngroups, mem == BMX_MEM_DEVICE ? out : nullptr)) return rc;
   return mem == BMX_MEM_HOST ? agg_collect(ctx, agg_records(ngroups), out) : BMX_OK;
 }
@@ -100,9 +83,7 @@ int bmx_where_top(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const ui
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
   if (const char* bad = where_top_bad_args(flags, k, out)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (mem != BMX_MEM_HOST && mem != BMX_MEM_DEVICE) return fail(ctx, BMX_ERR_INVALID, "bad mem kind");
-  if (!ctx) return fail(nullptr, BMX_ERR_INVALID, "null context");
-  if (int erc = enter(ctx)) return erc;
+  if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) return where_top_enqueue(ctx, base_field, W, flags, after, k, out, n_out, n_eligible);
   if (int rc = where_top_enqueue(ctx, base_field, W, flags, after, k, nullptr, nullptr, nullptr)) return rc;
   return top_collect_to(ctx, k, out, n_out, n_eligible);
@@ -113,7 +94,7 @@ int bmx_comm_where_aggregate(bmx_comm* c, uint32_t base_field, uint32_t nclauses
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (const char* bad = where_agg_bad_args(group_field, ngroups, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   return comm_agg_with(c, ngroups, out, [&](bmx_ctx* x) { return where_agg_enqueue(x, base_field, W, measure_field, group_field, group_lo, ngroups, nullptr); });
 }
 
@@ -122,7 +103,7 @@ int bmx_comm_where_top(bmx_comm* c, uint32_t base_field, uint32_t nclauses, cons
   WhereProg W;
   if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
   if (const char* bad = where_top_bad_args(flags, k, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (!c) return fail(c, BMX_ERR_INVALID, "null communicator");
+  if (int rc = where_comm_guard(c)) return rc;
   return comm_top_with(c, flags, k, out, n_out, n_eligible, [&](bmx_ctx* x) { return where_top_enqueue(x, base_field, W, flags, after, k, nullptr, nullptr, nullptr); });
 }
 

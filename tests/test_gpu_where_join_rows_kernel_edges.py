@@ -134,6 +134,53 @@ def test_caps_and_cursors_at_the_block_edges(wide):
                     jrm.ask(e, m, dict(qi, start=start, cap=cap), order)
 
 
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("blocks", [9, 17])
+def test_eight_blocks_per_workgroup(monkeypatch, blocks, wide):
+    """BMX_SCAN_SUB8_BLOCKS=1: the emit pass takes eight blocks per workgroup (k_jrows_emit<T, 8>); 9 and 17 blocks leave a last workgroup with one block. Sparse
+    selections take its one-scan path (at most 8192 matches in eight blocks), dense ones go block by block. Every third selected row has no inner node, so the
+    inner join's rank is not the left join's. Every answer equals the model's and, byte for byte, the one-block form's."""
+    n = (blocks - 1) * BLOCK + 5
+    base = (2**40 if wide else 0) + 7
+    sparse = np.unique(np.concatenate([np.arange(0, n, 509), np.arange(BLOCK - 1, n, BLOCK), np.arange(BLOCK, n, BLOCK), [n - 1]]))
+    pats = {"sparse": sparse, "dense": np.setdiff1d(np.arange(n), sparse), "exactly 8192 in the first eight blocks": np.arange(0, 8 * BLOCK, 8),
+            "8193 there": np.sort(np.concatenate([np.arange(0, 8 * BLOCK, 8), [3]]))}
+    fp = [streams.fnv1a32("jrows.edge.sub8.%d" % k) for k in range(len(pats))]
+    with bmx.Engine(8 * n) as e:
+        m = _by_position(e, n, base, 1000000 + blocks)
+        p = np.arange(n)
+        m.set(FL, p, 1000 + p, 7)
+        m.set(FO[0], p[p % 4 != 0], p[p % 4 != 0] * 2 - 9, 10 + p[p % 4 != 0] % 7)
+        m.set(FN[0], p[p % 4 != 1], p[p % 4 != 1] * 3 - 9, 11 + p[p % 4 != 1] % 7)
+        for f, rows in zip(fp, pats.values()):
+            m.set(f, rows, 1)
+        wam.load(e, m, [FL, FO[0], FN[0]] + fp)
+        jrm.apply_tombs(m, {FO[0]: p[p % 9 == 2], FN[0]: p[p % 6 == 1]}, e)
+        order = e.index_ids(FB)
+        assert np.array_equal(order, m.ids), "no position moved"
+        for (name, rows), f in zip(pats.items(), fp):
+            keyed = rows[np.arange(len(rows)) % 3 != 1]                 # every third selected row: its link is no key
+            q = QMAP(FB, [[(f, 1, 1)]], FL, [FO[0]], (1000 + keyed).tolist(), m.ids[(keyed * 7 + 1) % n].tolist(), [FN[0]], with_ts=True, cap=n)
+            M = jrm.map_of(m, q)
+            for inner_join in (False, True):
+                nm = len(keyed) if inner_join else len(rows)
+                for start, cap in ((0, n), (0, 0), (0, 1), (0, nm - 1), (0, nm), (0, BLOCK), (0, 8 * BLOCK - 1), (0, 8 * BLOCK + 1), (1, nm), (8 * BLOCK - 1, 3),
+                                   (8 * BLOCK + 1, n), (BLOCK, BLOCK), (nm - 1, n), (n - 1, 2)):
+                    qi = dict(q, inner=inner_join, start=start, cap=cap)
+                    tag = (blocks, name, inner_join, start, cap)
+                    want = jrm.answer(m, order, qi, M)
+                    assert start or int(want["res"]["n_match"]) == nm, tag
+                    monkeypatch.setenv("BMX_SCAN_SUB8_BLOCKS", "1")
+                    got8 = jrm.raw(e, qi)
+                    monkeypatch.delenv("BMX_SCAN_SUB8_BLOCKS")
+                    got1 = jrm.raw(e, qi)
+                    for got, form in ((got8, "eight blocks per workgroup"), (got1, "one block per workgroup")):
+                        assert jrm.check(got, want, qi) is None, (jrm.check(got, want, qi), tag, form)
+                    assert got8["res"].tobytes() == got1["res"].tobytes(), tag
+                    for k in ("ids", "vals", "ts", "in_ids", "in_vals", "in_ts"):
+                        assert got8[k].tobytes() == got1[k].tobytes(), (k, tag)
+
+
 def test_small_maps_whose_walks_wrap():
     """64-slot maps: 32 keys on one home, a cluster that wraps from slot 63 to 0, links that walk a whole cluster and miss; 70 keys into 64 slots give up"""
     same = jrm.keys_with_home(5, 64, 33)                               # 32 in the map, one more with the same home that is not
