@@ -85,7 +85,10 @@ EXPORTS_CLAIM = ["bmx_selfcheck_claim", "bmx_get_claim_mode"]
 EXPORTS_UPDATE = ["bmx_where_update", "bmx_comm_where_update"]
 # group-by over several fields (include/bmx_group_multi.h), likewise
 EXPORTS_GROUP_MULTI = ["bmx_where_group_multi", "bmx_comm_where_group_multi"]
-MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14   # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
+# graph traversal (include/bmx_reach.h), likewise
+EXPORTS_REACH = ["bmx_where_reach", "bmx_where_reach_from", "bmx_comm_where_reach", "bmx_comm_where_reach_from"]
+REACH_OVERFLOW, REACH_MORE, REACH_MAX_SET, REACH_MAX_DEPTH = 1, 2, 1 << 20, 255   # BMX_REACH_OVERFLOW, BMX_REACH_MORE (flags of bmx_reach_res), BMX_REACH_MAX_SET, BMX_REACH_MAX_DEPTH (bmx_reach.h bmx_where_reach)
+MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14  # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
 UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
 
@@ -398,6 +401,35 @@ def _semi_values(values):
     return v, len(v)
 
 
+class ReachRes(C.Structure):
+    """bmx_reach_res: what one bmx_where_reach / bmx_where_reach_from found besides its ids and depths (40 bytes); flags: REACH_OVERFLOW | REACH_MORE"""
+    _fields_ = [("n_match", C.c_uint64), ("set_size", C.c_uint64), ("n_seed", C.c_uint64), ("n_edges", C.c_uint64), ("rounds", C.c_uint32), ("flags", C.c_uint32)]
+
+
+REACH_RES_DTYPE = np.dtype([("n_match", "<u8"), ("set_size", "<u8"), ("n_seed", "<u8"), ("n_edges", "<u8"), ("rounds", "<u4"), ("flags", "<u4")])
+
+
+class ReachResult:
+    """One where_reach / where_reach_from answer: ids (uint64) and depth (uint8, 1..max_depth), min(n_match, cap) of each, in index order of the base field (none
+    on overflow or with count_only); n_match (the nodes reached, however small cap was; 0 on overflow), set_size (distinct values at the end, seeds included,
+    or on overflow a lower bound above set_cap), n_seed, n_edges, rounds (the largest depth in the answer), overflow, and more (some value has level max_depth:
+    a frontier is left unexplored)."""
+    __slots__ = ("ids", "depth", "n_match", "set_size", "n_seed", "n_edges", "rounds", "flags", "overflow", "more")
+
+    def __init__(self, res, ids, depth, cap):
+        r = np.frombuffer(bytes(res), REACH_RES_DTYPE)[0] if isinstance(res, ReachRes) else res
+        self.n_match, self.set_size, self.n_seed, self.n_edges = int(r["n_match"]), int(r["set_size"]), int(r["n_seed"]), int(r["n_edges"])
+        self.rounds, self.flags = int(r["rounds"]), int(r["flags"])
+        self.overflow, self.more = bool(self.flags & REACH_OVERFLOW), bool(self.flags & REACH_MORE)
+        k = min(self.n_match, int(cap))
+        self.ids = np.zeros(0, np.uint64) if ids is None else ids[:k].copy()
+        self.depth = np.zeros(0, np.uint8) if depth is None else depth[:k].copy()
+
+    def __repr__(self):
+        return "ReachResult(%d of %d nodes, %d rounds, set of %d from %d seeds over %d edges%s%s)" % (
+            len(self.ids), self.n_match, self.rounds, self.set_size, self.n_seed, self.n_edges, ", overflow" if self.overflow else "", ", more" if self.more else "")
+
+
 class JoinRes(C.Structure):
     """bmx_join_res: what one bmx_where_join_group / bmx_where_map_group found besides its records (184 bytes); flags: JOIN_MAP_OVERFLOW | JOIN_GROUP_OVERFLOW"""
     _fields_ = [("n_groups", C.c_uint64), ("map_size", C.c_uint64), ("n_inner", C.c_uint64), ("n_keyed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
@@ -657,6 +689,11 @@ def load_library():
     L.bmx_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp, i32]; L.bmx_where_in.restype = i32
     L.bmx_comm_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp]; L.bmx_comm_where_semijoin.restype = i32
     L.bmx_comm_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp]; L.bmx_comm_where_in.restype = i32
+    reach_out = [u32, u64, vp, vp, u64, vp]                                  # max_depth, set_cap, out_ids, out_depth, cap, res
+    L.bmx_where_reach.argtypes = [vp] + prog + [u32, u32, u32] + prog + [u32] + reach_out + [i32]; L.bmx_where_reach.restype = i32
+    L.bmx_where_reach_from.argtypes = [vp] + prog + [u32, u32, u32, vp, u64] + reach_out + [i32]; L.bmx_where_reach_from.restype = i32
+    L.bmx_comm_where_reach.argtypes = [vp] + prog + [u32, u32, u32] + prog + [u32] + reach_out; L.bmx_comm_where_reach.restype = i32
+    L.bmx_comm_where_reach_from.argtypes = [vp] + prog + [u32, u32, u32, vp, u64] + reach_out; L.bmx_comm_where_reach_from.restype = i32
     L.bmx_where_join_group.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u32, u64, vp, u64, vp, i32]; L.bmx_where_join_group.restype = i32
     L.bmx_where_map_group.argtypes = [vp] + prog + [u32, u32, vp, vp, u64, vp, u64, vp, i32]; L.bmx_where_map_group.restype = i32
     L.bmx_comm_where_join_group.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u32, u64, vp, u64, vp]; L.bmx_comm_where_join_group.restype = i32
@@ -1183,6 +1220,30 @@ class Engine:
                                       C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return SemiResult(res, ids, cap)
 
+    def where_reach(self, base, clauses, link, key, seed_base, seed_clauses, seed_field, max_depth=REACH_MAX_DEPTH, set_cap=65536, cap=None, count_only=False):
+        """Graph traversal (bmx_reach.h): the nodes of scan_where(base, clauses) reachable, over the edges link -> key of those nodes, from the values field
+        `seed_field` holds on the nodes of scan_where(seed_base, seed_clauses), with their breadth-first depth; swapping link and key walks toward the
+        ancestors. The closure runs on the device. cap None: room for the whole index of `base`; count_only: nothing is fetched. -> ReachResult (with overflow
+        set, n_match 0 and no ids when seeds and contributed values are more than set_cap)"""
+        cap = 0 if count_only else (self.index_size(base) if cap is None else int(cap))
+        ids = None if count_only else np.zeros(max(cap, 1), np.uint64)
+        depth = None if count_only else np.zeros(max(cap, 1), np.uint8)
+        res = ReachRes()
+        self._chk(self.L.bmx_where_reach(self.h, *_where_args(base, clauses), int(link), int(key), 0, *_where_args(seed_base, seed_clauses), int(seed_field),
+                                         int(max_depth), int(set_cap), _ptr(ids), _ptr(depth), cap, C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return ReachResult(res, ids, depth, cap)
+
+    def where_reach_from(self, base, clauses, link, key, values, max_depth=REACH_MAX_DEPTH, set_cap=65536, cap=None, count_only=False):
+        """where_reach with the seeds given as a list of 1..REACH_MAX_SET int64 values (duplicates allowed; a value outside +-(2^53 - 1) is skipped)"""
+        cap = 0 if count_only else (self.index_size(base) if cap is None else int(cap))
+        ids = None if count_only else np.zeros(max(cap, 1), np.uint64)
+        depth = None if count_only else np.zeros(max(cap, 1), np.uint8)
+        v, n = _semi_values(values)
+        res = ReachRes()
+        self._chk(self.L.bmx_where_reach_from(self.h, *_where_args(base, clauses), int(link), int(key), 0, _ptr(v), n, int(max_depth), int(set_cap), _ptr(ids),
+                                              _ptr(depth), cap, C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return ReachResult(res, ids, depth, cap)
+
     def where_join_group(self, base, clauses, link, inner_base, inner_clauses, key, attr, measure=None, cap=65536, map_cap=65536):
         """Lookup join (bmx_join.h): the selection of scan_where(base, clauses) grouped by the value field `attr` holds on the node of
         scan_where(inner_base, inner_clauses) whose field `key` equals the selected node's field `link` (the minimum of `attr` where several inner nodes share a
@@ -1444,6 +1505,18 @@ class Engine:
         """where_in into device memory; `values` is a device array of nvalues int64. Enqueue-only."""
         self._chk(self.L.bmx_where_in(self.h, *_where_args(base, clauses), int(link), SEMI_ANTI if anti else 0, _ptr(values), int(nvalues), _ptr(out_ids), int(cap),
                                       _ptr(res), MEM_DEVICE))
+
+    def where_reach_dev(self, base, clauses, link, key, seed_base, seed_clauses, seed_field, out_ids, out_depth, cap, res, max_depth=REACH_MAX_DEPTH, set_cap=65536):
+        """where_reach into device memory (out_ids: room for cap ids, out_depth: for cap bytes, or both None with cap 0; res: 40 bytes, a bmx_reach_res);
+        enqueue-only, all max_depth rounds included. After sync(), ReachResult(res.cpu().numpy().view(REACH_RES_DTYPE)[0], out_ids.cpu().numpy(),
+        out_depth.cpu().numpy(), cap) is what where_reach returns."""
+        self._chk(self.L.bmx_where_reach(self.h, *_where_args(base, clauses), int(link), int(key), 0, *_where_args(seed_base, seed_clauses), int(seed_field),
+                                         int(max_depth), int(set_cap), _ptr(out_ids), _ptr(out_depth), int(cap), _ptr(res), MEM_DEVICE))
+
+    def where_reach_from_dev(self, base, clauses, link, key, values, nvalues, out_ids, out_depth, cap, res, max_depth=REACH_MAX_DEPTH, set_cap=65536):
+        """where_reach_from into device memory; `values` is a device array of nvalues int64. Enqueue-only."""
+        self._chk(self.L.bmx_where_reach_from(self.h, *_where_args(base, clauses), int(link), int(key), 0, _ptr(values), int(nvalues), int(max_depth), int(set_cap),
+                                              _ptr(out_ids), _ptr(out_depth), int(cap), _ptr(res), MEM_DEVICE))
 
     def where_join_group_dev(self, base, clauses, link, inner_base, inner_clauses, key, attr, out, res, measure=None, cap=65536, map_cap=65536):
         """where_join_group into device memory (`out`: room for cap records of 56 bytes; res: 184 bytes, a bmx_join_res); enqueue-only. The records come in no
@@ -1778,6 +1851,28 @@ class Comm:
         ids = np.zeros(max(int(cap), 1), np.uint64)
         self._chk(fn(self.h, *args, _ptr(ids), int(cap), C.cast(C.byref(res), C.c_void_p)))
         return SemiResult(res, ids, cap)
+
+    def where_reach(self, base, clauses, link, key, seed_base, seed_clauses, seed_field, max_depth=REACH_MAX_DEPTH, set_cap=65536, cap=None, count_only=False):
+        """Engine.where_reach over all shards: the library steps the rounds and unites every level's values across the shards, so ids and depths are what
+        one engine holding the same rows gives, in shard order. cap None: it counts first (cap 0) and then fetches with room for exactly that."""
+        args = (*_where_args(base, clauses), int(link), int(key), 0, *_where_args(seed_base, seed_clauses), int(seed_field), int(max_depth), int(set_cap))
+        return self._reach(self.L.bmx_comm_where_reach, args, cap, count_only)
+
+    def where_reach_from(self, base, clauses, link, key, values, max_depth=REACH_MAX_DEPTH, set_cap=65536, cap=None, count_only=False):
+        """Engine.where_reach_from over all shards"""
+        v, n = _semi_values(values)
+        return self._reach(self.L.bmx_comm_where_reach_from, (*_where_args(base, clauses), int(link), int(key), 0, _ptr(v), n, int(max_depth), int(set_cap)), cap, count_only)
+
+    def _reach(self, fn, args, cap, count_only):
+        res = ReachRes()
+        if cap is None or count_only:
+            self._chk(fn(self.h, *args, None, None, 0, C.cast(C.byref(res), C.c_void_p)))
+            if count_only or res.flags & REACH_OVERFLOW:
+                return ReachResult(res, None, None, 0)
+            cap = int(res.n_match)
+        ids, depth = np.zeros(max(int(cap), 1), np.uint64), np.zeros(max(int(cap), 1), np.uint8)
+        self._chk(fn(self.h, *args, _ptr(ids), _ptr(depth), int(cap), C.cast(C.byref(res), C.c_void_p)))
+        return ReachResult(res, ids, depth, cap)
 
     def where_join_group(self, base, clauses, link, inner_base, inner_clauses, key, attr, measure=None, cap=65536, map_cap=65536):
         """Engine.where_join_group over all shards (every shard builds its own map, the library unites them by key with the minimum of the attributes and sends

@@ -43,6 +43,7 @@
 #include "join_rows_kernels.h"
 #include "update_kernels.h"
 #include "mgroup_kernels.h"
+#include "reach_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -389,6 +390,20 @@ struct UpdScratch {
   void release() { dev_free(recs); dev_free(applied); dev_free(ids); dev_free(counts); dev_free(ctr); dev_free(n_applied); dev_free(stats); dev_free(stage_res); cap = 0; }
 };
 
+// Scratch of the graph traversal (bmx_reach.inc): one link word and one depth byte per position of the base field's index (allocated by the first traversal and
+// grown with the largest index seen, like QuantScratch::vals), the state record, which every call's last kernel leaves zero again (clean), and the ids, depths
+// and result record of a BMX_MEM_HOST answer on their way down (`staged`: how many entries the last staged call had room for). The map is JoinScratch's.
+// Nothing here survives a call, so an index laid out anew needs no care.
+struct ReachScratch {
+  long long* link = nullptr; uint8_t* depth = nullptr; uint64_t pos_cap = 0;
+  ReachState* state = nullptr; bool clean = false;
+  uint64_t* stage_ids = nullptr; uint8_t* stage_depth = nullptr; uint64_t stage_cap = 0, staged = 0; bmx_reach_res* stage_res = nullptr;
+  void release() {
+    dev_free(link); dev_free(depth); dev_free(state); dev_free(stage_ids); dev_free(stage_depth); dev_free(stage_res);
+    pos_cap = 0; stage_cap = 0; staged = 0; clean = false;
+  }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -456,6 +471,7 @@ struct bmx_ctx {
   JoinScratch join;
   UpdScratch upd;
   MGroupScratch mgroup;
+  ReachScratch reach;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -782,6 +798,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->join.release();
   ctx->upd.release();
   ctx->mgroup.release();
+  ctx->reach.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1083,3 +1100,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_join_rows.inc" // (likewise; it uses bmx_join.inc's map scratch, bmx_rows.inc's mask pass, staging and column copy and bmx_where.inc's mask pass)
 #include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself; its mask pass is bmx_where.inc's)
 #include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid, fold and grouped-answer steps, and a scratch of its own)
+#include "bmx_reach.inc"     // (likewise; it uses bmx_join.inc's map scratch, bmx_semi.inc's grids and slot count and bmx_where.inc's mask pass)
