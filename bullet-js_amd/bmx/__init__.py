@@ -88,6 +88,9 @@ EXPORTS_GROUP_MULTI = ["bmx_where_group_multi", "bmx_comm_where_group_multi"]
 # graph traversal (include/bmx_reach.h), likewise
 EXPORTS_REACH = ["bmx_where_reach", "bmx_where_reach_from", "bmx_comm_where_reach", "bmx_comm_where_reach_from"]
 REACH_OVERFLOW, REACH_MORE, REACH_MAX_SET, REACH_MAX_DEPTH = 1, 2, 1 << 20, 255   # BMX_REACH_OVERFLOW, BMX_REACH_MORE (flags of bmx_reach_res), BMX_REACH_MAX_SET, BMX_REACH_MAX_DEPTH (bmx_reach.h bmx_where_reach)
+# the first node per group (include/bmx_first.h), likewise
+EXPORTS_FIRST = ["bmx_where_group_first", "bmx_comm_where_group_first"]
+FIRST_DESC, FIRST_OVERFLOW, FIRST_NO_NODE, FIRST_MAX_CAP = 2, 1, (1 << 64) - 1, 1 << 20   # BMX_FIRST_DESC (flags of the call, next to ROWS_TS), BMX_FIRST_OVERFLOW (flags of bmx_first_res), BMX_FIRST_NO_NODE, BMX_FIRST_MAX_CAP (bmx_first.h bmx_where_group_first)
 MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14  # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
 UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
@@ -335,6 +338,88 @@ def _rows_fields(fields, with_ts):
 
 def _rows_buffers(nfields, cap, with_ts):
     return np.zeros(max(cap, 1), np.uint64), np.zeros((nfields, max(cap, 1)), np.int64), np.zeros((nfields, max(cap, 1)), np.int64) if with_ts else None
+
+
+class FirstRec(C.Structure):
+    """bmx_first_rec: one record of bmx_where_group_first (40 bytes): the group value, its first node and that node's order value, the members, the contenders"""
+    _fields_ = [("key", C.c_int64), ("id", C.c_uint64), ("val", C.c_int64), ("n_match", C.c_uint64), ("n", C.c_uint64)]
+
+
+class FirstRes(C.Structure):
+    """bmx_first_res: what one bmx_where_group_first found besides its records (40 bytes); flags: FIRST_OVERFLOW"""
+    _fields_ = [("n_groups", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("total", C.c_uint64), ("absent", C.c_uint64), ("n_ordered", C.c_uint64)]
+
+
+FIRST_DTYPE = np.dtype([("key", "<i8"), ("id", "<u8"), ("val", "<i8"), ("n_match", "<u8"), ("n", "<u8")])
+FIRST_RES_DTYPE = np.dtype([("n_groups", "<u8"), ("flags", "<u4"), ("reserved", "<u4"), ("total", "<u8"), ("absent", "<u8"), ("n_ordered", "<u8")])
+
+
+class FirstResult:
+    """One where_group_first answer: records (FIRST_DTYPE, sorted by key; none on overflow), vals (int64, shape (nfields, n_groups): the cells of each record's
+    node; VAL_DELETED in a cell without data), ts (the clocks, same shape; ROWS_NO_CLOCK in an absent cell; None without with_ts), first = {key: id or None},
+    n_groups (the number of distinct group values, or on overflow a lower bound of it above cap), overflow, total (every selected node), absent (those without
+    a group value) and n_ordered (the contenders of all groups)."""
+    __slots__ = ("records", "vals", "ts", "first", "n_groups", "overflow", "total", "absent", "n_ordered")
+
+    def __init__(self, res, recs, vals, ts):
+        r = np.frombuffer(bytes(res), FIRST_RES_DTYPE)[0] if isinstance(res, FirstRes) else res
+        self.n_groups = int(r["n_groups"]); self.overflow = bool(int(r["flags"]) & FIRST_OVERFLOW)
+        self.total, self.absent, self.n_ordered = int(r["total"]), int(r["absent"]), int(r["n_ordered"])
+        m = 0 if self.overflow else self.n_groups
+        self.records = recs[:m].copy()
+        self.vals = vals[:, :m].copy()
+        self.ts = None if ts is None else ts[:, :m].copy()
+        self.first = {int(x["key"]): (int(x["id"]) if int(x["n"]) else None) for x in self.records}
+
+    def __repr__(self):
+        return "FirstResult(%d groups%s, total=%d, absent=%d, n_ordered=%d)" % (self.n_groups, ", overflow" if self.overflow else "", self.total, self.absent, self.n_ordered)
+
+
+def _first_tail(group, order, fields, desc, with_ts):
+    """-> (group_field, order_field, nfields, fields, flags) of bmx_where_group_first"""
+    nf, farr, flags = _rows_fields(fields, with_ts)
+    return (int(group), int(order), nf, farr, flags | (FIRST_DESC if desc else 0))
+
+
+def _first_buffers(nfields, cap, with_ts):
+    return np.zeros(max(cap, 1), FIRST_DTYPE), np.zeros((nfields, max(cap, 1)), np.int64), np.zeros((nfields, max(cap, 1)), np.int64) if with_ts else None
+
+
+def first_merge(lists, desc=False):
+    """The merge bmx_comm_where_group_first does with its shards' answers. `lists`: per shard (records, vals, ts) — records FIRST_DTYPE with distinct keys, vals
+    and ts of shape (nfields, len(records)) (ts may be None) — -> (records sorted ascending by key, vals, ts): n_match and n of equal keys add; the better
+    (val, id) under the order — val ascending, or descending with desc, then id ascending as an unsigned number — wins and brings ITS shard's cells; a
+    record without a contender never beats one with. Pure Python and numpy: no library, no GPU."""
+    best = {}
+    for recs, vals, ts in lists:
+        recs = np.asarray(recs, FIRST_DTYPE)
+        for i in range(len(recs)):
+            x = recs[i]
+            cells = (None if vals is None else [int(v) for v in np.asarray(vals)[:, i]], None if ts is None else [int(v) for v in np.asarray(ts)[:, i]])
+            cur = [int(x["key"]), int(x["id"]), int(x["val"]), int(x["n_match"]), int(x["n"]), cells]
+            old = best.get(cur[0])
+            if old is None:
+                best[cur[0]] = cur
+                continue
+            nm, n = old[3] + cur[3], old[4] + cur[4]
+            better = cur[4] and (not old[4] or ((cur[2] > old[2] if desc else cur[2] < old[2]) if cur[2] != old[2] else cur[1] < old[1]))
+            win = cur if better else old
+            win[3], win[4] = nm, n
+            best[cur[0]] = win
+    keys = sorted(best)
+    out = np.zeros(len(keys), FIRST_DTYPE)
+    nf = max([0] + [len(b[5][0]) for b in best.values() if b[5][0] is not None])
+    have_ts = any(b[5][1] is not None for b in best.values())
+    ovals = np.zeros((nf, len(keys)), np.int64)
+    ots = np.zeros((nf, len(keys)), np.int64) if have_ts else None
+    for i, k in enumerate(keys):
+        b = best[k]
+        out[i] = (b[0], b[1], b[2], b[3], b[4])
+        if nf:
+            ovals[:, i] = b[5][0]
+            if have_ts:
+                ots[:, i] = b[5][1]
+    return out, ovals, ots
 
 
 class UpdRes(C.Structure):
@@ -705,6 +790,9 @@ def load_library():
     L.bmx_comm_where_map_rows.argtypes = [vp] + prog + [u32, u32, C.POINTER(u32), vp, vp, u64, u32, C.POINTER(u32), u32, u32, u64, u64] + jr_out; L.bmx_comm_where_map_rows.restype = i32
     L.bmx_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u64, u64, vp, vp, vp, vp, i32]; L.bmx_where_rows.restype = i32
     L.bmx_comm_where_rows.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, C.POINTER(u32), u32, u32, u64, u64, vp, vp, vp, vp]; L.bmx_comm_where_rows.restype = i32
+    first = [u32, u32, u32, C.POINTER(u32), u32, u64, vp, vp, vp, vp]       # group, order, nfields, fields, flags, cap, out, out_val, out_ts, res
+    L.bmx_where_group_first.argtypes = [vp] + prog + first + [i32]; L.bmx_where_group_first.restype = i32
+    L.bmx_comm_where_group_first.argtypes = [vp] + prog + first; L.bmx_comm_where_group_first.restype = i32
     L.bmx_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp, i32]; L.bmx_where_group_multi.restype = i32
     L.bmx_comm_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp]; L.bmx_comm_where_group_multi.restype = i32
     upd = [u32, u32, u32, i64, i64, u32]
@@ -1151,6 +1239,17 @@ class Engine:
                                         C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return RowsResult(res, ids, vals, ts)
 
+    def where_group_first(self, base, clauses, group, order, fields=(), desc=False, with_ts=False, cap=65536):
+        """The first node per group (bmx_first.h): per distinct value of field `group` among the selection of scan_where(base, clauses), the node that comes
+        first by the value of field `order` (descending with desc), then by id (always ascending, unsigned), with the values (with_ts: and clocks) of
+        `fields` on that node. -> FirstResult (with overflow set and no records when there are more than cap distinct values)"""
+        cap = int(cap)
+        tail = _first_tail(group, order, fields, desc, with_ts)
+        out, vals, ts = _first_buffers(tail[2], cap, with_ts)
+        res = FirstRes()
+        self._chk(self.L.bmx_where_group_first(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return FirstResult(res, out, vals, ts)
+
     def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
         """Group-by over several fields (bmx_group_multi.h): count / sum / min / max of field `measure` over the selection of scan_where(base, clauses), one
         record per distinct key tuple that occurs among the selected nodes. keys: 1..4 of `field` (the value itself) or (field, origin, width) (the bucket
@@ -1480,6 +1579,14 @@ class Engine:
         nf, farr, flags = _rows_fields(fields, out_ts is not None)
         self._chk(self.L.bmx_where_rows(self.h, *_where_args(base, clauses), nf, farr, flags, int(start), int(cap), _ptr(out_ids), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
 
+    def where_group_first_dev(self, base, clauses, group, order, out, out_val, out_ts, res, fields=(), desc=False, cap=65536):
+        """where_group_first into device memory (`out`: room for cap records of 40 bytes; out_val: len(fields) columns of cap int64 each, field after field;
+        out_ts: the same for the clocks, or None for none; res: 40 bytes, a bmx_first_res); enqueue-only. The records come in no particular order, but row r of
+        every column belongs to out[r]; after sync(), res.cpu().numpy().view(FIRST_RES_DTYPE)[0] and out.cpu().numpy().view(FIRST_DTYPE)[:n] read them. The
+        program and the fields are host data."""
+        self._chk(self.L.bmx_where_group_first(self.h, *_where_args(base, clauses), *_first_tail(group, order, fields, desc, out_ts is not None), int(cap), _ptr(out),
+                                               _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
+
     def where_group_multi_dev(self, base, clauses, keys, out, res, measure=None, cap=65536):
         """where_group_multi into device memory (`out`: room for cap records of 80 bytes; res: 112 bytes, a bmx_group_res); enqueue-only. The keys are host
         data. The records come in no particular order; after sync(), MultiGroupResult(res.cpu().numpy().view(GROUP_RES_DTYPE)[0],
@@ -1808,6 +1915,15 @@ class Comm:
         ids, vals, ts = _rows_buffers(nf, int(cap), with_ts)
         self._chk(self.L.bmx_comm_where_rows(self.h, *args, int(cap), _ptr(ids), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
         return RowsResult(res, ids, vals, ts)
+
+    def where_group_first(self, base, clauses, group, order, fields=(), desc=False, with_ts=False, cap=65536):
+        """Engine.where_group_first over all shards: every shard answers with its own groups, the library merges them by key as first_merge does"""
+        cap = int(cap)
+        tail = _first_tail(group, order, fields, desc, with_ts)
+        out, vals, ts = _first_buffers(tail[2], cap, with_ts)
+        res = FirstRes()
+        self._chk(self.L.bmx_comm_where_group_first(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
+        return FirstResult(res, out, vals, ts)
 
     def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
         """Engine.where_group_multi over all shards: every shard answers with its own tuples, the library merges them as mgroup_merge does"""

@@ -44,6 +44,7 @@
 #include "update_kernels.h"
 #include "mgroup_kernels.h"
 #include "reach_kernels.h"
+#include "first_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -404,6 +405,20 @@ struct ReachScratch {
   }
 };
 
+// Scratch of the first node per group (bmx_first.inc), beside GroupScratch, whose table it uses: one id word per slot, which every query's last kernel leaves at
+// BMX_FIRST_NO_NODE again (clean), the two words per position of the base field's index that pass 1 leaves pass 2 (allocated by the first query and grown with
+// the largest index seen, like ReachScratch::link), and the records, columns (8-byte words, grown on demand) and result record of a BMX_MEM_HOST answer on their
+// way down. Nothing here survives a call, so an index laid out anew needs no care.
+struct FirstScratch {
+  unsigned long long* idw = nullptr; uint64_t slots = 0; bool clean = false;
+  long long* gw = nullptr; long long* ow = nullptr; uint64_t pos_cap = 0;
+  bmx_first_rec* stage = nullptr; unsigned long long* stage_cols = nullptr; bmx_first_res* stage_res = nullptr; uint64_t stage_cap = 0, stage_words = 0;
+  void release() {
+    dev_free(idw); dev_free(gw); dev_free(ow); dev_free(stage); dev_free(stage_cols); dev_free(stage_res);
+    slots = 0; clean = false; pos_cap = 0; stage_cap = 0; stage_words = 0;
+  }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -472,6 +487,7 @@ struct bmx_ctx {
   UpdScratch upd;
   MGroupScratch mgroup;
   ReachScratch reach;
+  FirstScratch first;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -799,6 +815,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->upd.release();
   ctx->mgroup.release();
   ctx->reach.release();
+  ctx->first.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1101,3 +1118,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_update.inc"    // (likewise; it calls bmx_merge.inc's merge_core with records it made itself; its mask pass is bmx_where.inc's)
 #include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid, fold and grouped-answer steps, and a scratch of its own)
 #include "bmx_reach.inc"     // (likewise; it uses bmx_join.inc's map scratch, bmx_semi.inc's grids and slot count and bmx_where.inc's mask pass)
+#include "bmx_first.inc"     // (likewise; it uses bmx_group.inc's table, scratch and grouped-answer steps)

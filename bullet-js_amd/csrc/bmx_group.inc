@@ -69,19 +69,29 @@ int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_
 inline bool group_key_less(const bmx_group_rec& a, const bmx_group_rec& b) { return a.key < b.key; }
 
 // Second half of a staged grouped answer: the result record, then (if they fit) the records, sorted by `less`. `recs` gets them; nothing of the caller's is
-// written. no_recs: the flag bits of the record that say no records were written. fn: the entry point, for the internal error's text.
+// written. no_recs: the flag bits of the record that say no records were written. fn: the entry point, for the internal error's text. perm (optional) gets the
+// sort's permutation: recs[i] was record perm[i] of the staging (a form that staged columns beside its records moves their rows the same way).
 template <class Rec, class Res, class Less>
-int grouped_collect(bmx_ctx* ctx, const Rec* stage, const Res* stage_res, uint32_t no_recs, uint64_t cap, Less less, const char* fn, std::vector<Rec>& recs, Res* res) {
+int grouped_collect(bmx_ctx* ctx, const Rec* stage, const Res* stage_res, uint32_t no_recs, uint64_t cap, Less less, const char* fn, std::vector<Rec>& recs, Res* res,
+                    std::vector<uint32_t>* perm = nullptr) {
   HIPCHK(hipMemcpyAsync(res, stage_res, sizeof(Res), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   recs.clear();
+  if (perm) perm->clear();
   if (res->flags & no_recs) return BMX_OK;
   if (res->n_groups > cap) return fail(ctx, BMX_ERR_INTERNAL, std::string(fn) + ": more records than cap without the overflow flag");
   recs.resize(res->n_groups);
   if (res->n_groups) {
     HIPCHK(hipMemcpyAsync(recs.data(), stage, res->n_groups * sizeof(Rec), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::sort(recs.begin(), recs.end(), less);
+    if (!perm) std::sort(recs.begin(), recs.end(), less);
+    else {
+      const std::vector<Rec> raw(recs);
+      perm->resize(raw.size());
+      for (uint32_t i = 0; i < raw.size(); i++) (*perm)[i] = i;
+      std::sort(perm->begin(), perm->end(), [&](uint32_t a, uint32_t b) { return less(raw[a], raw[b]); });
+      for (size_t i = 0; i < raw.size(); i++) recs[i] = raw[(*perm)[i]];
+    }
   }
   return BMX_OK;
 }
@@ -101,24 +111,31 @@ inline void group_fold_res(uint32_t g, bmx_group_res& tot, const bmx_group_res& 
   if (g == 0) { tot.absent = r.absent; tot.total = r.total; } else { group_fold(tot.absent, r.absent); group_fold(tot.total, r.total); }
 }
 
-// all = all UNION part: two lists sorted by `less` into one, the records of equal keys folded (tmp: scratch of the caller's)
-template <class Rec, class Less>
-void merge_sorted(std::vector<Rec>& all, const std::vector<Rec>& part, std::vector<Rec>& tmp, Less less) {
+// how two records of one key become one: the aggregates fold (every grouped answer whose record ends in a bmx_agg)
+struct GroupRecFold {
+  template <class Rec>
+  void operator()(Rec& m, const Rec& p) const { group_fold(m.agg, p.agg); }
+};
+
+// all = all UNION part: two lists sorted by `less` into one, the records of equal keys folded by `recfold` (tmp: scratch of the caller's)
+template <class Rec, class Less, class RecFold = GroupRecFold>
+void merge_sorted(std::vector<Rec>& all, const std::vector<Rec>& part, std::vector<Rec>& tmp, Less less, RecFold recfold = RecFold()) {
   tmp.clear(); tmp.reserve(all.size() + part.size());
   size_t i = 0, j = 0;
   while (i < all.size() || j < part.size()) {
     if (j == part.size() || (i < all.size() && less(all[i], part[j]))) tmp.push_back(all[i++]);
     else if (i == all.size() || less(part[j], all[i])) tmp.push_back(part[j++]);
-    else { Rec m = all[i++]; group_fold(m.agg, part[j++].agg); tmp.push_back(m); }
+    else { Rec m = all[i++]; recfold(m, part[j++]); tmp.push_back(m); }
   }
   all.swap(tmp);
 }
 
 // A grouped answer over the shards: enqueue(x) on every shard (entered here), then shard after shard collect(x, part, &r) — its sorted list and its record — and
 // fold(g, *tot, r), the form's own aggregates; the lists merged, equal keys folded. A shard that overflowed reports a lower bound of the number of groups: the
-// answer overflows (`overflow`: the form's flag bit) with the largest bound any shard or the union gives. Otherwise the records go to `out`.
-template <class Rec, class Res, class Less, class Enqueue, class Collect, class Fold>
-int comm_grouped(bmx_comm* c, uint64_t cap, uint32_t overflow, Less less, Rec* out, Res* tot, Enqueue enqueue, Collect collect, Fold fold) {
+// answer overflows (`overflow`: the form's flag bit) with the largest bound any shard or the union gives. Otherwise the records go to `out`. recfold:
+// merge_sorted's.
+template <class Rec, class Res, class Less, class Enqueue, class Collect, class Fold, class RecFold = GroupRecFold>
+int comm_grouped(bmx_comm* c, uint64_t cap, uint32_t overflow, Less less, Rec* out, Res* tot, Enqueue enqueue, Collect collect, Fold fold, RecFold recfold = RecFold()) {
   std::vector<Rec> all, part, tmp;
   uint64_t lower = 0;
   bool over = false;
@@ -132,7 +149,7 @@ int comm_grouped(bmx_comm* c, uint64_t cap, uint32_t overflow, Less less, Rec* o
       if (crc) return crc;
       fold(g, *tot, r);
       if (r.flags & overflow) { over = true; lower = std::max<uint64_t>(lower, r.n_groups); return (int)BMX_OK; }
-      merge_sorted(all, part, tmp, less);
+      merge_sorted(all, part, tmp, less, recfold);
       return (int)BMX_OK;
     });
   if (rc) return rc;

@@ -123,6 +123,20 @@ __device__ __forceinline__ void group_lane_add(AggLane& L, bool have_m, int64_t 
   if (have_m) { L.n++; L.slo += (unsigned long long)(uint32_t)mval; L.shi += mval >> 32; L.mn = mval < L.mn ? mval : L.mn; L.mx = mval > L.mx ? mval : L.mx; }
 }
 
+// the end of one row of a sweep, called by every lane of the wave: the row (go = false: none) into the record of its key (k_group_sweep; first_kernels.h)
+__device__ __forceinline__ void group_row_put(const GroupArgs& A, bool go, int64_t gval, bool have_m, int64_t mval, uint32_t lane, GroupLds& S) {
+  const unsigned long long act = __ballot(go);
+  if (!act) return;                                                  // (uniform)
+  // rows of one wave often share a key: the lanes that hold the first one's key add their count once
+  const int first = __ffsll((long long)act) - 1;
+  const long long k0 = __shfl((long long)gval, first);
+  const unsigned long long same = __ballot(go && (long long)gval == k0);
+  if (!go) return;
+  uint32_t nm = 1u;
+  if ((long long)gval == k0) nm = (int)lane == first ? (uint32_t)__popcll(same) : 0u;
+  if (nm || have_m) group_put(A, S, (long long)gval, nm, have_m, mval);
+}
+
 // one row of the sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company)
 template <class T>
 __device__ __forceinline__ void group_row(const PredWhere<T>& P, const GroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, GroupLds& S) {
@@ -141,17 +155,7 @@ __device__ __forceinline__ void group_row(const PredWhere<T>& P, const GroupArgs
     group_lane_add(Lt, have_m, mval);
     if (!have_g) group_lane_add(La, have_m, mval);
   }
-  const bool go = sel && have_g;
-  const unsigned long long act = __ballot(go);
-  if (!act) return;                                                  // (uniform)
-  // rows of one wave often share a key: the lanes that hold the first one's key add their count once
-  const int first = __ffsll((long long)act) - 1;
-  const long long k0 = __shfl((long long)gval, first);
-  const unsigned long long same = __ballot(go && (long long)gval == k0);
-  if (!go) return;
-  uint32_t nm = 1u;
-  if ((long long)gval == k0) nm = (int)lane == first ? (uint32_t)__popcll(same) : 0u;
-  if (nm || have_m) group_put(A, S, (long long)gval, nm, have_m, mval);
+  group_row_put(A, sel && have_g, gval, have_m, mval, lane, S);
 }
 
 // a lane's record -> one set of no-return atomics per workgroup (agg_end<0>)
