@@ -91,6 +91,9 @@ REACH_OVERFLOW, REACH_MORE, REACH_MAX_SET, REACH_MAX_DEPTH = 1, 2, 1 << 20, 255 
 # the first node per group (include/bmx_first.h), likewise
 EXPORTS_FIRST = ["bmx_where_group_first", "bmx_comm_where_group_first"]
 FIRST_DESC, FIRST_OVERFLOW, FIRST_NO_NODE, FIRST_MAX_CAP = 2, 1, (1 << 64) - 1, 1 << 20   # BMX_FIRST_DESC (flags of the call, next to ROWS_TS), BMX_FIRST_OVERFLOW (flags of bmx_first_res), BMX_FIRST_NO_NODE, BMX_FIRST_MAX_CAP (bmx_first.h bmx_where_group_first)
+# the first N nodes per group (include/bmx_group_top.h), likewise
+EXPORTS_GROUP_TOP = ["bmx_where_group_top", "bmx_comm_where_group_top"]
+GTOP_DESC, GTOP_OVERFLOW, GTOP_NO_NODE, GTOP_MAX_CAP, GTOP_MAX_PER, GTOP_MAX_ROWS = 2, 1, (1 << 64) - 1, 1 << 20, 16, 1 << 22   # BMX_GTOP_DESC (flags of the call, next to ROWS_TS), BMX_GTOP_OVERFLOW (flags of bmx_gtop_res), BMX_GTOP_NO_NODE, BMX_GTOP_MAX_CAP, BMX_GTOP_MAX_PER, BMX_GTOP_MAX_ROWS (bmx_group_top.h bmx_where_group_top)
 MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14  # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
 UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
@@ -420,6 +423,108 @@ def first_merge(lists, desc=False):
             if have_ts:
                 ots[:, i] = b[5][1]
     return out, ovals, ots
+
+
+class GtopGrp(C.Structure):
+    """bmx_gtop_grp: one group of bmx_where_group_top (32 bytes): the group value, the members, the contenders, the rows that carry a node"""
+    _fields_ = [("key", C.c_int64), ("n_match", C.c_uint64), ("n", C.c_uint64), ("n_rows", C.c_uint64)]
+
+
+class GtopRow(C.Structure):
+    """bmx_gtop_row: one row of a group (16 bytes): the node and its order value; GTOP_NO_NODE and VAL_DELETED behind the group's last row"""
+    _fields_ = [("id", C.c_uint64), ("val", C.c_int64)]
+
+
+class GtopRes(C.Structure):
+    """bmx_gtop_res: what one bmx_where_group_top found besides its groups (48 bytes); flags: GTOP_OVERFLOW"""
+    _fields_ = [("n_groups", C.c_uint64), ("flags", C.c_uint32), ("per", C.c_uint32), ("total", C.c_uint64), ("absent", C.c_uint64), ("n_ordered", C.c_uint64),
+                ("n_rows", C.c_uint64)]
+
+
+GTOP_GRP_DTYPE = np.dtype([("key", "<i8"), ("n_match", "<u8"), ("n", "<u8"), ("n_rows", "<u8")])
+GTOP_ROW_DTYPE = np.dtype([("id", "<u8"), ("val", "<i8")])
+GTOP_RES_DTYPE = np.dtype([("n_groups", "<u8"), ("flags", "<u4"), ("per", "<u4"), ("total", "<u8"), ("absent", "<u8"), ("n_ordered", "<u8"), ("n_rows", "<u8")])
+
+
+class GroupTopResult:
+    """One where_group_top answer: groups (GTOP_GRP_DTYPE, sorted by key; none on overflow), rows (GTOP_ROW_DTYPE, shape (n_groups, per): each group's first
+    contenders in order, padded with (GTOP_NO_NODE, VAL_DELETED)), vals (int64, shape (nfields, n_groups, per): the cells of each row's node; VAL_DELETED in a
+    cell without data), ts (the clocks, same shape; ROWS_NO_CLOCK in an absent cell; None without with_ts), top = {key: [ids in order]}, per, n_groups (the
+    number of distinct group values, or on overflow a lower bound of it above cap), overflow, total (every selected node), absent (those without a group
+    value), n_ordered (the contenders of all groups) and n_rows (the rows that carry a node)."""
+    __slots__ = ("groups", "rows", "vals", "ts", "top", "per", "n_groups", "overflow", "total", "absent", "n_ordered", "n_rows")
+
+    def __init__(self, res, groups, rows, vals, ts):
+        r = np.frombuffer(bytes(res), GTOP_RES_DTYPE)[0] if isinstance(res, GtopRes) else res
+        self.n_groups = int(r["n_groups"]); self.overflow = bool(int(r["flags"]) & GTOP_OVERFLOW); self.per = int(r["per"])
+        self.total, self.absent, self.n_ordered, self.n_rows = int(r["total"]), int(r["absent"]), int(r["n_ordered"]), int(r["n_rows"])
+        m, per = 0 if self.overflow else self.n_groups, self.per
+        nf = vals.shape[0]
+        self.groups = groups[:m].copy()
+        self.rows = rows.reshape(-1)[:m * per].reshape(m, per).copy()
+        self.vals = vals[:, :m * per].reshape(nf, m, per).copy()
+        self.ts = None if ts is None else ts[:, :m * per].reshape(nf, m, per).copy()
+        self.top = {int(g["key"]): [int(x) for x in self.rows[i]["id"][:int(g["n_rows"])]] for i, g in enumerate(self.groups)}
+
+    def __repr__(self):
+        return "GroupTopResult(%d groups%s, per=%d, n_rows=%d, total=%d, absent=%d, n_ordered=%d)" % (
+            self.n_groups, ", overflow" if self.overflow else "", self.per, self.n_rows, self.total, self.absent, self.n_ordered)
+
+
+def _gtop_tail(group, order, per, fields, desc, with_ts):
+    """-> (group_field, order_field, per, nfields, fields, flags) of bmx_where_group_top"""
+    nf, farr, flags = _rows_fields(fields, with_ts)
+    return (int(group), int(order), int(per), nf, farr, flags | (GTOP_DESC if desc else 0))
+
+
+def _gtop_buffers(nfields, cap, per, with_ts):
+    rows = max(cap * per, 1)
+    return (np.zeros(max(cap, 1), GTOP_GRP_DTYPE), np.zeros(rows, GTOP_ROW_DTYPE), np.zeros((nfields, rows), np.int64),
+            np.zeros((nfields, rows), np.int64) if with_ts else None)
+
+
+def gtop_merge(lists, per, desc=False):
+    """The merge bmx_comm_where_group_top does with its shards' answers. `lists`: per shard (groups, rows, vals, ts) — groups GTOP_GRP_DTYPE with distinct keys,
+    rows GTOP_ROW_DTYPE of shape (len(groups), per), vals and ts of shape (nfields, len(groups), per) (ts may be None) — -> (groups sorted ascending by key, rows,
+    vals, ts): n_match and n of equal keys add; the rows of a key are the first `per` of the union of the shards' rows that carry a node, under the order — val
+    ascending, or descending with desc, then id ascending as an unsigned number — and each row brings ITS shard's cells; n_rows is recomputed, and the rows
+    behind it are (GTOP_NO_NODE, VAL_DELETED) with absent cells. Pure Python and numpy: no library, no GPU."""
+    per = int(per)
+    acc = {}                                        # key -> [n_match, n, [(sort key, id, val, cells, clocks)]]
+    nf, have_ts = 0, False
+    for groups, rows, vals, ts in lists:
+        groups = np.asarray(groups, GTOP_GRP_DTYPE)
+        rows = np.asarray(rows, GTOP_ROW_DTYPE).reshape(len(groups), per)
+        vals = None if vals is None else np.asarray(vals)
+        ts = None if ts is None else np.asarray(ts)
+        if vals is not None:
+            nf = max(nf, vals.shape[0])
+        have_ts = have_ts or ts is not None
+        for g in range(len(groups)):
+            a = acc.setdefault(int(groups[g]["key"]), [0, 0, []])
+            a[0] += int(groups[g]["n_match"]); a[1] += int(groups[g]["n"])
+            for j in range(int(groups[g]["n_rows"])):
+                i, v = int(rows[g, j]["id"]), int(rows[g, j]["val"])
+                a[2].append(((-v if desc else v, i), i, v, None if vals is None else [int(x) for x in vals[:, g, j]], None if ts is None else [int(x) for x in ts[:, g, j]]))
+    keys = sorted(acc)
+    out = np.zeros(len(keys), GTOP_GRP_DTYPE)
+    orows = np.zeros((len(keys), per), GTOP_ROW_DTYPE)
+    orows["id"] = GTOP_NO_NODE; orows["val"] = VAL_DELETED
+    ovals = np.full((nf, len(keys), per), VAL_DELETED, np.int64)
+    ots = np.full((nf, len(keys), per), ROWS_NO_CLOCK, np.int64) if have_ts else None
+    for g, k in enumerate(keys):
+        nm, n, cand = acc[k]
+        cand.sort(key=lambda c: c[0])
+        cand = cand[:per]
+        out[g] = (k, nm, n, min(per, n))
+        assert len(cand) == min(per, n), "every shard delivered its first min(per, n) rows"
+        for j, c in enumerate(cand):
+            orows[g, j] = (c[1], c[2])
+            if nf and c[3] is not None:
+                ovals[:, g, j] = c[3]
+            if have_ts and c[4] is not None:
+                ots[:, g, j] = c[4]
+    return out, orows, ovals, ots
 
 
 class UpdRes(C.Structure):
@@ -793,6 +898,9 @@ def load_library():
     first = [u32, u32, u32, C.POINTER(u32), u32, u64, vp, vp, vp, vp]       # group, order, nfields, fields, flags, cap, out, out_val, out_ts, res
     L.bmx_where_group_first.argtypes = [vp] + prog + first + [i32]; L.bmx_where_group_first.restype = i32
     L.bmx_comm_where_group_first.argtypes = [vp] + prog + first; L.bmx_comm_where_group_first.restype = i32
+    gtop = [u32, u32, u32, u32, C.POINTER(u32), u32, u64, vp, vp, vp, vp, vp]  # group, order, per, nfields, fields, flags, cap, out, out_rows, out_val, out_ts, res
+    L.bmx_where_group_top.argtypes = [vp] + prog + gtop + [i32]; L.bmx_where_group_top.restype = i32
+    L.bmx_comm_where_group_top.argtypes = [vp] + prog + gtop; L.bmx_comm_where_group_top.restype = i32
     L.bmx_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp, i32]; L.bmx_where_group_multi.restype = i32
     L.bmx_comm_where_group_multi.argtypes = [vp] + prog + [u32, u32, C.POINTER(GroupKey), vp, u64, vp]; L.bmx_comm_where_group_multi.restype = i32
     upd = [u32, u32, u32, i64, i64, u32]
@@ -1250,6 +1358,18 @@ class Engine:
         self._chk(self.L.bmx_where_group_first(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return FirstResult(res, out, vals, ts)
 
+    def where_group_top(self, base, clauses, group, order, per, fields=(), desc=False, with_ts=False, cap=65536):
+        """The first `per` nodes per group (bmx_group_top.h): per distinct value of field `group` among the selection of scan_where(base, clauses), the `per`
+        nodes that come first by the value of field `order` (descending with desc), then by id (always ascending, unsigned), in that order, with the values
+        (with_ts: and clocks) of `fields` on each. -> GroupTopResult (with overflow set and no groups when there are more than cap distinct values)"""
+        cap, per = int(cap), int(per)
+        tail = _gtop_tail(group, order, per, fields, desc, with_ts)
+        ok = 1 <= per <= GTOP_MAX_PER and 1 <= cap <= GTOP_MAX_CAP and cap * per <= GTOP_MAX_ROWS        # (otherwise the library refuses: no buffers needed)
+        out, rows, vals, ts = _gtop_buffers(tail[3], cap if ok else 1, per if ok else 1, with_ts)
+        res = GtopRes()
+        self._chk(self.L.bmx_where_group_top(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(rows), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
+        return GroupTopResult(res, out, rows, vals, ts)
+
     def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
         """Group-by over several fields (bmx_group_multi.h): count / sum / min / max of field `measure` over the selection of scan_where(base, clauses), one
         record per distinct key tuple that occurs among the selected nodes. keys: 1..4 of `field` (the value itself) or (field, origin, width) (the bucket
@@ -1586,6 +1706,15 @@ class Engine:
         program and the fields are host data."""
         self._chk(self.L.bmx_where_group_first(self.h, *_where_args(base, clauses), *_first_tail(group, order, fields, desc, out_ts is not None), int(cap), _ptr(out),
                                                _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
+
+    def where_group_top_dev(self, base, clauses, group, order, per, out, out_rows, out_val, out_ts, res, fields=(), desc=False, cap=65536):
+        """where_group_top into device memory (`out`: room for cap groups of 32 bytes; out_rows: cap * per rows of 16 bytes; out_val: len(fields) columns of
+        cap * per int64 each, field after field; out_ts: the same for the clocks, or None for none; res: 48 bytes, a bmx_gtop_res); enqueue-only. The groups
+        come in no particular order, but block g of every array belongs to out[g]; after sync(), res.cpu().numpy().view(GTOP_RES_DTYPE)[0],
+        out.cpu().numpy().view(GTOP_GRP_DTYPE)[:n] and out_rows.cpu().numpy().view(GTOP_ROW_DTYPE)[:n * per] read them. The program and the fields are host
+        data."""
+        self._chk(self.L.bmx_where_group_top(self.h, *_where_args(base, clauses), *_gtop_tail(group, order, per, fields, desc, out_ts is not None), int(cap), _ptr(out),
+                                             _ptr(out_rows), _ptr(out_val), _ptr(out_ts), _ptr(res), MEM_DEVICE))
 
     def where_group_multi_dev(self, base, clauses, keys, out, res, measure=None, cap=65536):
         """where_group_multi into device memory (`out`: room for cap records of 80 bytes; res: 112 bytes, a bmx_group_res); enqueue-only. The keys are host
@@ -1924,6 +2053,16 @@ class Comm:
         res = FirstRes()
         self._chk(self.L.bmx_comm_where_group_first(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
         return FirstResult(res, out, vals, ts)
+
+    def where_group_top(self, base, clauses, group, order, per, fields=(), desc=False, with_ts=False, cap=65536):
+        """Engine.where_group_top over all shards: every shard answers with its own groups, the library merges them by key as gtop_merge does"""
+        cap, per = int(cap), int(per)
+        tail = _gtop_tail(group, order, per, fields, desc, with_ts)
+        ok = 1 <= per <= GTOP_MAX_PER and 1 <= cap <= GTOP_MAX_CAP and cap * per <= GTOP_MAX_ROWS        # (otherwise the library refuses: no buffers needed)
+        out, rows, vals, ts = _gtop_buffers(tail[3], cap if ok else 1, per if ok else 1, with_ts)
+        res = GtopRes()
+        self._chk(self.L.bmx_comm_where_group_top(self.h, *_where_args(base, clauses), *tail, cap, _ptr(out), _ptr(rows), _ptr(vals), _ptr(ts), C.cast(C.byref(res), C.c_void_p)))
+        return GroupTopResult(res, out, rows, vals, ts)
 
     def where_group_multi(self, base, clauses, keys, measure=None, cap=65536):
         """Engine.where_group_multi over all shards: every shard answers with its own tuples, the library merges them as mgroup_merge does"""

@@ -45,6 +45,7 @@
 #include "mgroup_kernels.h"
 #include "reach_kernels.h"
 #include "first_kernels.h"
+#include "gtop_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -419,6 +420,23 @@ struct FirstScratch {
   }
 };
 
+// Scratch of the first N nodes per group (bmx_group_top.inc), beside GroupScratch and FirstScratch, whose table, id words and words per position it uses: per slot
+// the previous winner, the round's extreme and the rank counter, which every query's last kernel leaves at rest again (clean), the rounds' counters, `per` winner
+// pairs per slot (grown to the largest slots * per asked so far; read only below the rank counter, so they need no rest state), and the groups, rows, columns
+// (8-byte words) and result record of a BMX_MEM_HOST answer on their way down. Nothing here survives a call.
+struct GtopScratch {
+  long long* pv = nullptr; unsigned long long* pid = nullptr; long long* ext = nullptr; uint32_t* rank = nullptr; GtopState* state = nullptr;
+  uint64_t slots = 0; bool clean = false;
+  bmx_gtop_row* win = nullptr; uint64_t win_rows = 0;
+  bmx_gtop_grp* stage = nullptr; bmx_gtop_row* stage_rows = nullptr; unsigned long long* stage_cols = nullptr; bmx_gtop_res* stage_res = nullptr;
+  uint64_t stage_cap = 0, stage_rows_cap = 0, stage_words = 0;
+  void release() {
+    dev_free(pv); dev_free(pid); dev_free(ext); dev_free(rank); dev_free(state); dev_free(win);
+    dev_free(stage); dev_free(stage_rows); dev_free(stage_cols); dev_free(stage_res);
+    slots = 0; clean = false; win_rows = 0; stage_cap = 0; stage_rows_cap = 0; stage_words = 0;
+  }
+};
+
 // The standing queries of one context (bmx_watch.inc). A watch: its prepared program, its base field, `prev` (the committed set, one bit per position of the base
 // field's index) and the stamp of the index layout that bitmap was sized and zeroed for (0: none yet). Shared by the watches: per watch the stamp of the layout it
 // last COMMITTED under (device words: a device-mode poll commits without the host), the two scratch masks and three count arrays of a poll, its totals record
@@ -488,6 +506,7 @@ struct bmx_ctx {
   MGroupScratch mgroup;
   ReachScratch reach;
   FirstScratch first;
+  GtopScratch gtop;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -816,6 +835,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->mgroup.release();
   ctx->reach.release();
   ctx->first.release();
+  ctx->gtop.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1119,3 +1139,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_group_multi.inc" // (likewise; it uses bmx_group.inc's slot count, finish grid, fold and grouped-answer steps, and a scratch of its own)
 #include "bmx_reach.inc"     // (likewise; it uses bmx_join.inc's map scratch, bmx_semi.inc's grids and slot count and bmx_where.inc's mask pass)
 #include "bmx_first.inc"     // (likewise; it uses bmx_group.inc's table, scratch and grouped-answer steps)
+#include "bmx_group_top.inc" // (likewise; it uses bmx_first.inc's passes 1 and 2 and bmx_group.inc's grouped-answer steps)

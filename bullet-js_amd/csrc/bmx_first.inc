@@ -2,8 +2,8 @@
 // guards are bmx_where.inc's (where_prepare, where_sweep, where_enter, where_comm_guard), the table, its scratch and the grouped-answer steps bmx_group.inc's
 // (group_scratch, group_slots, group_finish_grid, grouped_collect, comm_grouped), the kernels first_kernels.h. The context keeps what the form adds to
 // GroupScratch (FirstScratch): one id word per slot, which every query's last kernel leaves at BMX_FIRST_NO_NODE again (clean), the words per index position
-// that pass 1 leaves pass 2 (allocated by the first query, grown with the index) and the staging of a host-mode answer. Included by bmx.hip (one translation
-// unit), behind everything that was here before it.
+// that pass 1 leaves pass 2 (allocated by the first query, grown with the index) and the staging of a host-mode answer. Passes 1 and 2 are a step of their own
+// (first_passes), which bmx_group_top.inc enqueues too. Included by bmx.hip (one translation unit), behind everything that was here before it.
 namespace {
 
 struct FirstWant { uint32_t group_field, order_field, nfields; const uint32_t* fields; uint32_t flags; uint64_t cap; };
@@ -61,36 +61,25 @@ int first_stage(bmx_ctx* ctx, uint64_t cap, uint64_t words) {
   return BMX_OK;
 }
 
-// Enqueue one query over a prepared program; the records, the columns (stride w.cap) and the result record go to d_out / d_val / d_ts / d_res (device memory),
-// or, with d_out == nullptr, to the context's staging (first_collect fetches them). The arguments have been checked and the context entered. A value-ordered
-// view of the base field's index is neither read nor touched (where_run).
-int first_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const FirstWant& w, bmx_first_rec* d_out, int64_t* d_val, int64_t* d_ts, bmx_first_res* d_res) {
-  Index* ix;
-  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  if (int rc = group_scratch(ctx, w.cap)) return rc;
+// Passes 1 and 2 of one query over a prepared program (k_first_sweep, k_first_resolve): the table, the words per position and, per key that has a contender,
+// the smallest id on its extreme in the id word. F gets what the kernels behind them need. Both scratches are marked unclean; the caller marks them clean behind
+// its last kernel. The arguments have been checked and the context entered. A value-ordered view of the base field's index is neither read nor touched
+// (where_run).
+int first_passes(bmx_ctx* ctx, Index* ix, uint32_t base_field, const WhereProg& W, uint32_t group_field, uint32_t order_field, bool desc, uint64_t cap, FirstArgs& F) {
+  if (int rc = group_scratch(ctx, cap)) return rc;
   FirstScratch& s = ctx->first;
-  if (!d_out) {
-    if (int rc = first_stage(ctx, w.cap, w.cap * first_cols(w))) return rc;
-    d_out = s.stage; d_res = s.stage_res;
-    d_val = reinterpret_cast<int64_t*>(s.stage_cols); d_ts = d_val + (uint64_t)w.nfields * w.cap;
-  }
-  FirstArgs F{};
+  F = FirstArgs{};
   GroupArgs& A = F.G;
   A.keys = ctx->group.keys; A.acc = ctx->group.acc; A.S = ctx->group.state;
-  A.slots = group_slots(w.cap); A.cap = w.cap;
+  A.slots = group_slots(cap); A.cap = cap;
   if (int rc = first_scratch(ctx, A.slots, ix->n)) return rc;
-  A.measure = w.order_field; A.group = w.group_field;
-  A.m_src = where_agg_source(w.order_field, base_field); A.g_src = where_agg_source(w.group_field, base_field);
+  A.measure = order_field; A.group = group_field;
+  A.m_src = where_agg_source(order_field, base_field); A.g_src = where_agg_source(group_field, base_field);
   F.idw = s.idw;
-  F.same = (w.order_field == w.group_field && A.g_src == AGG_SRC_PROBE) ? 1u : 0u;
-  F.desc = (w.flags & BMX_FIRST_DESC) ? 1u : 0u;
+  F.same = (order_field == group_field && A.g_src == AGG_SRC_PROBE) ? 1u : 0u;
+  F.desc = desc ? 1u : 0u;
   F.gw = A.g_src == AGG_SRC_PROBE ? s.gw : nullptr;
   F.ow = ((A.m_src == AGG_SRC_PROBE && !F.same) || !F.gw) ? s.ow : nullptr;
-  FirstOut O{};
-  O.slots = ctx->slots; O.nslots = ctx->nslots;
-  O.out = d_out; O.out_val = d_val; O.out_ts = d_ts; O.res = d_res;
-  O.nfields = w.nfields; O.with_ts = (w.flags & BMX_ROWS_TS) ? 1u : 0u;
-  for (uint32_t f = 0; f < w.nfields; f++) O.field[f] = w.fields[f];
   ctx->group.clean = false; s.clean = false;
   where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
     hipLaunchKernelGGL((k_first_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, F);
@@ -103,6 +92,28 @@ int first_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const F
                        sizeof(T) == 4 ? reinterpret_cast<const T*>(ix->v32) : reinterpret_cast<const T*>(ix->v64), ix->ids, ix->n, F);
   });
   LAUNCHCHK("k_first_resolve");
+  return BMX_OK;
+}
+
+// Enqueue one query over a prepared program; the records, the columns (stride w.cap) and the result record go to d_out / d_val / d_ts / d_res (device memory),
+// or, with d_out == nullptr, to the context's staging (first_collect fetches them). The arguments have been checked and the context entered.
+int first_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const FirstWant& w, bmx_first_rec* d_out, int64_t* d_val, int64_t* d_ts, bmx_first_res* d_res) {
+  Index* ix;
+  if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
+  FirstScratch& s = ctx->first;
+  if (!d_out) {
+    if (int rc = first_stage(ctx, w.cap, w.cap * first_cols(w))) return rc;
+    d_out = s.stage; d_res = s.stage_res;
+    d_val = reinterpret_cast<int64_t*>(s.stage_cols); d_ts = d_val + (uint64_t)w.nfields * w.cap;
+  }
+  FirstArgs F;
+  if (int rc = first_passes(ctx, ix, base_field, W, w.group_field, w.order_field, (w.flags & BMX_FIRST_DESC) != 0, w.cap, F)) return rc;
+  const GroupArgs& A = F.G;
+  FirstOut O{};
+  O.slots = ctx->slots; O.nslots = ctx->nslots;
+  O.out = d_out; O.out_val = d_val; O.out_ts = d_ts; O.res = d_res;
+  O.nfields = w.nfields; O.with_ts = (w.flags & BMX_ROWS_TS) ? 1u : 0u;
+  for (uint32_t f = 0; f < w.nfields; f++) O.field[f] = w.fields[f];
   hipLaunchKernelGGL(k_first_finish, dim3(group_finish_grid(A.slots)), dim3(256), 0, ctx->stream, F, O, A.m_src != AGG_SRC_PROBE ? 1u : 0u);
   LAUNCHCHK("k_first_finish");
   ctx->group.clean = true; s.clean = true;

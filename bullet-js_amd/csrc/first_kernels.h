@@ -140,31 +140,53 @@ __global__ __launch_bounds__(AGG_THREADS) void k_first_sweep(uint64_t n, PredWhe
   group_end(&A.S->absent, La, S.w);
 }
 
+// the words kept for index position i, as loaded (VAL_DELETED where none is kept): is it a contender, and if so its group value and its order value (from the
+// words, and from the column where a field is the base)
+template <class T>
+__device__ __forceinline__ bool first_decode(const FirstArgs& F, const T* __restrict__ col, uint64_t i, long long& key, long long& val) {
+  bool ok = true;
+  if (F.gw) ok = key != VAL_DELETED;
+  if (F.ow) ok = ok && val != VAL_DELETED;
+  if (!ok) return false;
+  if (!F.gw || (!F.ow && !F.same)) {                                    // (uniform) a selected row: its column value is data
+    const long long c = (long long)col[i];
+    if (!F.gw) key = c;
+    if (!F.ow && !F.same) val = c;
+  }
+  if (F.same) val = key;
+  return true;
+}
+
+// what pass 1 left of index position i
+template <class T>
+__device__ __forceinline__ bool first_contender(const FirstArgs& F, const T* __restrict__ col, uint64_t i, long long& key, long long& val) {
+  key = VAL_DELETED; val = VAL_DELETED;
+  if (F.gw) key = __builtin_nontemporal_load(F.gw + i);
+  if (F.ow) val = __builtin_nontemporal_load(F.ow + i);
+  return first_decode<T>(F, col, i, key, val);
+}
+
+// the slot of `key` in the FINISHED table, with plain loads (behind the end of pass 1; false cannot happen without the overflow bit)
+__device__ __forceinline__ bool first_find(const GroupArgs& A, long long key, uint64_t& s) {
+  const uint64_t mask = A.slots - 1u;
+  s = group_mix(key) & mask;
+  for (uint64_t p = 0; p < A.slots; ++p, s = (s + 1u) & mask) {
+    const long long k = A.keys[s];
+    if (k == key) return true;
+    if (k == GROUP_EMPTY) break;
+  }
+  return false;
+}
+
 template <class T>
 __global__ __launch_bounds__(FIRST_THREADS) void k_first_resolve(const T* __restrict__ col, const uint64_t* __restrict__ ids, uint64_t n, FirstArgs F) {
   const GroupArgs& A = F.G;
   if (A.S->overflow != 0u || A.S->claims > A.cap) return;              // (uniform) no records will be written, and the table may lack keys
-  const uint64_t mask = A.slots - 1u;
   for (uint64_t i = (uint64_t)blockIdx.x * FIRST_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * FIRST_THREADS) {
-    long long key = VAL_DELETED, val = VAL_DELETED;
-    bool ok = true;
-    if (F.gw) { key = __builtin_nontemporal_load(F.gw + i); ok = key != VAL_DELETED; }
-    if (F.ow) { val = __builtin_nontemporal_load(F.ow + i); ok = ok && val != VAL_DELETED; }
-    if (!ok) continue;
-    if (!F.gw || (!F.ow && !F.same)) {                                  // (uniform) a selected row: its column value is data
-      const long long c = (long long)col[i];
-      if (!F.gw) key = c;
-      if (!F.ow && !F.same) val = c;
-    }
-    if (F.same) val = key;
-    uint64_t s = group_mix(key) & mask;
-    bool found = false;
-    for (uint64_t p = 0; p < A.slots; ++p, s = (s + 1u) & mask) {
-      const long long k = A.keys[s];
-      if (k == key) { found = true; break; }
-      if (k == GROUP_EMPTY) break;
-    }
-    if (!found) continue;                                               // (cannot happen without the overflow bit)
+    long long key, val;
+    if (!first_contender<T>(F, col, i, key, val)) continue;
+    uint64_t s;
+    if (!first_find(A, key, s)) continue;
     const long long ext = F.desc ? A.acc[s].mx : A.acc[s].mn;
     if (val != ext) continue;
     const unsigned long long id = ids[i];
