@@ -27,6 +27,7 @@ MAX_BATCH = 1 << 24
 AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measure" / "no grouping"), BMX_AGG_MAX_GROUPS (bmx_scan_aggregate)
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
+LIT_MINUS, LIT_SUBTRAHEND = 4, 8     # BMX_LIT_MINUS / BMX_LIT_SUBTRAHEND: the two entries of a field-to-field literal, lo <= a - b <= hi
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
 JOIN_MAP_OVERFLOW, JOIN_GROUP_OVERFLOW, JOIN_MAX_MAP = 1, 2, 1 << 20   # BMX_JOIN_MAP_OVERFLOW, BMX_JOIN_GROUP_OVERFLOW (flags of bmx_join_res), BMX_JOIN_MAX_MAP (bmx_join.h bmx_where_join_group)
@@ -189,11 +190,22 @@ def _where_top_tail(k, desc, after):
     return _top_args([], k, desc, after)[2:]          # (flags, cursor, k)
 
 
+def _where_entries(t):
+    """one literal of a clause -> its bmx_lit entries: one, or for ((a, b), lo, hi[, negated]) — lo <= a - b <= hi — the MINUS entry and its SUBTRAHEND entry"""
+    neg = LIT_NOT if len(t) > 3 and t[3] else 0
+    if isinstance(t[0], (tuple, list)):
+        a, b = t[0]
+        return [Lit(int(a), LIT_MINUS | neg, int(t[1]), int(t[2])), Lit(int(b), LIT_SUBTRAHEND, 0, 0)]
+    return [Lit(int(t[0]), neg, int(t[1]), int(t[2]))]
+
+
 def _where_args(base, clauses):
-    """clauses: a list of lists of (field, lo, hi) or (field, lo, hi, negated) -> (base_field, nclauses, clause_len, lits)"""
-    flat = [t for c in clauses for t in c]
-    lens = (C.c_uint32 * max(len(clauses), 1))(*[len(c) for c in clauses])
-    lits = (Lit * max(len(flat), 1))(*[Lit(int(t[0]), LIT_NOT if len(t) > 3 and t[3] else 0, int(t[1]), int(t[2])) for t in flat])
+    """clauses: a list of lists of (field, lo, hi), (field, lo, hi, negated) or, comparing two fields of a node, ((a, b), lo, hi[, negated])
+    -> (base_field, nclauses, clause_len, lits)"""
+    ents = [[e for t in c for e in _where_entries(t)] for c in clauses]
+    flat = [e for c in ents for e in c]
+    lens = (C.c_uint32 * max(len(clauses), 1))(*[len(c) for c in ents])
+    lits = (Lit * max(len(flat), 1))(*flat)
     return (int(base), len(clauses), lens, lits)
 
 

@@ -42,10 +42,10 @@ int quant_scratch(bmx_ctx* ctx, uint64_t rows) {
 // what the digit sweeps of one call read, fixed by its pass 0
 struct QuantSrc { bool fits32 = false /* the 4-byte base column; otherwise 8-byte values: the int64 column or the value scratch */; const void* col = nullptr; uint64_t n = 0; uint32_t nt = 0, blocks = 1; };
 
-template <class T>
-void quant_launch0(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, uint32_t blocks, const QuantArgs& A, bool probe) {
-  if (probe) hipLaunchKernelGGL((k_quant0<T, true>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
-  else hipLaunchKernelGGL((k_quant0<T, false>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
+template <class T, bool PAIRS>
+void quant_launch0(bmx_ctx* ctx, const Index* ix, const PredWhere<T, PAIRS>& P, uint32_t blocks, const QuantArgs& A, bool probe) {
+  if (probe) hipLaunchKernelGGL((k_quant0<T, true, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
+  else hipLaunchKernelGGL((k_quant0<T, false, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
 }
 
 // Pass 0 of one call over a prepared program, enqueued; *src: where its digit sweeps find the values. The context has been entered. A value-ordered view of the
@@ -59,7 +59,7 @@ int quant_enqueue0(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32
   QuantArgs A{};
   A.mask = ctx->scan.mask; A.vals = ctx->quant.vals; A.S = ctx->quant.state; A.measure = measure_field;
   ctx->quant.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { quant_launch0(ctx, ix, P, blocks, A, probe); });
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_plain_or_pairs(P, [&](const auto& Q) { quant_launch0(ctx, ix, Q, blocks, A, probe); }); });
   LAUNCHCHK("k_quant0");
   src->fits32 = !probe && ix->fits32; src->n = ix->n;
   src->col = probe ? static_cast<const void*>(ctx->quant.vals) : (ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64));

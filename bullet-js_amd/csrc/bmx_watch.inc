@@ -83,8 +83,9 @@ int watch_diff(bmx_ctx* ctx, uint32_t id) {
   if ((uint64_t)nb * (SCAN_BLOCK_ELEMS / 32) > w.prev_words) return fail(ctx, BMX_ERR_INTERNAL, "bmx_watch_poll: the index outgrew its columns without a new layout");
   if (int rc = S.ensure(ctx, nb)) return rc;
   where_sweep(ctx, ix, w.W, [&](const auto& P, uint32_t) {      // (one workgroup per block, as the scans' mask pass: the sweep grid is not used)
-    using T = decltype(where_value(P));
-    hipLaunchKernelGGL((k_watch_mask<PredWhere<T>>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, (const uint32_t*)w.prev, S.entered, S.counts, (uint32_t)S.blocks_cap);
+    where_plain_or_pairs(P, [&](const auto& Q) {
+      hipLaunchKernelGGL((k_watch_mask<std::decay_t<decltype(Q)>>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, Q, ix->n, (const uint32_t*)w.prev, S.entered, S.counts, (uint32_t)S.blocks_cap);
+    });
   });
   LAUNCHCHK("k_watch_mask");
   hipLaunchKernelGGL(k_watch_totals, dim3(1), dim3(SEL_THREADS), 0, ctx->stream, (const uint32_t*)S.counts, (const uint32_t*)(S.counts + S.blocks_cap),

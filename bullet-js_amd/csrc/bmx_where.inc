@@ -6,9 +6,10 @@
 // shard through where_run's deferred form and fetches with scan_collect, like bmx_comm_scan_filter.
 namespace {
 
-// The caller's program as the kernel takes it: the field table (fields other than the base field, in order of first use), per literal its slot, per clause its
+// The caller's program as the kernel takes it: the field table (fields other than the base field and ordered field pairs, in order of first use), per literal its slot, per clause its
 // literal range (inside a clause the literals on the base field first), per field the set of its literals, the bounds clamped to the value domain (a lower bound of -VAL_MAX keeps tombstones out of every range; an
-// upper bound of VAL_MAX changes no answer). Host arithmetic only. nullptr: the program is fine; otherwise why it is refused (nothing is written then).
+// upper bound of VAL_MAX changes no answer). A MINUS entry and the SUBTRAHEND entry behind it become one literal on the slot of their pair (A, B), with the
+// bounds as given. Host arithmetic only. nullptr: the program is fine; otherwise why it is refused (nothing is written then).
 const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, WhereProg* out) {
   if (nclauses == 0 || nclauses > WHERE_MAX_CLAUSES) return "bmx_scan_where needs 1..8 clauses";
   if (!clause_len || !lits) return "bmx_scan_where: null clause_len or lits";
@@ -23,22 +24,43 @@ const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t
   uint32_t l = 0, first = 0;                  // l: the kernel's literal number; first: the clause's first literal in the caller's list
   for (uint32_t c = 0; c < nclauses; first += clause_len[c], c++) {
     W.cbeg[c] = l;
+    // the entries one by one: the flag bits, and a MINUS entry and its SUBTRAHEND entry next to each other inside the clause
+    for (uint32_t k = 0; k < clause_len[c]; k++) {
+      const bmx_lit& in = lits[first + k];
+      if (in.flags & ~(BMX_LIT_NOT | BMX_LIT_MINUS | BMX_LIT_SUBTRAHEND)) return "bmx_scan_where: unknown flag bits";
+      if (in.flags & BMX_LIT_SUBTRAHEND) {
+        if (in.flags != BMX_LIT_SUBTRAHEND) return "bmx_scan_where: BMX_LIT_SUBTRAHEND goes with no other flag";
+        if (in.lo != 0 || in.hi != 0) return "bmx_scan_where: a BMX_LIT_SUBTRAHEND entry has lo = hi = 0";
+        if (k == 0 || !(lits[first + k - 1].flags & BMX_LIT_MINUS)) return "bmx_scan_where: a BMX_LIT_SUBTRAHEND entry follows no BMX_LIT_MINUS entry";
+        if (in.field == lits[first + k - 1].field) return "bmx_scan_where: a field minus itself";
+      } else if (in.flags & BMX_LIT_MINUS) {
+        if (k + 1 == clause_len[c]) return "bmx_scan_where: a BMX_LIT_MINUS entry ends its clause";
+        if (!(lits[first + k + 1].flags & BMX_LIT_SUBTRAHEND)) return "bmx_scan_where: a BMX_LIT_MINUS entry is followed by no BMX_LIT_SUBTRAHEND entry";
+      }
+    }
     // an AND does not care for its order: the literals on the base field go in front, so a lane whose column value fails one leaves the clause before any probe
     for (int probed = 0; probed < 2; probed++) {
       for (uint32_t k = 0; k < clause_len[c]; k++) {
         const bmx_lit& in = lits[first + k];
-        if (in.flags & ~BMX_LIT_NOT) return "bmx_scan_where: unknown flag bits";
-        if ((in.field != base_field) != (probed != 0)) continue;
+        if (in.flags & BMX_LIT_SUBTRAHEND) continue;               // (taken with the MINUS entry in front of it)
+        const bool pair = in.flags & BMX_LIT_MINUS;                // A - B: always among the probed, also when A is the base field
+        if ((pair || in.field != base_field) != (probed != 0)) continue;
         WhereLit& o = W.lit[l];
         o.neg = in.flags & BMX_LIT_NOT;
-        o.lo = above_tombstones(in.lo);
-        o.hi = std::min<int64_t>(in.hi, VAL_MAX);
+        o.lo = pair ? in.lo : above_tombstones(in.lo);             // (a difference is no stored value: its bounds are taken as given)
+        o.hi = pair ? in.hi : std::min<int64_t>(in.hi, VAL_MAX);
         if (!probed) { o.slot = 0; W.base_lits |= 1u << l; l++; continue; }
+        const uint32_t second = pair ? lits[first + k + 1].field : 0u;
         uint32_t s = 0;
-        while (s < W.nfields && W.field[s] != in.field) s++;
+        while (s < W.nfields && (W.field[s] != in.field || ((W.pairs >> s) & 1u) != (uint32_t)pair || (pair && W.field2[s] != second))) s++;
         if (s == W.nfields) {
-          if (s == WHERE_MAX_FIELDS) return "bmx_scan_where: more than 8 fields besides the base field";
+          if (s == WHERE_MAX_FIELDS) return pair ? "bmx_scan_where: no slot left for a field pair (8 fields and pairs besides the base field)"
+                                                 : "bmx_scan_where: more than 8 fields besides the base field";
           W.field[W.nfields++] = in.field;
+          if (pair) {
+            W.field2[s] = second;
+            W.pairs |= (1u | (in.field == base_field ? 1u << WHERE_PAIR_A_BASE : 0u) | (second == base_field ? 1u << WHERE_PAIR_B_BASE : 0u)) << s;
+          }
         }
         o.slot = s + 1u;
         W.flits[s] |= 1u << l;
@@ -58,8 +80,17 @@ PredWhere<T> where_pred(bmx_ctx* ctx, const Index* ix, const WhereProg& W) {
   P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = W;
   return P;
 }
-template <class T>
-T where_value(const PredWhere<T>&);      // (never defined) decltype(where_value(P)): the width of a predicate
+template <class T, bool PAIRS>
+T where_value(const PredWhere<T, PAIRS>&);      // (never defined) decltype(where_value(P)): the width of a predicate
+// For the kernels that are built with and without the pair path (where_kernels.h PredWhere's PAIRS): f(the predicate), the pair path compiled in only when the
+// program has a pair slot, so a program of plain literals runs the registers and the occupancy it always ran.
+template <class T, class F>
+decltype(auto) where_plain_or_pairs(const PredWhere<T>& P, F&& f) {
+  if (P.W.pairs) return f(P);
+  PredWhere<T, false> Q;
+  Q.v = P.v; Q.ids = P.ids; Q.slots = P.slots; Q.nslots = P.nslots; Q.nt = P.nt; Q.W = P.W;
+  return f(Q);
+}
 // the grid of the sweeps: no workgroup with fewer than four rounds of loads to spread its one flush over
 template <class T>
 uint32_t where_agg_grid(bmx_ctx* ctx, const Index* ix) { return sweep_grid(ctx, ix->n, 4ull * TOP_THREADS * TOP_U * (16 / sizeof(T))); }

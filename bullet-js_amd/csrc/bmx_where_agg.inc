@@ -41,10 +41,10 @@ int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   return BMX_OK;
 }
 
-template <class T>
-int where_top_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, const TopArgs& A, uint32_t k) {
+template <class T, bool PAIRS>
+int where_top_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T, PAIRS>& P, const TopArgs& A, uint32_t k) {
   return top_launch_with<T, true>(ctx, ix, A, k, [&](const T*, uint32_t blocks, uint32_t) {
-    hipLaunchKernelGGL((k_where_top0<T>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
+    hipLaunchKernelGGL((k_where_top0<T, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
   });
 }
 
@@ -60,7 +60,7 @@ int where_top_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   A.desc = flags & BMX_TOP_DESC;
   top_set_cursor(A, after);
   ctx->top.clean = false;
-  if (int rc = where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return where_top_launch(ctx, ix, P, A, k); })) return rc;     // (the grid is top_launch_with's own)
+  if (int rc = where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return where_plain_or_pairs(P, [&](const auto& Q) { return where_top_launch(ctx, ix, Q, A, k); }); })) return rc;     // (the grid is top_launch_with's own)
   return top_launch_finish(ctx, A, k, d_out, d_n_out, d_n_eligible);
 }
 

@@ -128,8 +128,8 @@ __host__ __device__ inline bmx_quant_res quant_result(unsigned long long n_match
   return r;
 }
 
-template <class T, bool PROBE>
-__global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T> P, QuantArgs A) {
+template <class T, bool PROBE, bool PAIRS>      // (PAIRS: the program has a field pair; where_kernels.h PredWhere)
+__global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T, PAIRS> P, QuantArgs A) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_m[TOP_WAVES], s_n[TOP_WAVES], s_mn[TOP_WAVES], s_mx[TOP_WAVES];

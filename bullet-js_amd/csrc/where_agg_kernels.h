@@ -70,8 +70,8 @@ __global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere
   agg_end<G>(A, L, S);
 }
 
-template <class T>
-__global__ __launch_bounds__(TOP_THREADS) void k_where_top0(uint64_t n, PredWhere<T> P, TopArgs A) {
+template <class T, bool PAIRS>      // (PAIRS: the program has a field pair; where_kernels.h PredWhere)
+__global__ __launch_bounds__(TOP_THREADS) void k_where_top0(uint64_t n, PredWhere<T, PAIRS> P, TopArgs A) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES], s_mn[TOP_WAVES], s_mx[TOP_WAVES];

@@ -7,6 +7,9 @@
 // A lane keeps two words: `truth`, one bit per literal, and `known`, one bit per probed field. The first literal of a field that a live clause reaches probes
 // the field and sets the truth bits of ALL its literals (WhereProg::flits), so later literals of that field — in this clause or another — are bit tests. There is
 // no per-field value array: indexed at run time it would live in scratch.
+// A slot of the field table is a probed field or an ordered pair of fields (A, B), whose literals range over A - B (bmx_where.h BMX_LIT_MINUS). The pair's
+// two values are fetched inside the same divergent branch — each from the column value when it is the base field, from a probe otherwise — and the slot's
+// truth bits are set from the difference as a plain slot's are from the value. Whether a slot is a pair is the same in every lane.
 // The clauses and literals are walked in loops whose counters are the same in every lane, so the literal constants come out of the kernel arguments through
 // scalar loads; only the probe sits under a divergent branch. A lane drops out of a clause at its first false literal and out of the walk at its first true
 // clause; the loops end early when no lane of the wave is left in them.
@@ -18,23 +21,29 @@ namespace bmx {
 
 constexpr uint32_t WHERE_MAX_CLAUSES = BMX_WHERE_MAX_CLAUSES, WHERE_MAX_LITS = BMX_WHERE_MAX_LITS, WHERE_MAX_FIELDS = BMX_WHERE_MAX_FIELDS;
 
-// one literal as the kernel takes it: slot 0 = the base field (the column value), slot s > 0 = WhereProg::field[s - 1]; bounds clamped to +-VAL_MAX
+// one literal as the kernel takes it: slot 0 = the base field (the column value), slot s > 0 = WhereProg::field[s - 1] or the pair there; bounds clamped to
+// +-VAL_MAX (a pair's: as given)
 struct WhereLit { uint32_t slot, neg; int64_t lo, hi; };
 static_assert(sizeof(WhereLit) == sizeof(bmx_lit), "a literal stays 24 bytes");
-// the prepared program (bmx_where.inc where_prepare): 888 bytes; PredWhere, the kernel argument that carries it, is 928
+// the prepared program (bmx_where.inc where_prepare): 920 bytes; PredWhere, the kernel argument that carries it, is 960
 struct WhereProg {
   uint32_t nclauses, nfields;
   uint32_t base_lits;                       // bit l: literal l is on the base field
-  uint32_t pad;
+  uint32_t pairs;                           // per slot s: bit s = the slot is a pair (A, B) and its literals range over A - B; bit 8 + s = A is the base field
+                                            // (the column value, no probe); bit 16 + s = B is
   uint32_t cbeg[WHERE_MAX_CLAUSES + 1];     // clause c = literals [cbeg[c], cbeg[c + 1]), those on the base field first
-  uint32_t field[WHERE_MAX_FIELDS];         // the probed fields, in order of first use
-  uint32_t flits[WHERE_MAX_FIELDS];         // bit l: literal l is on field[s]
+  uint32_t field[WHERE_MAX_FIELDS];         // the slots in order of first use: a probed field, or the A of a pair
+  uint32_t field2[WHERE_MAX_FIELDS];        // the B of a pair slot
+  uint32_t flits[WHERE_MAX_FIELDS];         // bit l: literal l is on slot s
   WhereLit lit[WHERE_MAX_LITS];
 };
+constexpr uint32_t WHERE_PAIR_A_BASE = 8u, WHERE_PAIR_B_BASE = 16u;      // shifts inside WhereProg::pairs
 
-static_assert(sizeof(WhereProg) == 888, "the program stays far below the 4 KB of kernel arguments");
+static_assert(sizeof(WhereProg) == 920, "the program stays far below the 4 KB of kernel arguments");
 
-template <class T>
+// PAIRS = false compiles the pair path out: for a program without a pair slot (WhereProg::pairs == 0, the host's promise: bmx_where.inc where_plain_or_pairs).
+// Only the kernels that would lose a wave of occupancy to the pair path's registers are built both ways (k_watch_mask, k_quant0, k_where_top0); every other one takes the default.
+template <class T, bool PAIRS = true>
 struct PredWhere {   // T = int32_t / int64_t: the width of the base field's value column; 16 bytes per lane and load
   static constexpr int E = 16 / (int)sizeof(T);
   static constexpr T TOMB = sizeof(T) == 4 ? (T)INT32_MIN : (T)INT64_MIN;      // what a tombstoned row looks like in the column (scan_kernels.h v32_of)
@@ -58,10 +67,19 @@ struct PredWhere {   // T = int32_t / int64_t: the width of the base field's val
           const uint32_t fb = 1u << (s - 1u);
           if (alive && !(known & fb)) {                            // the one divergent branch: this lane needs the field now
             if (!known) id = ids[i];
-            int64_t y = VAL_DELETED;
-            const bool have = agg_probe(slots, nslots, id, W.field[s - 1u], y);
+            // A, or the plain field: from a probe unless it is the base field of a pair. A probe that finds no row leaves VAL_DELETED, which is also what a
+            // tombstoned row holds (agg_probe finds that one): no flag is kept across the second probe, each side is tested for VAL_DELETED behind it.
+            int64_t y = x;
+            if (!PAIRS || !(W.pairs & (fb << WHERE_PAIR_A_BASE))) { y = VAL_DELETED; agg_probe(slots, nslots, id, W.field[s - 1u], y); }      // (uniform)
+            bool have = true;                                      // (a plain literal: lo >= -VAL_MAX keeps VAL_DELETED out of every range)
+            if (PAIRS && (W.pairs & fb)) {                         // (uniform) a pair: both sides hold data, y = A - B (exact: |A|, |B| <= VAL_MAX)
+              int64_t b = x;                                       // (the bounds of a pair literal are as given and keep nothing out: `have` does)
+              if (!(W.pairs & (fb << WHERE_PAIR_B_BASE))) { b = VAL_DELETED; agg_probe(slots, nslots, id, W.field2[s - 1u], b); }
+              have = y != VAL_DELETED && b != VAL_DELETED;
+              y = (int64_t)((uint64_t)y - (uint64_t)b);
+            }
             for (uint32_t bm = W.flits[s - 1u]; bm; bm &= bm - 1u) {
-              const uint32_t j = (uint32_t)__ffs((int)bm) - 1u;    // (lo >= -VAL_MAX: a tombstone is inside no range)
+              const uint32_t j = (uint32_t)__ffs((int)bm) - 1u;
               truth |= (uint32_t)((have && y >= W.lit[j].lo && y <= W.lit[j].hi) != (W.lit[j].neg != 0u)) << j;
             }
             known |= fb;

@@ -131,7 +131,8 @@ class DeviceGraph {
   }
   /* Boolean filter (bmx_scan_where, include/bmx_where.h): the nodes holding data in field `base` for which some clause of clauses has all of its literals
    * true. clauses: [[[field, lo, hi, not], ...], ...] — a literal is true iff the node's row of field holds data inside lo..hi; with a truthy `not` it is
-   * the exact complement, so true for an absent or deleted field too. -> BigUint64Array of node ids, in index order of `base` (shard after shard). */
+   * the exact complement, so true for an absent or deleted field too. [field, lo, hi, not, field2] compares two fields of the node: true iff both hold
+   * data and lo <= field - field2 <= hi. -> BigUint64Array of node ids, in index order of `base` (shard after shard). */
   scanWhere(base, clauses) {
     if (this.preOp) this.preOp();
     return this.comm ? this.native.commScanWhere(this.comm, base, clauses) : this.native.scanWhere(this.handle, base, clauses);

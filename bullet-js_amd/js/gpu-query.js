@@ -38,8 +38,13 @@ function cmpVal(a, b) {
 
 /* where() / whereTop() on the host: the truth of one normalised literal for one child of the store */
 function literalTruth(child, t) {
-  const x = child && typeof child === "object" ? child[t.field] : undefined;
+  let x = child && typeof child === "object" ? child[t.field] : undefined;
   let pos = x !== null && x !== undefined;
+  if (t.minus !== undefined) {             // field - minus: both present; anything but two numbers gives NaN, inside no bounds (`undefined > x` is false)
+    const y = child && typeof child === "object" ? child[t.minus] : undefined;
+    pos = pos && y !== null && y !== undefined;
+    x = pos && typeof x === "number" && typeof y === "number" ? x - y : NaN;
+  }
   if (pos) pos = t.eq ? x === t.min : (t.min === -Infinity || x >= t.min) && (t.max === Infinity || x <= t.max);
   return pos !== t.not;
 }
@@ -394,7 +399,9 @@ class GpuQuery {
    * Boolean filter: OR of AND-clauses over fields of the same child node, with NOT and with defined behaviour for absent fields — the shapes of
    * filter(path, fn) that an AND of ranges cannot say (docs/querying.md Example 8: `user.active === true && user.age < 30 && user.role !== "admin"`).
    * clauses: [[{field, min, max, not}, ...], ...]; {field, eq: v} is min = max = v and {field, ne: v} is its negation; a bound left out (or +-Infinity) is
-   * not checked, so {field} alone tests presence and {field, not: true} absence.
+   * not checked, so {field} alone tests presence and {field, not: true} absence. {field, minus: "other", ...} compares two fields of the child: the bounds
+   * are on field - other (`o.shipped > o.due` is {field: "shipped", minus: "due", min: 1} on integers), true iff both are present and the difference is
+   * inside; its negation is true when either is missing.
    * opts.over (required) names the field that defines the universe: only children that carry it are candidates — the children filter() would iterate,
    * provided every child the caller cares about carries it. A literal is true iff the child's field is present (not null / undefined) and inside its bounds;
    * a negated literal is the exact complement, so it is true for a child WITHOUT the field, as `undefined !== "admin"` is.
@@ -420,33 +427,37 @@ class GpuQuery {
   }
 
   /* The program of where(), whereAggregate() and whereTop(), normalised: {field, eq: v} is min = max = v, {field, ne: v} its negation, a bound left out (or
-   * +-Infinity) is open. -> {norm, base (the index of `over`), native}: native is the program as the device takes it ([[[field, lo, hi, not], ...], ...], possibly
+   * +-Infinity) is open. -> {norm, base (the index of `over`), native}: native is the program as the device takes it ([[[field, lo, hi, not(, field2)], ...], ...], possibly
    * empty: no clause can be true) when every index involved is an integer index, and null when one lives on the host. */
   _whereProgram(path, clauses, over) {
     const open = (x) => x === undefined || x === null || x === Infinity || x === -Infinity;
     const norm = clauses.map((c) => c.map((t) => {
-      if ("eq" in t) return { field: t.field, min: t.eq, max: t.eq, eq: true, not: !!t.not };
-      if ("ne" in t) return { field: t.field, min: t.ne, max: t.ne, eq: true, not: !t.not };
-      return { field: t.field, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
+      const minus = t.minus === undefined || t.minus === null ? undefined : t.minus;      // {field, minus: other, ...}: the bounds are on field - other
+      if (minus !== undefined && minus === t.field) throw new RangeError("bmx: where compares a field with another field, not with itself");
+      if ("eq" in t) return { field: t.field, minus, min: t.eq, max: t.eq, eq: true, not: !!t.not };
+      if ("ne" in t) return { field: t.field, minus, min: t.ne, max: t.ne, eq: true, not: !t.not };
+      return { field: t.field, minus, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
     }));
     const base = this._fresh(path, over);
     // Which side answers is decided before a DEVICE index of a literal's field is built (it needs the device; the host evaluation reads the store and
     // needs none): "device" = every child that carries the field has a safe integer there, "absent" = no child carries it (_fieldKind).
     const kinds = new Map();
-    for (const c of norm) for (const t of c) if (!kinds.has(t.field)) kinds.set(t.field, this._fieldKind(path, t.field));
+    for (const c of norm) for (const t of c) for (const f of t.minus === undefined ? [t.field] : [t.field, t.minus]) if (!kinds.has(f)) kinds.set(f, this._fieldKind(path, f));
     const onDevice = base.kind === "device" && Array.from(kinds.values()).every((k) => k !== "host");
     if (!onDevice) return { norm, base, native: null };
     const num = (x) => typeof x === "number" && !Number.isNaN(x);
     // A field no child carries is decided here: its positive literals are false (their clause goes), its negated ones true (the literal goes); a clause
-    // left without a literal is true for every candidate, which a presence literal on the base field says.
+    // left without a literal is true for every candidate, which a presence literal on the base field says. A pair with such a side is decided the same way.
+    const absent = (t) => kinds.get(t.field) === "absent" || (t.minus !== undefined && kinds.get(t.minus) === "absent");
     const native = [];
     for (const c of norm) {
-      if (c.some((t) => kinds.get(t.field) === "absent" && !t.not)) continue;
-      const lits = c.filter((t) => kinds.get(t.field) !== "absent").map((t) => {
+      if (c.some((t) => absent(t) && !t.not)) continue;
+      const lits = c.filter((t) => !absent(t)).map((t) => {
         const f = this._fresh(path, t.field).deviceField;
+        const tail = t.minus === undefined ? [] : [this._fresh(path, t.minus).deviceField];      // [f, lo, hi, not, f2]: lo <= f - f2 <= hi
         // bounds no integer satisfies (a string against an integer field, a fraction as eq): the empty range, whose negation is always true
-        if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not];
-        return [f, Math.ceil(t.min), Math.floor(t.max), t.not];
+        if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not, ...tail];
+        return [f, Math.ceil(t.min), Math.floor(t.max), t.not, ...tail];
       });
       native.push(lits.length ? lits : [[base.deviceField, -Infinity, Infinity, false]]);
     }

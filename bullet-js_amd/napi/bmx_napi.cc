@@ -546,26 +546,36 @@ napi_value where_answer(napi_env env, Handle<Comm>* h, uint32_t base, uint32_t n
 }
 /* Boolean filters (bmx_where.h bmx_scan_where): thin bindings, no logic.
  * scanWhere(handle, base, [[[field, lo, hi, not], ...], ...]) / commScanWhere(comm, ...) -> BigUint64Array: the nodes holding data in field `base` for which some
- * clause has all of its literals true (not: a truthy fourth entry negates the literal), in index order of `base`. */
-// [[[field, lo, hi, not], ...], ...] -> the program as bmx_scan_where takes it; false with a JS error pending
+ * clause has all of its literals true (not: a truthy fourth entry negates the literal), in index order of `base`. A fifth entry, [field, lo, hi, not, field2],
+ * compares two fields of the node: lo <= field - field2 <= hi (bmx_where.h BMX_LIT_MINUS). */
+// [[[field, lo, hi, not(, field2)], ...], ...] -> the program as bmx_scan_where takes it; false with a JS error pending
 struct Program { uint32_t nc = 0; uint32_t lens[BMX_WHERE_MAX_CLAUSES]; std::vector<bmx_lit> lits; };
 bool get_program(napi_env env, napi_value clauses, Program* P) {
   if (napi_get_array_length(env, clauses, &P->nc) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
   if (P->nc == 0 || P->nc > BMX_WHERE_MAX_CLAUSES) { napi_throw_range_error(env, nullptr, "bmx: where needs 1..8 clauses"); return false; }
   for (uint32_t c = 0; c < P->nc; c++) {
     napi_value cl;
-    if (napi_get_element(env, clauses, c, &cl) != napi_ok || napi_get_array_length(env, cl, &P->lens[c]) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
-    if (P->lens[c] == 0 || P->lens[c] > 8 || P->lits.size() + P->lens[c] > BMX_WHERE_MAX_LITS) { napi_throw_range_error(env, nullptr, "bmx: a where clause has 1..8 literals, a program 32 at most"); return false; }
-    for (uint32_t k = 0; k < P->lens[c]; k++) {
-      napi_value t, e[4]; bmx_lit L{0, 0, 0, 0}; bool neg = false;
+    uint32_t nl;
+    if (napi_get_element(env, clauses, c, &cl) != napi_ok || napi_get_array_length(env, cl, &nl) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
+    P->lens[c] = 0;      // in entries: a literal [f, lo, hi, not, f2] (lo <= f - f2 <= hi) takes two, the BMX_LIT_MINUS entry and its BMX_LIT_SUBTRAHEND entry
+    for (uint32_t k = 0; k < nl && k < 8; k++) {
+      napi_value t, e[5]; bmx_lit L{0, 0, 0, 0}; bool neg = false;
       bool ok = napi_get_element(env, cl, k, &t) == napi_ok;
-      for (uint32_t j = 0; ok && j < 4; j++) ok = napi_get_element(env, t, j, &e[j]) == napi_ok;
-      if (!ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
+      for (uint32_t j = 0; ok && j < 5; j++) ok = napi_get_element(env, t, j, &e[j]) == napi_ok;
+      napi_valuetype second = napi_undefined;
+      if (!ok || napi_typeof(env, e[4], &second) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
       if (!get_u32(env, e[0], &L.field) || !get_i64(env, e[1], &L.lo) || !get_i64(env, e[2], &L.hi)) return false;
       if (napi_coerce_to_bool(env, e[3], &e[3]) != napi_ok || napi_get_value_bool(env, e[3], &neg) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_coerce_to_bool"); return false; }
-      L.flags = neg ? BMX_LIT_NOT : 0u;
-      P->lits.push_back(L);
+      const bool pair = second != napi_undefined && second != napi_null;
+      L.flags = (neg ? BMX_LIT_NOT : 0u) | (pair ? BMX_LIT_MINUS : 0u);
+      P->lits.push_back(L); P->lens[c]++;
+      if (pair) {
+        bmx_lit B{0, BMX_LIT_SUBTRAHEND, 0, 0};
+        if (!get_u32(env, e[4], &B.field)) return false;
+        P->lits.push_back(B); P->lens[c]++;
+      }
     }
+    if (nl == 0 || nl > 8 || P->lens[c] > 8 || P->lits.size() > BMX_WHERE_MAX_LITS) { napi_throw_range_error(env, nullptr, "bmx: a where clause has 1..8 literals, a program 32 at most"); return false; }
   }
   return true;
 }

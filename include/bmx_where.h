@@ -17,6 +17,15 @@
  *   is never taken for a small value: {NOT, lo = INT64_MIN, hi = anything} is true on a tombstone because the field is absent. A literal on base_field is
  *   evaluated on the column value and costs no probe; every other distinct field is probed at most once per candidate, however many literals name it, and only
  *   for candidates whose answer still depends on it.
+ * Field-to-field literals (`o.shipped > o.due`, `s.end - s.start <= 3600`): an entry with BMX_LIT_MINUS names field A and the bounds (and may carry
+ *   BMX_LIT_NOT); the NEXT entry of the same clause names field B as {field = B, flags = BMX_LIT_SUBTRAHEND, lo = 0, hi = 0}. The two entries are one literal:
+ *   true iff the node's rows of A and of B both hold data and lo <= value(A) - value(B) <= hi. With BMX_LIT_NOT it is the exact complement, so true when
+ *   either side is absent or tombstoned (`undefined > x` is false on the reference). Values lie in +-(2^53 - 1), so the difference is exact in int64
+ *   (|d| <= 2^54 - 2); the bounds are taken as given, not clamped: a == b is [0, 0], a != b the same with NOT, a > b is [1, INT64_MAX], a <= b + 5 is
+ *   [INT64_MIN, 5], "both present" is [INT64_MIN, INT64_MAX]; lo > hi is never true and, negated, always. Either side may be base_field: it is then the
+ *   column value and costs no probe. Both entries count toward clause_len (<= 8) and toward BMX_WHERE_MAX_LITS. An ordered pair (A, B) takes one of the
+ *   BMX_WHERE_MAX_FIELDS slots that the distinct plain fields besides base_field also take; (A, B) and (B, A) are different slots; several literals on one
+ *   pair share the slot and its probes. A field used both alone and inside a pair is probed in each of its slots (there is no cache across slots).
  * Answer: node ids in position order of base_field's index columns (the order bmx_scan_filter gives without a view). *n_out is the number of matches even when
  *   cap is smaller; nothing is written at or beyond out_ids[cap]; out_ids == NULL counts only.
  * mem: as for bmx_scan_filter. BMX_MEM_HOST is synchronous; BMX_MEM_DEVICE takes out_ids and n_out as device pointers and only enqueues. An ordinary entry
@@ -25,7 +34,9 @@
  *   bmx_scan_top does. Answering from the view when every clause bounds base_field is a follow-up.
  * BMX_ERR_INVALID, before any device work and without writing anything: nclauses outside 1..BMX_WHERE_MAX_CLAUSES, a clause_len of 0 or above 8, more than
  *   BMX_WHERE_MAX_LITS literals in all, more than BMX_WHERE_MAX_FIELDS distinct fields besides base_field, unknown flag bits, clause_len or lits NULL, a bad mem,
- *   a NULL context / communicator.
+ *   a NULL context / communicator. And, each with a text of its own: a BMX_LIT_MINUS entry that ends its clause or is followed by anything but a
+ *   BMX_LIT_SUBTRAHEND entry, a BMX_LIT_SUBTRAHEND entry not preceded by a BMX_LIT_MINUS entry, BMX_LIT_SUBTRAHEND together with any other bit or with
+ *   lo / hi not 0, A == B, a pair that would need a ninth slot.
  * bmx_comm_scan_where (host memory): the shards' answers one after the other, the way bmx_comm_scan_filter works; every shard's sweep is enqueued before the
  *   first answer is fetched. A node's rows all live on the shard that owns its id, so the set equals the set one context holding the same rows gives. */
 #ifndef BMX_WHERE_H
@@ -38,9 +49,11 @@ extern "C" {
 
 typedef struct bmx_lit { uint32_t field; uint32_t flags; int64_t lo, hi; } bmx_lit;   /* 24 bytes, same layout as bmx_term */
 #define BMX_LIT_NOT           1u
+#define BMX_LIT_MINUS         4u    /* this entry is A, lo, hi [, NOT]; the NEXT entry names B */
+#define BMX_LIT_SUBTRAHEND    8u    /* {field = B, flags = exactly this, lo = 0, hi = 0} */
 #define BMX_WHERE_MAX_CLAUSES 8u
 #define BMX_WHERE_MAX_LITS    32u   /* over all clauses */
-#define BMX_WHERE_MAX_FIELDS  8u    /* distinct fields other than base_field */
+#define BMX_WHERE_MAX_FIELDS  8u    /* slots: distinct fields other than base_field, and ordered field pairs */
 
 int bmx_scan_where(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits,
                    uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem);
