@@ -5,7 +5,7 @@ after, from two compiler logs. No GPU needed.
 
 once on the parent commit and once on this tree, then
 
-  python bench_micro/where_diff_resources.py BEFORE.log AFTER.log > profiles/where_diff_resources.txt
+  python bench_micro/where_diff_resources.py BEFORE.log AFTER.log ["what the tree adds"] > profiles/where_diff_resources.txt
 
 Exit status 1 if a kernel gained scratch or lost a wave of occupancy."""
 import re
@@ -14,6 +14,8 @@ import sys
 
 FAMILIES = ["k_scan_mask", "k_scan_emit", "k_where_agg", "k_group_sweep", "k_watch_mask", "k_rows_emit", "k_semi_build", "k_join_group_sweep", "k_jrows_emit",
             "k_upd_emit", "k_mgroup_sweep", "k_reach_prepare", "k_first_sweep", "k_quant0"]
+CLOCKED = ("k_first_sweep", "k_group_sweep", "k_join_build", "k_join_group_sweep", "k_jrows_build", "k_mgroup_sweep", "k_reach_prepare", "k_reach_seed",
+           "k_semi_build", "k_where_agg")      # families whose last template argument says whether the clock literals are compiled in
 KEYS = [("VGPRs", "VGPRs"), ("TotalSGPRs", "SGPRs"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "occupancy")]
 
 
@@ -61,6 +63,18 @@ def table(path):
 def before_name(s):
     """the parent's name of a kernel of this tree; None: the kernel is new. PredWhere's second argument (the pair path compiled in) defaults to true; the
     kernels built both ways carry it as `false` when it is off, and their `true` build runs programs with a pair only, which the parent refuses."""
+    # A tree with the clock literals: every build of a kernel is held against the parent's build that ran the same programs.
+    #   Pred{RowsFrom,JRowsFrom,Semi,Upd}<T, CLOCKS>        -> <T>           (the parent had the one build)
+    #   k_x<..., CLOCKS> of the CLOCKED families             -> k_x<...>      (the same)
+    #   k_scan_mask<PredWhere<T, PAIRS, CLOCKS>, ...>        -> <T, true>     (the parent's id scan had the one build, pair path in it, for every program;
+    #                                                                          so <T, false, false>, the plain programs' build, shows fewer registers)
+    #   k_watch_mask<PredWhere<T, PAIRS, CLOCKS>>            -> <T, PAIRS>    (built both ways by the parent already)
+    t = re.sub(r"(Pred(?:RowsFrom|JRowsFrom|Semi|Upd)<\w+), (?:true|false)>", r"\1>", s)
+    if family(t) in CLOCKED:
+        t = re.sub(r", (?:true|false)>$", ">", t)
+    t = re.sub(r"PredWhere<(\w+), (true|false), (?:true|false)>", (lambda m: "PredWhere<%s, true>" % m.group(1)) if family(t) == "k_scan_mask" else r"PredWhere<\1, \2>", t)
+    if t != s:
+        return t
     if family(s) in ("k_quant0", "k_where_top0"):
         return re.sub(r", false>$", ">", s) if s.endswith(", false>") else None
     if "PredWhere<int, false>" in s or "PredWhere<long, false>" in s:
@@ -70,14 +84,14 @@ def before_name(s):
     return re.sub(r"PredWhere<(\w+), true>", r"PredWhere<\1>", s)
 
 
-def main(before_path, after_path):
+def main(before_path, after_path, what="field-to-field literals"):
     before, after = table(before_path), table(after_path)
     bad, seen = [], set()
-    print("kernel resource usage, gfx950, -O3: before (parent commit) -> after (field-to-field literals)")
+    print("kernel resource usage, gfx950, -O3: before (parent commit) -> after (%s)" % what)
     print("%-9s %-9s %-8s %-10s kernel" % tuple(k for _, k in KEYS))
     for s in sorted(after):
         seen.add(family(s))
-        a, b = after[s], before.get(before_name(s) or "")
+        a, b = after[s], before.get(s) or before.get(before_name(s) or "")      # (a parent that builds kernels both ways already knows this tree's names)
         cells = ["%s->%d" % ("new" if b is None else b[k], a[k]) for k, _ in KEYS]
         print("%-9s %-9s %-8s %-10s %s%s" % (*cells, s, "" if b else "   (programs with a field pair only)"))
         if b is not None and (a[KEYS[2][0]] > b[KEYS[2][0]] or a[KEYS[3][0]] < b[KEYS[3][0]]):
@@ -89,4 +103,4 @@ def main(before_path, after_path):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:4]))

@@ -28,6 +28,7 @@ AGG_NO_FIELD, AGG_MAX_GROUPS = 0xFFFFFFFF, 65536   # BMX_AGG_NO_FIELD ("no measu
 TOP_DESC, TOP_MAX_K = 1, 4096   # BMX_TOP_DESC, BMX_TOP_MAX_K (bmx_top.h bmx_scan_top)
 LIT_NOT, WHERE_MAX_CLAUSES, WHERE_MAX_LITS, WHERE_MAX_FIELDS = 1, 8, 32, 8   # BMX_LIT_NOT and the limits of one program (bmx_where.h bmx_scan_where)
 LIT_MINUS, LIT_SUBTRAHEND = 4, 8     # BMX_LIT_MINUS / BMX_LIT_SUBTRAHEND: the two entries of a field-to-field literal, lo <= a - b <= hi
+LIT_CLOCK, LIT_CLOCK_TOMB = 16, 32   # BMX_LIT_CLOCK / BMX_LIT_CLOCK_TOMB: the literal ranges over the row's clock; a row that holds data / a tombstoned row qualifies
 GROUP_OVERFLOW, GROUP_MAX_CAP = 1, 1 << 20   # BMX_GROUP_OVERFLOW (flags of bmx_group_res), BMX_GROUP_MAX_CAP (bmx_group.h bmx_where_group)
 ROWS_MAX_FIELDS, ROWS_TS, ROWS_NO_CLOCK = 8, 1, -1   # BMX_ROWS_MAX_FIELDS, BMX_ROWS_TS (flags), BMX_ROWS_NO_CLOCK (the clock of an absent cell) (bmx_rows.h bmx_where_rows)
 JOIN_MAP_OVERFLOW, JOIN_GROUP_OVERFLOW, JOIN_MAX_MAP = 1, 2, 1 << 20   # BMX_JOIN_MAP_OVERFLOW, BMX_JOIN_GROUP_OVERFLOW (flags of bmx_join_res), BMX_JOIN_MAX_MAP (bmx_join.h bmx_where_join_group)
@@ -178,7 +179,8 @@ def top_merge(lists, k, desc=False):
 
 
 class Lit(C.Structure):
-    """bmx_lit: one literal of a bmx_scan_where program (24 bytes, the layout of bmx_term); flags: LIT_NOT"""
+    """bmx_lit: one literal of a bmx_scan_where program (24 bytes, the layout of bmx_term); flags: LIT_NOT, LIT_MINUS, LIT_SUBTRAHEND,
+    LIT_CLOCK, LIT_CLOCK_TOMB"""
     _fields_ = [("field", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
@@ -190,9 +192,23 @@ def _where_top_tail(k, desc, after):
     return _top_args([], k, desc, after)[2:]          # (flags, cursor, k)
 
 
+class Clock:
+    """The field of a clock literal: (Clock(field, data=True, tombs=False), lo, hi[, negated]) is true iff the node's row of `field` exists in a state named
+    here (data, tombstoned) and lo <= its clock <= hi; negated it is the exact complement (bmx_where.h BMX_LIT_CLOCK, BMX_LIT_CLOCK_TOMB)."""
+    __slots__ = ("field", "flags")
+
+    def __init__(self, field, data=True, tombs=False):
+        if not (data or tombs):
+            raise ValueError("bmx.Clock: a clock literal names data, tombstones or both")
+        self.field, self.flags = int(field), (LIT_CLOCK if data else 0) | (LIT_CLOCK_TOMB if tombs else 0)
+
+
 def _where_entries(t):
-    """one literal of a clause -> its bmx_lit entries: one, or for ((a, b), lo, hi[, negated]) — lo <= a - b <= hi — the MINUS entry and its SUBTRAHEND entry"""
+    """one literal of a clause -> its bmx_lit entries: one, or for ((a, b), lo, hi[, negated]) — lo <= a - b <= hi — the MINUS entry and its SUBTRAHEND entry;
+    (Clock(f, ...), lo, hi[, negated]) ranges over the clock of f's row"""
     neg = LIT_NOT if len(t) > 3 and t[3] else 0
+    if isinstance(t[0], Clock):
+        return [Lit(t[0].field, t[0].flags | neg, int(t[1]), int(t[2]))]
     if isinstance(t[0], (tuple, list)):
         a, b = t[0]
         return [Lit(int(a), LIT_MINUS | neg, int(t[1]), int(t[2])), Lit(int(b), LIT_SUBTRAHEND, 0, 0)]
@@ -200,7 +216,8 @@ def _where_entries(t):
 
 
 def _where_args(base, clauses):
-    """clauses: a list of lists of (field, lo, hi), (field, lo, hi, negated) or, comparing two fields of a node, ((a, b), lo, hi[, negated])
+    """clauses: a list of lists of (field, lo, hi), (field, lo, hi, negated), comparing two fields of a node ((a, b), lo, hi[, negated]), or over a row's clock
+    (Clock(field, ...), lo, hi[, negated])
     -> (base_field, nclauses, clause_len, lits)"""
     ents = [[e for t in c for e in _where_entries(t)] for c in clauses]
     flat = [e for c in ents for e in c]

@@ -81,8 +81,8 @@ int first_passes(bmx_ctx* ctx, Index* ix, uint32_t base_field, const WhereProg& 
   F.gw = A.g_src == AGG_SRC_PROBE ? s.gw : nullptr;
   F.ow = ((A.m_src == AGG_SRC_PROBE && !F.same) || !F.gw) ? s.ow : nullptr;
   ctx->group.clean = false; s.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_first_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, F);
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_first_sweep<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, F);
   });
   LAUNCHCHK("k_first_sweep");
   const uint32_t rgrid = sweep_grid(ctx, ix->n, 8ull * FIRST_THREADS);

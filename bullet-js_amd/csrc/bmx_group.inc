@@ -55,8 +55,8 @@ int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_
   A.measure = measure_field; A.group = group_field;
   A.m_src = where_agg_source(measure_field, base_field); A.g_src = where_agg_source(group_field, base_field);
   s.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_group_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_group_sweep<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
   });
   LAUNCHCHK("k_group_sweep");
   hipLaunchKernelGGL(k_group_finish, dim3(group_finish_grid(A.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,

@@ -63,8 +63,8 @@ int mgroup_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32
   while ((1ull << A.shift) < A.T.slots) A.shift++;
   for (uint32_t j = 0; j < nkeys; j++) A.k[j] = MGroupKey{keys[j].origin, keys[j].width, keys[j].field, where_agg_source(keys[j].field, base_field)};
   s.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_mgroup_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_mgroup_sweep<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
   });
   LAUNCHCHK("k_mgroup_sweep");
   hipLaunchKernelGGL(k_mgroup_finish, dim3(group_finish_grid(A.T.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,

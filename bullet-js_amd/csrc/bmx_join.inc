@@ -60,8 +60,8 @@ int join_build(bmx_ctx* ctx, const JoinArgs& J, uint32_t in_base_field, const Wh
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t ksrc = where_agg_source(key_field, in_base_field);
   const uint32_t asrc = attr_field == key_field ? JOIN_SRC_KEY : where_agg_source(attr_field, in_base_field);
-  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_join_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc, attr_field, asrc);
+  where_sweep_c(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_join_build<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc, attr_field, asrc);
   });
   LAUNCHCHK("k_join_build");
   return BMX_OK;
@@ -82,8 +82,8 @@ int join_sweep(bmx_ctx* ctx, const JoinArgs& J, uint32_t base_field, const Where
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
   GroupArgs A;
   if (int rc = join_group_args(ctx, base_field, w, &A)) return rc;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_join_group_sweep<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, J);
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_join_group_sweep<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, J);
   });
   LAUNCHCHK("k_join_group_sweep");
   hipLaunchKernelGGL(k_join_finish, dim3(semi_finish_grid(std::max(A.slots, J.slots))), dim3(JOIN_THREADS), 0, ctx->stream, A, J, d_out ? d_out : ctx->group.stage,

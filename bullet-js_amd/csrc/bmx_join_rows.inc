@@ -46,8 +46,8 @@ int jrows_build(bmx_ctx* ctx, const JoinArgs& J, uint32_t in_base_field, const W
   Index* ix;
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t ksrc = where_agg_source(key_field, in_base_field);
-  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_jrows_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc);
+  where_sweep_c(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_jrows_build<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, J, key_field, ksrc);
   });
   LAUNCHCHK("k_jrows_build");
   return BMX_OK;
@@ -79,7 +79,8 @@ int jrows_mask(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const JRow
   const JRowsLink L = jrows_link(J, w.link_field, base_field);
   return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(join rows)", &ctx->rows.masked, [&](const auto& P) {
     using T = decltype(where_value(P));
-    return PredJRowsFrom<T>{PredRowsFrom<T>{P, start}, L};
+    constexpr bool C = where_clocks<decltype(P)>;
+    return PredJRowsFrom<T, C>{PredRowsFrom<T, C>{P, start}, L};
   });
 }
 

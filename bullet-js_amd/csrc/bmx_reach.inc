@@ -51,8 +51,8 @@ int reach_seed(bmx_ctx* ctx, const ReachRun& R, uint32_t seed_base_field, const 
   Index* ix;
   if (int rc = fresh_index(ctx, seed_base_field, &ix)) return rc;
   const uint32_t src = where_agg_source(seed_field, seed_base_field);
-  where_sweep(ctx, ix, WS, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_reach_seed<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, R.J, R.A.S, seed_field, src);
+  where_sweep_c(ctx, ix, WS, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_reach_seed<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, R.J, R.A.S, seed_field, src);
   });
   LAUNCHCHK("k_reach_seed");
   return BMX_OK;
@@ -87,8 +87,8 @@ int reach_prepare(bmx_ctx* ctx, ReachRun* R, uint32_t base_field, const WherePro
   R->K = ReachKey{ix->ids, ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64), ctx->slots, ctx->nslots, w.key_field,
                   where_agg_source(w.key_field, base_field)};
   const uint32_t src = where_agg_source(w.link_field, base_field);
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_reach_prepare<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, R->A, w.link_field, src);
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_reach_prepare<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, R->A, w.link_field, src);
   });
   LAUNCHCHK("k_reach_prepare");
   return BMX_OK;

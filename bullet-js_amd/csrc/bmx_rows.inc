@@ -24,7 +24,7 @@ const char* rows_bad_args(const RowsWant& w, uint64_t cap, const uint64_t* out_i
 // Pass 1 of one call on one context: the base index brought up to date, the mask of the selected positions from `start` on and the counts per block into the
 // scans' scratch. The context has been entered.
 int rows_mask(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint64_t start) {
-  return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(rows)", &ctx->rows.masked, [&](const auto& P) { return PredRowsFrom<decltype(where_value(P))>{P, start}; });
+  return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(rows)", &ctx->rows.masked, [&](const auto& P) { return PredRowsFrom<decltype(where_value(P)), where_clocks<decltype(P)>>{P, start}; });
 }
 
 // Pass 2 behind rows_mask: up to `cap` rows into the columns d_ids / d_val / d_ts of stride cap and the record into d_res (all device memory).

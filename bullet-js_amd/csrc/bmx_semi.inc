@@ -65,8 +65,8 @@ int semi_build(bmx_ctx* ctx, const SemiArgs& A, uint32_t in_base_field, const Wh
   Index* ix;
   if (int rc = fresh_index(ctx, in_base_field, &ix)) return rc;
   const uint32_t src = where_agg_source(key_field, in_base_field);
-  where_sweep(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_semi_build<decltype(where_value(P))>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, key_field, src);
+  where_sweep_c(ctx, ix, WI, [&](const auto& P, uint32_t blocks) {
+    hipLaunchKernelGGL((k_semi_build<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, key_field, src);
   });
   LAUNCHCHK("k_semi_build");
   return BMX_OK;
@@ -79,9 +79,9 @@ int semi_insert_list(bmx_ctx* ctx, const SemiArgs& A, const long long* d_values,
   return BMX_OK;
 }
 
-template <class T>
-int semi_scan(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, const SemiArgs& A, uint32_t base_field, const SemiWant& w, uint64_t* d_ids, uint64_t d_cap) {
-  PredSemi<T> Q;
+template <class T, bool CLOCKS>
+int semi_scan(bmx_ctx* ctx, const Index* ix, const PredWhere<T, true, CLOCKS>& P, const SemiArgs& A, uint32_t base_field, const SemiWant& w, uint64_t* d_ids, uint64_t d_cap) {
+  PredSemi<T, CLOCKS> Q;
   Q.P = P;
   Q.keys = A.keys; Q.slots = A.slots; Q.S = A.S; Q.cap = A.cap;
   Q.link = w.link_field; Q.link_src = where_agg_source(w.link_field, base_field); Q.anti = w.flags & BMX_SEMI_ANTI;
@@ -100,7 +100,7 @@ int semi_probe(bmx_ctx* ctx, const SemiArgs& A, uint32_t base_field, const Where
     if (d_cap) { if (int rc = semi_stage_ids(ctx, d_cap)) return rc; d_ids = s.stage_ids; }
     s.staged = d_cap;
   }
-  if (int rc = where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return semi_scan(ctx, ix, P, A, base_field, w, d_ids, d_cap); })) return rc;     // (the grid is run_scan_t's own)
+  if (int rc = where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t) { return semi_scan(ctx, ix, P, A, base_field, w, d_ids, d_cap); })) return rc;     // (the grid is run_scan_t's own)
   hipLaunchKernelGGL(k_semi_finish, dim3(semi_finish_grid(A.slots)), dim3(SEMI_THREADS), 0, ctx->stream, A, d_res ? d_res : s.stage_res);
   LAUNCHCHK("k_semi_finish");
   s.clean = true;

@@ -51,7 +51,7 @@ int upd_ensure(bmx_ctx* ctx, uint64_t scap) {
 // scans' scratch, the nodes without source and outside the range into the counter shards. The context has been entered.
 int upd_mask(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const UpdWant& w, uint64_t start) {
   return where_mask_pass(ctx, base_field, W, "launch k_scan_mask(update)", &ctx->upd.masked,
-    [&](const auto& P) { using T = decltype(where_value(P)); return PredUpd<T>{PredRowsFrom<T>{P, start}, w.S, ctx->upd.ctr}; },
+    [&](const auto& P) { using T = decltype(where_value(P)); constexpr bool C = where_clocks<decltype(P)>; return PredUpd<T, C>{PredRowsFrom<T, C>{P, start}, w.S, ctx->upd.ctr}; },
     [](bmx_ctx* x) { return upd_ensure(x, 0); });      // (the counter shards, in front of the launch that reads their address)
 }
 

@@ -8,7 +8,7 @@ namespace {
 
 // The caller's program as the kernel takes it: the field table (fields other than the base field and ordered field pairs, in order of first use), per literal its slot, per clause its
 // literal range (inside a clause the literals on the base field first), per field the set of its literals, the bounds clamped to the value domain (a lower bound of -VAL_MAX keeps tombstones out of every range; an
-// upper bound of VAL_MAX changes no answer). A MINUS entry and the SUBTRAHEND entry behind it become one literal on the slot of their pair (A, B), with the
+// upper bound of VAL_MAX changes no answer). A clock literal goes to the plain slot of its field (the base field has one for its clock literals) with the bounds as given. A MINUS entry and the SUBTRAHEND entry behind it become one literal on the slot of their pair (A, B), with the
 // bounds as given. Host arithmetic only. nullptr: the program is fine; otherwise why it is refused (nothing is written then).
 const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, WhereProg* out) {
   if (nclauses == 0 || nclauses > WHERE_MAX_CLAUSES) return "bmx_scan_where needs 1..8 clauses";
@@ -27,7 +27,11 @@ const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t
     // the entries one by one: the flag bits, and a MINUS entry and its SUBTRAHEND entry next to each other inside the clause
     for (uint32_t k = 0; k < clause_len[c]; k++) {
       const bmx_lit& in = lits[first + k];
-      if (in.flags & ~(BMX_LIT_NOT | BMX_LIT_MINUS | BMX_LIT_SUBTRAHEND)) return "bmx_scan_where: unknown flag bits";
+      if (in.flags & ~(BMX_LIT_NOT | BMX_LIT_MINUS | BMX_LIT_SUBTRAHEND | BMX_LIT_CLOCK | BMX_LIT_CLOCK_TOMB)) return "bmx_scan_where: unknown flag bits";
+      if (in.flags & (BMX_LIT_CLOCK | BMX_LIT_CLOCK_TOMB)) {       // a clock literal ranges over one row's clock, never over a difference
+        if (in.flags & BMX_LIT_MINUS) return "bmx_scan_where: a clock literal goes with no BMX_LIT_MINUS";
+        if (in.flags & BMX_LIT_SUBTRAHEND) return "bmx_scan_where: a clock literal goes with no BMX_LIT_SUBTRAHEND";
+      }
       if (in.flags & BMX_LIT_SUBTRAHEND) {
         if (in.flags != BMX_LIT_SUBTRAHEND) return "bmx_scan_where: BMX_LIT_SUBTRAHEND goes with no other flag";
         if (in.lo != 0 || in.hi != 0) return "bmx_scan_where: a BMX_LIT_SUBTRAHEND entry has lo = hi = 0";
@@ -44,11 +48,12 @@ const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t
         const bmx_lit& in = lits[first + k];
         if (in.flags & BMX_LIT_SUBTRAHEND) continue;               // (taken with the MINUS entry in front of it)
         const bool pair = in.flags & BMX_LIT_MINUS;                // A - B: always among the probed, also when A is the base field
-        if ((pair || in.field != base_field) != (probed != 0)) continue;
+        const bool clock = in.flags & (BMX_LIT_CLOCK | BMX_LIT_CLOCK_TOMB);      // the row's clock: always among the probed, the index column holds no clocks
+        if ((pair || clock || in.field != base_field) != (probed != 0)) continue;
         WhereLit& o = W.lit[l];
-        o.neg = in.flags & BMX_LIT_NOT;
-        o.lo = pair ? in.lo : above_tombstones(in.lo);             // (a difference is no stored value: its bounds are taken as given)
-        o.hi = pair ? in.hi : std::min<int64_t>(in.hi, VAL_MAX);
+        o.flags = (in.flags & BMX_LIT_NOT ? WHERE_LIT_NOT : 0u) | (in.flags & BMX_LIT_CLOCK ? WHERE_LIT_CLOCK_DATA : 0u) | (in.flags & BMX_LIT_CLOCK_TOMB ? WHERE_LIT_CLOCK_TOMB : 0u);
+        o.lo = pair || clock ? in.lo : above_tombstones(in.lo);    // (a difference or a clock is no stored value: its bounds are taken as given)
+        o.hi = pair || clock ? in.hi : std::min<int64_t>(in.hi, VAL_MAX);
         if (!probed) { o.slot = 0; W.base_lits |= 1u << l; l++; continue; }
         const uint32_t second = pair ? lits[first + k + 1].field : 0u;
         uint32_t s = 0;
@@ -62,6 +67,7 @@ const char* where_prepare(uint32_t base_field, uint32_t nclauses, const uint32_t
             W.pairs |= (1u | (in.field == base_field ? 1u << WHERE_PAIR_A_BASE : 0u) | (second == base_field ? 1u << WHERE_PAIR_B_BASE : 0u)) << s;
           }
         }
+        if (clock) W.pairs |= 1u << (WHERE_SLOT_CLOCK + s);       // (a field's value literals and clock literals share its plain slot and its one probe)
         o.slot = s + 1u;
         W.flits[s] |= 1u << l;
         l++;
@@ -80,16 +86,31 @@ PredWhere<T> where_pred(bmx_ctx* ctx, const Index* ix, const WhereProg& W) {
   P.ids = ix->ids; P.slots = ctx->slots; P.nslots = ctx->nslots; P.nt = ix->n * sizeof(T) > SCAN_NT_BYTES; P.W = W;
   return P;
 }
-template <class T, bool PAIRS>
-T where_value(const PredWhere<T, PAIRS>&);      // (never defined) decltype(where_value(P)): the width of a predicate
-// For the kernels that are built with and without the pair path (where_kernels.h PredWhere's PAIRS): f(the predicate), the pair path compiled in only when the
-// program has a pair slot, so a program of plain literals runs the registers and the occupancy it always ran.
+template <class T, bool PAIRS, bool CLOCKS>
+T where_value(const PredWhere<T, PAIRS, CLOCKS>&);      // (never defined) decltype(where_value(P)): the width of a predicate
+// For the kernels that are built with and without the pair path and the clock literals (where_kernels.h PredWhere's PAIRS): f(the predicate), those compiled in
+// only when the program has a pair slot or a clock literal (either sets bits of W.pairs), so a program of plain literals runs the registers and the occupancy it
+// always ran.
+template <class P>
+constexpr bool where_clocks = std::decay_t<P>::HAS_CLOCKS;      // where_clocks<decltype(P)>: is the clock literals' code compiled into this predicate
+template <bool PAIRS, bool CLOCKS, class T>
+PredWhere<T, PAIRS, CLOCKS> where_pred_as(const PredWhere<T>& P) {
+  PredWhere<T, PAIRS, CLOCKS> Q;
+  Q.v = P.v; Q.ids = P.ids; Q.slots = P.slots; Q.nslots = P.nslots; Q.nt = P.nt; Q.W = P.W;
+  return Q;
+}
 template <class T, class F>
 decltype(auto) where_plain_or_pairs(const PredWhere<T>& P, F&& f) {
   if (P.W.pairs) return f(P);
-  PredWhere<T, false> Q;
-  Q.v = P.v; Q.ids = P.ids; Q.slots = P.slots; Q.nslots = P.nslots; Q.nt = P.nt; Q.W = P.W;
-  return f(Q);
+  return f(where_pred_as<false, false>(P));
+}
+// ... and three ways, for the id scan (the other sweeps choose between the last two: where_sweep_c, where_mask_pass): a program of plain literals, one with pair slots and no clock literal, one with a clock literal. Each runs the code it
+// needs and no more; the first two run what they ran before there were clock literals.
+template <class T, class F>
+decltype(auto) where_by_paths(const PredWhere<T>& P, F&& f) {
+  if (!P.W.pairs) return f(where_pred_as<false, false>(P));
+  if (!(P.W.pairs >> WHERE_SLOT_CLOCK)) return f(where_pred_as<true, false>(P));
+  return f(P);
 }
 // the grid of the sweeps: no workgroup with fewer than four rounds of loads to spread its one flush over
 template <class T>
@@ -101,6 +122,16 @@ inline uint32_t where_agg_source(uint32_t field, uint32_t base_field) { return f
 template <class F>
 auto where_sweep(bmx_ctx* ctx, const Index* ix, const WhereProg& W, F&& f) {
   return by_width(ix->fits32, [&](auto t) { using T = decltype(t); return f(where_pred<T>(ctx, ix, W), where_agg_grid<T>(ctx, ix)); });
+}
+
+// ... for the sweeps whose kernels are built with and without the clock literals (their CLOCKS argument): f gets the build without them, which is the code these
+// kernels ran before there were clock literals, unless the program has one.
+template <class F>
+auto where_sweep_c(bmx_ctx* ctx, const Index* ix, const WhereProg& W, F&& f) {
+  return where_sweep(ctx, ix, W, [&](const auto& P, uint32_t grid) {
+    if (W.pairs >> WHERE_SLOT_CLOCK) return f(P, grid);
+    return f(where_pred_as<true, false>(P), grid);
+  });
 }
 
 // What every entry point over one context ends its own checks with, in this order: the mem kind, the context, the context entered.
@@ -128,8 +159,12 @@ int where_mask_pass(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, const
   if (ready) if (int rc = ready(ctx)) return rc;
   const uint32_t nb = (uint32_t)((std::max<uint64_t>(ix->n, 1) + SCAN_BLOCK_ELEMS - 1) / SCAN_BLOCK_ELEMS);
   by_width(ix->fits32, [&](auto t) {
-    auto P = make(where_pred<decltype(t)>(ctx, ix, W));
-    hipLaunchKernelGGL((k_scan_mask<decltype(P), true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
+    const auto launch = [&](const auto& Q) {                        // (the clock literals' code only for a program that has one, as where_sweep_c)
+      auto P = make(Q);
+      hipLaunchKernelGGL((k_scan_mask<decltype(P), true>), dim3(nb), dim3(SEL_THREADS), 0, ctx->stream, P, ix->n, ctx->scan.mask, ctx->scan.counts);
+    };
+    const auto P0 = where_pred<decltype(t)>(ctx, ix, W);
+    if (W.pairs >> WHERE_SLOT_CLOCK) launch(P0); else launch(where_pred_as<true, false>(P0));
   });
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail_hip(ctx, e, what);      // (LAUNCHCHK with a text that is no literal)
   *out = RowsScratch::Masked{ix->ids, ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64), ix->n, ix->layout, ix->fits32, nb};
@@ -156,7 +191,7 @@ void page_note(bool& cut, Res& tot, uint32_t g, uint64_t next_pos, bool more) {
 int where_run(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint64_t* out_ids, uint64_t cap, uint64_t* n_out, int mem, bool deferred) {
   Index* ix;
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  return where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return run_scan_t<false>(ctx, P, ix, out_ids, cap, n_out, mem, deferred); });
+  return where_sweep(ctx, ix, W, [&](const auto& P, uint32_t) { return where_by_paths(P, [&](const auto& Q) { return run_scan_t<false>(ctx, Q, ix, out_ids, cap, n_out, mem, deferred); }); });
 }
 
 }  // namespace

@@ -11,11 +11,11 @@ const char* where_agg_bad_args(uint32_t group_field, uint32_t ngroups, const bmx
 const char* where_top_bad_args(uint32_t flags, uint32_t k, const bmx_top_rec* out) { return top_bad_args(1, WHERE_AGG_NO_TERMS, flags, k, out); }
 
 // the sweep of one aggregate: flat, grouped in LDS, or grouped in device memory
-template <class T>
-void where_agg_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T>& P, uint32_t blocks, const AggArgs& A) {
-  if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
-  else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
-  else hipLaunchKernelGGL((k_where_agg<T, 2>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+template <class T, bool CLOCKS>
+void where_agg_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T, true, CLOCKS>& P, uint32_t blocks, const AggArgs& A) {
+  if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+  else hipLaunchKernelGGL((k_where_agg<T, 2, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
 }
 
 // Enqueue one aggregate over a prepared program; the records go to d_out (device memory), or, with d_out == nullptr, to the context's staging buffer
@@ -32,7 +32,7 @@ int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   A.m_src = where_agg_source(measure_field, base_field); A.g_src = ngroups ? where_agg_source(group_field, base_field) : AGG_SRC_NONE;
   A.nterms = 0;
   ctx->agg.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_agg_launch(ctx, ix, P, blocks, A); });
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_agg_launch(ctx, ix, P, blocks, A); });
   LAUNCHCHK("k_where_agg");
   hipLaunchKernelGGL(k_agg_finish, dim3(std::min<uint32_t>((nrec + 255) / 256, 64)), dim3(256), 0, ctx->stream, ctx->agg.raw, d_out ? d_out : ctx->agg.stage, nrec,
                      A.m_src != AGG_SRC_PROBE ? 1u : 0u);

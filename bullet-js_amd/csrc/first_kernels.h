@@ -60,8 +60,8 @@ struct FirstOut {
 };
 
 // one row of pass 1, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company); gs / os: the row's words for pass 2
-template <class T>
-__device__ __forceinline__ void first_row(const PredWhere<T>& P, const FirstArgs& F, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La,
+template <class T, bool CLOCKS>
+__device__ __forceinline__ void first_row(const PredWhere<T, true, CLOCKS>& P, const FirstArgs& F, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La,
                                           GroupLds& S, long long& gs, long long& os) {
   const GroupArgs& A = F.G;
   int64_t mval = x, gval = x;
@@ -97,8 +97,8 @@ __device__ __forceinline__ void first_store_unit(long long* w, uint64_t unit, co
   }
 }
 
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_first_sweep(uint64_t n, PredWhere<T> P, FirstArgs F) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_first_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, FirstArgs F) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;

@@ -138,8 +138,8 @@ __device__ __forceinline__ void group_row_put(const GroupArgs& A, bool go, int64
 }
 
 // one row of the sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company)
-template <class T>
-__device__ __forceinline__ void group_row(const PredWhere<T>& P, const GroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, GroupLds& S) {
+template <class T, bool CLOCKS>
+__device__ __forceinline__ void group_row(const PredWhere<T, true, CLOCKS>& P, const GroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, GroupLds& S) {
   int64_t mval = x, gval = x;
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
   if (sel) {
@@ -165,8 +165,8 @@ __device__ __forceinline__ void group_end(AggRaw* dst, AggLane& L, AggLds<0>& W)
   agg_end<0>(B, L, W);
 }
 
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T> P, GroupArgs A) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;

@@ -91,8 +91,8 @@ __device__ __forceinline__ bool join_find(const JoinPair* __restrict__ map, uint
 }
 
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field; attr_src: likewise, or JOIN_SRC_KEY
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_join_build(uint64_t n, PredWhere<T> P, JoinArgs A, uint32_t key_field, uint32_t key_src, uint32_t attr_field, uint32_t attr_src) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_join_build(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs A, uint32_t key_field, uint32_t key_src, uint32_t attr_field, uint32_t attr_src) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES], s_k[TOP_WAVES];
@@ -151,8 +151,8 @@ __device__ __forceinline__ void join_lane_add(AggLane& L, bool on, bool have_m, 
 }
 
 // one row of the group sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company). A.group / A.g_src are the LINK's.
-template <class T>
-__device__ __forceinline__ void join_row(const PredWhere<T>& P, const GroupArgs& A, const JoinPair* __restrict__ map, uint64_t mslots, bool sel, int64_t x, uint64_t pos,
+template <class T, bool CLOCKS>
+__device__ __forceinline__ void join_row(const PredWhere<T, true, CLOCKS>& P, const GroupArgs& A, const JoinPair* __restrict__ map, uint64_t mslots, bool sel, int64_t x, uint64_t pos,
                                          uint32_t lane, AggLane& Lt, AggLane& La, AggLane& Lu, GroupLds& S) {
   int64_t mval = x, lval = x;
   long long gval = JOIN_NO_ATTR;
@@ -185,8 +185,8 @@ __device__ __forceinline__ void join_row(const PredWhere<T>& P, const GroupArgs&
   if (nm || have_m) group_put(A, S, gval, nm, have_m, mval);
 }
 
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_join_group_sweep(uint64_t n, PredWhere<T> P, GroupArgs A, JoinArgs J) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_join_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A, JoinArgs J) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;

@@ -41,8 +41,8 @@ __host__ __device__ inline unsigned long long jrows_id(long long w) { return (un
 static_assert((unsigned long long)JOIN_NO_ATTR == (BMX_JROWS_NO_NODE ^ JROWS_BIAS), "the reserved id is the word of a slot without attribute");
 
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_jrows_build(uint64_t n, PredWhere<T> P, JoinArgs A, uint32_t key_field, uint32_t key_src) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_jrows_build(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs A, uint32_t key_field, uint32_t key_src) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES], s_k[TOP_WAVES];
@@ -100,10 +100,10 @@ __device__ __forceinline__ long long jrows_resolve(const JRowsLink& L, const T* 
   return w;
 }
 
-template <class T>
+template <class T, bool CLOCKS>
 struct PredJRowsFrom {   // the outer program behind a cursor AND (link value is a key of the map)
   static constexpr int E = PredWhere<T>::E;
-  PredRowsFrom<T> R;
+  PredRowsFrom<T, CLOCKS> R;
   JRowsLink L;
   __device__ uint32_t mask(uint64_t first, uint64_t n) const {
     if (!join_map_fits(L.S, L.mcap)) return 0u;                         // (uniform)

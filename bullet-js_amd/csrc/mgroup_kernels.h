@@ -83,8 +83,8 @@ __device__ __forceinline__ long long mgroup_bucket(long long v, long long origin
 }
 
 // one row of the sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company)
-template <class T>
-__device__ __forceinline__ void mgroup_row(const PredWhere<T>& P, const MGroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, MGroupLds& S) {
+template <class T, bool CLOCKS>
+__device__ __forceinline__ void mgroup_row(const PredWhere<T, true, CLOCKS>& P, const MGroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, MGroupLds& S) {
   int64_t mval = x;
   long long k0 = 0, k1 = 0, k2 = 0, k3 = 0;
   bool have_m = A.T.m_src == 0u, have_g = true;
@@ -131,8 +131,8 @@ __device__ __forceinline__ void mgroup_row(const PredWhere<T>& P, const MGroupAr
   if (nm || have_m) group_put(A.T, S.G, (long long)word, nm, have_m, mval);
 }
 
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_mgroup_sweep(uint64_t n, PredWhere<T> P, MGroupArgs A) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_mgroup_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, MGroupArgs A) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ MGroupLds S;

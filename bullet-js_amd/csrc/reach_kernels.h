@@ -95,8 +95,8 @@ __device__ __forceinline__ bool reach_has(const JoinPair* __restrict__ map, uint
 }
 
 // seed_src: 0 = the seed base field's column, AGG_SRC_PROBE = one probe of seed_field
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_reach_seed(uint64_t n, PredWhere<T> P, JoinArgs J, ReachState* R, uint32_t seed_field, uint32_t seed_src) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_reach_seed(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs J, ReachState* R, uint32_t seed_field, uint32_t seed_src) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES];
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_reach_list(const long long* __
 }
 
 // link_src: 0 = the base field's column, AGG_SRC_PROBE = one probe of link_field. Writes link[0, n) and depth[0, n).
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_reach_prepare(uint64_t n, PredWhere<T> P, ReachArgs A, uint32_t link_field, uint32_t link_src) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_reach_prepare(uint64_t n, PredWhere<T, true, CLOCKS> P, ReachArgs A, uint32_t link_field, uint32_t link_src) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES];

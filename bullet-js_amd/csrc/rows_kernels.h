@@ -23,10 +23,10 @@ namespace bmx {
 
 constexpr uint32_t ROWS_MAX_FIELDS = BMX_ROWS_MAX_FIELDS;
 
-template <class T>
+template <class T, bool CLOCKS>
 struct PredRowsFrom {   // PredWhere over the positions from `start` on
   static constexpr int E = PredWhere<T>::E;
-  PredWhere<T> P; uint64_t start;
+  PredWhere<T, true, CLOCKS> P; uint64_t start;
   __device__ uint32_t mask(uint64_t first, uint64_t n) const {
     if (first + E <= start) return 0u;
     return P.mask_from(first, n, start);

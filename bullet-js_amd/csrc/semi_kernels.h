@@ -94,8 +94,8 @@ __device__ __forceinline__ void semi_count_end(unsigned long long c, unsigned lo
 }
 
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field
-template <class T>
-__global__ __launch_bounds__(AGG_THREADS) void k_semi_build(uint64_t n, PredWhere<T> P, SemiArgs A, uint32_t key_field, uint32_t key_src) {
+template <class T, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_semi_build(uint64_t n, PredWhere<T, true, CLOCKS> P, SemiArgs A, uint32_t key_field, uint32_t key_src) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES];
@@ -128,10 +128,10 @@ __global__ __launch_bounds__(SEMI_THREADS) void k_semi_insert(const long long* _
   semi_count_end(cnt_l, s_n, SEMI_THREADS / 64, &A.S->n_inner);
 }
 
-template <class T>
+template <class T, bool CLOCKS>
 struct PredSemi {   // the outer program AND (link value in the set) / AND NOT (...)
   static constexpr int E = PredWhere<T>::E;
-  PredWhere<T> P;
+  PredWhere<T, true, CLOCKS> P;
   const long long* keys; uint64_t slots;
   const SemiState* S; uint64_t cap;               // the overflow state: the bit, or more claims than set_cap
   uint32_t link, link_src, anti;                  // link_src: 0 = the base field's column, AGG_SRC_PROBE = one probe of `link`

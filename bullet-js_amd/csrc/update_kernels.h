@@ -59,11 +59,11 @@ __device__ __forceinline__ uint32_t upd_wave_sum(uint32_t c) {
   return (uint32_t)__popcll(__ballot((c & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((c & 2u) != 0u)) + 4u * (uint32_t)__popcll(__ballot((c & 4u) != 0u));
 }
 
-template <class T>
+template <class T, bool CLOCKS>
 struct PredUpd {   // the program behind a cursor AND (the node's record can be written)
   static constexpr int E = PredWhere<T>::E;
   static_assert(E < 8, "upd_wave_sum takes a lane's count in three bits");
-  PredRowsFrom<T> R;
+  PredRowsFrom<T, CLOCKS> R;
   UpdSrc S;
   unsigned long long* ctr;                        // UPD_CTR_SHARDS x UPD_CTR_STRIDE words
   __device__ uint32_t mask(uint64_t first, uint64_t n) const {

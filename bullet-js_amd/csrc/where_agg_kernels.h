@@ -31,8 +31,8 @@ __device__ __forceinline__ T where_pick(const V& x, int e) {
 }
 
 // a candidate the program selected: the measure and the group value (the column value x, or one probe each), then the add. The table is P's.
-template <int G, class T>
-__device__ __forceinline__ void where_agg_row(const PredWhere<T>& P, const AggArgs& A, int64_t x, uint64_t pos, AggLane& L, AggLds<G>& S) {
+template <int G, class T, bool CLOCKS>
+__device__ __forceinline__ void where_agg_row(const PredWhere<T, true, CLOCKS>& P, const AggArgs& A, int64_t x, uint64_t pos, AggLane& L, AggLds<G>& S) {
   int64_t mval = x, gval = x;
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
   // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers
@@ -52,8 +52,8 @@ __device__ __forceinline__ void where_agg_row(const PredWhere<T>& P, const AggAr
   agg_add<G>(A, L, S, g, have_m, mval);
 }
 
-template <class T, int G>
-__global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T> P, AggArgs A) {
+template <class T, int G, bool CLOCKS>
+__global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T, true, CLOCKS> P, AggArgs A) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ AggLds<G> S;

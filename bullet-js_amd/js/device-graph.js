@@ -132,7 +132,8 @@ class DeviceGraph {
   /* Boolean filter (bmx_scan_where, include/bmx_where.h): the nodes holding data in field `base` for which some clause of clauses has all of its literals
    * true. clauses: [[[field, lo, hi, not], ...], ...] — a literal is true iff the node's row of field holds data inside lo..hi; with a truthy `not` it is
    * the exact complement, so true for an absent or deleted field too. [field, lo, hi, not, field2] compares two fields of the node: true iff both hold
-   * data and lo <= field - field2 <= hi. -> BigUint64Array of node ids, in index order of `base` (shard after shard). */
+   * data and lo <= field - field2 <= hi. [field, lo, hi, not, null, states] ranges over the CLOCK of the field's row: true iff the row exists in a state that
+   * `states` names (1 data, 2 deleted, 3 either) and lo <= clock <= hi (BMX_LIT_CLOCK / BMX_LIT_CLOCK_TOMB). -> BigUint64Array of node ids, in index order of `base` (shard after shard). */
   scanWhere(base, clauses) {
     if (this.preOp) this.preOp();
     return this.comm ? this.native.commScanWhere(this.comm, base, clauses) : this.native.scanWhere(this.handle, base, clauses);

@@ -45,10 +45,16 @@ function literalTruth(child, t) {
     pos = pos && y !== null && y !== undefined;
     x = pos && typeof x === "number" && typeof y === "number" ? x - y : NaN;
   }
+  if (t.clock !== undefined) {             // the clock of the row: a host index is built, never patched, so a present field is a data row of clock 1 (HOST_CLOCK)
+    pos = pos && t.clock !== "deleted";    // and an absent or deleted field is no row at all
+    x = HOST_CLOCK;
+  }
   if (pos) pos = t.eq ? x === t.min : (t.min === -Infinity || x >= t.min) && (t.max === Infinity || x <= t.max);
   return pos !== t.not;
 }
 
+const HOST_CLOCK = 1;                 // the clock of every row of an index as built (_buildDevice loads with clock 1); patches of a device index use 2, 3, ...
+const CLOCK_STATES = { data: 1, deleted: 2, any: 3 };      // the sixth entry of a native literal (bmx_where.h BMX_LIT_CLOCK = data, BMX_LIT_CLOCK_TOMB = deleted)
 const ORDERED_AUTO = 0xffffffff;      // BMX_INDEX_ORDERED_AUTO: the engine weighs a sort against the scans it saves
 const orderedOpt = (v) => (v === "auto" ? ORDERED_AUTO : v >>> 0);
 
@@ -401,7 +407,11 @@ class GpuQuery {
    * clauses: [[{field, min, max, not}, ...], ...]; {field, eq: v} is min = max = v and {field, ne: v} is its negation; a bound left out (or +-Infinity) is
    * not checked, so {field} alone tests presence and {field, not: true} absence. {field, minus: "other", ...} compares two fields of the child: the bounds
    * are on field - other (`o.shipped > o.due` is {field: "shipped", minus: "due", min: 1} on integers), true iff both are present and the difference is
-   * inside; its negation is true when either is missing.
+   * inside; its negation is true when either is missing. {field, clock: "data" | "deleted" | "any", ...} ranges over the CLOCK of the field's row in the
+   * index, with the same bound keys: true iff the row exists in the named state and its clock is inside. The clock of an index GpuQuery built is its patch
+   * sequence — 1 for every row of a build, 2, 3, ... for the rows each later patch rewrote ("what changed since patch N" is {clock: "data", min: N + 1}) —
+   * and a field that is deleted leaves the index at the next build, so "deleted" selects only in a device-sourced index, whose rows carry the table's own
+   * clocks and tombstones. whereRows(..., {clocks: true}) reports the clocks a term ranges over.
    * opts.over (required) names the field that defines the universe: only children that carry it are candidates — the children filter() would iterate,
    * provided every child the caller cares about carries it. A literal is true iff the child's field is present (not null / undefined) and inside its bounds;
    * a negated literal is the exact complement, so it is true for a child WITHOUT the field, as `undefined !== "admin"` is.
@@ -434,9 +444,12 @@ class GpuQuery {
     const norm = clauses.map((c) => c.map((t) => {
       const minus = t.minus === undefined || t.minus === null ? undefined : t.minus;      // {field, minus: other, ...}: the bounds are on field - other
       if (minus !== undefined && minus === t.field) throw new RangeError("bmx: where compares a field with another field, not with itself");
-      if ("eq" in t) return { field: t.field, minus, min: t.eq, max: t.eq, eq: true, not: !!t.not };
-      if ("ne" in t) return { field: t.field, minus, min: t.ne, max: t.ne, eq: true, not: !t.not };
-      return { field: t.field, minus, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
+      const clock = t.clock === undefined || t.clock === null ? undefined : t.clock;      // {field, clock: state, ...}: the bounds are on the clock of the field's row
+      if (clock !== undefined && !(clock in CLOCK_STATES)) throw new RangeError('bmx: a clock term names "data", "deleted" or "any"');
+      if (clock !== undefined && minus !== undefined) throw new RangeError("bmx: a clock term takes no minus");
+      if ("eq" in t) return { field: t.field, minus, clock, min: t.eq, max: t.eq, eq: true, not: !!t.not };
+      if ("ne" in t) return { field: t.field, minus, clock, min: t.ne, max: t.ne, eq: true, not: !t.not };
+      return { field: t.field, minus, clock, min: open(t.min) ? -Infinity : t.min, max: open(t.max) ? Infinity : t.max, eq: false, not: !!t.not };
     }));
     const base = this._fresh(path, over);
     // Which side answers is decided before a DEVICE index of a literal's field is built (it needs the device; the host evaluation reads the store and
@@ -454,7 +467,8 @@ class GpuQuery {
       if (c.some((t) => absent(t) && !t.not)) continue;
       const lits = c.filter((t) => !absent(t)).map((t) => {
         const f = this._fresh(path, t.field).deviceField;
-        const tail = t.minus === undefined ? [] : [this._fresh(path, t.minus).deviceField];      // [f, lo, hi, not, f2]: lo <= f - f2 <= hi
+        // [f, lo, hi, not, f2]: lo <= f - f2 <= hi; [f, lo, hi, not, null, states]: lo <= clock of f's row <= hi
+        const tail = t.clock !== undefined ? [null, CLOCK_STATES[t.clock]] : t.minus === undefined ? [] : [this._fresh(path, t.minus).deviceField];
         // bounds no integer satisfies (a string against an integer field, a fraction as eq): the empty range, whose negation is always true
         if (!num(t.min) || !num(t.max)) return [f, 1, 0, t.not, ...tail];
         return [f, Math.ceil(t.min), Math.floor(t.max), t.not, ...tail];
@@ -645,6 +659,7 @@ class GpuQuery {
    * where() that also reads (bmx_where_rows): the children that where(path, clauses, {over}) selects, each with the values of fieldNames — what
    * filter(path, fn) followed by .value() on every node, or map(path, fn) (src/bullet-query.js:322-333), does on the host.
    * opts: over (required), cap (children per page; left out: all of them), start (the .next of the page before).
+   * opts.clocks: the answer also carries clocks[i] = {name: clock} — the clock of the field's row in its index (see where()), undefined where there is no row.
    * -> {paths, rows, nMatch, next}: paths[i] is the path of the i-th delivered child, rows[i] = {name: value} with undefined for a cell without data (the
    * field is absent, null or deleted); nMatch counts the selected children from the cursor on; next is the cursor of the following page, null behind the last.
    * When every index involved — the program's and the projected fields' — is an integer index the device answers, in index order of `over`; a cursor is bound
@@ -654,7 +669,9 @@ class GpuQuery {
   whereRows(path, clauses, fieldNames, opts = {}) {
     if (opts.over === undefined || opts.over === null) throw new TypeError("bmx: whereRows needs opts.over, the field that defines the universe");
     const names = Array.from(new Set(fieldNames));
-    const done = (paths, rows, nMatch, next) => ({ paths, rows, nMatch, next });
+    const withClocks = !!opts.clocks;          // also clocks[i] = {name: clock of the field's row, undefined where there is none}
+    let clocks = withClocks ? [] : undefined;
+    const done = (paths, rows, nMatch, next) => (withClocks ? { paths, rows, clocks, nMatch, next } : { paths, rows, nMatch, next });
     if (!clauses || clauses.length === 0) return done([], [], 0, null);
     const { norm, base, native } = this._whereProgram(path, clauses, opts.over);
     const kinds = names.map((f) => this._fieldKind(path, f));
@@ -665,7 +682,7 @@ class GpuQuery {
       if (native.length === 0) return done([], [], 0, null);
       const present = names.filter((f, j) => kinds[j] === "device");       // (a field no child carries is undefined everywhere: nothing to ask)
       if (present.length > 8) throw new RangeError("bmx: whereRows projects 8 distinct fields at most");
-      const r = this.graph.whereRows(base.deviceField, native, present.map((f) => this._fresh(path, f).deviceField), { cap, start: start ? start.at : null });
+      const r = this.graph.whereRows(base.deviceField, native, present.map((f) => this._fresh(path, f).deviceField), { cap, start: start ? start.at : null, ts: withClocks });
       if (start && start.layout !== r.layout) {
         const err = new Error("bmx: the cursor belongs to an older layout of the index; start over");
         err.code = "BMX_STALE_CURSOR";
@@ -681,6 +698,12 @@ class GpuQuery {
         for (const f of names) row[f] = undefined;
         present.forEach((f, j) => { const v = r.vals[j][i]; if (v !== NONE) row[f] = Number(v); });
         rows[i] = row;
+        if (withClocks) {
+          const ck = {};
+          for (const f of names) ck[f] = undefined;
+          present.forEach((f, j) => { const c = r.ts[j][i]; if (c >= 0n) ck[f] = Number(c); });      // (NO_CLOCK = -1: no row)
+          clocks.push(ck);
+        }
       }
       const more = r.nMatch > n;
       return done(paths, rows, r.nMatch, more ? { at: this.graph.comm ? [r.nextShard, r.nextPos] : r.nextPos, layout: r.layout } : null);
@@ -697,6 +720,7 @@ class GpuQuery {
       for (const f of names) { const v = child ? child[f] : undefined; row[f] = v === null ? undefined : v; }
       return row;
     });
+    if (withClocks) clocks = rows.map((row) => { const ck = {}; for (const f of names) ck[f] = row[f] === undefined ? undefined : HOST_CLOCK; return ck; });
     const end = from + page.length;
     return done(paths, rows, selected.length - from, end < selected.length ? { at: end, layout: 0 } : null);
   }

@@ -547,7 +547,9 @@ napi_value where_answer(napi_env env, Handle<Comm>* h, uint32_t base, uint32_t n
 /* Boolean filters (bmx_where.h bmx_scan_where): thin bindings, no logic.
  * scanWhere(handle, base, [[[field, lo, hi, not], ...], ...]) / commScanWhere(comm, ...) -> BigUint64Array: the nodes holding data in field `base` for which some
  * clause has all of its literals true (not: a truthy fourth entry negates the literal), in index order of `base`. A fifth entry, [field, lo, hi, not, field2],
- * compares two fields of the node: lo <= field - field2 <= hi (bmx_where.h BMX_LIT_MINUS). */
+ * compares two fields of the node: lo <= field - field2 <= hi (bmx_where.h BMX_LIT_MINUS). A sixth entry, [field, lo, hi, not, null, states], makes the
+ * literal range over the CLOCK of the field's row (bmx_where.h BMX_LIT_CLOCK, BMX_LIT_CLOCK_TOMB): states 1 = a row that holds data qualifies, 2 = a tombstoned
+ * row, 3 = either. */
 // [[[field, lo, hi, not(, field2)], ...], ...] -> the program as bmx_scan_where takes it; false with a JS error pending
 struct Program { uint32_t nc = 0; uint32_t lens[BMX_WHERE_MAX_CLAUSES]; std::vector<bmx_lit> lits; };
 bool get_program(napi_env env, napi_value clauses, Program* P) {
@@ -559,15 +561,20 @@ bool get_program(napi_env env, napi_value clauses, Program* P) {
     if (napi_get_element(env, clauses, c, &cl) != napi_ok || napi_get_array_length(env, cl, &nl) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_array_length"); return false; }
     P->lens[c] = 0;      // in entries: a literal [f, lo, hi, not, f2] (lo <= f - f2 <= hi) takes two, the BMX_LIT_MINUS entry and its BMX_LIT_SUBTRAHEND entry
     for (uint32_t k = 0; k < nl && k < 8; k++) {
-      napi_value t, e[5]; bmx_lit L{0, 0, 0, 0}; bool neg = false;
+      napi_value t, e[6]; bmx_lit L{0, 0, 0, 0}; bool neg = false;
       bool ok = napi_get_element(env, cl, k, &t) == napi_ok;
-      for (uint32_t j = 0; ok && j < 5; j++) ok = napi_get_element(env, t, j, &e[j]) == napi_ok;
-      napi_valuetype second = napi_undefined;
-      if (!ok || napi_typeof(env, e[4], &second) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
+      for (uint32_t j = 0; ok && j < 6; j++) ok = napi_get_element(env, t, j, &e[j]) == napi_ok;
+      napi_valuetype second = napi_undefined, sixth = napi_undefined;
+      if (!ok || napi_typeof(env, e[4], &second) != napi_ok || napi_typeof(env, e[5], &sixth) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_get_element"); return false; }
       if (!get_u32(env, e[0], &L.field) || !get_i64(env, e[1], &L.lo) || !get_i64(env, e[2], &L.hi)) return false;
       if (napi_coerce_to_bool(env, e[3], &e[3]) != napi_ok || napi_get_value_bool(env, e[3], &neg) != napi_ok) { napi_throw_error(env, nullptr, "N-API call failed: napi_coerce_to_bool"); return false; }
       const bool pair = second != napi_undefined && second != napi_null;
-      L.flags = (neg ? BMX_LIT_NOT : 0u) | (pair ? BMX_LIT_MINUS : 0u);
+      uint32_t states = 0;      // the sixth entry: which row states a clock literal names
+      if (sixth != napi_undefined && sixth != napi_null) {
+        if (!get_u32(env, e[5], &states)) return false;
+        if (states == 0 || states > 3) { napi_throw_range_error(env, nullptr, "bmx: a clock literal names states 1 (data), 2 (deleted) or 3 (either)"); return false; }
+      }
+      L.flags = (neg ? BMX_LIT_NOT : 0u) | (pair ? BMX_LIT_MINUS : 0u) | (states & 1u ? BMX_LIT_CLOCK : 0u) | (states & 2u ? BMX_LIT_CLOCK_TOMB : 0u);
       P->lits.push_back(L); P->lens[c]++;
       if (pair) {
         bmx_lit B{0, BMX_LIT_SUBTRAHEND, 0, 0};

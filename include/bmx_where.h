@@ -26,6 +26,17 @@
  *   column value and costs no probe. Both entries count toward clause_len (<= 8) and toward BMX_WHERE_MAX_LITS. An ordered pair (A, B) takes one of the
  *   BMX_WHERE_MAX_FIELDS slots that the distinct plain fields besides base_field also take; (A, B) and (B, A) are different slots; several literals on one
  *   pair share the slot and its probes. A field used both alone and inside a pair is probed in each of its slots (there is no cache across slots).
+ * Clock literals ("written after clock T", "deleted since T", "exists in any state"): an entry with BMX_LIT_CLOCK, BMX_LIT_CLOCK_TOMB or both ranges over the
+ *   CLOCK of the node's row of `field`, not over its value. It is true iff the row exists, its state is one the bits name (data for BMX_LIT_CLOCK, a tombstone,
+ *   val == BMX_VAL_DELETED, for BMX_LIT_CLOCK_TOMB, either for both) and lo <= ts <= hi, both inclusive; ts is the clock bmx_get_rows reports (and the row
+ *   projection with clocks). With BMX_LIT_NOT it is the exact complement: true for an absent row, for a row in a state the literal does not name and for a clock outside the
+ *   range. The state decides and no sentinel is involved, so the bounds are taken as given, not clamped (clocks lie in 0..2^53 - 1,
+ *   so no stored row could tell the difference); lo > hi is never true and, negated, always.
+ *   {CLOCK_TOMB, INT64_MIN, INT64_MAX} is "the field is deleted", both bits over the full range "a row exists" (a plain literal cannot tell a tombstone from
+ *   an absent row). The index column holds no clocks, so a clock literal on base_field is a probed literal: it takes a slot and reads the base field's own
+ *   row; BMX_LIT_CLOCK_TOMB alone on base_field is never true, the candidates hold data. All plain and clock literals of one field share ONE slot and ONE
+ *   probe: the clock lies in the 32 bytes the value comes from. Pair slots stay apart. A clock bit goes with neither BMX_LIT_MINUS nor BMX_LIT_SUBTRAHEND
+ *   (differences of clocks are not offered).
  * Answer: node ids in position order of base_field's index columns (the order bmx_scan_filter gives without a view). *n_out is the number of matches even when
  *   cap is smaller; nothing is written at or beyond out_ids[cap]; out_ids == NULL counts only.
  * mem: as for bmx_scan_filter. BMX_MEM_HOST is synchronous; BMX_MEM_DEVICE takes out_ids and n_out as device pointers and only enqueues. An ordinary entry
@@ -36,7 +47,8 @@
  *   BMX_WHERE_MAX_LITS literals in all, more than BMX_WHERE_MAX_FIELDS distinct fields besides base_field, unknown flag bits, clause_len or lits NULL, a bad mem,
  *   a NULL context / communicator. And, each with a text of its own: a BMX_LIT_MINUS entry that ends its clause or is followed by anything but a
  *   BMX_LIT_SUBTRAHEND entry, a BMX_LIT_SUBTRAHEND entry not preceded by a BMX_LIT_MINUS entry, BMX_LIT_SUBTRAHEND together with any other bit or with
- *   lo / hi not 0, A == B, a pair that would need a ninth slot.
+ *   lo / hi not 0, A == B, a pair that would need a ninth slot, a clock bit together with BMX_LIT_MINUS, a clock bit together with BMX_LIT_SUBTRAHEND. A
+ *   clock literal that would need a ninth slot is refused as a ninth field is.
  * bmx_comm_scan_where (host memory): the shards' answers one after the other, the way bmx_comm_scan_filter works; every shard's sweep is enqueued before the
  *   first answer is fetched. A node's rows all live on the shard that owns its id, so the set equals the set one context holding the same rows gives. */
 #ifndef BMX_WHERE_H
@@ -51,6 +63,8 @@ typedef struct bmx_lit { uint32_t field; uint32_t flags; int64_t lo, hi; } bmx_l
 #define BMX_LIT_NOT           1u
 #define BMX_LIT_MINUS         4u    /* this entry is A, lo, hi [, NOT]; the NEXT entry names B */
 #define BMX_LIT_SUBTRAHEND    8u    /* {field = B, flags = exactly this, lo = 0, hi = 0} */
+#define BMX_LIT_CLOCK         16u   /* the literal ranges over the row's clock; a row that holds data qualifies */
+#define BMX_LIT_CLOCK_TOMB    32u   /* the literal ranges over the row's clock; a tombstoned row qualifies */
 #define BMX_WHERE_MAX_CLAUSES 8u
 #define BMX_WHERE_MAX_LITS    32u   /* over all clauses */
 #define BMX_WHERE_MAX_FIELDS  8u    /* slots: distinct fields other than base_field, and ordered field pairs */
