@@ -5,7 +5,7 @@ after, from two compiler logs. No GPU needed.
 
 once on the parent commit and once on this tree, then
 
-  python bench_micro/where_diff_resources.py BEFORE.log AFTER.log ["what the tree adds"] > profiles/where_diff_resources.txt
+  python bench_micro/where_diff_resources.py BEFORE.log AFTER.log ["what the tree adds" ["what the new kernels run"]] > profiles/where_diff_resources.txt
 
 Exit status 1 if a kernel gained scratch or lost a wave of occupancy."""
 import re
@@ -16,6 +16,7 @@ FAMILIES = ["k_scan_mask", "k_scan_emit", "k_where_agg", "k_group_sweep", "k_wat
             "k_upd_emit", "k_mgroup_sweep", "k_reach_prepare", "k_first_sweep", "k_quant0"]
 CLOCKED = ("k_first_sweep", "k_group_sweep", "k_join_build", "k_join_group_sweep", "k_jrows_build", "k_mgroup_sweep", "k_reach_prepare", "k_reach_seed",
            "k_semi_build", "k_where_agg")      # families whose last template argument says whether the clock literals are compiled in
+EXPR = {"k_where_agg": 4, "k_group_sweep": 3, "k_quant0": 4}      # families whose last template argument (of this many) says whether the measure is computed (bmx_expr.h)
 KEYS = [("VGPRs", "VGPRs"), ("TotalSGPRs", "SGPRs"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "occupancy")]
 
 
@@ -63,6 +64,11 @@ def table(path):
 def before_name(s):
     """the parent's name of a kernel of this tree; None: the kernel is new. PredWhere's second argument (the pair path compiled in) defaults to true; the
     kernels built both ways carry it as `false` when it is off, and their `true` build runs programs with a pair only, which the parent refuses."""
+    # A tree with the computed measures: the build without them is held against the parent's build of the same name less the flag; the build with them is new.
+    if family(s) in EXPR and s.count(",") + 1 == EXPR[family(s)]:
+        if s.endswith(", true>"):
+            return None
+        return re.sub(r", false>$", ">", s)      # (the parent of that tree has the clock literals: its names are this tree's less the last flag)
     # A tree with the clock literals: every build of a kernel is held against the parent's build that ran the same programs.
     #   Pred{RowsFrom,JRowsFrom,Semi,Upd}<T, CLOCKS>        -> <T>           (the parent had the one build)
     #   k_x<..., CLOCKS> of the CLOCKED families             -> k_x<...>      (the same)
@@ -84,7 +90,7 @@ def before_name(s):
     return re.sub(r"PredWhere<(\w+), true>", r"PredWhere<\1>", s)
 
 
-def main(before_path, after_path, what="field-to-field literals"):
+def main(before_path, after_path, what="field-to-field literals", new="programs with a field pair only"):
     before, after = table(before_path), table(after_path)
     bad, seen = [], set()
     print("kernel resource usage, gfx950, -O3: before (parent commit) -> after (%s)" % what)
@@ -93,7 +99,7 @@ def main(before_path, after_path, what="field-to-field literals"):
         seen.add(family(s))
         a, b = after[s], before.get(s) or before.get(before_name(s) or "")      # (a parent that builds kernels both ways already knows this tree's names)
         cells = ["%s->%d" % ("new" if b is None else b[k], a[k]) for k, _ in KEYS]
-        print("%-9s %-9s %-8s %-10s %s%s" % (*cells, s, "" if b else "   (programs with a field pair only)"))
+        print("%-9s %-9s %-8s %-10s %s%s" % (*cells, s, "" if b else "   (%s)" % new))
         if b is not None and (a[KEYS[2][0]] > b[KEYS[2][0]] or a[KEYS[3][0]] < b[KEYS[3][0]]):
             bad.append(s)
     missing = [f for f in FAMILIES if f not in seen]
@@ -103,4 +109,4 @@ def main(before_path, after_path, what="field-to-field literals"):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:4]))
+    sys.exit(main(*sys.argv[1:5]))

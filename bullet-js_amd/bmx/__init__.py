@@ -96,6 +96,10 @@ FIRST_DESC, FIRST_OVERFLOW, FIRST_NO_NODE, FIRST_MAX_CAP = 2, 1, (1 << 64) - 1, 
 # the first N nodes per group (include/bmx_group_top.h), likewise
 EXPORTS_GROUP_TOP = ["bmx_where_group_top", "bmx_comm_where_group_top"]
 GTOP_DESC, GTOP_OVERFLOW, GTOP_NO_NODE, GTOP_MAX_CAP, GTOP_MAX_PER, GTOP_MAX_ROWS = 2, 1, (1 << 64) - 1, 1 << 20, 16, 1 << 22   # BMX_GTOP_DESC (flags of the call, next to ROWS_TS), BMX_GTOP_OVERFLOW (flags of bmx_gtop_res), BMX_GTOP_NO_NODE, BMX_GTOP_MAX_CAP, BMX_GTOP_MAX_PER, BMX_GTOP_MAX_ROWS (bmx_group_top.h bmx_where_group_top)
+# computed measures (include/bmx_expr.h), likewise
+EXPORTS_EXPR = ["bmx_where_aggregate_expr", "bmx_where_group_expr", "bmx_where_quantiles_expr", "bmx_comm_where_aggregate_expr", "bmx_comm_where_group_expr",
+                "bmx_comm_where_quantiles_expr"]
+EXPR_ADD, EXPR_SUB, EXPR_MUL = 1, 2, 3   # BMX_EXPR_ADD, BMX_EXPR_SUB, BMX_EXPR_MUL (bmx_expr.h)
 MGROUP_MAX_KEYS, MGROUP_MAX_CAP4 = 4, 1 << 14  # BMX_MGROUP_MAX_KEYS, BMX_MGROUP_MAX_CAP4 (bmx_group_multi.h bmx_where_group_multi)
 UPD_SET, UPD_DELETE, UPD_COPY, UPD_ADD, UPD_FORCE, UPD_MAX_CAP = 0, 1, 2, 3, 1, 1 << 24   # the ops, BMX_UPD_FORCE (flags), BMX_UPD_MAX_CAP (bmx_update.h bmx_where_update)
 
@@ -773,6 +777,30 @@ def _quant_tail(measure, qs):
     return (int(measure), len(qs), arr)
 
 
+class Expr(C.Structure):
+    """bmx_expr: a computed measure, value(a) op value(b) of the selected node (16 bytes). bmx.Expr(a, op, b) with op "+", "-" or "*"; a node whose a or b is
+    absent or tombstoned is undefined, one whose exact result lies outside +-(2^53 - 1) is out of range, and neither is measured (bmx_expr.h)"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("op", C.c_uint32), ("reserved", C.c_uint32)]
+    OPS = {"+": EXPR_ADD, "-": EXPR_SUB, "*": EXPR_MUL}
+
+    def __init__(self, a, op, b):
+        if op not in self.OPS:
+            raise ValueError('bmx.Expr: op is "+", "-" or "*"')
+        super().__init__(int(a), int(b), self.OPS[op], 0)
+
+
+class ExprRes(C.Structure):
+    """bmx_expr_res: the selected nodes a computed measure left unmeasured (16 bytes): n_undef (an operand absent or tombstoned), n_range (the exact result
+    outside +-(2^53 - 1))"""
+    _fields_ = [("n_undef", C.c_uint64), ("n_range", C.c_uint64)]
+
+    def __repr__(self):
+        return "ExprRes(n_undef=%d, n_range=%d)" % (self.n_undef, self.n_range)
+
+
+EXPR_RES_DTYPE = np.dtype([("n_undef", "<u8"), ("n_range", "<u8")])
+
+
 class WatchRes(C.Structure):
     """bmx_watch_res: what one bmx_watch_poll found (32 bytes); flags: WATCH_RESET, WATCH_OVERFLOW"""
     _fields_ = [("n_entered", C.c_uint64), ("n_left", C.c_uint64), ("n_match", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -904,6 +932,12 @@ def load_library():
     L.bmx_where_quantiles.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, vp, vp, i32]; L.bmx_where_quantiles.restype = i32
     L.bmx_comm_where_quantiles.argtypes = [vp, u32, u32, C.POINTER(u32), C.POINTER(Lit), u32, u32, vp, vp, vp]; L.bmx_comm_where_quantiles.restype = i32
     prog = [u32, u32, C.POINTER(u32), C.POINTER(Lit)]
+    L.bmx_where_aggregate_expr.argtypes = [vp] + prog + [vp, u32, i64, u32, vp, vp, i32]; L.bmx_where_aggregate_expr.restype = i32
+    L.bmx_where_group_expr.argtypes = [vp] + prog + [vp, u32, vp, u64, vp, vp, i32]; L.bmx_where_group_expr.restype = i32
+    L.bmx_where_quantiles_expr.argtypes = [vp] + prog + [vp, u32, vp, vp, vp, vp, i32]; L.bmx_where_quantiles_expr.restype = i32
+    L.bmx_comm_where_aggregate_expr.argtypes = [vp] + prog + [vp, u32, i64, u32, vp, vp]; L.bmx_comm_where_aggregate_expr.restype = i32
+    L.bmx_comm_where_group_expr.argtypes = [vp] + prog + [vp, u32, vp, u64, vp, vp]; L.bmx_comm_where_group_expr.restype = i32
+    L.bmx_comm_where_quantiles_expr.argtypes = [vp] + prog + [vp, u32, vp, vp, vp, vp]; L.bmx_comm_where_quantiles_expr.restype = i32
     L.bmx_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp, i32]; L.bmx_where_semijoin.restype = i32
     L.bmx_where_in.argtypes = [vp] + prog + [u32, u32, vp, u64, vp, u64, vp, i32]; L.bmx_where_in.restype = i32
     L.bmx_comm_where_semijoin.argtypes = [vp] + prog + [u32, u32] + prog + [u32, u64, vp, u64, vp]; L.bmx_comm_where_semijoin.restype = i32
@@ -1364,6 +1398,32 @@ class Engine:
         self._chk(self.L.bmx_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), C.cast(C.byref(res), C.c_void_p), MEM_HOST))
         return out[:len(qs)].copy(), res
 
+    def where_aggregate_expr(self, base, clauses, expr, group=None, group_lo=0, ngroups=0):
+        """where_aggregate with a computed measure (bmx_expr.h): expr = bmx.Expr(a, op, b), the measure of a selected node is value(a) op value(b).
+        -> (what where_aggregate returns, ExprRes)"""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        x = ExprRes()
+        self._chk(self.L.bmx_where_aggregate_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), *_where_agg_tail(None, group, group_lo, ngroups)[1:],
+                                                  _ptr(out), C.cast(C.byref(x), C.c_void_p), MEM_HOST))
+        return agg_results(out, int(ngroups)), x
+
+    def where_group_expr(self, base, clauses, group, expr, cap=65536):
+        """where_group with a computed measure (bmx_expr.h). -> (GroupResult, ExprRes)"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res, x = GroupRes(), ExprRes()
+        self._chk(self.L.bmx_where_group_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), _group_tail(None, group)[1], _ptr(out), int(cap),
+                                              C.cast(C.byref(res), C.c_void_p), C.cast(C.byref(x), C.c_void_p), MEM_HOST))
+        return GroupResult(res, out), x
+
+    def where_quantiles_expr(self, base, clauses, expr, qs):
+        """where_quantiles with a computed measure (bmx_expr.h): the sample is value(a) op value(b) of the selected nodes where it is defined and in range.
+        -> (records, QuantRes, ExprRes)"""
+        out = np.zeros(max(len(qs), 1), QUANT_REC_DTYPE)
+        res, x = QuantRes(), ExprRes()
+        self._chk(self.L.bmx_where_quantiles_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), *_quant_tail(0, qs)[1:], _ptr(out),
+                                                  C.cast(C.byref(res), C.c_void_p), C.cast(C.byref(x), C.c_void_p), MEM_HOST))
+        return out[:len(qs)].copy(), res, x
+
     def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=0):
         """Row projection (bmx_rows.h): the selection of scan_where(base, clauses) from index position `start` on, and for each of the first cap selected nodes
         its id and the values (with_ts: and clocks) of `fields`, in one call. cap None: room for the whole index. -> RowsResult; its next_pos is the `start` of
@@ -1721,6 +1781,22 @@ class Engine:
         sync(), out.cpu().numpy().view(QUANT_REC_DTYPE) and res.cpu().numpy().view(QUANT_RES_DTYPE)[0] read them. The program and qs are host data."""
         self._chk(self.L.bmx_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), _ptr(res), MEM_DEVICE))
 
+    def where_aggregate_expr_dev(self, base, clauses, expr, out, xres=None, group=None, group_lo=0, ngroups=0):
+        """where_aggregate_expr into device memory (`out` as for where_aggregate_dev; xres: 16 bytes, a bmx_expr_res, or None); enqueue-only. After sync(),
+        xres.cpu().numpy().view(EXPR_RES_DTYPE)[0] reads the counters. The program and the expression are host data."""
+        self._chk(self.L.bmx_where_aggregate_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), *_where_agg_tail(None, group, group_lo, ngroups)[1:],
+                                                  _ptr(out), _ptr(xres), MEM_DEVICE))
+
+    def where_group_expr_dev(self, base, clauses, group, expr, out, res, xres=None, cap=65536):
+        """where_group_expr into device memory (`out`, res as for where_group_dev; xres as for where_aggregate_expr_dev); enqueue-only."""
+        self._chk(self.L.bmx_where_group_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), _group_tail(None, group)[1], _ptr(out), int(cap),
+                                              _ptr(res), _ptr(xres), MEM_DEVICE))
+
+    def where_quantiles_expr_dev(self, base, clauses, expr, qs, out, res=None, xres=None):
+        """where_quantiles_expr into device memory (`out`, res as for where_quantiles_dev; xres as for where_aggregate_expr_dev); enqueue-only."""
+        self._chk(self.L.bmx_where_quantiles_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), *_quant_tail(0, qs)[1:], _ptr(out), _ptr(res),
+                                                  _ptr(xres), MEM_DEVICE))
+
     def where_rows_dev(self, base, clauses, fields, cap, out_ids, out_val, out_ts, res, start=0):
         """where_rows into device memory (out_ids: room for cap ids; out_val: len(fields) columns of cap int64 each, field after field; out_ts: the same for
         the clocks, or None for none; res: 40 bytes, a bmx_rows_res); enqueue-only. After sync(), res.cpu().numpy().view(ROWS_RES_DTYPE)[0] reads the record.
@@ -2060,6 +2136,30 @@ class Comm:
         res = QuantRes()
         self._chk(self.L.bmx_comm_where_quantiles(self.h, *_where_args(base, clauses), *_quant_tail(measure, qs), _ptr(out), C.cast(C.byref(res), C.c_void_p)))
         return out[:len(qs)].copy(), res
+
+    def where_aggregate_expr(self, base, clauses, expr, group=None, group_lo=0, ngroups=0):
+        """Engine.where_aggregate_expr over all shards: the records one engine holding the same rows gives; the shards' n_undef and n_range add"""
+        out = np.zeros(int(ngroups) + 1, AGG_DTYPE)
+        x = ExprRes()
+        self._chk(self.L.bmx_comm_where_aggregate_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p),
+                                                       *_where_agg_tail(None, group, group_lo, ngroups)[1:], _ptr(out), C.cast(C.byref(x), C.c_void_p)))
+        return agg_results(out, int(ngroups)), x
+
+    def where_group_expr(self, base, clauses, group, expr, cap=65536):
+        """Engine.where_group_expr over all shards, merged by key as where_group's answers are"""
+        out = np.zeros(max(int(cap), 1), GROUP_DTYPE)
+        res, x = GroupRes(), ExprRes()
+        self._chk(self.L.bmx_comm_where_group_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), _group_tail(None, group)[1], _ptr(out), int(cap),
+                                                   C.cast(C.byref(res), C.c_void_p), C.cast(C.byref(x), C.c_void_p)))
+        return GroupResult(res, out), x
+
+    def where_quantiles_expr(self, base, clauses, expr, qs):
+        """Engine.where_quantiles_expr over all shards: one select stepped over all of them, as where_quantiles"""
+        out = np.zeros(max(len(qs), 1), QUANT_REC_DTYPE)
+        res, x = QuantRes(), ExprRes()
+        self._chk(self.L.bmx_comm_where_quantiles_expr(self.h, *_where_args(base, clauses), C.cast(C.byref(expr), C.c_void_p), *_quant_tail(0, qs)[1:], _ptr(out),
+                                                       C.cast(C.byref(res), C.c_void_p), C.cast(C.byref(x), C.c_void_p)))
+        return out[:len(qs)].copy(), res, x
 
     def where_rows(self, base, clauses, fields, cap=None, with_ts=False, start=(0, 0)):
         """Engine.where_rows over the shards, shard after shard from the cursor start = (shard, position) on: the rows one engine holding the same rows gives,

@@ -46,6 +46,7 @@
 #include "reach_kernels.h"
 #include "first_kernels.h"
 #include "gtop_kernels.h"
+#include "expr_kernels.h"
 
 namespace bmx {   // csrc/ordered_sort.hip (rocPRIM's radix sort, an object of its own)
 hipError_t sort_pairs_i32(void* tmp, size_t* tmp_bytes, const int32_t* kin, int32_t lo, unsigned bits, uint32_t* kout, const uint32_t* vin, uint32_t* vout, size_t n, hipStream_t s);
@@ -382,6 +383,14 @@ struct QuantScratch {
   void release() { dev_free(state); dev_free(vals); dev_free(stage); vals_cap = 0; clean = false; }
 };
 
+// Scratch of the computed measures (bmx_expr.inc): the two counters of bmx_expr_res, which every query's last kernel (k_expr_finish) leaves zero again (clean), and
+// the record of a BMX_MEM_HOST or sharded answer on its way down.
+struct ExprScratch {
+  ExprState* state = nullptr; bmx_expr_res* stage = nullptr;
+  bool clean = false;
+  void release() { dev_free(state); dev_free(stage); clean = false; }
+};
+
 // Scratch of the update by query (bmx_update.inc): the staging slab of records the emit pass fills and the merge reads, the winners' indices and ids (`cap` of
 // each, grown on demand), the words between the passes (counts: what the host waits for; ctr: the sharded counters of the mask pass, zero between two calls), the
 // merge's count and stats, the record of a BMX_MEM_HOST answer on its way down, and what a call's mask pass leaves its emit pass (as RowsScratch::masked).
@@ -507,6 +516,7 @@ struct bmx_ctx {
   ReachScratch reach;
   FirstScratch first;
   GtopScratch gtop;
+  ExprScratch expr;
   WatchState watch;
   Profiling prof;
   ViewShared view;                    // what the indexes' value-ordered views share
@@ -836,6 +846,7 @@ void bmx_destroy(bmx_ctx* ctx) {
   ctx->reach.release();
   ctx->first.release();
   ctx->gtop.release();
+  ctx->expr.release();
   ctx->watch.release();
   ctx->prof.release();
   if (ctx->host_rows) (void)hipHostFree(ctx->host_rows);
@@ -1140,3 +1151,4 @@ int bmx_profile_read_scan(bmx_ctx* ctx, float ms_out[2], uint32_t* n_calls) { re
 #include "bmx_reach.inc"     // (likewise; it uses bmx_join.inc's map scratch, bmx_semi.inc's grids and slot count and bmx_where.inc's mask pass)
 #include "bmx_first.inc"     // (likewise; it uses bmx_group.inc's table, scratch and grouped-answer steps)
 #include "bmx_group_top.inc" // (likewise; it uses bmx_first.inc's passes 1 and 2 and bmx_group.inc's grouped-answer steps)
+#include "bmx_expr.inc"      // (likewise; it calls the enqueue, collect and combine steps of bmx_where_agg.inc, bmx_group.inc and bmx_quant.inc with a computed measure)

@@ -42,9 +42,10 @@ int group_scratch(bmx_ctx* ctx, uint64_t cap) {
 
 // Enqueue one group-by over a prepared program; the records and the result record go to d_out / d_res (device memory), or, with d_out == nullptr, to the
 // context's staging buffers (group_collect fetches them). The arguments have been checked and the context entered. A value-ordered view of the base field's
-// index is neither read nor touched (where_run).
+// index is neither read nor touched (where_run). EXPR: the measure is X's expression, as in where_agg_enqueue.
+template <bool EXPR = false>
 int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t group_field, uint64_t cap, bmx_group_rec* d_out,
-                  bmx_group_res* d_res) {
+                  bmx_group_res* d_res, const ExprArgs<EXPR>& X = ExprArgs<EXPR>()) {
   Index* ix;
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
   if (int rc = group_scratch(ctx, cap)) return rc;
@@ -53,10 +54,10 @@ int group_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_
   A.keys = s.keys; A.acc = s.acc; A.S = s.state;
   A.slots = group_slots(cap); A.cap = cap;                         // (a query uses the head of a table that an earlier, larger one left empty)
   A.measure = measure_field; A.group = group_field;
-  A.m_src = where_agg_source(measure_field, base_field); A.g_src = where_agg_source(group_field, base_field);
+  A.m_src = EXPR ? AGG_SRC_PROBE : where_agg_source(measure_field, base_field); A.g_src = where_agg_source(group_field, base_field);
   s.clean = false;
   where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) {
-    hipLaunchKernelGGL((k_group_sweep<decltype(where_value(P)), where_clocks<decltype(P)>>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+    hipLaunchKernelGGL((k_group_sweep<decltype(where_value(P)), where_clocks<decltype(P)>, EXPR>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, X);
   });
   LAUNCHCHK("k_group_sweep");
   hipLaunchKernelGGL(k_group_finish, dim3(group_finish_grid(A.slots)), dim3(256), 0, ctx->stream, A, d_out ? d_out : s.stage, d_out ? d_res : s.stage_res,
@@ -97,6 +98,16 @@ int grouped_collect(bmx_ctx* ctx, const Rec* stage, const Res* stage_res, uint32
 }
 int group_collect(bmx_ctx* ctx, uint64_t cap, std::vector<bmx_group_rec>& recs, bmx_group_res* res) {
   return grouped_collect(ctx, ctx->group.stage, ctx->group.stage_res, BMX_GROUP_OVERFLOW, cap, group_key_less, "bmx_where_group", recs, res);
+}
+
+// ... and into the caller's host memory: what a host-mode call ends with
+int group_collect_to(bmx_ctx* ctx, uint64_t cap, bmx_group_rec* out, bmx_group_res* res) {
+  std::vector<bmx_group_rec> recs;
+  bmx_group_res r;
+  if (int rc = group_collect(ctx, cap, recs, &r)) return rc;
+  if (!recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(bmx_group_rec));
+  *res = r;
+  return BMX_OK;
 }
 
 // a += b: counts and 128-bit sums add, minima and maxima fold (comm_agg_with's combine)
@@ -172,12 +183,7 @@ int bmx_where_group(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const 
   if (int erc = where_enter(ctx, mem)) return erc;
   if (mem == BMX_MEM_DEVICE) return group_enqueue(ctx, base_field, W, measure_field, group_field, cap, out, res);
   if (int rc = group_enqueue(ctx, base_field, W, measure_field, group_field, cap, nullptr, nullptr)) return rc;
-  std::vector<bmx_group_rec> recs;
-  bmx_group_res r;
-  if (int rc = group_collect(ctx, cap, recs, &r)) return rc;
-  if (!recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(bmx_group_rec));
-  *res = r;
-  return BMX_OK;
+  return group_collect_to(ctx, cap, out, res);
 }
 
 int bmx_comm_where_group(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field,

@@ -42,24 +42,26 @@ int quant_scratch(bmx_ctx* ctx, uint64_t rows) {
 // what the digit sweeps of one call read, fixed by its pass 0
 struct QuantSrc { bool fits32 = false /* the 4-byte base column; otherwise 8-byte values: the int64 column or the value scratch */; const void* col = nullptr; uint64_t n = 0; uint32_t nt = 0, blocks = 1; };
 
-template <class T, bool PAIRS>
-void quant_launch0(bmx_ctx* ctx, const Index* ix, const PredWhere<T, PAIRS>& P, uint32_t blocks, const QuantArgs& A, bool probe) {
-  if (probe) hipLaunchKernelGGL((k_quant0<T, true, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
-  else hipLaunchKernelGGL((k_quant0<T, false, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A);
+template <class T, bool PAIRS, bool EXPR>
+void quant_launch0(bmx_ctx* ctx, const Index* ix, const PredWhere<T, PAIRS>& P, uint32_t blocks, const QuantArgs& A, bool probe, const ExprArgs<EXPR>& X) {
+  if (EXPR || probe) hipLaunchKernelGGL((k_quant0<T, true, PAIRS, EXPR>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A, X);
+  else if constexpr (!EXPR) hipLaunchKernelGGL((k_quant0<T, false, PAIRS>), dim3(blocks), dim3(TOP_THREADS), 0, ctx->stream, ix->n, P, A, X);
 }
 
 // Pass 0 of one call over a prepared program, enqueued; *src: where its digit sweeps find the values. The context has been entered. A value-ordered view of the
-// base field's index is neither read nor touched (where_run).
-int quant_enqueue0(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, QuantSrc* src) {
+// base field's index is neither read nor touched (where_run). EXPR: the sample value is X's expression (bmx_expr.inc has made X and enqueues k_expr_finish
+// behind the query); measure_field is not read then, and the value goes through the scratch whatever the operands are.
+template <bool EXPR = false>
+int quant_enqueue0(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, QuantSrc* src, const ExprArgs<EXPR>& X = ExprArgs<EXPR>()) {
   Index* ix;
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
-  const bool probe = measure_field != base_field;
+  const bool probe = EXPR || measure_field != base_field;
   if (int rc = ctx->scan.ensure(ctx, std::max<uint64_t>(ix->n, 1), 0)) return rc;     // the scans' mask: one bit per index position
   if (int rc = quant_scratch(ctx, probe ? std::max<uint64_t>(ix->n, 1) : 0)) return rc;
   QuantArgs A{};
   A.mask = ctx->scan.mask; A.vals = ctx->quant.vals; A.S = ctx->quant.state; A.measure = measure_field;
   ctx->quant.clean = false;
-  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_plain_or_pairs(P, [&](const auto& Q) { quant_launch0(ctx, ix, Q, blocks, A, probe); }); });
+  where_sweep(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_plain_or_pairs(P, [&](const auto& Q) { quant_launch0(ctx, ix, Q, blocks, A, probe, X); }); });
   LAUNCHCHK("k_quant0");
   src->fits32 = !probe && ix->fits32; src->n = ix->n;
   src->col = probe ? static_cast<const void*>(ctx->quant.vals) : (ix->fits32 ? static_cast<const void*>(ix->v32) : static_cast<const void*>(ix->v64));
@@ -86,9 +88,11 @@ int quant_finish(bmx_ctx* ctx, uint32_t nq, bmx_quant_rec* d_out, bmx_quant_res*
 }
 
 // Enqueue one whole query: the records go to d_out and the result to d_res (device memory; d_res may be null), or, with d_out == nullptr, both to the staging.
-int quant_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t nq, const QuantQs& qs, bmx_quant_rec* d_out, bmx_quant_res* d_res) {
+template <bool EXPR = false>
+int quant_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t nq, const QuantQs& qs, bmx_quant_rec* d_out, bmx_quant_res* d_res,
+                  const ExprArgs<EXPR>& X = ExprArgs<EXPR>()) {
   QuantSrc s;
-  if (int rc = quant_enqueue0(ctx, base_field, W, measure_field, &s)) return rc;
+  if (int rc = quant_enqueue0(ctx, base_field, W, measure_field, &s, X)) return rc;
   hipLaunchKernelGGL(k_quant_init, dim3(1), dim3(64), 0, ctx->stream, ctx->quant.state, nq, qs);
   LAUNCHCHK("k_quant_init");
   // the worst case of digits: 32 bits of (key - min) in the 4-byte column, the 54-bit value domain (a difference below 2^54) otherwise. The first digit has one
@@ -110,19 +114,8 @@ QuantQs quant_copy_qs(uint32_t nq, const bmx_quant_q* qs) {
   return q;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bmx_where_quantiles(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field, uint32_t nq,
-                        const bmx_quant_q* qs, bmx_quant_rec* out, bmx_quant_res* res, int mem) {
-  WhereProg W;
-  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (const char* bad = quant_bad_args(nq, qs, out)) return fail(ctx, BMX_ERR_INVALID, bad);
-  if (int erc = where_enter(ctx, mem)) return erc;
-  const QuantQs q = quant_copy_qs(nq, qs);      // read now: the caller may reuse qs as soon as the call returns
-  if (mem == BMX_MEM_DEVICE) return quant_enqueue(ctx, base_field, W, measure_field, nq, q, out, res);
-  if (int rc = quant_enqueue(ctx, base_field, W, measure_field, nq, q, nullptr, nullptr)) return rc;
+// second half of a host-mode query: wait for it and copy its records and its result down
+int quant_collect(bmx_ctx* ctx, uint32_t nq, bmx_quant_rec* out, bmx_quant_res* res) {
   uint8_t h[QUANT_STAGE_BYTES];
   HIPCHK(hipMemcpyAsync(h, ctx->quant.stage, QUANT_STAGE_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -131,20 +124,17 @@ int bmx_where_quantiles(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, co
   return BMX_OK;
 }
 
-// The quantiles of the shards do not combine: the communicator runs the select itself. Pass 0 on every shard, the counts and the extremes folded here, then per
-// digit the select record (live prefixes, the common minimum) up to every shard, every shard's sweep, the histograms down and added, the bins found here by
-// quant_search / quant_step / quant_relist — what k_quant_find runs. At most 5 rounds of at most nq x 16 KB per shard.
-int bmx_comm_where_quantiles(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field, uint32_t nq,
-                             const bmx_quant_q* qs, bmx_quant_rec* out, bmx_quant_res* res) {
-  WhereProg W;
-  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
-  if (const char* bad = quant_bad_args(nq, qs, out)) return fail(c, BMX_ERR_INVALID, bad);
-  if (int rc = where_comm_guard(c)) return rc;
+// The quantiles of the shards do not combine: the communicator runs the select itself. Pass 0 on every shard (enqueue0(shard, &its QuantSrc); the shard has been
+// entered), the counts and the extremes folded here, then per digit the select record (live prefixes, the common minimum) up to every shard, every shard's
+// sweep, the histograms down and added, the bins found here by quant_search / quant_step / quant_relist — what k_quant_find runs. At most 5 rounds of at most
+// nq x 16 KB per shard. The arguments have been checked.
+template <class Enqueue0>
+int comm_quant_with(bmx_comm* c, uint32_t nq, const bmx_quant_q* qs, bmx_quant_rec* out, bmx_quant_res* res, Enqueue0 enqueue0) {
   DevGuard guard;
   std::vector<QuantSrc> src(c->N);
   unsigned long long n_match = 0, n = 0, kmin = ~0ull, kmax = 0;
   int rc = comm_two_phase(c,
-    [&](uint32_t g, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : quant_enqueue0(x, base_field, W, measure_field, &src[g]); },
+    [&](uint32_t g, bmx_ctx* x) { const int erc = enter(x); return erc ? erc : enqueue0(x, &src[g]); },
     [&](uint32_t, bmx_ctx* ctx) {
       if (int erc = enter(ctx)) return erc;
       unsigned long long h[4];
@@ -192,6 +182,32 @@ int bmx_comm_where_quantiles(bmx_comm* c, uint32_t base_field, uint32_t nclauses
   for (uint32_t i = 0; i < nq; i++) out[i] = quant_record(Q, i);
   if (res) *res = quant_result(n_match, n, kmin, kmax);
   return BMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmx_where_quantiles(bmx_ctx* ctx, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field, uint32_t nq,
+                        const bmx_quant_q* qs, bmx_quant_rec* out, bmx_quant_res* res, int mem) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (const char* bad = quant_bad_args(nq, qs, out)) return fail(ctx, BMX_ERR_INVALID, bad);
+  if (int erc = where_enter(ctx, mem)) return erc;
+  const QuantQs q = quant_copy_qs(nq, qs);      // read now: the caller may reuse qs as soon as the call returns
+  if (mem == BMX_MEM_DEVICE) return quant_enqueue(ctx, base_field, W, measure_field, nq, q, out, res);
+  if (int rc = quant_enqueue(ctx, base_field, W, measure_field, nq, q, nullptr, nullptr)) return rc;
+  return quant_collect(ctx, nq, out, res);
+}
+
+// bmx_where_quantiles over the shards (host memory): comm_quant_with
+int bmx_comm_where_quantiles(bmx_comm* c, uint32_t base_field, uint32_t nclauses, const uint32_t* clause_len, const bmx_lit* lits, uint32_t measure_field, uint32_t nq,
+                             const bmx_quant_q* qs, bmx_quant_rec* out, bmx_quant_res* res) {
+  WhereProg W;
+  if (const char* bad = where_prepare(base_field, nclauses, clause_len, lits, &W)) return fail(c, BMX_ERR_INVALID, bad);
+  if (const char* bad = quant_bad_args(nq, qs, out)) return fail(c, BMX_ERR_INVALID, bad);
+  if (int rc = where_comm_guard(c)) return rc;
+  return comm_quant_with(c, nq, qs, out, res, [&](bmx_ctx* x, QuantSrc* src) { return quant_enqueue0(x, base_field, W, measure_field, src); });
 }
 
 }  // extern "C"

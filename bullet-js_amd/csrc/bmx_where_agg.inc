@@ -10,18 +10,21 @@ const bmx_term WHERE_AGG_NO_TERMS[1] = {};
 const char* where_agg_bad_args(uint32_t group_field, uint32_t ngroups, const bmx_agg* out) { return agg_bad_args(1, WHERE_AGG_NO_TERMS, group_field, ngroups, out); }
 const char* where_top_bad_args(uint32_t flags, uint32_t k, const bmx_top_rec* out) { return top_bad_args(1, WHERE_AGG_NO_TERMS, flags, k, out); }
 
-// the sweep of one aggregate: flat, grouped in LDS, or grouped in device memory
-template <class T, bool CLOCKS>
-void where_agg_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T, true, CLOCKS>& P, uint32_t blocks, const AggArgs& A) {
-  if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
-  else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
-  else hipLaunchKernelGGL((k_where_agg<T, 2, CLOCKS>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A);
+// the sweep of one aggregate: flat, grouped in LDS, or grouped in device memory. EXPR: with a computed measure X (bmx_expr.inc), otherwise X is empty
+template <class T, bool CLOCKS, bool EXPR>
+void where_agg_launch(bmx_ctx* ctx, const Index* ix, const PredWhere<T, true, CLOCKS>& P, uint32_t blocks, const AggArgs& A, const ExprArgs<EXPR>& X) {
+  if (A.ngroups == 0) hipLaunchKernelGGL((k_where_agg<T, 0, CLOCKS, EXPR>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, X);
+  else if (A.ngroups <= AGG_LDS_GROUPS) hipLaunchKernelGGL((k_where_agg<T, 1, CLOCKS, EXPR>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, X);
+  else hipLaunchKernelGGL((k_where_agg<T, 2, CLOCKS, EXPR>), dim3(blocks), dim3(AGG_THREADS), 0, ctx->stream, ix->n, P, A, X);
 }
 
 // Enqueue one aggregate over a prepared program; the records go to d_out (device memory), or, with d_out == nullptr, to the context's staging buffer
 // (agg_collect fetches them). The arguments have been checked and the context entered. A value-ordered view of the base field's index is neither read nor
-// touched (where_run).
-int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* d_out) {
+// touched (where_run). EXPR: the measure is X's expression (bmx_expr.inc has made X and enqueues k_expr_finish behind this); measure_field is not read then, and
+// n is counted per row: no class of node makes n == n_match, not even base * base.
+template <bool EXPR = false>
+int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uint32_t measure_field, uint32_t group_field, int64_t group_lo, uint32_t ngroups, bmx_agg* d_out,
+                      const ExprArgs<EXPR>& X = ExprArgs<EXPR>()) {
   Index* ix;
   if (int rc = fresh_index(ctx, base_field, &ix)) return rc;
   const uint32_t nrec = agg_records(ngroups);
@@ -29,10 +32,10 @@ int where_agg_enqueue(bmx_ctx* ctx, uint32_t base_field, const WhereProg& W, uin
   AggArgs A{};
   A.slots = ctx->slots; A.nslots = ctx->nslots; A.acc = ctx->agg.raw;
   A.group_lo = group_lo; A.ngroups = ngroups; A.measure = measure_field; A.group = group_field;
-  A.m_src = where_agg_source(measure_field, base_field); A.g_src = ngroups ? where_agg_source(group_field, base_field) : AGG_SRC_NONE;
+  A.m_src = EXPR ? AGG_SRC_PROBE : where_agg_source(measure_field, base_field); A.g_src = ngroups ? where_agg_source(group_field, base_field) : AGG_SRC_NONE;
   A.nterms = 0;
   ctx->agg.clean = false;
-  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_agg_launch(ctx, ix, P, blocks, A); });
+  where_sweep_c(ctx, ix, W, [&](const auto& P, uint32_t blocks) { where_agg_launch(ctx, ix, P, blocks, A, X); });
   LAUNCHCHK("k_where_agg");
   hipLaunchKernelGGL(k_agg_finish, dim3(std::min<uint32_t>((nrec + 255) / 256, 64)), dim3(256), 0, ctx->stream, ctx->agg.raw, d_out ? d_out : ctx->agg.stage, nrec,
                      A.m_src != AGG_SRC_PROBE ? 1u : 0u);

@@ -137,24 +137,31 @@ __device__ __forceinline__ void group_row_put(const GroupArgs& A, bool go, int64
   if (nm || have_m) group_put(A, S, (long long)gval, nm, have_m, mval);
 }
 
-// one row of the sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company)
-template <class T, bool CLOCKS>
-__device__ __forceinline__ void group_row(const PredWhere<T, true, CLOCKS>& P, const GroupArgs& A, bool sel, int64_t x, uint64_t pos, uint32_t lane, AggLane& Lt, AggLane& La, GroupLds& S) {
+// one row of the sweep, called by every lane of the wave (sel = false: the lane only keeps the wave's votes company). EXPR: where_agg_row's; `total` and
+// `absent` take the node as its class says (the host sets A.m_src = AGG_SRC_PROBE: n is counted per row).
+template <class T, bool CLOCKS, bool EXPR>
+__device__ __forceinline__ void group_row(const PredWhere<T, true, CLOCKS>& P, const GroupArgs& A, const ExprArgs<EXPR>& X, bool sel, int64_t x, uint64_t pos, uint32_t lane,
+                                          AggLane& Lt, AggLane& La, GroupLds& S, ExprWave& C) {
   int64_t mval = x, gval = x;
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
+  uint32_t cls = EXPR_DEFINED;
   if (sel) {
-    // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe, as where_agg_row does it
+    if constexpr (EXPR) have_m = expr_fetch(P.slots, P.nslots, P.ids, X, A.g_src, A.group, x, pos, mval, gval, have_g, cls);
+    else {
+      // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe, as where_agg_row does it
 #pragma unroll 1
-    for (uint32_t k = 0; k < 2u; k++) {
-      if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
-      int64_t y;
-      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
-        if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
+      for (uint32_t k = 0; k < 2u; k++) {
+        if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
+        int64_t y;
+        if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
+          if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
+        }
       }
     }
     group_lane_add(Lt, have_m, mval);
     if (!have_g) group_lane_add(La, have_m, mval);
   }
+  if constexpr (EXPR) expr_count(C, cls);
   group_row_put(A, sel && have_g, gval, have_m, mval, lane, S);
 }
 
@@ -165,8 +172,8 @@ __device__ __forceinline__ void group_end(AggRaw* dst, AggLane& L, AggLds<0>& W)
   agg_end<0>(B, L, W);
 }
 
-template <class T, bool CLOCKS>
-__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A) {
+template <class T, bool CLOCKS, bool EXPR = false>      // (EXPR: a computed measure, bmx_expr.h; X is empty without one)
+__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A, ExprArgs<EXPR> X) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;
@@ -175,6 +182,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhe
   }
   __syncthreads();
   AggLane Lt, La;
+  ExprWave C;
   const uint32_t lane = threadIdx.x & 63u;
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
 #pragma unroll 1
@@ -182,7 +190,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhe
       const T xe = where_pick<T, E>(x, e);
       const uint64_t pos = unit * E + (uint64_t)e;
       const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
-      group_row<T>(P, A, sel, (int64_t)xe, pos, lane, Lt, La, S);
+      group_row<T>(P, A, X, sel, (int64_t)xe, pos, lane, Lt, La, S, C);
     }
   });
   __syncthreads();
@@ -195,6 +203,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhe
   group_end(&A.S->total, Lt, S.w);
   __syncthreads();                                                      // (thread 0 has read the waves' partials of `total`)
   group_end(&A.S->absent, La, S.w);
+  expr_end(X, C);
 }
 
 __device__ __forceinline__ bmx_agg group_compose(const AggRaw& x, uint32_t n_is_match) {

@@ -128,8 +128,12 @@ __host__ __device__ inline bmx_quant_res quant_result(unsigned long long n_match
   return r;
 }
 
-template <class T, bool PROBE, bool PAIRS>      // (PAIRS: the program has a field pair; where_kernels.h PredWhere)
-__global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T, PAIRS> P, QuantArgs A) {
+// EXPR (bmx_expr.h): the sample value is X's expression of two fields, computed per SELECTED candidate and left in the value scratch: PROBE's route, whatever
+// the operands are. The bit is "selected AND the node is defined".
+template <class T, bool PROBE, bool PAIRS, bool EXPR = false>      // (PAIRS: the program has a field pair; where_kernels.h PredWhere)
+__global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T, PAIRS> P, QuantArgs A, ExprArgs<EXPR> X) {
+  static_assert(!EXPR || PROBE, "a computed measure goes through the value scratch");
+  ExprWave C;
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_m[TOP_WAVES], s_n[TOP_WAVES], s_mn[TOP_WAVES], s_mx[TOP_WAVES];
@@ -144,11 +148,14 @@ __global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T,
       const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
       bool have = sel;
       int64_t v = (int64_t)xe;
+      uint32_t cls = EXPR_DEFINED;
       if (PROBE && sel) {                                        // (pos < n: a selected row exists)
         int64_t y;
-        have = agg_probe(P.slots, P.nslots, P.ids[pos], A.measure, y) && y != VAL_DELETED;
+        if constexpr (EXPR) { bool hg = false; int64_t g = 0; have = expr_fetch(P.slots, P.nslots, P.ids, X, AGG_SRC_NONE, 0u, (int64_t)xe, pos, y, g, hg, cls); }
+        else have = agg_probe(P.slots, P.nslots, P.ids[pos], A.measure, y) && y != VAL_DELETED;
         if (have) { v = y; A.vals[pos] = y; }
       }
+      if constexpr (EXPR) expr_count(C, cls);
       nib |= (uint32_t)have << e;
       cnt_m += sel ? 1u : 0u;
       if (have) { const unsigned long long u = top_key(v, 0u); cnt_n++; mn = u < mn ? u : mn; mx = u > mx ? u : mx; }
@@ -175,6 +182,7 @@ __global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T,
     if (m) atomicAdd(&A.S->n_match, m);
     if (c) { atomicAdd(&A.S->n, c); atomicMin(&A.S->kmin, a); atomicMax(&A.S->kmax, b); }
   }
+  expr_end(X, C);
 }
 
 __global__ void k_quant_init(QuantState* __restrict__ S, uint32_t nq, QuantQs qs) {

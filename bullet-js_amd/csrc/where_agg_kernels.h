@@ -16,6 +16,7 @@
 #pragma once
 #include "where_kernels.h"
 #include "top_kernels.h"
+#include "expr_kernels.h"
 
 namespace bmx {
 
@@ -31,17 +32,24 @@ __device__ __forceinline__ T where_pick(const V& x, int e) {
 }
 
 // a candidate the program selected: the measure and the group value (the column value x, or one probe each), then the add. The table is P's.
-template <int G, class T, bool CLOCKS>
-__device__ __forceinline__ void where_agg_row(const PredWhere<T, true, CLOCKS>& P, const AggArgs& A, int64_t x, uint64_t pos, AggLane& L, AggLds<G>& S) {
+// EXPR (bmx_expr.h): the measure is X's expression of two fields, fetched with the group value through expr_fetch's one copy of the probe; a node that is
+// undefined or out of range is a node without its measure; -> its class. The host sets A.m_src = AGG_SRC_PROBE for it: n is counted per row in every G.
+template <int G, class T, bool CLOCKS, bool EXPR>
+__device__ __forceinline__ uint32_t where_agg_row(const PredWhere<T, true, CLOCKS>& P, const AggArgs& A, const ExprArgs<EXPR>& X, int64_t x, uint64_t pos, AggLane& L,
+                                                  AggLds<G>& S) {
   int64_t mval = x, gval = x;
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
-  // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers
+  uint32_t cls = EXPR_DEFINED;
+  if constexpr (EXPR) have_m = expr_fetch(P.slots, P.nslots, P.ids, X, A.g_src, A.group, x, pos, mval, gval, have_g, cls);
+  else {
+    // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers
 #pragma unroll 1
-  for (uint32_t k = 0; k < 2u; k++) {
-    if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
-    int64_t y;
-    if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
-      if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
+    for (uint32_t k = 0; k < 2u; k++) {
+      if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
+      int64_t y;
+      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
+        if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
+      }
     }
   }
   uint32_t g = 0;
@@ -50,24 +58,29 @@ __device__ __forceinline__ void where_agg_row(const PredWhere<T, true, CLOCKS>& 
     g = (have_g && gval >= A.group_lo && d < (uint64_t)A.ngroups) ? (uint32_t)d : A.ngroups;
   }
   agg_add<G>(A, L, S, g, have_m, mval);
+  return cls;
 }
 
-template <class T, int G, bool CLOCKS>
-__global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T, true, CLOCKS> P, AggArgs A) {
+template <class T, int G, bool CLOCKS, bool EXPR = false>      // (EXPR: a computed measure, bmx_expr.h; X is empty without one)
+__global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T, true, CLOCKS> P, AggArgs A, ExprArgs<EXPR> X) {
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ AggLds<G> S;
   AggLane L;
+  ExprWave C;
   agg_begin<G>(A, S);
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
 #pragma unroll 1
     for (int e = 0; e < E; e++) {
       const T xe = where_pick<T, E>(x, e);
       const uint64_t pos = unit * E + (uint64_t)e;
-      if (P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) where_agg_row<G>(P, A, (int64_t)xe, pos, L, S);
+      uint32_t cls = EXPR_DEFINED;
+      if (P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) cls = where_agg_row<G>(P, A, X, (int64_t)xe, pos, L, S);
+      if constexpr (EXPR) expr_count(C, cls);
     }
   });
   agg_end<G>(A, L, S);
+  expr_end(X, C);
 }
 
 template <class T, bool PAIRS>      // (PAIRS: the program has a field pair; where_kernels.h PredWhere)
