@@ -4,14 +4,15 @@
 //
 // k_first_sweep<T>   : pass 1, k_group_sweep's shape and pieces: top_sweep over the base field's value column, PredWhere::row() evaluated once per candidate,
 //                      the group and the order value from the column or from one agg_probe each (one probe for both when they are the same field), made after
-//                      the match is known; the row then goes where a row of bmx_where_group goes with measure = order field (group_row_put: the wave's count
-//                      combine, the LDS cache, the bypass, the flush, the find-or-claim walk with its claim counter and give-up rule are group_kernels.h's, not
-//                      copies). So per key the table holds n_match, n and BOTH extremes of the contenders' order values (64-bit atomic min and max). It also
-//                      leaves, per index position, what pass 2 needs so that it probes nothing: a word gw[pos] when the group field is not the base column
-//                      (the group value of a selected node that has one, else BMX_VAL_DELETED) and a word ow[pos] when the order field is not the base column
-//                      (the order value of a selected node that has one, else BMX_VAL_DELETED). When both come from the column the order word is kept anyway:
-//                      it is then the only record of which positions the program selected. A lane holds the words of its E positions in registers and
-//                      stores them as whole 16-byte vectors behind the unit's last row, so consecutive lanes write consecutive addresses.
+//                      the match is known; the row then goes where a row of bmx_where_group goes with measure = order field (group_row_put, group_cache_begin
+//                      and group_cache_end: the wave's count combine, the LDS cache, the bypass, the flush, the find-or-claim walk with its claim counter and
+//                      give-up rule are group_kernels.h's, not copies). So per key the table holds n_match, n and BOTH extremes of the contenders' order values
+//                      (64-bit atomic min and max). It also leaves, per index position, what pass 2 needs so that it probes nothing: a word gw[pos] when the
+//                      group field is not the base column (the group value of a selected node that has one, else BMX_VAL_DELETED) and a word ow[pos] when the
+//                      order field is not the base column (the order value of a selected node that has one, else BMX_VAL_DELETED). When both come from the
+//                      column the order word is kept anyway: it is then the only record of which positions the program selected. A lane holds the words of its
+//                      E positions in registers and stores them as whole 16-byte vectors behind the unit's last row, so consecutive lanes write consecutive
+//                      addresses.
 // k_first_resolve<T> : pass 2, a streaming sweep of those words (and of the column where a field is the base field). A position is a CONTENDER iff every word
 //                      kept for it is not BMX_VAL_DELETED. A contender finds its key's slot with PLAIN loads and, if its value equals the slot's extreme
 //                      (minimum, or maximum with BMX_FIRST_DESC), lowers the slot's id word with one unsigned 64-bit atomicMin of ids[pos] (behind a relaxed
@@ -67,15 +68,8 @@ __device__ __forceinline__ void first_row(const PredWhere<T, true, CLOCKS>& P, c
   int64_t mval = x, gval = x;
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
   if (sel) {
-    // the group field (k = 0) and the order field (k = 1) through ONE copy of the probe, as group_row does it
-#pragma unroll 1
-    for (uint32_t k = 0; k < 2u; k++) {
-      if ((k ? A.m_src : A.g_src) != AGG_SRC_PROBE || (k && F.same)) continue;   // (uniform)
-      int64_t y;
-      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.measure : A.group, y) && y != VAL_DELETED) {
-        if (k) { mval = y; have_m = true; } else { gval = y; have_g = true; }
-      }
-    }
+    // (same: the order field is the group field, which has the one probe)
+    where_two_fields(P, pos, A.g_src, A.group, gval, have_g, F.same ? AGG_SRC_NONE : A.m_src, A.measure, mval, have_m);
     if (F.same) { mval = gval; have_m = have_g; }
     group_lane_add(Lt, have_m, mval);
     if (!have_g) group_lane_add(La, have_m, mval);
@@ -102,42 +96,25 @@ __global__ __launch_bounds__(AGG_THREADS) void k_first_sweep(uint64_t n, PredWhe
   constexpr int E = PredWhere<T>::E;
   typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {
-    S.key[e] = GROUP_EMPTY; S.nm[e] = 0u; S.n[e] = 0u; S.mn[e] = INT64_MAX; S.mx[e] = INT64_MIN; S.slo[e] = 0ull; S.shi[e] = 0ll;
-  }
-  __syncthreads();
+  group_cache_begin(S);
   AggLane Lt, La;
   const uint32_t lane = threadIdx.x & 63u;
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
     long long gq[E], oq[E];                                             // (indexed by unrolled counters only: registers)
 #pragma unroll
     for (int k = 0; k < E; k++) { gq[k] = VAL_DELETED; oq[k] = VAL_DELETED; }
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
+    where_unit_rows<T>(P, unit, x, cnt, [&](int e, T xe, uint64_t pos, bool sel) {
       long long gs, os;
       first_row<T>(P, F, sel, (int64_t)xe, pos, lane, Lt, La, S, gs, os);
 #pragma unroll
       for (int k = 0; k < E; k++) { gq[k] = e == k ? gs : gq[k]; oq[k] = e == k ? os : oq[k]; }
-    }
+    });
     if (cnt) {                                                          // a unit of the column (its rows beyond the column: "no contender", inside the padding)
       if (F.gw) first_store_unit<E>(F.gw, unit, gq, P.nt);
       if (F.ow) first_store_unit<E>(F.ow, unit, oq, P.nt);
     }
   });
-  __syncthreads();
-  const GroupArgs& A = F.G;
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {   // the flush: every key the workgroup cached, once
-    const long long k = S.key[e];
-    const uint32_t nm = S.nm[e];
-    uint64_t slot;
-    if (k != GROUP_EMPTY && nm && group_slot(A, k, slot)) agg_flush_one(A.acc + slot, nm, S.n[e], S.mn[e], S.mx[e], S.slo[e], S.shi[e]);
-  }
-  group_end(&A.S->total, Lt, S.w);
-  __syncthreads();                                                      // (thread 0 has read the waves' partials of `total`)
-  group_end(&A.S->absent, La, S.w);
+  group_cache_end(F.G, S, Lt, La);
 }
 
 // the words kept for index position i, as loaded (VAL_DELETED where none is kept): is it a contender, and if so its group value and its order value (from the
@@ -196,7 +173,6 @@ __global__ __launch_bounds__(FIRST_THREADS) void k_first_resolve(const T* __rest
 
 // n_is_match: every member had its order value (the order field is the base field): n = n_match. `slots` is a multiple of 64.
 __global__ __launch_bounds__(256) void k_first_finish(FirstArgs F, FirstOut O, uint32_t n_is_match) {
-  __shared__ uint32_t s_last;
   const GroupArgs& A = F.G;
   GroupState* S = A.S;
   const unsigned long long claims = S->claims;
@@ -206,13 +182,9 @@ __global__ __launch_bounds__(256) void k_first_finish(FirstArgs F, FirstOut O, u
     const uint64_t s = b + lane;
     const long long k = A.keys[s];
     const bool occ = k != GROUP_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                 // (uniform)
+    if (!__ballot(occ)) continue;                                       // (uniform)
     if (fits) {
-      unsigned long long base = 0;
-      if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-      base = __shfl(base, 0);
-      const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long r = wave_rank(occ, &S->nout, lane);
       const bool w = occ && r < A.cap;
       unsigned long long id = FIRST_NO_NODE;
       if (w) {
@@ -234,15 +206,12 @@ __global__ __launch_bounds__(256) void k_first_finish(FirstArgs F, FirstOut O, u
     }
     if (occ) { A.keys[s] = GROUP_EMPTY; A.acc[s] = GROUP_RAW_EMPTY; F.idw[s] = FIRST_NO_NODE; }
   }
-  __syncthreads();                                                      // every lane of the workgroup has read the state record and ranked its slots
-  if (threadIdx.x == 0) s_last = atomicAdd(&S->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // no workgroup reads the state record any more
+  if (last_workgroup(&S->done) && threadIdx.x == 0) {                   // no workgroup reads the state record any more
     bmx_first_res o;
     o.n_groups = claims; o.flags = fits ? 0u : BMX_FIRST_OVERFLOW; o.reserved = 0u;
     o.total = S->total.nm; o.absent = S->absent.nm; o.n_ordered = S->total.n - S->absent.n;
     *O.res = o;
-    S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
+    group_state_reset(S);
   }
 }
 

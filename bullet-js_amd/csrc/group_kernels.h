@@ -4,9 +4,9 @@
 //                    decides the candidates exactly as k_where_agg does. A selected row's measure and group value are the column value when the field is the base
 //                    field, otherwise one agg_probe each, made after the match is known. The row is added to `total` (and to `absent` when its group value is
 //                    absent or tombstoned) in the lane's registers, and to the record of its key.
-// k_group_finish   : one sweep of the table's slots. Occupied slots are ranked by wave ballot + popcount into one counter; if the distinct keys fit the caller's
-//                    cap the 128-bit sums are composed and the records written. Every slot goes back to its empty state; the workgroup that finishes last
-//                    writes `res` and puts the state record back too.
+// k_group_finish   : one sweep of the table's slots. Occupied slots are ranked by wave ballot + popcount into one counter (top_kernels.h wave_rank); if the
+//                    distinct keys fit the caller's cap the 128-bit sums are composed and the records written. Every slot goes back to its empty state; the
+//                    workgroup that finishes last (last_workgroup) writes `res` and puts the state record back too (group_state_reset).
 // k_group_clear    : table and state to their empty state (new scratch, or a query that did not get as far as its last kernel).
 //
 // The table (device memory, GroupScratch): `slots` = max(64, next power of two >= 2 * cap) entries of a key word and an AggRaw accumulator. An empty slot's key
@@ -25,6 +25,10 @@
 // Which of more than four keys of a set get its ways depends on who comes first; the answer does not. The occupied entries are flushed once behind the
 // workgroup's last row: one find-or-claim and at most 6 memory-side atomics per key and workgroup. Within a wave, the lanes that hold the first selected
 // lane's key add their count once (ballot + popcount, as k_top_digit does).
+//
+// One definition each, for this family and the ones built on it (first_, gtop_, mgroup_, semi_, join_, join_rows_, reach_kernels.h): group_row_put (the
+// wave's key combine), group_cache_begin / group_cache_end (the LDS cache around a sweep: clear, flush, the two records' tail), last_workgroup and
+// group_state_reset. The row walk and the field fetch are where_agg_kernels.h's. The find-or-claim walk has three copies (group_slot says why).
 #pragma once
 #include "where_agg_kernels.h"
 #include "../../include/bmx_group.h"
@@ -70,7 +74,27 @@ struct GroupLds {
 
 constexpr AggRaw GROUP_RAW_EMPTY = AggRaw{0ull, 0ull, INT64_MAX, INT64_MIN, 0ull, 0ll};
 
-// the slot of `key` in the global table, found or claimed; false: no room (the overflow bit is up)
+__device__ __forceinline__ void group_state_reset(GroupState* S) {
+  S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
+}
+
+// The "last workgroup" step of a finish kernel, called by every thread behind its part of the sweep: a barrier (every thread of the workgroup has read the
+// state record and done its slots), one count into `done`, -> true in every thread of the workgroup that counted last: nobody else reads the record any more.
+__device__ __forceinline__ bool last_workgroup(uint32_t* done) {
+  __shared__ uint32_t s_last;
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = atomicAdd(done, 1u) == gridDim.x - 1u ? 1u : 0u;
+  __syncthreads();
+  return s_last != 0u;
+}
+
+// The slot of `key` in the global table, found or claimed; false: no room (the overflow bit is up). The find-or-claim walk of the family: from the key's home
+// slot, linear with wrap; relaxed agent-scope load; an empty word is claimed with one CAS and one no-return add to the claim counter; the word a lost CAS
+// returned is looked at before moving on (it may be this key, claimed by another lane); a key already present costs no atomic. The walk gives up at every
+// 64th step once more than `cap` keys are claimed, and in a table without room. semi_insert and join_kernels.h's join_slot are the same walk over their own
+// tables, each in a copy of its own, and a change to one goes into the others by hand. Measured: one shared definition (a claim that falls through to the
+// k == key test, the stride a callable) leaves every figure of the resource table alone but spills 6 more scalar registers in k_group_sweep's computed
+// builds, makes bmx_where_group 3 to 6 us slower where the walk is inlined on the bypass path of the row loop, and costs semi_insert a third of its speed.
 __device__ __forceinline__ bool group_slot(const GroupArgs& A, long long key, uint64_t& slot) {
   const uint64_t mask = A.slots - 1u;
   uint64_t s = group_mix(key) & mask;
@@ -123,7 +147,7 @@ __device__ __forceinline__ void group_lane_add(AggLane& L, bool have_m, int64_t 
   if (have_m) { L.n++; L.slo += (unsigned long long)(uint32_t)mval; L.shi += mval >> 32; L.mn = mval < L.mn ? mval : L.mn; L.mx = mval > L.mx ? mval : L.mx; }
 }
 
-// the end of one row of a sweep, called by every lane of the wave: the row (go = false: none) into the record of its key (k_group_sweep; first_kernels.h)
+// the end of one row of every grouped sweep, called by every lane of the wave: the row (go = false: none) into the record of its key
 __device__ __forceinline__ void group_row_put(const GroupArgs& A, bool go, int64_t gval, bool have_m, int64_t mval, uint32_t lane, GroupLds& S) {
   const unsigned long long act = __ballot(go);
   if (!act) return;                                                  // (uniform)
@@ -147,17 +171,7 @@ __device__ __forceinline__ void group_row(const PredWhere<T, true, CLOCKS>& P, c
   uint32_t cls = EXPR_DEFINED;
   if (sel) {
     if constexpr (EXPR) have_m = expr_fetch(P.slots, P.nslots, P.ids, X, A.g_src, A.group, x, pos, mval, gval, have_g, cls);
-    else {
-      // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe, as where_agg_row does it
-#pragma unroll 1
-      for (uint32_t k = 0; k < 2u; k++) {
-        if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
-        int64_t y;
-        if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
-          if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
-        }
-      }
-    }
+    else where_two_fields(P, pos, A.m_src, A.measure, mval, have_m, A.g_src, A.group, gval, have_g);
     group_lane_add(Lt, have_m, mval);
     if (!have_g) group_lane_add(La, have_m, mval);
   }
@@ -172,29 +186,18 @@ __device__ __forceinline__ void group_end(AggRaw* dst, AggLane& L, AggLds<0>& W)
   agg_end<0>(B, L, W);
 }
 
-template <class T, bool CLOCKS, bool EXPR = false>      // (EXPR: a computed measure, bmx_expr.h; X is empty without one)
-__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A, ExprArgs<EXPR> X) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
-  __shared__ GroupLds S;
+// The workgroup's cache around a sweep, called by every thread. group_cache_begin: every entry empty, visible to the workgroup.
+__device__ __forceinline__ void group_cache_begin(GroupLds& S) {
   for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {
     S.key[e] = GROUP_EMPTY; S.nm[e] = 0u; S.n[e] = 0u; S.mn[e] = INT64_MAX; S.mx[e] = INT64_MIN; S.slo[e] = 0ull; S.shi[e] = 0ll;
   }
   __syncthreads();
-  AggLane Lt, La;
-  ExprWave C;
-  const uint32_t lane = threadIdx.x & 63u;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
-      group_row<T>(P, A, X, sel, (int64_t)xe, pos, lane, Lt, La, S, C);
-    }
-  });
+}
+// group_cache_end, behind the workgroup's last row: the flush (every key the workgroup cached, once: one find-or-claim and one set of atomics), then the
+// lanes' records of `total` and of `absent` through the one AggLds<0>, one after the other
+__device__ __forceinline__ void group_cache_end(const GroupArgs& A, GroupLds& S, AggLane& Lt, AggLane& La) {
   __syncthreads();
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {   // the flush: every key the workgroup cached, once
+  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {
     const long long k = S.key[e];
     const uint32_t nm = S.nm[e];
     uint64_t slot;
@@ -203,6 +206,17 @@ __global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhe
   group_end(&A.S->total, Lt, S.w);
   __syncthreads();                                                      // (thread 0 has read the waves' partials of `total`)
   group_end(&A.S->absent, La, S.w);
+}
+
+template <class T, bool CLOCKS, bool EXPR = false>      // (EXPR: a computed measure, bmx_expr.h; X is empty without one)
+__global__ __launch_bounds__(AGG_THREADS) void k_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A, ExprArgs<EXPR> X) {
+  __shared__ GroupLds S;
+  group_cache_begin(S);
+  AggLane Lt, La;
+  ExprWave C;
+  const uint32_t lane = threadIdx.x & 63u;
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) { group_row<T>(P, A, X, sel, (int64_t)xe, pos, lane, Lt, La, S, C); });
+  group_cache_end(A, S, Lt, La);
   expr_end(X, C);
 }
 
@@ -216,7 +230,6 @@ __device__ __forceinline__ bmx_agg group_compose(const AggRaw& x, uint32_t n_is_
 
 // n_is_match: every match had its measure (or there is none): n = n_match. `slots` is a multiple of 64: a wave's 64 lanes are inside the table or beyond it together.
 __global__ __launch_bounds__(256) void k_group_finish(GroupArgs A, bmx_group_rec* __restrict__ out, bmx_group_res* __restrict__ res, uint32_t n_is_match) {
-  __shared__ uint32_t s_last;
   GroupState* S = A.S;
   const unsigned long long claims = S->claims;
   const bool fits = claims <= A.cap && S->overflow == 0u;
@@ -225,32 +238,25 @@ __global__ __launch_bounds__(256) void k_group_finish(GroupArgs A, bmx_group_rec
     const uint64_t s = b + lane;
     const long long k = A.keys[s];
     const bool occ = k != GROUP_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                 // (uniform)
+    if (!__ballot(occ)) continue;                                       // (uniform)
     if (fits) {
-      unsigned long long base = 0;
-      if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-      base = __shfl(base, 0);
-      const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long r = wave_rank(occ, &S->nout, lane);
       if (occ && r < A.cap) { bmx_group_rec o; o.key = k; o.agg = group_compose(A.acc[s], n_is_match); out[r] = o; }
     }
     if (occ) { A.keys[s] = GROUP_EMPTY; A.acc[s] = GROUP_RAW_EMPTY; }
   }
-  __syncthreads();                                                      // every lane of the workgroup has read the state record and ranked its slots
-  if (threadIdx.x == 0) s_last = atomicAdd(&S->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // no workgroup reads the state record any more
+  if (last_workgroup(&S->done) && threadIdx.x == 0) {                   // no workgroup reads the state record any more
     bmx_group_res o;
     o.n_groups = claims; o.flags = fits ? 0u : BMX_GROUP_OVERFLOW; o.reserved = 0u;
     o.absent = group_compose(S->absent, n_is_match); o.total = group_compose(S->total, n_is_match);
     *res = o;
-    S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
+    group_state_reset(S);
   }
 }
 
 __global__ __launch_bounds__(256) void k_group_clear(long long* __restrict__ keys, AggRaw* __restrict__ acc, uint64_t slots, GroupState* __restrict__ S) {
   for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * 256u) { keys[s] = GROUP_EMPTY; acc[s] = GROUP_RAW_EMPTY; }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) group_state_reset(S);
 }
 
 }  // namespace bmx

@@ -161,7 +161,6 @@ __global__ __launch_bounds__(256) void k_gtop_advance(FirstArgs F, GtopArgs G, u
 
 // n_is_match: every member had its order value (the order field is the base field): n = n_match. `slots` is a multiple of 64.
 __global__ __launch_bounds__(256) void k_gtop_finish(FirstArgs F, GtopArgs G, GtopOut O, uint32_t n_is_match) {
-  __shared__ uint32_t s_last;
   const GroupArgs& A = F.G;
   GroupState* S = A.S;
   const unsigned long long claims = S->claims;
@@ -172,13 +171,9 @@ __global__ __launch_bounds__(256) void k_gtop_finish(FirstArgs F, GtopArgs G, Gt
     const uint64_t s = b + lane;
     const long long k = A.keys[s];
     const bool occ = k != GROUP_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                 // (uniform)
+    if (!__ballot(occ)) continue;                                       // (uniform)
     if (fits) {
-      unsigned long long base = 0;
-      if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-      base = __shfl(base, 0);
-      const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long r = wave_rank(occ, &S->nout, lane);
       const bool w = occ && r < A.cap;
       uint32_t nr = 0;
       if (w) {
@@ -210,17 +205,14 @@ __global__ __launch_bounds__(256) void k_gtop_finish(FirstArgs F, GtopArgs G, Gt
       G.pv[s] = INT64_MIN; G.pid[s] = 0ull; G.ext[s] = INT64_MAX; G.rank[s] = 0u;
     }
   }
-  __syncthreads();                                                      // every lane of the workgroup has read the state records and ranked its slots
-  if (threadIdx.x == 0) s_last = atomicAdd(&S->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // no workgroup reads the state records any more
+  if (last_workgroup(&S->done) && threadIdx.x == 0) {                   // no workgroup reads the state records any more
     bmx_gtop_res o;
     o.n_groups = claims; o.flags = fits ? 0u : BMX_GTOP_OVERFLOW; o.per = G.per;
     o.total = S->total.nm; o.absent = S->absent.nm; o.n_ordered = S->total.n - S->absent.n;
     o.n_rows = 0ull;                                                    // the rounds' counts, final since the last k_gtop_advance (none ran on overflow: 0)
     for (uint32_t j = 0; j < GTOP_MAX_PER; j++) { o.n_rows += G.T->given[j]; G.T->given[j] = 0u; }
     *O.res = o;
-    S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
+    group_state_reset(S);
   }
 }
 

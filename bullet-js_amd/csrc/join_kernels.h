@@ -9,8 +9,8 @@
 //                         +-VAL_MAX is skipped and not counted; a val outside +-VAL_MAX is "no attribute".
 // k_join_group_sweep<T> : k_group_sweep's shape and LDS cache. Per selected row: the measure and the link (the column, or one agg_probe each), a read-only walk of
 //                         the map with plain 16-byte loads, then `total` plus `absent` or `unmatched` in the lane's registers, or group_put with the mapped
-//                         attribute as the key (with the wave's same-key vote). The three lane records leave the workgroup one after another through the one
-//                         AggLds<0>. With the map's overflow state set the kernel returns at once: nothing is grouped and every record stays empty.
+//                         attribute as the key (group_row_put: the wave's same-key vote). The three lane records leave the workgroup one after another through
+//                         the one AggLds<0>. With the map's overflow state set the kernel returns at once: nothing is grouped and every record stays empty.
 // k_join_export         : the occupied pairs compacted into two lists by wave ballot + popcount (the sharded form's phase 1).
 // k_join_finish         : the group records ranked and written as k_group_finish does; both tables back to empty; the workgroup that finishes last writes `res`
 //                         and puts both state records back.
@@ -19,12 +19,12 @@
 // The map (device memory, JoinScratch): `slots` = max(64, next power of two >= 2 * map_cap) 16-byte {key, val} pairs: a lookup is one random access and one
 // aligned 16-byte load brings both words. An empty key is JOIN_EMPTY = INT64_MIN = BMX_VAL_DELETED, a val of JOIN_NO_ATTR = INT64_MAX means "no attribute";
 // neither is a data value. Home slot and walk are semi_insert's (group_mix(key) & (slots - 1), linear with wrap), so tests/group_model.py's home /
-// keys_with_home / walk describe this table too. Insert: find-or-claim as semi_insert does (relaxed agent-scope loads of the key words, one atomicCAS on an empty
-// word, the word the CAS returned looked at before moving on; a key already present costs no atomic), then the minimum: the val word of every slot is
-// JOIN_NO_ATTR before the launch and only ever decreases, so an atomicMin is issued only when a relaxed agent-scope load of the word shows a value above the
-// node's attribute — the skip is exact, and an inner side of 10^7 nodes with five keys does not send 10^7 atomics to five addresses. A lane may lower the val
-// of a slot the moment it sees its key there: no lane waits for another or spins on a word another lane must write. The only loop is the walk, bounded by
-// `slots`; it gives up at every 64th step once more than map_cap keys are claimed and raises the overflow bit, as semi_insert does.
+// keys_with_home / walk describe this table too. Insert: join_slot, group_slot's walk over the pairs' key words, as semi_insert (relaxed agent-scope loads,
+// one atomicCAS on an empty word, the word the CAS returned looked at before moving on; a key already present costs no atomic), then the minimum: the val word
+// of every slot is JOIN_NO_ATTR before the launch and only ever decreases, so an atomicMin is issued only when a relaxed agent-scope load of the word shows a
+// value above the node's attribute — the skip is exact, and an inner side of 10^7 nodes with five keys does not send 10^7 atomics to five addresses. A lane may
+// lower the val of a slot the moment it sees its key there: no lane waits for another or spins on a word another lane must write. The only loop is the walk,
+// bounded by `slots`; it gives up at every 64th step once more than map_cap keys are claimed and raises the overflow bit, as semi_insert does.
 #pragma once
 #include "semi_kernels.h"
 #include "../../include/bmx_join.h"
@@ -58,24 +58,37 @@ struct JoinArgs {
 
 __device__ __forceinline__ bool join_map_fits(const JoinState* S, uint64_t cap) { return S->overflow == 0u && S->claims <= cap; }
 
-// the pair (key, val) into the map: find or claim the key's slot, then lower its val (val == JOIN_NO_ATTR: the key alone)
-__device__ __forceinline__ void join_insert(const JoinArgs& A, long long key, long long val) {
+__device__ __forceinline__ void join_state_reset(JoinState* S) {
+  S->claims = 0ull; S->n_inner = 0ull; S->n_keyed = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->unmatched = GROUP_RAW_EMPTY;
+}
+
+// the slot of `key` in the map, for join_insert and reach_kernels.h's reach_insert: group_slot's find-or-claim walk over the pairs' key words, in a copy of its
+// own (group_slot says why). false: no room (the overflow bit is up); claimed: by this lane, just now
+__device__ __forceinline__ bool join_slot(const JoinArgs& A, long long key, uint64_t& slot, bool& claimed) {
   const uint64_t mask = A.slots - 1u;
   uint64_t s = group_mix(key) & mask;
-  bool found = false;
+  claimed = false;
   for (uint64_t p = 0; p < A.slots; ++p, s = (s + 1u) & mask) {
     long long k = __hip_atomic_load(&A.map[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (k == JOIN_EMPTY) {
       k = (long long)atomicCAS(reinterpret_cast<unsigned long long*>(&A.map[s].key), (unsigned long long)JOIN_EMPTY, (unsigned long long)key);
-      if (k == JOIN_EMPTY) { atomicAdd(&A.S->claims, 1ull); k = key; }
+      if (k == JOIN_EMPTY) { atomicAdd(&A.S->claims, 1ull); claimed = true; k = key; }
     }
-    if (k == key) { found = true; break; }                               // present (or just claimed, by this lane or another with the same key)
+    if (k == key) { slot = s; return true; }                             // present (or just claimed, by this lane or another with the same key)
     if ((p & 63u) == 63u && __hip_atomic_load(&A.S->claims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > A.cap) break;
   }
-  if (!found) { atomicOr(&A.S->overflow, 1u); return; }
-  if (val == JOIN_NO_ATTR) return;
-  // (the word only ever decreases: a value at or below val now stays there)
+  atomicOr(&A.S->overflow, 1u);
+  return false;
+}
+// the val of slot s down to `val` (the word only ever decreases: a value at or below val now stays there, and costs no atomic)
+__device__ __forceinline__ void join_lower(const JoinArgs& A, uint64_t s, long long val) {
   if (__hip_atomic_load(&A.map[s].val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > val) atomicMin(&A.map[s].val, val);
+}
+
+// the pair (key, val) into the map: find or claim the key's slot, then lower its val (val == JOIN_NO_ATTR: the key alone)
+__device__ __forceinline__ void join_insert(const JoinArgs& A, long long key, long long val) {
+  uint64_t s; bool claimed;
+  if (join_slot(A, key, s, claimed) && val != JOIN_NO_ATTR) join_lower(A, s, val);
 }
 
 // the val of `key` in the map; false: not a key. Plain loads: nobody writes the map while the group sweep runs.
@@ -93,34 +106,27 @@ __device__ __forceinline__ bool join_find(const JoinPair* __restrict__ map, uint
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field; attr_src: likewise, or JOIN_SRC_KEY
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_join_build(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs A, uint32_t key_field, uint32_t key_src, uint32_t attr_field, uint32_t attr_src) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES], s_k[TOP_WAVES];
   unsigned long long cnt_l = 0, key_l = 0;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) {
+    if (!sel) return;
+    cnt_l++;
+    int64_t key = (int64_t)xe, attr = (int64_t)xe;
+    bool have_k = key_src == 0u, have_a = attr_src == 0u;
+    // the key (k = 0) and the attribute (k = 1) through ONE copy of the probe. Not where_two_fields: the skip of k = 1 depends on what k = 0 found in this lane.
 #pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      if (!P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) continue;
-      cnt_l++;
-      int64_t key = (int64_t)xe, attr = (int64_t)xe;
-      bool have_k = key_src == 0u, have_a = attr_src == 0u;
-      // the key (k = 0) and the attribute (k = 1) through ONE copy of the probe, as group_row does it
-#pragma unroll 1
-      for (uint32_t k = 0; k < 2u; k++) {
-        if ((k ? attr_src : key_src) != AGG_SRC_PROBE) continue;         // (uniform)
-        if (k && !have_k) continue;                                       // (a keyless node's attribute is never looked at)
-        int64_t y;
-        if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? attr_field : key_field, y) && y != VAL_DELETED) {
-          if (k) { attr = y; have_a = true; } else { key = y; have_k = true; }
-        }
+    for (uint32_t k = 0; k < 2u; k++) {
+      if ((k ? attr_src : key_src) != AGG_SRC_PROBE) continue;         // (uniform)
+      if (k && !have_k) continue;                                       // (a keyless node's attribute is never looked at)
+      int64_t y;
+      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? attr_field : key_field, y) && y != VAL_DELETED) {
+        if (k) { attr = y; have_a = true; } else { key = y; have_k = true; }
       }
-      if (!have_k) continue;
-      key_l++;
-      if (attr_src == JOIN_SRC_KEY) { attr = key; have_a = true; }
-      join_insert(A, (long long)key, have_a ? (long long)attr : JOIN_NO_ATTR);
     }
+    if (!have_k) return;
+    key_l++;
+    if (attr_src == JOIN_SRC_KEY) { attr = key; have_a = true; }
+    join_insert(A, (long long)key, have_a ? (long long)attr : JOIN_NO_ATTR);
   });
   semi_count_end(cnt_l, s_n, TOP_WAVES, &A.S->n_inner);
   semi_count_end(key_l, s_k, TOP_WAVES, &A.S->n_keyed);
@@ -158,66 +164,27 @@ __device__ __forceinline__ void join_row(const PredWhere<T, true, CLOCKS>& P, co
   long long gval = JOIN_NO_ATTR;
   bool have_m = A.m_src == 0u, have_l = A.g_src == 0u, go = false;
   if (sel) {
-    // the measure (k = 0) and the link (k = 1) through ONE copy of the probe
-#pragma unroll 1
-    for (uint32_t k = 0; k < 2u; k++) {
-      if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;          // (uniform)
-      int64_t y;
-      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
-        if (k) { lval = y; have_l = true; } else { mval = y; have_m = true; }
-      }
-    }
+    where_two_fields(P, pos, A.m_src, A.measure, mval, have_m, A.g_src, A.group, lval, have_l);
     const bool in = have_l && join_find(map, mslots, (long long)lval, gval);
     group_lane_add(Lt, have_m, mval);
     join_lane_add(Lu, !in, have_m, mval);
     join_lane_add(La, in && gval == JOIN_NO_ATTR, have_m, mval);
     go = in && gval != JOIN_NO_ATTR;
   }
-  const unsigned long long act = __ballot(go);
-  if (!act) return;                                                    // (uniform)
-  // rows of one wave often map to one attribute: the lanes that hold the first one's add their count once
-  const int first = __ffsll((long long)act) - 1;
-  const long long k0 = __shfl(gval, first);
-  const unsigned long long same = __ballot(go && gval == k0);
-  if (!go) return;
-  uint32_t nm = 1u;
-  if (gval == k0) nm = (int)lane == first ? (uint32_t)__popcll(same) : 0u;
-  if (nm || have_m) group_put(A, S, gval, nm, have_m, mval);
+  group_row_put(A, go, gval, have_m, mval, lane, S);                   // (rows of one wave often map to one attribute)
 }
 
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_join_group_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, GroupArgs A, JoinArgs J) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ GroupLds S;
   if (!join_map_fits(J.S, J.cap)) return;                                // (uniform: the build is complete) nothing is grouped, every record stays empty
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {
-    S.key[e] = GROUP_EMPTY; S.nm[e] = 0u; S.n[e] = 0u; S.mn[e] = INT64_MAX; S.mx[e] = INT64_MIN; S.slo[e] = 0ull; S.shi[e] = 0ll;
-  }
-  __syncthreads();
+  group_cache_begin(S);
   AggLane Lt, La, Lu;
   const uint32_t lane = threadIdx.x & 63u;
   const JoinPair* map = J.map;
   const uint64_t mslots = J.slots;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
-      join_row<T>(P, A, map, mslots, sel, (int64_t)xe, pos, lane, Lt, La, Lu, S);
-    }
-  });
-  __syncthreads();
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {   // the flush: every attribute the workgroup cached, once
-    const long long k = S.key[e];
-    const uint32_t nm = S.nm[e];
-    uint64_t slot;
-    if (k != GROUP_EMPTY && nm && group_slot(A, k, slot)) agg_flush_one(A.acc + slot, nm, S.n[e], S.mn[e], S.mx[e], S.slo[e], S.shi[e]);
-  }
-  group_end(&A.S->total, Lt, S.w);
-  __syncthreads();                                                      // (thread 0 has read the waves' partials of `total`)
-  group_end(&A.S->absent, La, S.w);
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) { join_row<T>(P, A, map, mslots, sel, (int64_t)xe, pos, lane, Lt, La, Lu, S); });
+  group_cache_end(A, S, Lt, La);
   __syncthreads();
   group_end(&J.S->unmatched, Lu, S.w);
 }
@@ -230,19 +197,14 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_join_export(JoinArgs A, long l
   for (uint64_t b = (uint64_t)blockIdx.x * JOIN_THREADS + (threadIdx.x & ~63u); b < A.slots; b += (uint64_t)gridDim.x * JOIN_THREADS) {
     const join_ll2 kv = *reinterpret_cast<const join_ll2*>(A.map + b + lane);
     const bool occ = kv.x != JOIN_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                  // (uniform)
-    unsigned long long base = 0;
-    if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-    base = __shfl(base, 0);
-    const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+    if (!__ballot(occ)) continue;                                        // (uniform)
+    const unsigned long long r = wave_rank(occ, &S->nout, lane);
     if (occ && r < A.cap) { out_keys[r] = kv.x; out_vals[r] = kv.y; }
   }
 }
 
 // A.slots == 0: no group table to sweep (the sharded form's phase 1); A.S is read and put back all the same.
 __global__ __launch_bounds__(JOIN_THREADS) void k_join_finish(GroupArgs A, JoinArgs J, bmx_group_rec* __restrict__ out, bmx_join_res* __restrict__ res, uint32_t n_is_match) {
-  __shared__ uint32_t s_last;
   GroupState* S = A.S;
   JoinState* M = J.S;
   const unsigned long long claims = S->claims;
@@ -252,37 +214,30 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_join_finish(GroupArgs A, JoinA
     const uint64_t s = b + lane;
     const long long k = A.keys[s];
     const bool occ = k != GROUP_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                 // (uniform)
+    if (!__ballot(occ)) continue;                                       // (uniform)
     if (fits) {
-      unsigned long long base = 0;
-      if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-      base = __shfl(base, 0);
-      const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long r = wave_rank(occ, &S->nout, lane);
       if (occ && r < A.cap) { bmx_group_rec o; o.key = k; o.agg = group_compose(A.acc[s], n_is_match); out[r] = o; }
     }
     if (occ) { A.keys[s] = GROUP_EMPTY; A.acc[s] = GROUP_RAW_EMPTY; }
   }
   for (uint64_t s = (uint64_t)blockIdx.x * JOIN_THREADS + threadIdx.x; s < J.slots; s += (uint64_t)gridDim.x * JOIN_THREADS)
     if (J.map[s].key != JOIN_EMPTY) { JoinPair e; e.key = JOIN_EMPTY; e.val = JOIN_NO_ATTR; J.map[s] = e; }
-  __syncthreads();                                                      // every lane of the workgroup has read the state records and ranked its slots
-  if (threadIdx.x == 0) s_last = atomicAdd(&M->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // no workgroup reads the state records any more
+  if (last_workgroup(&M->done) && threadIdx.x == 0) {                   // no workgroup reads the state records any more
     const bool mfits = join_map_fits(M, J.cap);
     bmx_join_res o;
     o.n_groups = mfits ? claims : 0ull; o.map_size = M->claims; o.n_inner = M->n_inner; o.n_keyed = M->n_keyed;
     o.flags = (mfits ? 0u : BMX_JOIN_MAP_OVERFLOW) | (fits ? 0u : BMX_JOIN_GROUP_OVERFLOW); o.reserved = 0u;
     o.absent = group_compose(S->absent, n_is_match); o.unmatched = group_compose(M->unmatched, n_is_match); o.total = group_compose(S->total, n_is_match);
     *res = o;
-    S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
-    M->claims = 0ull; M->n_inner = 0ull; M->n_keyed = 0ull; M->nout = 0ull; M->overflow = 0u; M->done = 0u; M->unmatched = GROUP_RAW_EMPTY;
+    group_state_reset(S);
+    join_state_reset(M);
   }
 }
 
 __global__ __launch_bounds__(JOIN_THREADS) void k_join_clear(JoinPair* __restrict__ map, uint64_t slots, JoinState* __restrict__ S) {
   for (uint64_t s = (uint64_t)blockIdx.x * JOIN_THREADS + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * JOIN_THREADS) { JoinPair e; e.key = JOIN_EMPTY; e.val = JOIN_NO_ATTR; map[s] = e; }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { S->claims = 0ull; S->n_inner = 0ull; S->n_keyed = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->unmatched = GROUP_RAW_EMPTY; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) join_state_reset(S);
 }
 
 }  // namespace bmx

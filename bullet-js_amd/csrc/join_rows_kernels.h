@@ -43,25 +43,15 @@ static_assert((unsigned long long)JOIN_NO_ATTR == (BMX_JROWS_NO_NODE ^ JROWS_BIA
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_jrows_build(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs A, uint32_t key_field, uint32_t key_src) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES], s_k[TOP_WAVES];
   unsigned long long cnt_l = 0, key_l = 0;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      if (!P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) continue;
-      cnt_l++;
-      const uint64_t id = P.ids[pos];
-      int64_t key = (int64_t)xe;
-      bool have = key_src == 0u;
-      if (key_src == AGG_SRC_PROBE) have = agg_probe(P.slots, P.nslots, id, key_field, key) && key != VAL_DELETED;
-      if (!have) continue;
-      key_l++;
-      join_insert(A, (long long)key, jrows_word(id));
-    }
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) {
+    if (!sel) return;
+    cnt_l++;
+    int64_t key = (int64_t)xe;
+    if (!where_field(P, pos, key_src, key_field, key)) return;
+    key_l++;
+    join_insert(A, (long long)key, jrows_word(P.ids[pos]));
   });
   semi_count_end(cnt_l, s_n, TOP_WAVES, &A.S->n_inner);
   semi_count_end(key_l, s_k, TOP_WAVES, &A.S->n_keyed);
@@ -93,7 +83,7 @@ template <class T>
 __device__ __forceinline__ long long jrows_resolve(const JRowsLink& L, const T* __restrict__ v, const uint64_t* __restrict__ ids, const Slot* __restrict__ slots, uint64_t nslots, uint64_t pos) {
   int64_t y = VAL_DELETED;
   bool have;
-  if (L.link_src == 0u) { y = (int64_t)v[pos]; have = true; }           // a selected row holds data
+  if (L.link_src == 0u) { y = (int64_t)v[pos]; have = true; }           // a selected row holds data (not where_field: the column value is not at hand)
   else have = agg_probe(slots, nslots, ids[pos], L.link, y) && y != VAL_DELETED;
   long long w = JOIN_NO_ATTR;
   if (!have || !join_find(L.map, L.mslots, (long long)y, w)) w = JOIN_NO_ATTR;
@@ -225,20 +215,16 @@ __global__ __launch_bounds__(SEL_THREADS) void k_jrows_emit(const uint32_t* __re
 
 // rows != 0: behind k_jrows_emit, which wrote n_match, n_out, next_pos and layout; rows == 0: no rows were asked for (the sharded form's phase 1)
 __global__ __launch_bounds__(JOIN_THREADS) void k_jrows_finish(JoinArgs J, bmx_jrows_res* __restrict__ res, uint32_t rows) {
-  __shared__ uint32_t s_last;
   JoinState* M = J.S;
   for (uint64_t s = (uint64_t)blockIdx.x * JOIN_THREADS + threadIdx.x; s < J.slots; s += (uint64_t)gridDim.x * JOIN_THREADS)
     if (J.map[s].key != JOIN_EMPTY) { JoinPair e; e.key = JOIN_EMPTY; e.val = JOIN_NO_ATTR; J.map[s] = e; }
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&M->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // only this thread reads the state record in this kernel
+  if (last_workgroup(&M->done) && threadIdx.x == 0) {                   // only this thread reads the state record in this kernel
     const bool mfits = join_map_fits(M, J.cap);
     if (!rows) { res->n_match = 0ull; res->n_out = 0ull; res->next_pos = 0ull; res->layout = 0ull; }
     res->n_joined = rows && mfits ? M->nout : 0ull;
     res->map_size = M->claims; res->n_inner = M->n_inner; res->n_keyed = M->n_keyed;
     res->flags = mfits ? 0u : BMX_JOIN_MAP_OVERFLOW; res->next_shard = 0u;
-    M->claims = 0ull; M->n_inner = 0ull; M->n_keyed = 0ull; M->nout = 0ull; M->overflow = 0u; M->done = 0u;
+    join_state_reset(M);                                                // (`unmatched` was empty already: as k_join_clear leaves the record)
   }
 }
 

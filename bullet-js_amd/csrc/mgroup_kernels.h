@@ -4,8 +4,8 @@
 // k_mgroup_sweep<T> : k_group_sweep's sweep (one read of the base field's value column, PredWhere::row() decides the candidates). A selected row's key values
 //                     are the column value when the field is the base field, otherwise one agg_probe each, made after the match is known; a row that lacks
 //                     ANY of them goes to `absent` and touches no table. Every other row turns each value into a CODE through that key's dictionary, packs
-//                     the codes into one word and is aggregated under that word by group_kernels.h's own machinery (group_put: the LDS cache of 256 x 4 ways
-//                     and the bypass; group_slot; the wave-level dedupe of the first lane's word) in a tuple table of this call's own scratch.
+//                     the codes into one word and is aggregated under that word by group_kernels.h's own machinery (group_row_put: the wave-level dedupe of
+//                     the first lane's word; group_put: the LDS cache of 256 x 4 ways and the bypass; group_slot) in a tuple table of this call's own scratch.
 // k_mgroup_finish   : k_group_finish over the tuple table. A record's keys are read back through the dictionaries: dict_j[code_j]. Every tuple slot goes back
 //                     to its empty state; the workgroup that finishes last writes `res` and puts the tuple table's state record back.
 // k_mgroup_clear    : the dictionaries and their state records to their empty state BEHIND the finish, which reads them (slots == 0); everything (new
@@ -34,7 +34,6 @@ namespace bmx {
 constexpr uint32_t MGROUP_KEYS = BMX_MGROUP_MAX_KEYS;
 static_assert(sizeof(bmx_mgroup_rec) == 80 && sizeof(bmx_group_key) == 24, "the records of bmx_group_multi.h");
 static_assert(MGROUP_KEYS == 4, "mgroup_row keeps the key values in four named registers");
-static_assert(MGROUP_KEYS * GROUP_SETS == GROUP_CACHE, "k_mgroup_sweep empties both caches in one loop");
 
 struct MGroupKey { long long origin, width; uint32_t field, src; };   // src: 0 = the base field's column, AGG_SRC_PROBE = one probe of `field`
 
@@ -89,14 +88,13 @@ __device__ __forceinline__ void mgroup_row(const PredWhere<T, true, CLOCKS>& P, 
   long long k0 = 0, k1 = 0, k2 = 0, k3 = 0;
   bool have_m = A.T.m_src == 0u, have_g = true;
   if (sel) {
-    // the keys (j < nkeys) and the measure (j == nkeys) through ONE copy of the probe, as group_row does it; the values stay in named registers
+    // the keys (j < nkeys) and the measure (j == nkeys) through ONE copy of the probe (where_field); the values stay in named registers
 #pragma unroll 1
     for (uint32_t j = 0; j <= A.nkeys; j++) {
       const bool is_m = j == A.nkeys;
       const uint32_t src = is_m ? A.T.m_src : A.k[j & 3u].src;        // (uniform)
       int64_t y = x;
-      bool have = src == 0u;
-      if (src == AGG_SRC_PROBE) have = agg_probe(P.slots, P.nslots, P.ids[pos], is_m ? A.T.measure : A.k[j & 3u].field, y) && y != VAL_DELETED;
+      const bool have = where_field(P, pos, src, is_m ? A.T.measure : A.k[j & 3u].field, y);
       if (is_m) { if (src == AGG_SRC_PROBE && have) { mval = y; have_m = true; } continue; }
       if (!have) { have_g = false; continue; }
       const long long b = mgroup_bucket((long long)y, A.k[j].origin, A.k[j].width);
@@ -119,54 +117,22 @@ __device__ __forceinline__ void mgroup_row(const PredWhere<T, true, CLOCKS>& P, 
     if (mgroup_code(D, S, j, v, code)) word |= (unsigned long long)code << (j * A.shift);
     else go = false;                                                   // (that dictionary's overflow bit is up)
   }
-  const unsigned long long act = __ballot(go);
-  if (!act) return;                                                    // (uniform)
-  // rows of one wave often share a tuple: the lanes that hold the first one's word add their count once (group_row's tail)
-  const int first = __ffsll((long long)act) - 1;
-  const long long w0 = __shfl((long long)word, first);
-  const unsigned long long same = __ballot(go && (long long)word == w0);
-  if (!go) return;
-  uint32_t nm = 1u;
-  if ((long long)word == w0) nm = (int)lane == first ? (uint32_t)__popcll(same) : 0u;
-  if (nm || have_m) group_put(A.T, S.G, (long long)word, nm, have_m, mval);
+  group_row_put(A.T, go, (int64_t)word, have_m, mval, lane, S.G);      // (rows of one wave often share a tuple)
 }
 
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_mgroup_sweep(uint64_t n, PredWhere<T, true, CLOCKS> P, MGroupArgs A) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ MGroupLds S;
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {
-    S.G.key[e] = GROUP_EMPTY; S.G.nm[e] = 0u; S.G.n[e] = 0u; S.G.mn[e] = INT64_MAX; S.G.mx[e] = INT64_MIN; S.G.slo[e] = 0ull; S.G.shi[e] = 0ll;
-    S.dval[e] = GROUP_EMPTY; S.dcode[e] = MGROUP_NOCODE;
-  }
-  __syncthreads();
+  for (uint32_t e = threadIdx.x; e < MGROUP_KEYS * MGROUP_DSETS; e += AGG_THREADS) { S.dval[e] = GROUP_EMPTY; S.dcode[e] = MGROUP_NOCODE; }
+  group_cache_begin(S.G);
   AggLane Lt, La;
   const uint32_t lane = threadIdx.x & 63u;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
-      mgroup_row<T>(P, A, sel, (int64_t)xe, pos, lane, Lt, La, S);
-    }
-  });
-  __syncthreads();
-  for (uint32_t e = threadIdx.x; e < GROUP_CACHE; e += AGG_THREADS) {   // the flush: every word the workgroup cached, once
-    const long long k = S.G.key[e];
-    const uint32_t nm = S.G.nm[e];
-    uint64_t slot;
-    if (k != GROUP_EMPTY && nm && group_slot(A.T, k, slot)) agg_flush_one(A.T.acc + slot, nm, S.G.n[e], S.G.mn[e], S.G.mx[e], S.G.slo[e], S.G.shi[e]);
-  }
-  group_end(&A.T.S->total, Lt, S.G.w);
-  __syncthreads();                                                      // (thread 0 has read the waves' partials of `total`)
-  group_end(&A.T.S->absent, La, S.G.w);
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) { mgroup_row<T>(P, A, sel, (int64_t)xe, pos, lane, Lt, La, S); });
+  group_cache_end(A.T, S.G, Lt, La);
 }
 
 // k_group_finish over the tuple table; the keys of a record come back through the dictionaries. n_is_match and the wave / slots rule as there.
 __global__ __launch_bounds__(256) void k_mgroup_finish(MGroupArgs A, bmx_mgroup_rec* __restrict__ out, bmx_group_res* __restrict__ res, uint32_t n_is_match) {
-  __shared__ uint32_t s_last;
   GroupState* S = A.T.S;
   unsigned long long claims = S->claims, most = claims;
   bool fits = claims <= A.T.cap && S->overflow == 0u;
@@ -183,13 +149,9 @@ __global__ __launch_bounds__(256) void k_mgroup_finish(MGroupArgs A, bmx_mgroup_
     const uint64_t s = b + lane;
     const long long w = A.T.keys[s];
     const bool occ = w != GROUP_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                 // (uniform)
+    if (!__ballot(occ)) continue;                                       // (uniform)
     if (fits) {
-      unsigned long long base = 0;
-      if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-      base = __shfl(base, 0);
-      const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long r = wave_rank(occ, &S->nout, lane);
       if (occ && r < A.T.cap) {
         bmx_mgroup_rec o;
 #pragma unroll
@@ -201,15 +163,12 @@ __global__ __launch_bounds__(256) void k_mgroup_finish(MGroupArgs A, bmx_mgroup_
     }
     if (occ) { A.T.keys[s] = GROUP_EMPTY; A.T.acc[s] = GROUP_RAW_EMPTY; }
   }
-  __syncthreads();                                                      // every lane of the workgroup has read the state record and ranked its slots
-  if (threadIdx.x == 0) s_last = atomicAdd(&S->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                     // no workgroup reads the state record any more
+  if (last_workgroup(&S->done) && threadIdx.x == 0) {                   // no workgroup reads the state record any more
     bmx_group_res o;
     o.n_groups = claims; o.flags = fits ? 0u : BMX_GROUP_OVERFLOW; o.reserved = 0u;
     o.absent = group_compose(S->absent, n_is_match); o.total = group_compose(S->total, n_is_match);
     *res = o;
-    S->claims = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; S->absent = GROUP_RAW_EMPTY; S->total = GROUP_RAW_EMPTY;
+    group_state_reset(S);
   }
 }
 
@@ -221,7 +180,7 @@ __global__ __launch_bounds__(256) void k_mgroup_clear(long long* __restrict__ di
   for (uint64_t s = t; s < slots; s += step) { keys[s] = GROUP_EMPTY; acc[s] = GROUP_RAW_EMPTY; }
   if (t <= MGROUP_KEYS) {
     GroupState* R = t < MGROUP_KEYS ? DS + t : S;
-    if (t < MGROUP_KEYS || slots) { R->claims = 0ull; R->nout = 0ull; R->overflow = 0u; R->done = 0u; R->absent = GROUP_RAW_EMPTY; R->total = GROUP_RAW_EMPTY; }
+    if (t < MGROUP_KEYS || slots) group_state_reset(R);
   }
 }
 

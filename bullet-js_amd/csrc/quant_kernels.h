@@ -141,6 +141,7 @@ __global__ __launch_bounds__(TOP_THREADS) void k_quant0(uint64_t n, PredWhere<T,
   const uint64_t nu = (n + E - 1) / E;
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
     uint32_t nib = 0;
+    // (its own copy of where_unit_rows' walk: through the helper the PROBE builds take 4 to 6 more VGPRs and two of them lose a wave of occupancy)
 #pragma unroll 1
     for (int e = 0; e < E; e++) {
       const T xe = where_pick<T, E>(x, e);

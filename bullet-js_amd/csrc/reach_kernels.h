@@ -24,7 +24,7 @@
 // k_reach_export     : the keys of one level compacted into a list by wave ballot + popcount (the sharded forms, after every round).
 // k_reach_finish     : the map back to empty; the workgroup that finishes last writes `res` and puts both state records back.
 //
-// reach_insert is join_insert's find-or-claim plus the minimum, with one addition: a successful claim made at level r adds one to new_keys[r] with a no-return
+// reach_insert is join_insert's two steps (join_slot, join_lower), with one addition: a successful claim made at level r adds one to new_keys[r] with a no-return
 // atomic. A value is claimed in the round that first meets it, and every insert of round r carries r, so new_keys[r] is the number of values of level r: it
 // drives the early-out of round r + 1, and new_keys[max_depth] != 0 is BMX_REACH_MORE.
 //
@@ -64,22 +64,10 @@ struct ReachArgs {
 };
 
 __device__ __forceinline__ void reach_insert(const JoinArgs& A, ReachState* R, long long key, uint32_t level) {
-  const uint64_t mask = A.slots - 1u;
-  uint64_t s = group_mix(key) & mask;
-  bool found = false;
-  for (uint64_t p = 0; p < A.slots; ++p, s = (s + 1u) & mask) {
-    long long k = __hip_atomic_load(&A.map[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == JOIN_EMPTY) {
-      k = (long long)atomicCAS(reinterpret_cast<unsigned long long*>(&A.map[s].key), (unsigned long long)JOIN_EMPTY, (unsigned long long)key);
-      if (k == JOIN_EMPTY) { atomicAdd(&A.S->claims, 1ull); atomicAdd(&R->new_keys[level], 1u); k = key; }
-    }
-    if (k == key) { found = true; break; }                               // present (or just claimed, by this lane or another with the same key)
-    if ((p & 63u) == 63u && __hip_atomic_load(&A.S->claims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > A.cap) break;
-  }
-  if (!found) { atomicOr(&A.S->overflow, 1u); return; }
-  // (the word only ever decreases: a level at or below this one stays there)
-  const long long lv = (long long)level;
-  if (__hip_atomic_load(&A.map[s].val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > lv) atomicMin(&A.map[s].val, lv);
+  uint64_t s; bool claimed;
+  if (!join_slot(A, key, s, claimed)) return;
+  if (claimed) atomicAdd(&R->new_keys[level], 1u);
+  join_lower(A, s, (long long)level);
 }
 
 // is `key` in the map with a level <= max_level? One walk, plain 16-byte loads (the header comment: why that is exact while the round inserts).
@@ -97,22 +85,13 @@ __device__ __forceinline__ bool reach_has(const JoinPair* __restrict__ map, uint
 // seed_src: 0 = the seed base field's column, AGG_SRC_PROBE = one probe of seed_field
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_reach_seed(uint64_t n, PredWhere<T, true, CLOCKS> P, JoinArgs J, ReachState* R, uint32_t seed_field, uint32_t seed_src) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES];
   unsigned long long cnt_l = 0;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      if (!P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) continue;
-      cnt_l++;
-      int64_t key = (int64_t)xe;
-      bool have = seed_src == 0u;
-      if (seed_src == AGG_SRC_PROBE) have = agg_probe(P.slots, P.nslots, P.ids[pos], seed_field, key) && key != VAL_DELETED;
-      if (have) reach_insert(J, R, (long long)key, 0u);
-    }
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) {
+    if (!sel) return;
+    cnt_l++;
+    int64_t key = (int64_t)xe;
+    if (where_field(P, pos, seed_src, seed_field, key)) reach_insert(J, R, (long long)key, 0u);
   });
   semi_count_end(cnt_l, s_n, TOP_WAVES, &R->n_seed);
 }
@@ -138,19 +117,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_reach_prepare(uint64_t n, PredW
   __shared__ unsigned long long s_n[TOP_WAVES];
   unsigned long long cnt_l = 0;
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      const bool sel = P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos);
-      if ((uint32_t)e >= cnt) continue;                                   // (beyond the column: nothing to write)
+    where_unit_rows<T>(P, unit, x, cnt, [&](int e, T xe, uint64_t pos, bool sel) {
+      if ((uint32_t)e >= cnt) return;                                     // (beyond the column: nothing to write)
       int64_t y = (int64_t)xe;
-      bool have = sel && link_src == 0u;                                  // a selected row holds data
-      if (sel && link_src == AGG_SRC_PROBE) have = agg_probe(P.slots, P.nslots, P.ids[pos], link_field, y) && y != VAL_DELETED;
+      const bool have = sel && where_field(P, pos, link_src, link_field, y);      // (a selected row holds data)
       cnt_l += have ? 1ull : 0ull;
       A.link[pos] = have ? (long long)y : REACH_NO_LINK;
       A.depth[pos] = (uint8_t)0;
-    }
+    });
   });
   semi_count_end(cnt_l, s_n, TOP_WAVES, &A.S->n_edges);
 }
@@ -194,7 +168,7 @@ __global__ __launch_bounds__(REACH_THREADS) void k_reach_round(uint64_t n, Reach
         any = true;
         int64_t key = 0;
         bool have;
-        if (K.key_src == 0u) { key = (int64_t)col[pos]; have = true; }    // an edge node's base row holds data
+        if (K.key_src == 0u) { key = (int64_t)col[pos]; have = true; }    // an edge node's base row holds data (no PredWhere here: not where_field)
         else have = agg_probe(K.slots, K.nslots, K.ids[pos], K.key_field, key) && key != VAL_DELETED;
         if (have) reach_insert(J, S, (long long)key, r);
       }
@@ -308,25 +282,17 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_reach_export(JoinArgs J, Reach
   for (uint64_t b = (uint64_t)blockIdx.x * JOIN_THREADS + (threadIdx.x & ~63u); b < J.slots; b += (uint64_t)gridDim.x * JOIN_THREADS) {
     const join_ll2 kv = *reinterpret_cast<const join_ll2*>(J.map + b + lane);
     const bool occ = kv.x != JOIN_EMPTY && kv.y == level;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                  // (uniform)
-    unsigned long long base = 0;
-    if (lane == 0u) base = atomicAdd(&R->nout, (unsigned long long)__popcll(bal));
-    base = __shfl(base, 0);
-    const unsigned long long rk = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+    if (!__ballot(occ)) continue;                                        // (uniform)
+    const unsigned long long rk = wave_rank(occ, &R->nout, lane);
     if (occ && rk < J.cap) out[rk] = kv.x;
   }
 }
 
 __global__ __launch_bounds__(JOIN_THREADS) void k_reach_finish(JoinArgs J, ReachState* R, bmx_reach_res* __restrict__ res, uint32_t max_depth) {
-  __shared__ uint32_t s_last;
   JoinState* M = J.S;
   for (uint64_t s = (uint64_t)blockIdx.x * JOIN_THREADS + threadIdx.x; s < J.slots; s += (uint64_t)gridDim.x * JOIN_THREADS)
     if (J.map[s].key != JOIN_EMPTY) { JoinPair e; e.key = JOIN_EMPTY; e.val = JOIN_NO_ATTR; J.map[s] = e; }
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&M->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (!s_last) return;                                                  // (uniform) no other workgroup reads the state records any more
+  if (!last_workgroup(&M->done)) return;                                // (uniform) no other workgroup reads the state records any more
   if (threadIdx.x == 0) {
     const bool fits = join_map_fits(M, J.cap);
     bmx_reach_res o;
@@ -334,7 +300,7 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_reach_finish(JoinArgs J, Reach
     o.rounds = fits ? R->rounds : 0u;
     o.flags = fits ? (R->new_keys[max_depth] ? BMX_REACH_MORE : 0u) : BMX_REACH_OVERFLOW;
     *res = o;
-    M->claims = 0ull; M->n_inner = 0ull; M->n_keyed = 0ull; M->nout = 0ull; M->overflow = 0u; M->done = 0u; M->unmatched = GROUP_RAW_EMPTY;
+    join_state_reset(M);
     R->n_seed = 0ull; R->n_edges = 0ull; R->n_match = 0ull; R->nout = 0ull; R->rounds = 0u; R->pad = 0u;
   }
   __syncthreads();                                                      // (thread 0 has read new_keys[max_depth])

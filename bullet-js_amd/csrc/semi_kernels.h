@@ -20,7 +20,8 @@
 // The table (device memory, SemiScratch): `slots` = max(64, next power of two >= 2 * set_cap) key words, SEMI_EMPTY = INT64_MIN = BMX_VAL_DELETED = empty, which
 // is never a data value and never inserted. The HOME slot of a key is group_mix(key) & (slots - 1) — group_kernels.h's function, the 64-bit finalizer of
 // MurmurHash3 — and probing is linear with wrap, so tests/group_model.py's mix / home / keys_with_home / walk describe this table too.
-// Insert: walk from the home slot reading key words with relaxed agent-scope atomic loads; stop at the key itself; claim an empty word with one 64-bit atomicCAS;
+// Insert (group_kernels.h group_slot's walk; semi_insert says why it has a copy of its own): walk from the home slot reading key words with relaxed
+// agent-scope atomic loads; stop at the key itself; claim an empty word with one 64-bit atomicCAS;
 // on a lost CAS look at the word the CAS returned (it may be this key, claimed by another lane) before moving on. A key that is already present costs no atomic:
 // an inner side of 10^7 nodes with 5 distinct keys sends 5 + a few lost CASes to memory, not 10^7. A successful claim adds one to the claim counter with a
 // no-return add. No lane waits for another or spins on a word another lane must write; the only loop is the walk, bounded by `slots`. Once more than set_cap keys
@@ -53,6 +54,14 @@ struct SemiArgs {
   uint64_t slots, cap;                            // this query's: the head of a table that may be larger
 };
 
+__device__ __forceinline__ void semi_state_reset(SemiState* S) {
+  S->claims = 0ull; S->n_inner = 0ull; S->n_match = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u;
+}
+
+// `key` into the table: group_slot's walk (group_kernels.h), in a copy of its own. Measured: every path that claims leaves the loop at once here, so the
+// compiler puts the wave's one add to the claim counter BEHIND the loop; in one shared definition, where a claim falls through, the add sits inside the
+// walk, and a build of 10^6 distinct keys takes 4.6 ms instead of 3.4 (profiles/kernel_sharing_timings.txt). A change to one of the walks goes into the
+// others by hand.
 __device__ __forceinline__ void semi_insert(const SemiArgs& A, long long key) {
   const uint64_t mask = A.slots - 1u;
   uint64_t s = group_mix(key) & mask;
@@ -96,22 +105,13 @@ __device__ __forceinline__ void semi_count_end(unsigned long long c, unsigned lo
 // key_src: 0 = the inner base field's column, AGG_SRC_PROBE = one probe of key_field
 template <class T, bool CLOCKS>
 __global__ __launch_bounds__(AGG_THREADS) void k_semi_build(uint64_t n, PredWhere<T, true, CLOCKS> P, SemiArgs A, uint32_t key_field, uint32_t key_src) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ unsigned long long s_n[TOP_WAVES];
   unsigned long long cnt_l = 0;
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      if (!P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) continue;
-      cnt_l++;
-      int64_t key = (int64_t)xe;
-      bool have = key_src == 0u;
-      if (key_src == AGG_SRC_PROBE) have = agg_probe(P.slots, P.nslots, P.ids[pos], key_field, key) && key != VAL_DELETED;
-      if (have) semi_insert(A, (long long)key);
-    }
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) {
+    if (!sel) return;
+    cnt_l++;
+    int64_t key = (int64_t)xe;
+    if (where_field(P, pos, key_src, key_field, key)) semi_insert(A, (long long)key);
   });
   semi_count_end(cnt_l, s_n, TOP_WAVES, &A.S->n_inner);
 }
@@ -161,36 +161,28 @@ __global__ __launch_bounds__(SEMI_THREADS) void k_semi_export(SemiArgs A, long l
   for (uint64_t b = (uint64_t)blockIdx.x * SEMI_THREADS + (threadIdx.x & ~63u); b < A.slots; b += (uint64_t)gridDim.x * SEMI_THREADS) {
     const long long k = A.keys[b + lane];
     const bool occ = k != SEMI_EMPTY;
-    const unsigned long long bal = __ballot(occ);
-    if (!bal) continue;                                                  // (uniform)
-    unsigned long long base = 0;
-    if (lane == 0u) base = atomicAdd(&S->nout, (unsigned long long)__popcll(bal));
-    base = __shfl(base, 0);
-    const unsigned long long r = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+    if (!__ballot(occ)) continue;                                        // (uniform)
+    const unsigned long long r = wave_rank(occ, &S->nout, lane);
     if (occ && r < A.cap) out[r] = k;
   }
 }
 
 __global__ __launch_bounds__(SEMI_THREADS) void k_semi_finish(SemiArgs A, bmx_semi_res* __restrict__ res) {
-  __shared__ uint32_t s_last;
   SemiState* S = A.S;
   for (uint64_t s = (uint64_t)blockIdx.x * SEMI_THREADS + threadIdx.x; s < A.slots; s += (uint64_t)gridDim.x * SEMI_THREADS)
     if (A.keys[s] != SEMI_EMPTY) A.keys[s] = SEMI_EMPTY;
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&S->done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) {                                      // only this thread reads the state record in this kernel
+  if (last_workgroup(&S->done) && threadIdx.x == 0) {                    // only this thread reads the state record in this kernel
     const bool fits = S->overflow == 0u && S->claims <= A.cap;
     bmx_semi_res o;
     o.n_match = fits ? S->n_match : 0ull; o.set_size = S->claims; o.n_inner = S->n_inner; o.flags = fits ? 0u : BMX_SEMI_OVERFLOW; o.reserved = 0u;
     *res = o;
-    S->claims = 0ull; S->n_inner = 0ull; S->n_match = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u;
+    semi_state_reset(S);
   }
 }
 
 __global__ __launch_bounds__(SEMI_THREADS) void k_semi_clear(long long* __restrict__ keys, uint64_t slots, SemiState* __restrict__ S) {
   for (uint64_t s = (uint64_t)blockIdx.x * SEMI_THREADS + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * SEMI_THREADS) keys[s] = SEMI_EMPTY;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { S->claims = 0ull; S->n_inner = 0ull; S->n_match = 0ull; S->nout = 0ull; S->overflow = 0u; S->done = 0u; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) semi_state_reset(S);
 }
 
 }  // namespace bmx

@@ -12,7 +12,8 @@
 // k_top_digit<T, PROBE>  : one digit (TOP_DIGIT_BITS bits) of the rows that share the prefix found so far: LDS histogram per workgroup (a wave whose rows all fall
 //                          into one bin adds once), one no-return global atomic per non-empty bin and workgroup. Digits run over the value first, then over the id.
 // k_top_find             : the bin that holds the row of rank k; prefix, rows below, done flag; clears the histogram.
-// k_top_compact<T, PROBE>: every eligible row at or below the boundary -> {key, id}, ranked by wave ballot + popcount into one counter.
+// k_top_compact<T, PROBE>: every eligible row at or below the boundary -> {key, id}, ranked by wave ballot + popcount into one counter (wave_rank, which
+//                          every finish and export kernel of the where family ranks with too).
 // k_top_finish           : one workgroup, bitonic sort of the candidates in LDS, the first min(k, n_eligible) records with the key turned back into the value, the
 //                          two counts, and the state left ready for the next query.
 // Every pass behind "done" returns after reading the state record, so the host enqueues the worst-case chain and nothing comes back between the passes.
@@ -94,6 +95,16 @@ __device__ __forceinline__ void top_sweep(const T* __restrict__ col, uint64_t n,
       f(i, x[u], cnt);
     }
   }
+}
+
+// Wave-ranked compaction, called by all 64 lanes of a wave of which at least one has occ set: lane 0 takes the wave's popcount out of `counter` with one
+// atomic, and a lane with occ set gets that base plus the occ lanes below it (the others: a rank nobody uses).
+__device__ __forceinline__ unsigned long long wave_rank(bool occ, unsigned long long* counter, uint32_t lane) {
+  const unsigned long long bal = __ballot(occ);
+  unsigned long long base = 0;
+  if (lane == 0u) base = atomicAdd(counter, (unsigned long long)__popcll(bal));
+  base = __shfl(base, 0);
+  return base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
 }
 
 // behind the cursor? (id_known: the caller has the row's id already)
@@ -279,15 +290,9 @@ __global__ __launch_bounds__(TOP_THREADS) void k_top_compact(const T* __restrict
         else if (word != vfix) ok = word < vfix;
         else ok = sh >= 64u || (A.ids[pos] >> sh) <= pre;
       }
-      const unsigned long long bal = __ballot(ok);
-      if (bal) {
-        unsigned long long base = 0;
-        if ((int)lane == __ffsll((long long)bal) - 1) base = atomicAdd(&S->ncand, (unsigned long long)__popcll(bal));
-        base = __shfl(base, __ffsll((long long)bal) - 1);
-        if (ok) {
-          const unsigned long long at = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
-          if (at < TOP_CAND) { cand_u[at] = u; cand_id[at] = A.ids[pos]; }
-        }
+      if (__ballot(ok)) {                                      // (uniform)
+        const unsigned long long at = wave_rank(ok, &S->ncand, lane);
+        if (ok && at < TOP_CAND) { cand_u[at] = u; cand_id[at] = A.ids[pos]; }
       }
     }
   });

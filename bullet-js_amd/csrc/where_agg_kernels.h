@@ -13,6 +13,8 @@
 // row() walks its clauses in loops that end on wave votes, so every lane of a wave has to reach it the same number of times: top_sweep calls its functor once
 // per unit in every lane (cnt == 0 beyond the column), and the functor calls row() for all E rows of the unit, with valid = false for a row beyond the column
 // or a tombstoned position. As in PredWhere::mask, the E rows are one copy of the walk: the element is picked with selects, not with a run-time index.
+// where_unit_rows is that walk and where_sweep the whole sweep, for every kernel of the family but k_where_top0 and k_quant0, which keep a copy and say why;
+// where_field and where_two_fields fetch a selected node's fields.
 #pragma once
 #include "where_kernels.h"
 #include "top_kernels.h"
@@ -31,6 +33,48 @@ __device__ __forceinline__ T where_pick(const V& x, int e) {
   return xe;
 }
 
+// The rows of one unit of top_sweep, in ONE copy of the walk: f(e, xe, pos, sel) for e = 0 .. E - 1, sel = the program selects the row at index position pos
+// (never a row beyond the column or a tombstoned position). Every lane reaches row() and f E times: f may vote, or return at once on sel = false.
+template <class T, class P, class V, class F>
+__device__ __forceinline__ void where_unit_rows(const P& pred, uint64_t unit, const V& x, uint32_t cnt, F&& f) {
+  constexpr int E = PredWhere<T>::E;
+#pragma unroll 1
+  for (int e = 0; e < E; e++) {
+    const T xe = where_pick<T, E>(x, e);
+    const uint64_t pos = unit * E + (uint64_t)e;
+    f(e, xe, pos, pred.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos));
+  }
+}
+// ... of every unit of the base field's value column: the whole sweep of a kernel with nothing to do per unit
+template <class T, class P, class F>
+__device__ __forceinline__ void where_sweep(uint64_t n, const P& pred, F&& f) {
+  typedef T vec_t __attribute__((ext_vector_type(PredWhere<T>::E)));
+  top_sweep<T>(pred.v, n, pred.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) { where_unit_rows<T>(pred, unit, x, cnt, f); });
+}
+
+// A field of the selected node at pos: src == 0, the base field, whose column value the caller has put into y; src == AGG_SRC_PROBE, one probe of `field`
+// through the program's table; any other src: none. -> the node holds data there (y: the value)
+template <class P>
+__device__ __forceinline__ bool where_field(const P& pred, uint64_t pos, uint32_t src, uint32_t field, int64_t& y) {
+  bool have = src == 0u;
+  if (src == AGG_SRC_PROBE) have = agg_probe(pred.slots, pred.nslots, pred.ids[pos], field, y) && y != VAL_DELETED;      // (uniform)
+  return have;
+}
+// Two such fields through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers. The caller has set
+// (y, have) of both for src == 0; field k is touched only where src_k == AGG_SRC_PROBE and the node holds data there.
+template <class P>
+__device__ __forceinline__ void where_two_fields(const P& pred, uint64_t pos, uint32_t src0, uint32_t field0, int64_t& y0, bool& have0, uint32_t src1, uint32_t field1,
+                                                 int64_t& y1, bool& have1) {
+#pragma unroll 1
+  for (uint32_t k = 0; k < 2u; k++) {
+    if ((k ? src1 : src0) != AGG_SRC_PROBE) continue;                // (uniform)
+    int64_t y;
+    if (agg_probe(pred.slots, pred.nslots, pred.ids[pos], k ? field1 : field0, y) && y != VAL_DELETED) {
+      if (k) { y1 = y; have1 = true; } else { y0 = y; have0 = true; }
+    }
+  }
+}
+
 // a candidate the program selected: the measure and the group value (the column value x, or one probe each), then the add. The table is P's.
 // EXPR (bmx_expr.h): the measure is X's expression of two fields, fetched with the group value through expr_fetch's one copy of the probe; a node that is
 // undefined or out of range is a node without its measure; -> its class. The host sets A.m_src = AGG_SRC_PROBE for it: n is counted per row in every G.
@@ -41,17 +85,7 @@ __device__ __forceinline__ uint32_t where_agg_row(const PredWhere<T, true, CLOCK
   bool have_m = A.m_src == 0u, have_g = A.g_src == 0u;
   uint32_t cls = EXPR_DEFINED;
   if constexpr (EXPR) have_m = expr_fetch(P.slots, P.nslots, P.ids, X, A.g_src, A.group, x, pos, mval, gval, have_g, cls);
-  else {
-    // the measure (k = 0) and the group field (k = 1) through ONE copy of the probe: a second inlined copy costs the grouped forms their last free scalar registers
-#pragma unroll 1
-    for (uint32_t k = 0; k < 2u; k++) {
-      if ((k ? A.g_src : A.m_src) != AGG_SRC_PROBE) continue;        // (uniform)
-      int64_t y;
-      if (agg_probe(P.slots, P.nslots, P.ids[pos], k ? A.group : A.measure, y) && y != VAL_DELETED) {
-        if (k) { gval = y; have_g = true; } else { mval = y; have_m = true; }
-      }
-    }
-  }
+  else where_two_fields(P, pos, A.m_src, A.measure, mval, have_m, A.g_src, A.group, gval, have_g);
   uint32_t g = 0;
   if (G) {   // (the difference of two int64 is exact mod 2^64 once gval >= group_lo)
     const uint64_t d = (uint64_t)gval - (uint64_t)A.group_lo;
@@ -63,21 +97,14 @@ __device__ __forceinline__ uint32_t where_agg_row(const PredWhere<T, true, CLOCK
 
 template <class T, int G, bool CLOCKS, bool EXPR = false>      // (EXPR: a computed measure, bmx_expr.h; X is empty without one)
 __global__ __launch_bounds__(AGG_THREADS) void k_where_agg(uint64_t n, PredWhere<T, true, CLOCKS> P, AggArgs A, ExprArgs<EXPR> X) {
-  constexpr int E = PredWhere<T>::E;
-  typedef T vec_t __attribute__((ext_vector_type(E)));
   __shared__ AggLds<G> S;
   AggLane L;
   ExprWave C;
   agg_begin<G>(A, S);
-  top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
-#pragma unroll 1
-    for (int e = 0; e < E; e++) {
-      const T xe = where_pick<T, E>(x, e);
-      const uint64_t pos = unit * E + (uint64_t)e;
-      uint32_t cls = EXPR_DEFINED;
-      if (P.row((uint32_t)e < cnt && xe != PredWhere<T>::TOMB, (int64_t)xe, pos)) cls = where_agg_row<G>(P, A, X, (int64_t)xe, pos, L, S);
-      if constexpr (EXPR) expr_count(C, cls);
-    }
+  where_sweep<T>(n, P, [&](int, T xe, uint64_t pos, bool sel) {
+    uint32_t cls = EXPR_DEFINED;
+    if (sel) cls = where_agg_row<G>(P, A, X, (int64_t)xe, pos, L, S);
+    if constexpr (EXPR) expr_count(C, cls);
   });
   agg_end<G>(A, L, S);
   expr_end(X, C);
@@ -92,6 +119,8 @@ __global__ __launch_bounds__(TOP_THREADS) void k_where_top0(uint64_t n, PredWher
   const uint64_t nu = (n + E - 1) / E;
   top_sweep<T>(P.v, n, P.nt ? 1u : 0u, [&](uint64_t unit, const vec_t& x, uint32_t cnt) {
     uint32_t nib = 0;
+    // (its own copy of where_unit_rows' walk. Measured: through the helper, with the same register counts, bmx_where_top is 6 to 10 us slower at every
+    // selectivity; with this copy it is level. profiles/kernel_sharing_timings.txt)
 #pragma unroll 1
     for (int e = 0; e < E; e++) {
       const T xe = where_pick<T, E>(x, e);
